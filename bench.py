@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """KSD-gradient steps/s on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,9 +14,15 @@ One step = one epoch body of ksd_vi_quantum.py:110-161 with TVD tracking off: ba
 KSD = sqrt(clamp(q^T K_p q)), dL/dq, 2P parameter-shift circuits -> grad, clip, Adam, scheduler.
 S and K_p are built once before the timed region (they do not depend on theta).
 
-Timing: W warm-up steps, then R repeats of EXACTLY K steps, each repeat bracketed by a barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over the ranks; `value` = K / median repeat
-(R >= 5 and R * K steps >= 2 s, so that a 2 % change can be ranked; min / max are reported beside it).
+Timing: W warm-up steps, then EXACTLY K timed steps bracketed by a barrier + torch.cuda.synchronize() on both
+sides and reduced with MAX over the ranks; `value` = K / elapsed, `ms_per_step` = elapsed / K.  `--repeats R`
+times R such repeats and reports the median (0: R >= 5 and R * K steps >= 2 s; min / max beside it).
+`--dump-outputs DIR` writes what the last timed step computed (loss, grad_norm, q, theta, theta_grad) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+A plain run does only that.  `--full` adds everything else: phase spans and per-kernel roofline rows, the
+labelled extras (prefix sharing, adjoint engine, MFMA kernels), the `series` workloads, the gate-apply
+micro-benchmark, the CPU baseline and, for N > 1, the sharded-vs-unsharded self-test.
 
 N > 1 (strong scaling: the same step, split): the 2P shifted circuits are dealt to the ranks, the upper
 triangle of K_p is sharded in strip pairs; one all-reduce (K q) and one all-gather (gradient scalars) per
@@ -299,18 +305,44 @@ def make_vi(workload, dev, process_group=None, overlap=0):
     return vi, x
 
 
-def run_repeat(vi, step_fn, opt_state, clip, K, D, dev):
-    """EXACTLY K steps between barrier + synchronize on both sides; MAX over the ranks of the elapsed seconds."""
+def run_repeat(vi, step_fn, opt_state, clip, K, D, dev, last=None):
+    """EXACTLY K steps between barrier + synchronize on both sides; MAX over the ranks of the elapsed seconds.
+    `last` (a list): receives what the last step returned."""
     params, opt, sched = opt_state
     losses = []
     D.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(K):
-        losses.append(step_fn(params, opt, sched, clip)[0])
+        out = step_fn(params, opt, sched, clip)
+        losses.append(out[0])
     torch.cuda.synchronize(dev)
     D.barrier()
+    if last is not None and K > 0:
+        last[:] = [out]
     return D.max_over_ranks(time.perf_counter() - t0), losses
+
+
+def step_outputs(vi, out):
+    """What a caller of the timed step holds after it: the step's (loss, clipped-gradient norm, q) and the updated
+    parameters with their (clipped, float32) gradient -- host copies, float32 / float64 as computed."""
+    loss, grad_norm, q = out
+    theta = vi.born_machine.theta
+    arrs = {"loss": loss, "grad_norm": grad_norm, "q": q, "theta": theta.detach(), "theta_grad": theta.grad}
+    return {k: np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64))
+            for k, v in arrs.items() if v is not None}
+
+
+def write_outputs(outputs, out_dir):
+    """--dump-outputs: one DIR/<name>.npy per array (at most 64 MB in all)."""
+    total = sum(a.nbytes for a in outputs.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than 64 MB")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def phase_means(timers):
@@ -354,8 +386,10 @@ def dist_selftest(dev, D):
     return out
 
 
-def measure(workload, dev, D, args, steps, warmup, repeats, want_extras):
-    """Builds the trainer for `workload`, runs warm-up + repeats; returns everything rank 0 needs for the record."""
+def measure(workload, dev, D, args, steps, warmup, repeats, want_extras, want_phases=True, want_outputs=False):
+    """Builds the trainer for `workload`, runs warm-up + repeats; returns everything rank 0 needs for the record.
+    want_phases: event spans of the phases (recorded in the timed region of eager steps, or in a few eager steps after
+    it); want_outputs: host copies of what the last timed step returned (`outputs`), taken before anything else runs."""
     from tensornetworks_amd import backend
     n, layers, ansatz, gram_mode = WORKLOADS[workload]
     vi, x = make_vi(workload, dev, overlap=args.overlap)
@@ -386,18 +420,20 @@ def measure(workload, dev, D, args, steps, warmup, repeats, want_extras):
     else:
         for _ in range(warmup):
             losses.append(step_fn(*opt_state, clip)[0])
-    vi.timers = None if use_graph else {}
+    vi.timers = None if (use_graph or not want_phases) else {}
     elapsed = []
-    first, ls = run_repeat(vi, step_fn, opt_state, clip, steps, D, dev)
+    last = []
+    first, ls = run_repeat(vi, step_fn, opt_state, clip, steps, D, dev, last)
     elapsed.append(first)
     losses += ls
     R = repeats if repeats > 0 else int(min(50, max(5, math.ceil(2.0 / max(first, 1e-6)))))
     for _ in range(R - 1):
-        e, ls = run_repeat(vi, step_fn, opt_state, clip, steps, D, dev)
+        e, ls = run_repeat(vi, step_fn, opt_state, clip, steps, D, dev, last)
         elapsed.append(e)
         losses += ls
+    outputs = step_outputs(vi, last[0]) if (want_outputs and last) else None
     timers = vi.timers
-    if use_graph:          # phase spans cannot be recorded inside a graph: take them from a few eager steps afterwards
+    if use_graph and want_phases:      # phase spans cannot be recorded inside a graph: take them from a few eager steps afterwards
         vi.timers = {}
         for _ in range(5):
             vi.training_step_async(*opt_state, clip)
@@ -436,7 +472,7 @@ def measure(workload, dev, D, args, steps, warmup, repeats, want_extras):
     if use_graph and graphed.adam is not None:
         losses = graphed.adam.history()[0].cpu().tolist()      # all epochs, the graph's eager warm-up steps included
     return {"vi": vi, "P": P, "theta0": theta0, "elapsed": elapsed, "timers": timers, "losses": losses, "graph": use_graph,
-            "extra_adjoint": extra_adjoint,
+            "extra_adjoint": extra_adjoint, "outputs": outputs,
             "precompute_s": precompute_s, "extra_share": extra_share, "n": n, "layers": layers, "ansatz": ansatz,
             "gram_mode": gram_mode}
 
@@ -625,7 +661,7 @@ def bench_adversarial(args, dev, D):
         elapsed = []
         hist = None
         graphed = 0
-        for _ in range(max(3, args.repeats)):
+        for _ in range(args.repeats if args.repeats > 0 else 3):
             D.barrier()
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
@@ -634,8 +670,12 @@ def bench_adversarial(args, dev, D):
             D.barrier()
             elapsed.append(D.max_over_ranks(time.perf_counter() - t0))
             graphed = adv.graphed_epochs
-        adv.timers = {}                       # phase spans: a few eager epochs afterwards (no events inside a graph)
-        adv.train(x, num_epochs=max(4, args.steps // 2), graph_epochs=False, **kw)
+        if args.dump_outputs is not None and D.rank == 0:     # what the last timed train() call handed back
+            write_outputs({**{k: np.asarray(v, dtype=np.float64) for k, v in hist.items() if isinstance(v, list) and v},
+                           "theta": adv.born_machine.theta.detach().cpu().numpy()}, args.dump_outputs)
+        if args.full:
+            adv.timers = {}                   # phase spans: a few eager epochs afterwards (no events inside a graph)
+            adv.train(x, num_epochs=max(4, args.steps // 2), graph_epochs=False, **kw)
     per = sorted(1e3 * e / args.steps for e in elapsed)
     med = float(np.median(per))
     P = adv.born_machine.num_ansatz_params
@@ -649,7 +689,7 @@ def bench_adversarial(args, dev, D):
            "repeats": {"n": len(per), "ms_per_step_median": round(med, 4), "ms_per_step_min": round(per[0], 4), "ms_per_step_max": round(per[-1], 4)},
            "launch": (f"{graphed} of {args.steps} epochs per call replayed from one HIP graph (the first two run eagerly and the "
                       "third captures)" if graphed else "eager kernel launches") + (f"; capture failed: {adv.graph_error}" if adv.graph_error else ""),
-           "phase_ms": {**phase_means(adv.timers), "note": "event spans of eager epochs run after the timed region"},
+           "phase_ms": {**phase_means(adv.timers), "note": "event spans of eager epochs run after the timed region"} if args.full else None,
            "roofline": None, "cpu_baseline": None,
            "note": "torch-op composition around the HIP circuit engine (sampling, table gathers, MLP): no kernel of its own, "
                    "so no roofline row; the Born step's backward is 2P parameter-shift circuits",
@@ -689,10 +729,18 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=0, help="repeats of the K timed steps (0 = at least 5 and at least 2 s in all)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="repeats of the K timed steps (1, the default: exactly K timed steps; 0 = at least 5 and at least 2 s in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: phase spans, per-kernel roofline rows, the labelled extras, the series "
+                         "workloads, the gate-apply micro-benchmark, the CPU baseline and (N > 1) the sharded-vs-unsharded "
+                         "self-test; without it the run sets up, warms up, times the K steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, grad_norm, q, theta, theta_grad) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--workload", default="n16_L6_dense", choices=sorted(WORKLOADS) + sorted(ADV_WORKLOADS))
-    ap.add_argument("--series", default="auto", help="'auto': also measure n20_L8_kron (BASELINE config 4) beside the default "
-                                                      "workload; 'none'; or a workload name")
+    ap.add_argument("--series", default="auto", help="with --full: 'auto': also measure n20_L8_kron (BASELINE config 4) beside "
+                                                      "the default workload; 'none'; or a workload name")
     ap.add_argument("--dist-selftest", action="store_true", help="N > 1: check the sharded step against an un-sharded recomputation first")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gate-bench", action="store_true")
@@ -736,7 +784,7 @@ def main(argv=None):
     torch.cuda.set_device(dev)
     D = Dist(dev)
     world, rank = D.world, D.rank
-    if world > 1 and not args.no_dist_selftest:
+    if world > 1 and args.full and not args.no_dist_selftest:
         args.dist_selftest = True
 
     from tensornetworks_amd import backend
@@ -761,18 +809,22 @@ def main(argv=None):
     selftest = dist_selftest(dev, D) if (args.dist_selftest and world > 1) else None
 
     m = measure(args.workload, dev, D, args, args.steps, args.warmup, args.repeats,
-                want_extras=not args.debug_flags and not args.no_extras)
+                want_extras=args.full and not args.debug_flags and not args.no_extras, want_phases=args.full,
+                want_outputs=args.dump_outputs is not None and rank == 0)
+    if m["outputs"] is not None:
+        write_outputs(m["outputs"], args.dump_outputs)
     m["is_main"] = True
     m["workload"] = args.workload
-    kern, config, phases = kernel_table(m, D, args)
-    med_ms, rep = summarize(m, args.steps)
-    phases_per_rank = D.gather_objects({"rank": rank, **phases})
     vi = m["vi"]
+    if args.full:
+        kern, config, phases = kernel_table(m, D, args)
+        phases_per_rank = D.gather_objects({"rank": rank, **phases})
+    else:
+        config = {"n_qubits": m["n"], "layers": m["layers"], "ansatz": m["ansatz"], "params": m["P"],
+                  "circuits_per_step": 1 + 2 * m["P"], "gram": m["gram_mode"]}
+    med_ms, rep = summarize(m, args.steps)
     rec = None
     if rank == 0:
-        dom_name = max(kern, key=lambda k_: kern[k_]["ms_per_step"])
-        roof = dict(kern[dom_name])
-        roof["kernel"] = dom_name
         value = 1e3 / med_ms
         rec = {
             "metric": "ksd_gradient_steps_per_sec", "value": round(value, 4), "unit": "steps/s",
@@ -783,21 +835,30 @@ def main(argv=None):
                        "optimizer": "adam lr=0.005 cosine clip=10",
                        "parallelism": f"paramshift + gram {'strip-pair' if vi._K_pairs is not None else 'row'} shard x{world}",
                        "dist_backend": D.backend if world > 1 else None},
-            "repeats": rep, "roofline": roof, "kernels": kern,
-            "extras": {"prefix_sharing": m["extra_share"], "adjoint_engine": m["extra_adjoint"]},
+            "repeats": rep,
             "launch": "one HIP graph replay per step (make_graphed_step)" if m["graph"] else "eager kernel launches",
             "overlap": {"mode": {False: "sequential", True: "second stream", "partition": "cu-partition"}[vi.overlap_streams],
                         "measured_choice": vi.overlap_choice},
             "gram_placement": vi.gram_placement,
-            "phase_ms": {**phases, "note": "event spans on the stream the kernels are launched on, mean over the timed region; "
-                                           "allreduce / allgather are inside stein / finish"},
-            "phase_ms_per_rank": phases_per_rank,
             "precompute_seconds": round(m["precompute_s"], 3),
             "host_sync": "per step (loss.item())" if args.host_sync else "deferred: K steps back to back, losses read after the repeat",
             "loss_first_last": [float(m["losses"][0]), float(m["losses"][-1])],
         }
+        if args.full:
+            dom_name = max(kern, key=lambda k_: kern[k_]["ms_per_step"])
+            rec.update({
+                "roofline": {**kern[dom_name], "kernel": dom_name}, "kernels": kern,
+                "extras": {"prefix_sharing": m["extra_share"], "adjoint_engine": m["extra_adjoint"]},
+                "phase_ms": {**phases, "note": "event spans on the stream the kernels are launched on, mean over the timed region; "
+                                               "allreduce / allgather are inside stein / finish"},
+                "phase_ms_per_rank": phases_per_rank})
         if selftest is not None:
             rec["dist_selftest"] = selftest
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(rec))
+        D.close()
+        return
     if rank == 0 and world == 1 and m["gram_mode"] == "dense" and not args.no_extras and not args.debug_flags and vi._K is not None:
         # the two matrix-core kernels of the path on this run's own K_p (MFMA utilisation against the fp64 matrix peak)
         rec["extras"]["mfma"] = mfma_extras(vi, dev, m["n"])

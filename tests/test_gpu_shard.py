@@ -90,11 +90,11 @@ def test_row_shard_messages_assemble_to_the_full_contraction(dev, W, n):
 
 
 def test_bench_dist_selftest_two_ranks(dev, tmp_path):
-    """`bench.py --gpus 2 --dist-selftest` as the driver's torchrun would start it (env-variable rendezvous), with gloo
-    because both ranks share this box's one GPU: the self-test compares the all-reduced contraction and the gathered
+    """`bench.py --gpus 2 --dist-selftest --full` as the driver's torchrun would start it (env-variable rendezvous), with
+    gloo because both ranks share this box's one GPU: the self-test compares the all-reduced contraction and the gathered
     gradient with an un-sharded recomputation on every rank, then the bench emits its JSON line with per-phase
     milliseconds per rank."""
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "n12_L4_dense", "--dist-selftest",
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "n12_L4_dense", "--dist-selftest", "--full",
             "--no-cpu-baseline", "--no-gate-bench", "--no-extras", "--series", "n8_L4_dense", "--repeats", "1"]
     codes = run_ranks(shard_worker.bench_rank, 2, (argv, str(tmp_path)), timeout=900)
     assert codes == [0, 0], (codes, _errors(tmp_path))
@@ -113,15 +113,15 @@ def test_bench_starts_its_own_ranks(dev, tmp_path):
     """`python bench.py --gpus 2` with NO rendezvous in the environment (the way the driver starts the --gpus 1 run): the
     process starts the two ranks itself before touching the GPU (a child `python -m torch.distributed.run`), relays rank
     0's JSON line and the children's exit code.  gloo here because the ranks share this box's one GPU (bench.py picks
-    it when there are fewer GPUs than ranks); the sharded-vs-unsharded self-test is on by default for N > 1."""
+    it when there are fewer GPUs than ranks); with --full the sharded-vs-unsharded self-test is on by default for N > 1."""
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                              "BORNVI_DIST_BACKEND")}
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--workload", "n12_L4_dense", "--no-cpu-baseline", "--no-gate-bench", "--no-extras", "--series", "none",
-                        "--repeats", "1"], env=env, cwd=repo, capture_output=True, text=True, timeout=900)
+                        "--workload", "n12_L4_dense", "--full", "--no-cpu-baseline", "--no-gate-bench", "--no-extras", "--series",
+                        "none", "--repeats", "1"], env=env, cwd=repo, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
