@@ -5,10 +5,12 @@ small_random initialisation, Adam lr = 0.005 with cosine annealing, clip 10, 100
 the reference makes is the package the two classes are imported from.  Prints the learned
 distribution beside the exact posterior and the TVD statistics the reference prints; no plotting.
 
-    python examples/run_sprinkler_quantum_ksd.py [--epochs 1000] [--device cuda:0] [--no-host-sync]
+    python examples/run_sprinkler_quantum_ksd.py [--epochs 1000] [--device cuda:0] [--no-host-sync] [--shots S]
 
 --no-host-sync: the same epochs without the per-epoch loss.item() (train(host_sync=False): one HIP-graph replay per
-epoch at this size is not used because a TVD per epoch is requested; the losses are read back at the log points)."""
+epoch at this size is not used because a TVD per epoch is requested; the losses are read back at the log points).
+--shots S: finite-shot training, as with qml.device(..., shots=S) in the reference: every circuit evaluation of a step
+is the histogram of S draws (seeded from the torch seed); TVDs and the final table are of the exact learned q."""
 import argparse
 import os
 import sys
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="torch seed of the small_random initialisation")
     ap.add_argument("--no-host-sync", action="store_true")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--shots", type=int, default=None, help="draws per circuit evaluation (default: exact probabilities)")
     args = ap.parse_args()
 
     import torch
@@ -46,10 +49,13 @@ def main():
     vi = KSDVariationalInference(bayesian_network=network, latent_vars_names=latent, observed_vars_names=observed,
                                  qbm_num_latent_vars=len(latent), qbm_ansatz_layers=args.layers, qbm_conditioning_dim=0,
                                  qbm_pennylane_device_name="default.qubit", qbm_ansatz_type=args.ansatz,
-                                 qbm_init_method="small_random", base_kernel_length_scale=1.0, pytorch_device=args.device)
+                                 qbm_init_method="small_random", base_kernel_length_scale=1.0, pytorch_device=args.device,
+                                 **({"qbm_shots": args.shots} if args.shots is not None else {}))
     n_params = sum(p.numel() for p in vi.born_machine.parameters() if p.requires_grad)
     print(f"Born machine: {len(latent)} qubits, {args.layers} layers of {args.ansatz}, {n_params} parameters; "
           f"Adam lr {args.lr} with cosine annealing, clip 10, {args.epochs} epochs on {args.device}")
+    if args.shots is not None:
+        print(f"Finite shots: {args.shots} draws per circuit evaluation (seed {vi.born_machine.shot_seed})")
 
     t0 = time.perf_counter()
     history = vi.train(x_observation_dict=evidence, num_epochs=args.epochs, lr_born_machine=args.lr, verbose=not args.quiet,
@@ -57,7 +63,10 @@ def main():
                        adam_betas=(0.9, 0.999), **({"host_sync": False} if args.no_host_sync else {}))
     seconds = time.perf_counter() - t0
 
-    learned = vi.born_machine.get_prob_dict(x_condition=None)
+    if args.shots is None:
+        learned = vi.born_machine.get_prob_dict(x_condition=None)
+    else:       # the exact learned distribution, not one more histogram of it
+        learned = dict(zip(vi.born_machine.all_outcomes_tuples, vi.born_machine.exact_probabilities().cpu().tolist()))
     print(f"\n{'outcome ' + str(tuple(latent)):<22} | {'true P(z|x)':<13} | {'learned Q(z|x)':<15} | difference")
     print("-" * 70)
     worst = 0.0

@@ -292,6 +292,20 @@ int bornvi_ksd_grad_finish(bornvi_handle h, int n, const double* shifted, int n_
                            const double* y, const double* ksd2, double* loss_out,
                            double* dLdq_out, double* grad, bornvi_stream stream);
 
+/* ---- finite-shot measurement (qml.probs under shots = S): freq dev [B, 2^n] = counts / S of S independent draws from
+ * each row of probs dev [B, 2^n] (exact multinomial sampling; every entry an exact count / S, rows sum to S / S).
+ * freq == probs (in place) is allowed, any other overlap is not.  Row r is circuit id 0 (the base circuit) if
+ * include_base and r == 0, else, with j = r - include_base and p = p_begin + (j / 2) p_stride, id 2p + 1 (+ shift) or
+ * 2p + 2 (- shift) for even / odd j: the row layout of bornvi_paramshift_probs_strided.  The draws are a pure function
+ * of (seed, *epoch_dev, id, draw index) through Philox4x32-10 (kernels_shots.hip states the exact function), so they do
+ * not depend on how the rows are batched or sharded.  epoch_dev: int64 in device memory, read by the kernels (a graph
+ * replay sees the value current at replay time; its low 32 bits enter the counter).  A probability-0 entry is never
+ * drawn; a row of zeros yields zeros.  1 <= shots <= 2^31 - 1.  Workspace: bornvi_shots_workspace_bytes(h, n, B). */
+size_t bornvi_shots_workspace_bytes(bornvi_handle h, int n, int B);
+int bornvi_shots_histogram(bornvi_handle h, int n, int B, const double* probs, double* freq, long long shots,
+                           unsigned long long seed, const long long* epoch_dev, int include_base, int p_begin,
+                           int p_stride, void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
 /* Gradient hand-off to the optimiser (replaces the float cast of the parameter-shift VJP and
  * torch.nn.utils.clip_grad_norm_(params, gradient_clip_norm), ksd_vi_quantum.py:153): grad32 dev [P] float32 =
  * float32(grad64) * min(1, max_norm / (||float32(grad64)||_2 + 1e-6)); total_norm dev [1] float32 = that norm. */

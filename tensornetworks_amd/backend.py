@@ -295,8 +295,9 @@ def paramshift_dot_finish(token, w, ksd2=None):
     return loss, grad
 
 
-def paramshift_grad(ansatz_type, n, layers, theta, dLdq, p_begin, p_end, p_stride=1):
-    """grad[i] = 1/2 dLdq . (q(theta + pi/2 e_p) - q(theta - pi/2 e_p)) for p = p_begin + i p_stride < p_end, float64."""
+def paramshift_grad(ansatz_type, n, layers, theta, dLdq, p_begin, p_end, p_stride=1, shots=None):
+    """grad[i] = 1/2 dLdq . (q(theta + pi/2 e_p) - q(theta - pi/2 e_p)) for p = p_begin + i p_stride < p_end, float64.
+    shots = (S, seed, epoch tensor): the shifted distributions are replaced by histograms of S draws (shots_histogram)."""
     dev = theta.device
     h = _ext.handle_for(dev)
     aid = ansatz_id(ansatz_type)
@@ -308,6 +309,9 @@ def paramshift_grad(ansatz_type, n, layers, theta, dLdq, p_begin, p_end, p_strid
     if ns == 0:
         return grad
     shifted = paramshift_probs(ansatz_type, n, layers, theta, p_begin, p_end, include_base=False, p_stride=p_stride)
+    if shots is not None:
+        S, seed, epoch = shots
+        shots_histogram(shifted, n, S, seed, epoch, include_base=False, p_begin=p_begin, p_stride=p_stride, out=shifted)
     # dot products on the device: reuse the finishing kernel with ksd2 = 1 (loss = 1, scale = 1/2)
     one = torch.ones(1, dtype=torch.float64, device=dev)
     h.call("bornvi_ksd_grad_finish", n, _ptr(shifted), ns, _ptr(dLdq), _ptr(one), None, None, _ptr(grad),
@@ -383,6 +387,44 @@ def born_probs(state, n):
     probs = torch.empty(state.shape, dtype=torch.float64, device=dev)
     h.call("bornvi_born_probs", n, state.numel() >> n, _ptr(state), _ptr(probs), _ext.stream_ptr(dev))
     return probs
+
+
+# ---- finite shots -------------------------------------------------------------------------------------
+SHOTS_MAX = (1 << 31) - 1
+
+
+def shots_histogram(probs, n, shots, seed, epoch, include_base=True, p_begin=0, p_stride=1, out=None, ws_tag="shots"):
+    """Finite-shot measurement of B Born distributions (bornvi_shots_histogram): probs float64 [B, 2^n] on the GPU ->
+    frequencies counts / shots [B, 2^n] of `shots` exact multinomial draws per row.  Row r is circuit id 0 (base) if
+    include_base and r == 0, else 2p + 1 / 2p + 2 for the (+p, -p) rows of p = p_begin, p_begin + p_stride, ... -- the
+    layout of paramshift_probs; the draws are a pure function of (seed, epoch, circuit id, draw index).  epoch: an int64
+    device tensor [1] (read by the kernel: a captured graph sees its value at replay time).  out: destination [B, 2^n]
+    (may be `probs` itself: in place); default a new tensor."""
+    dev = probs.device
+    h = _ext.handle_for(dev)
+    _chk_n(n)
+    if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)) or not (1 <= int(shots) <= SHOTS_MAX):
+        raise BornviError(f"shots must be an integer in [1, 2^31 - 1], got {shots!r}")
+    if probs.numel() % (1 << n):
+        raise BornviError("probs: element count is not a multiple of 2^n")
+    _chk(probs, torch.float64, dev, "probs")
+    B = probs.numel() >> n
+    _chk(epoch, torch.int64, dev, "epoch", 1)
+    if out is None:
+        out = torch.empty((B, 1 << n), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", B << n)
+        if out.data_ptr() != probs.data_ptr():
+            a0, a1 = probs.data_ptr(), probs.data_ptr() + 8 * probs.numel()
+            b0, b1 = out.data_ptr(), out.data_ptr() + 8 * out.numel()
+            if a0 < b1 and b0 < a1:
+                raise BornviError("shots_histogram: out overlaps probs without being the same buffer")
+    if B == 0:
+        return out
+    ws = _ws(dev, _cached_size(h, "bornvi_shots_workspace_bytes", int(n), int(B)), ws_tag)
+    h.call("bornvi_shots_histogram", int(n), int(B), _ptr(probs), _ptr(out), int(shots), int(seed) & ((1 << 64) - 1),
+           _ptr(epoch), 1 if include_base else 0, int(p_begin), int(p_stride), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out
 
 
 # ---- Stein ---------------------------------------------------------------------------------------

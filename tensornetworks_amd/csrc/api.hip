@@ -1059,6 +1059,35 @@ int bornvi_ksd_grad_finish(bornvi_handle h, int n, const double* shifted, int n_
   return BORNVI_OK;
 }
 
+size_t bornvi_shots_workspace_bytes(bornvi_handle h, int n, int B) {
+  if (!h) return 0;
+  if (n < 1 || n > 30 || B < 0) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  return shots_workspace_bytes(n, B);
+}
+
+int bornvi_shots_histogram(bornvi_handle h, int n, int B, const double* probs, double* freq, long long shots,
+                           unsigned long long seed, const long long* epoch_dev, int include_base, int p_begin, int p_stride,
+                           void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (n < 1 || n > 30 || B < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  if (shots < 1 || shots > 2147483647ll) return fail(h, BORNVI_ERR_INVALID, "shots must be in [1, 2^31 - 1]");
+  if (B > 0 && (!probs || !freq || !epoch_dev)) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (p_begin < 0 || p_stride < 1) return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+  const long long rows_p = B - (include_base ? 1 : 0);
+  if (rows_p > 0 && 2ll * (p_begin + ((rows_p - 1) >> 1) * (long long)p_stride) + 2 > 0xffffffffll)
+    return fail(h, BORNVI_ERR_INVALID, "circuit ids beyond 32 bits");
+  // one 512-thread workgroup per (row, block of 2^12): the grid's thread count must fit 32 bits
+  const long long wgs = (long long)B * (n > 12 ? (1ll << (n - 12)) : 1);
+  if (wgs * 512 > 0xffffffffll) return fail(h, BORNVI_ERR_INVALID, "batch too large for one launch");
+  if (B > 0 && (!workspace || workspace_bytes < shots_workspace_bytes(n, B)))
+    return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  if (B == 0) return BORNVI_OK;
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_shots_histogram(n, B, probs, freq, (int)shots, seed, epoch_dev, include_base ? 1 : 0, p_begin, p_stride,
+                                   workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 int bornvi_clip_cast_grad(bornvi_handle h, int P, const double* grad64, double max_norm, float* grad32,
                           float* total_norm, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;

@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "plan.cpp"]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "plan.cpp"]
 HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
@@ -27,6 +27,8 @@ RESOURCE_BUDGET = {
     "gram_mfma_kernel": (0, 0),
     "circuit_pass_fast_kernelILb0": (20, 0),      # (20 bytes: spilled SGPRs of the set-up code, outside the tile loop)
     "circuit_pass_r3_kernelILb0": (0, 0),         # 8 amplitudes per thread: <= 128 VGPRs (four waves per SIMD) without scratch
+    "shots_mass_kernel": (0, 0),                  # finite-shot sampler (kernels_shots.hip): no scratch anywhere
+    "shots_draw_kernel": (0, 0),
     "circuit_pass_r3_kernelILb1": (24, 4),        # its fused-dot instantiation (last pass only): 8 weights more per thread; the few
                                                   # spilled address words are reloaded at the end of a trip, not inside the stages
 }

@@ -58,6 +58,12 @@ hipError_t launch_clip_adam(const double* g64, int P, double max_norm, const dou
                             float* norm_hist, hipStream_t st);
 hipError_t launch_dldq(const double* y, const double* ksd2, int n, double* dLdq, double* loss_out, hipStream_t st);
 
+// ---- finite-shot measurement (kernels_shots.hip) ------------------------------------------------------
+size_t shots_workspace_bytes(int n, long long B);
+hipError_t launch_shots_histogram(int n, long long B, const double* probs, double* freq, int shots, unsigned long long seed,
+                                  const long long* epoch_dev, int include_base, int p_begin, int p_stride, void* ws,
+                                  hipStream_t st);
+
 // ---- adjoint differentiation (kernels_adjoint.hip): gate-block walks over one / two states ------------
 struct AdjRotBlock {      // consecutive one-qubit gates of one wire, applied e = 0 first (kinds: plan.hpp GateKind)
   int wire, nrot;

@@ -1,0 +1,213 @@
+// Finite-shot measurement: S exact multinomial draws from each of B Born-distribution rows -> frequencies counts / S
+// (bornvi_shots_histogram).
+//
+// Draws are a pure function of (seed, epoch, global circuit id, level, block, draw index) through a counter-based
+// Philox4x32-10 (Random123's round function and constants, restated here; no rocRAND):
+//   key     = (seed & 0xffffffff, seed >> 32)
+//   counter = (m, (level << 24) | block, circuit id, epoch & 0xffffffff) -> 4 words w0..w3;
+//   draws 2m and 2m + 1 of that (level, block) take u = ((w1:w0) >> 11) 2^-53 and u = ((w3:w2) >> 11) 2^-53, in [0, 1).
+// A row of 2^n outcomes is cut into blocks of 2^12; the block masses form the row of the next level (2^(n-12) entries,
+// cut again while longer than one block).  The top level holds one block and gets all S draws; a block with m draws
+// (its count at the level above) draws m outcomes from its own contents:  x = first i with cdf[i] > u cdf[last]
+// (cdf = inclusive prefix sums of the block), or the block's last non-zero entry if no cdf[i] exceeds it (rounding).
+// Given the counts of the level above, the draws inside a block are conditionally i.i.d. from the block's normalised
+// contents, so the level-0 counts are one exact multinomial sample of the row: no normal or Poisson approximation.
+// A probability-0 outcome is never drawn; a row whose entries are all zero yields zeros.
+//
+// Traffic: the mass kernel reads every row once, the draw kernel reads it once more and writes the frequencies
+// (in place allowed: a workgroup reads its whole block into LDS before it writes it): 3 B 2^n 8 bytes.
+// Counts are integers kept in LDS per block and written once: no global atomics, deterministic.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+
+namespace bornvi {
+
+namespace {
+constexpr int SH_BLOCK_BITS = 12, SH_BLOCK = 1 << SH_BLOCK_BITS;
+constexpr int SH_THREADS = 512, SH_EPT = SH_BLOCK / SH_THREADS;     // draw kernel: 8 consecutive entries per thread in the scan
+constexpr int SM_THREADS = 256, SM_EPT = SH_BLOCK / SM_THREADS;     // mass kernel
+
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
+    const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
+    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+
+__device__ __forceinline__ double unit53(uint32_t lo, uint32_t hi) {
+  return (double)((((uint64_t)hi << 32) | lo) >> 11) * 0x1p-53;
+}
+
+// global circuit id of batch row r in the layout of bornvi_paramshift_probs_strided: base = 0, +p = 2p + 1, -p = 2p + 2
+__device__ __forceinline__ uint32_t circuit_id(long long r, int include_base, int p_begin, int p_stride) {
+  if (include_base) {
+    if (r == 0) return 0u;
+    --r;
+  }
+  const long long p = p_begin + (r >> 1) * (long long)p_stride;
+  return (uint32_t)(2 * p + 1 + (r & 1));
+}
+
+// masses[row][b] = sum of block b of row `row` of src ([B][len], len = nblk * 2^12); grid = nblk * B workgroups
+__global__ __launch_bounds__(SM_THREADS) void shots_mass_kernel(const double* __restrict__ src, long long len, long long nblk,
+                                                                double* __restrict__ masses) {
+  __shared__ double part[SM_THREADS / 64];
+  const long long g = blockIdx.x;
+  const double* __restrict__ p = src + (g / nblk) * len + (g % nblk) * SH_BLOCK;
+  const int t = threadIdx.x;
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < SM_EPT; ++i) s += p[t + i * SM_THREADS];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if ((t & 63) == 0) part[t >> 6] = s;
+  __syncthreads();
+  if (t == 0) {
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < SM_THREADS / 64; ++w) tot += part[w];
+    masses[g] = tot;
+  }
+}
+
+// One workgroup per (row, block of `blk` entries): draws the block's m outcomes (m = counts_in[row][b], or `shots` at the
+// top level) and writes either frequencies count / shots (level 0, into freq) or integer counts (into counts_out).
+__global__ __launch_bounds__(SH_THREADS) void shots_draw_kernel(const double* src, long long len, int blk, long long nblk,
+                                                                const int* __restrict__ counts_in, double* freq,
+                                                                int* __restrict__ counts_out, int shots, uint32_t seed_lo,
+                                                                uint32_t seed_hi, const long long* __restrict__ epoch_dev,
+                                                                int level, int include_base, int p_begin, int p_stride) {
+  __shared__ double cdf[SH_BLOCK];
+  __shared__ int hist[SH_BLOCK];
+  __shared__ double tsum[2][SH_THREADS];
+  __shared__ int lastnz;
+  const int t = threadIdx.x;
+  const long long g = blockIdx.x;
+  const long long row = g / nblk, b = g % nblk;
+  const long long base = row * len + b * (long long)blk;
+  const int m = counts_in ? counts_in[g] : shots;
+
+  for (int i = t; i < blk; i += SH_THREADS) {
+    cdf[i] = src[base + i];
+    hist[i] = 0;
+  }
+  if (t == 0) lastnz = -1;
+  __syncthreads();
+  // inclusive scan: 8 consecutive entries per thread, then a scan of the 512 thread totals
+  const int c0 = t * SH_EPT, c1 = min(c0 + SH_EPT, blk);
+  double run = 0.0;
+  int nz = -1;
+  for (int i = c0; i < c1; ++i) {
+    const double v = cdf[i];
+    if (v > 0.0) nz = i;
+    run += v;
+    cdf[i] = run;
+  }
+  if (nz >= 0) atomicMax(&lastnz, nz);
+  tsum[0][t] = run;
+  __syncthreads();
+  int cur = 0;
+  for (int off = 1; off < SH_THREADS; off <<= 1) {
+    const double v = tsum[cur][t] + (t >= off ? tsum[cur][t - off] : 0.0);
+    tsum[cur ^ 1][t] = v;
+    cur ^= 1;
+    __syncthreads();
+  }
+  if (t > 0 && c0 < c1) {
+    const double pre = tsum[cur][t - 1];
+    for (int i = c0; i < c1; ++i) cdf[i] = pre + cdf[i];
+  }
+  __syncthreads();
+
+  if (m > 0) {
+    const double total = cdf[blk - 1];
+    const int last = lastnz;
+    const uint32_t cid = circuit_id(row, include_base, p_begin, p_stride);
+    const uint32_t ep = (uint32_t)(unsigned long long)(*epoch_dev);
+    const uint32_t lb = ((uint32_t)level << 24) | (uint32_t)b;
+    const int npairs = (int)(((long long)m + 1) >> 1);
+    for (int pr = t; pr < npairs; pr += SH_THREADS) {
+      const uint4 w = philox4x32_10(make_uint4((uint32_t)pr, lb, cid, ep), seed_lo, seed_hi);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (2 * pr + h >= m) break;
+        const double u = h ? unit53(w.z, w.w) : unit53(w.x, w.y);
+        const double x = u * total;
+        int lo = 0, hi = blk;                 // first i with cdf[i] > x
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (cdf[mid] > x) hi = mid;
+          else lo = mid + 1;
+        }
+        if (lo >= blk) lo = last;
+        if (lo >= 0) atomicAdd(&hist[lo], 1);
+      }
+    }
+  }
+  __syncthreads();
+  if (counts_out) {
+    for (int i = t; i < blk; i += SH_THREADS) counts_out[base + i] = hist[i];
+  } else {
+    const double S = (double)shots;
+    for (int i = t; i < blk; i += SH_THREADS) freq[base + i] = (double)hist[i] / S;
+  }
+}
+
+// entries of every level above level 0: 2^(n-12), 2^(n-24), ... while the level below is longer than one block
+int shot_levels(int n, long long* lens) {
+  int L = 0;
+  long long len = 1ll << n;
+  lens[L++] = len;
+  while (len > SH_BLOCK) {
+    len >>= SH_BLOCK_BITS;
+    lens[L++] = len;
+  }
+  return L;
+}
+}  // namespace
+
+size_t shots_workspace_bytes(int n, long long B) {
+  long long lens[8];
+  const int L = shot_levels(n, lens);
+  size_t bytes = 256;
+  for (int l = 1; l < L; ++l) bytes += (size_t)B * lens[l] * (sizeof(double) + sizeof(int)) + 256;
+  return bytes;
+}
+
+hipError_t launch_shots_histogram(int n, long long B, const double* probs, double* freq, int shots, unsigned long long seed,
+                                  const long long* epoch_dev, int include_base, int p_begin, int p_stride, void* ws,
+                                  hipStream_t st) {
+  if (B == 0) return hipSuccess;
+  long long lens[8];
+  const int L = shot_levels(n, lens);
+  double* masses[8] = {nullptr};
+  int* counts[8] = {nullptr};
+  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  for (int l = 1; l < L; ++l) {
+    masses[l] = (double*)w;
+    counts[l] = (int*)(w + (size_t)B * lens[l] * sizeof(double));
+    w += ((size_t)B * lens[l] * (sizeof(double) + sizeof(int)) + 255) & ~(size_t)255;
+  }
+  const uint32_t slo = (uint32_t)seed, shi = (uint32_t)(seed >> 32);
+  for (int l = 0; l + 1 < L; ++l) {
+    const long long nblk = lens[l] >> SH_BLOCK_BITS;
+    hipLaunchKernelGGL(shots_mass_kernel, dim3((unsigned)(nblk * B)), dim3(SM_THREADS), 0, st, l ? masses[l] : probs, lens[l],
+                       nblk, masses[l + 1]);
+  }
+  for (int l = L - 1; l >= 0; --l) {
+    const int blk = (int)(lens[l] < SH_BLOCK ? lens[l] : SH_BLOCK);
+    const long long nblk = lens[l] / blk;
+    hipLaunchKernelGGL(shots_draw_kernel, dim3((unsigned)(nblk * B)), dim3(SH_THREADS), 0, st, l ? masses[l] : probs, lens[l],
+                       blk, nblk, l + 1 < L ? counts[l + 1] : nullptr, l ? nullptr : freq, l ? counts[l] : nullptr, shots,
+                       slo, shi, epoch_dev, l, include_base, p_begin, p_stride);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace bornvi

@@ -15,6 +15,10 @@ arithmetic happens:
 
 S (scores) and K_p are computed once per `train()` call on the GPU.  With a torch.distributed
 process group the 2P shifted circuits are sharded over the ranks (paramshift_shard.py).
+
+Finite shots (qbm_shots=S): the base and the 2P shifted distributions of a step are replaced by histograms of S draws
+each (backend.shots_histogram, every row its own draws) before the contraction; loss sqrt(max(q^T K_p q^, 1e-12)) and
+gradient 1/2 dL/dq^ . (q^+_p - q^-_p) are the plug-in estimates PennyLane's parameter-shift rule gives under shots.
 """
 import os
 import time
@@ -151,12 +155,16 @@ class KSDVariationalInference:
                  qbm_init_method: str = "small_random",
                  base_kernel_length_scale: float = 1.0,
                  pytorch_device: str = 'cpu',
-                 *, gram_mode: str = "auto", process_group=None):
+                 *, gram_mode: str = "auto", process_group=None, qbm_shots=None, shot_seed=None):
         """Arguments up to `pytorch_device` are the reference's (ksd_vi_quantum.py:19-30).
         Keyword-only extras: gram_mode in {"auto", "dense", "kron"} (dense Gram matrix vs matrix-free
         Kronecker mat-vec; "auto" = dense up to n = 16); process_group = torch.distributed group over
         which the parameter-shift circuits are sharded (None = default group if initialised;
-        paramshift_shard.SOLO = never shard)."""
+        paramshift_shard.SOLO = never shard); qbm_shots = S: finite-shot training (every circuit evaluation of a step
+        is a histogram of S draws; QuantumBornMachine(shots=...)), shot_seed = the draws' seed (None: one draw from
+        torch's global CPU generator; pass the same seed, or seed torch alike, on every rank).  With shots the step
+        always runs the un-fused, sequential path (overlap_streams and fused_dot do not apply: the fused dot has no
+        probabilities to sample); the TVD and best-parameter snapshot of train() use the exact q_theta."""
         if int(qbm_num_latent_vars) != len(latent_vars_names):
             # the scores are [2^len(latent_vars_names), len(latent_vars_names)] while the circuit has
             # qbm_num_latent_vars qubits: the device kernels would index one with the other's sizes
@@ -180,7 +188,9 @@ class KSDVariationalInference:
             conditioning_dim=qbm_conditioning_dim,
             device_name=qbm_pennylane_device_name,
             ansatz_type=qbm_ansatz_type,
-            init_method=qbm_init_method
+            init_method=qbm_init_method,
+            shots=qbm_shots,
+            shot_seed=shot_seed
         ).to(pytorch_device)
         self.born_machine.process_group = process_group
 
@@ -403,7 +413,7 @@ class KSDVariationalInference:
         rank, ws = shard.world(self.process_group)
         n = self.num_latent_vars
         self.overlap_streams = False
-        if ws != 1 or not self._use_dense() or n < 14:
+        if ws != 1 or not self._use_dense() or n < 14 or self.born_machine.shots is not None:
             return
         dev = self._S.device
         theta64 = self.born_machine.theta.detach().to(device=dev, dtype=torch.float64).contiguous()
@@ -474,6 +484,8 @@ class KSDVariationalInference:
         rank, ws = shard.world(self.process_group)
         lo, hi, step = shard.shard_params(P, rank, ws)
         n_local = len(range(lo, hi, step))
+        if self.born_machine.shots is not None:
+            return self._ksd_and_grad_shots(theta64, lo, hi, step, n_local)
         if self.grad_engine == "adjoint":
             with self._timed("circuits"):
                 state, q = backend.adjoint_state(at, n, L, theta64)
@@ -570,6 +582,39 @@ class KSDVariationalInference:
             with self._timed("allgather"):
                 grad = shard.all_gather_grad(grad_local, P, self.process_group)
         return loss, grad, q
+
+    def _ksd_and_grad_shots(self, theta64, lo, hi, step, n_local):
+        """ksd_and_grad with finite shots: the un-fused batch (base row, then the (+p, -p) rows of this rank's parameters),
+        every row replaced in place by the histogram of S draws keyed by its global circuit id at the machine's epoch, the
+        epoch advanced on the device (a graph replay draws afresh), then the usual contraction and finish on the
+        histograms.  Returns (loss estimate [1], grad estimate [P], the exact q [2^n])."""
+        bm = self.born_machine
+        if self.grad_engine != "paramshift":
+            raise ValueError("finite shots need grad_engine='paramshift': adjoint gradients are exact")
+        n, L, at = self.num_latent_vars, bm.ansatz_layers, bm.ansatz_type
+        dev = theta64.device
+        with self._timed("circuits"):
+            probs = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=True, p_stride=step)
+        q = probs[0].clone()
+        epoch = bm.shot_epoch(dev)
+        with self._timed("shots"):
+            backend.shots_histogram(probs, n, bm.shots, bm.shot_seed, epoch, include_base=True, p_begin=lo, p_stride=step,
+                                    out=probs)
+            epoch.add_(1)
+        with self._timed("stein"):
+            ksd2, y = self._stein_contract(probs[0])
+        with self._timed("finish"):
+            loss, grad_local, _ = backend.ksd_grad_finish(n, probs[1:], n_local, y, ksd2)
+            with self._timed("allgather"):
+                grad = shard.all_gather_grad(grad_local, theta64.numel(), self.process_group)
+        return loss, grad, q
+
+    def _tvd_probabilities(self, x_condition=None):
+        """The distribution train() measures the TVD of: the reference's get_probabilities(), or with shots the exact
+        q_theta (an evaluation metric, not a training signal: DESIGN.md section 8)."""
+        if self.born_machine.shots is not None:
+            return self.born_machine.exact_probabilities()
+        return self.born_machine.get_probabilities(x_condition=x_condition)
 
     def make_optimizer(self, lr_born_machine, num_epochs, use_lr_scheduler=True, optimizer_type="adam",
                        adam_betas=(0.9, 0.999), capturable=False):
@@ -794,8 +839,12 @@ class KSDVariationalInference:
                 if torch.is_tensor(true_posterior_for_tvd):
                     # array form (stein_utils.true_posterior_table): no dict of 2^n tuples; like the reference the
                     # distribution AFTER this epoch's update is compared (one more circuit, :168)
-                    q_now = self.born_machine.get_probabilities(x_condition=qbm_x_condition_input).detach().squeeze()
+                    q_now = self._tvd_probabilities(x_condition=qbm_x_condition_input).detach().squeeze()
                     tvd = float(tvd_table(true_posterior_for_tvd.to(q_now.device), q_now))
+                elif self.born_machine.shots is not None:
+                    current_q_dist_dict = dict(zip(self.born_machine.all_outcomes_tuples,
+                                                   self._tvd_probabilities().cpu().tolist()))
+                    tvd = calculate_tvd(true_posterior_for_tvd, current_q_dist_dict)
                 else:
                     current_q_dist_dict = self.born_machine.get_prob_dict(x_condition=qbm_x_condition_input)
                     tvd = calculate_tvd(true_posterior_for_tvd, current_q_dist_dict)
@@ -883,7 +932,7 @@ class KSDVariationalInference:
                 losses.append(loss_t)
                 norms.append(gn)
             if tvd_table_dev is not None:     # like the reference: the distribution AFTER this epoch's update (:168)
-                q_now = self.born_machine.get_probabilities().detach().squeeze()
+                q_now = self._tvd_probabilities().detach().squeeze()
                 tvds.append(tvd_table(tvd_table_dev.to(q_now.device), q_now))
             if verbose and epoch % log_every == 0:
                 print(f"  Epoch {epoch+1} Q Probs (first 4): {q[:4].detach().cpu().numpy()}")

@@ -16,6 +16,11 @@ Numerics: theta is float32 (reference :42-47) and is upcast exactly to float64; 
 complex128; probabilities are returned as float64 (quirk Q9 in SURVEY.md).  The gradient is the
 two-term parameter-shift rule with shift pi/2 (what `diff_method="parameter-shift"` does at
 :58/:90/:114), evaluated as 2P extra circuits, optionally sharded over the ranks of a process group.
+
+Finite shots (keyword-only `shots=S`, what `qml.device(..., shots=S)` gives `qml.probs`): every circuit evaluation
+returns the histogram counts / S of S independent draws from its Born distribution, sampled on the GPU
+(backend.shots_histogram); the base circuit and each shifted circuit of the backward get their own draws.  The draws
+are a pure function of (shot_seed, the machine's epoch counter, circuit id, draw index); every call advances the counter.
 """
 import numpy as np
 import torch
@@ -26,15 +31,26 @@ from . import paramshift_shard as shard
 from .utils import generate_all_binary_outcomes
 
 
+def check_shots(shots):
+    """None, or the shot count as an int in [1, 2^31 - 1]; ValueError for anything else (0, negatives, 1000.0, True)."""
+    if shots is None:
+        return None
+    if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)):
+        raise ValueError(f"shots must be None or a positive integer, got {shots!r}")
+    if not (1 <= int(shots) <= backend.SHOTS_MAX):
+        raise ValueError(f"shots must be in [1, 2^31 - 1], got {shots!r}")
+    return int(shots)
+
+
 class _BornviDevice:
     """Stand-in for the `qml.device(...)` object kept in `self.dev` (reference :28)."""
 
-    def __init__(self, name, wires):
+    def __init__(self, name, wires, shots=None):
         self.name = name
         self.short_name = name
         self.wires = tuple(range(wires))
         self.num_wires = wires
-        self.shots = None
+        self.shots = shots
         self.backend = "bornvi-hip-gfx950"
 
     def __repr__(self):
@@ -50,6 +66,13 @@ class _CircuitProbs(torch.autograd.Function):
         th64 = weights.detach().to(device=dev, dtype=torch.float64).contiguous()
         probs = backend.circuit_probs(machine.ansatz_type, machine.num_latent_vars, machine.ansatz_layers,
                                       th64.view(1, -1))[0]
+        ctx.epoch = None
+        if machine.shots is not None:      # the histogram of S draws (circuit id 0), in place; the backward's shifted
+            ep = machine.shot_epoch(dev)    # circuits draw at the same epoch with their own ids
+            backend.shots_histogram(probs.view(1, -1), machine.num_latent_vars, machine.shots, machine.shot_seed, ep,
+                                    out=probs.view(1, -1))
+            ctx.epoch = ep.clone()
+            ep.add_(1)
         ctx.machine = machine
         ctx.save_for_backward(th64)
         ctx.out_device = weights.device
@@ -65,7 +88,8 @@ class _CircuitProbs(torch.autograd.Function):
         P = th64.numel()
         rank, ws = shard.world(m.process_group)
         lo, hi, step = shard.shard_params(P, rank, ws)
-        local = backend.paramshift_grad(m.ansatz_type, m.num_latent_vars, m.ansatz_layers, th64, dLdq, lo, hi, step)
+        shots = None if ctx.epoch is None else (m.shots, m.shot_seed, ctx.epoch)
+        local = backend.paramshift_grad(m.ansatz_type, m.num_latent_vars, m.ansatz_layers, th64, dLdq, lo, hi, step, shots=shots)
         full = shard.all_gather_grad(local, P, m.process_group)
         return full.to(device=ctx.out_device, dtype=ctx.in_dtype), None
 
@@ -73,7 +97,7 @@ class _CircuitProbs(torch.autograd.Function):
 class QuantumBornMachine(nn.Module):
     def __init__(self, num_latent_vars, ansatz_layers=1, conditioning_dim=0,
                  device_name="default.qubit", ansatz_type="hardware_efficient",
-                 init_method="small_random"):
+                 init_method="small_random", *, shots=None, shot_seed=None):
         """
         Args (reference quantum_born_machine.py:8-21):
             num_latent_vars (int): number of qubits
@@ -83,6 +107,11 @@ class QuantumBornMachine(nn.Module):
                 on the HIP statevector engine
             ansatz_type (str): "hardware_efficient", "all_to_all", anything else = "basic"
             init_method (str): "zero", "small_random", anything else = uniform [0, 2 pi)
+        Keyword-only extras:
+            shots (int or None): None = exact probabilities (the reference's shots=None); S >= 1 = every circuit
+                evaluation returns the histogram of S draws (self.dev.shots reports S)
+            shot_seed (int or None): 64-bit seed of the draws; None with shots set = one draw from torch's global CPU
+                generator (after the initialisation of theta), so torch.manual_seed makes a run reproducible
         """
         super().__init__()
         self.num_latent_vars = num_latent_vars
@@ -91,7 +120,8 @@ class QuantumBornMachine(nn.Module):
         self.ansatz_layers = ansatz_layers
         self.process_group = None      # set by the trainer to shard the parameter-shift circuits
 
-        self.dev = _BornviDevice(device_name, num_latent_vars)
+        self.shots = check_shots(shots)
+        self.dev = _BornviDevice(device_name, num_latent_vars, self.shots)
 
         if ansatz_type in ("hardware_efficient", "all_to_all"):
             self.num_ansatz_params = ansatz_layers * 3 * num_latent_vars       # reference :31-36
@@ -106,6 +136,12 @@ class QuantumBornMachine(nn.Module):
             init = torch.rand(self.num_ansatz_params, dtype=torch.float32) * 2 * torch.pi
         self.theta = nn.Parameter(init)
 
+        self.shot_seed = None
+        self._shot_epoch = None
+        if self.shots is not None:
+            self.shot_seed = (int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if shot_seed is None
+                              else int(shot_seed) & ((1 << 64) - 1))
+
         self._outcomes = None
         if num_latent_vars == 0:
             self._outcomes = [()]
@@ -113,6 +149,21 @@ class QuantumBornMachine(nn.Module):
         def pqc(weights, x_inputs=None):
             return _CircuitProbs.apply(weights, self)
         self.pqc = pqc
+
+    def shot_epoch(self, device):
+        """The device int64 [1] epoch counter of the shot draws (created at 0 on first use on `device`).  Advanced by
+        every sampled evaluation -- by the trainer's step too -- so that no two evaluations share draws."""
+        if self._shot_epoch is None or self._shot_epoch.device != torch.device(device):
+            self._shot_epoch = torch.zeros(1, dtype=torch.int64, device=device)
+        return self._shot_epoch
+
+    def exact_probabilities(self):
+        """q_theta over all 2^n states (float64, no autograd, on theta.device) whatever `shots` is: the trainer's TVD
+        and best-parameter snapshot are evaluation metrics and use it."""
+        dev = backend.compute_device(self.theta.device)
+        th64 = self.theta.detach().to(device=dev, dtype=torch.float64).contiguous()
+        return backend.circuit_probs(self.ansatz_type, self.num_latent_vars, self.ansatz_layers,
+                                     th64.view(1, -1))[0].to(self.theta.device)
 
     @property
     def all_outcomes_tuples(self):
@@ -125,7 +176,8 @@ class QuantumBornMachine(nn.Module):
         return self._outcomes
 
     def get_probabilities(self, x_condition=None):
-        """q_theta(z|x) over all 2^n states (float64), differentiable w.r.t. theta (reference :132-137)."""
+        """q_theta(z|x) over all 2^n states (float64), differentiable w.r.t. theta (reference :132-137); with shots, a
+        fresh histogram of S draws per call (its backward samples the shifted circuits)."""
         if self.conditioning_dim > 0 and x_condition is not None:
             print("Warning: Conditioning with x_condition not fully implemented in PQC ansatz yet.")
         return self.pqc(weights=self.theta)
