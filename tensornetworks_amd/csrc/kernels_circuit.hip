@@ -470,23 +470,6 @@ __global__ __launch_bounds__(512) void circuit_pass_kernel(
 //     final FMAs that each overwrite the operand they read last): the compiler's version needed 32 register
 //     moves per gate to merge the conditional gate back into the amplitude registers.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double uniform_to_sgpr(double v) {
-  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-
-template <int I>
-__device__ __forceinline__ void op_u1_inplace_s(double (&ar)[16], double (&ai)[16], const double (&U)[8]) {
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    if (j & (1 << I)) continue;
-    gate_pair_inplace_s(ar[j], ai[j], ar[j | (1 << I)], ai[j | (1 << I)], U);
-  }
-}
-
-#ifndef BORNVI_U_SGPR
-#define BORNVI_U_SGPR 0
-#endif
-
 template <int I>
 __device__ __forceinline__ void op_u1_inplace(double (&ar)[16], double (&ai)[16], const double (&U)[8]) {
 #pragma unroll
@@ -512,26 +495,6 @@ __device__ __forceinline__ void apply_sign_bits(uint32_t m, double (&ar)[16], do
 // a large-tile workgroup reach the end of a stage together; 16 ds_write_b128 per wave issued in one burst by all of
 // them kept the LDS write path (~80 B/clk/CU) busy for ~1600 cycles per stage with the VALU idle.  Same operations on
 // the same values: bit-identical results.
-#ifndef BORNVI_SKIP_ZERO_TILES
-#define BORNVI_SKIP_ZERO_TILES 1   // 0: run the first pass's all-zero tiles through the stages like any other (A/B)
-#endif
-#ifndef BORNVI_GATE_PRIO
-#define BORNVI_GATE_PRIO 0       // experiment: s_setprio level while a wave runs its gates (0 = off)
-#endif
-#if BORNVI_GATE_PRIO
-#define BORNVI_PRIO_OFF() __builtin_amdgcn_s_setprio(0)
-#else
-#define BORNVI_PRIO_OFF() do { } while (0)
-#endif
-#ifndef BORNVI_EARLY_WRITE
-#define BORNVI_EARLY_WRITE 1     // large-tile instantiation only (LT below); 0: round-1 stage body everywhere (A/B)
-#endif
-#ifndef BORNVI_EARLY_STORE
-#define BORNVI_EARLY_STORE 1     // the same for a direct last stage's HBM stores
-#endif
-#ifndef BORNVI_U_PREFETCH
-#define BORNVI_U_PREFETCH 1      // with BORNVI_EARLY_WRITE: two matrix register sets, matrix reads ahead of the amplitude reads
-#endif
 template <int I, bool POST>
 __device__ __forceinline__ void op_u1_last_and_write(double (&ar)[16], double (&ai)[16], const double (&U)[8], uint32_t post_bits,
                                                      double2* __restrict__ tile, uint32_t wa0, const uint32_t (&G)[10]) {
@@ -559,13 +522,11 @@ __device__ __forceinline__ void op_u1_last_and_write(double (&ar)[16], double (&
 // The same for a direct last stage (IO == 2): the pair's two results go straight to HBM behind its gate -- the 16
 // stores of the tile are spread over the last gate instead of one burst per wave (a 1-KiB store takes ~100 cycles of the
 // CU's memory pipe).  Still exactly 16 stores per wave and tile, all behind the trip's loads.
-#ifndef BORNVI_FIN_HOIST
-#define BORNVI_FIN_HOIST 1      // one test of `fin` per last gate (two copies of the gate) instead of one per store: -1.3 %
-#endif
+// One test of `fin` per last gate (two copies of the gate) instead of one per store: -1.3 %.
 template <int I, bool POST, int FIN = -1>
 __device__ __forceinline__ void op_u1_last_and_store(double (&ar)[16], double (&ai)[16], const double (&U)[8], uint32_t post_bits,
                                                      uint32_t ha0, const uint32_t (&hbm_basis)[4], void* hbm_base, bool fin) {
-  if (BORNVI_FIN_HOIST && FIN < 0) {
+  if (FIN < 0) {
     if (fin) op_u1_last_and_store<I, POST, 1>(ar, ai, U, post_bits, ha0, hbm_basis, hbm_base, true);
     else op_u1_last_and_store<I, POST, 0>(ar, ai, U, post_bits, ha0, hbm_basis, hbm_base, false);
     return;
@@ -608,15 +569,13 @@ __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const dou
                                            uint32_t hbm_off, const uint32_t (&hbm_basis)[4], void* hbm_base, bool fin,
                                            bool cross) {
   double ar[16], ai[16];
-#if BORNVI_U_PREFETCH
   // (first: LDS returns in order, so the first gate can start as soon as ITS amplitudes have arrived behind the matrix)
   double Ua[8], Ub[8];
-  constexpr bool EARLY = BORNVI_EARLY_WRITE && LT && !DEBUG && NG > 0 && (IO != 2 || BORNVI_EARLY_STORE);
+  constexpr bool EARLY = LT && !DEBUG && NG > 0;
   if (EARLY) {
     load_u(Us, Ua);
     if (NG > 1) load_u(Us + 4, Ub);
   }
-#endif
   if (IO == 1) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) { ar[j] = v[j].x; ai[j] = v[j].y; }
@@ -640,10 +599,7 @@ __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const dou
     __syncthreads();
   }
   if (PRE) apply_sign_bits(my_sg & 0xffffu, ar, ai);
-#if BORNVI_GATE_PRIO
-  if (LT && NG > 0) __builtin_amdgcn_s_setprio(BORNVI_GATE_PRIO);   // experiment: the wave inside its gates wins the issue arbitration
-#endif
-  if (BORNVI_EARLY_WRITE && LT && !DEBUG && NG > 0 && (IO != 2 || BORNVI_EARLY_STORE)) {
+  if (EARLY) {
     constexpr int LAST = NG > 0 ? NG - 1 : 0;
     uint32_t wa0 = (IO == 2) ? hbm_off : (my_rw >> 16) << 4;
     // the last gate with its write-back: to LDS, or (direct last stage) to HBM
@@ -652,9 +608,7 @@ __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const dou
       asm volatile("" : "+v"(wa0));   /* the write base is formed here, before the last gate */                \
       if (IO == 2) op_u1_last_and_store<LAST, POST>(ar, ai, U_, my_sg >> 16, wa0, hbm_basis, hbm_base, fin);   \
       else op_u1_last_and_write<LAST, POST>(ar, ai, U_, my_sg >> 16, tile, wa0, G);                            \
-      BORNVI_PRIO_OFF();                                                                                        \
     } while (0)
-#if BORNVI_U_PREFETCH
     // two matrix register sets: the next gate's four broadcast LDS reads are in flight under the current gate's FMAs
     // (the early write-back freed the registers for the second set)
     if (NG == 1) { BORNVI_LAST_GATE(Ua); return; }
@@ -667,38 +621,14 @@ __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const dou
     op_u1_inplace<2>(ar, ai, Ua);
     BORNVI_LAST_GATE(Ub);
     return;
-#else
-    double U[8];
-    if (NG > 1) { load_u(Us, U); op_u1_inplace<0>(ar, ai, U); }
-    if (NG > 2) { load_u(Us + 4, U); op_u1_inplace<1>(ar, ai, U); }
-    if (NG > 3) { load_u(Us + 8, U); op_u1_inplace<2>(ar, ai, U); }
-    load_u(Us + 4 * LAST, U);
-    BORNVI_LAST_GATE(U);
-    return;
-#endif
 #undef BORNVI_LAST_GATE
   }
   if (!(DEBUG && (dbg & 1))) {
     double U[8];
-#if BORNVI_U_SGPR
-    // the wave-uniform matrix goes from LDS through a VGPR staging set into scalar registers; the next gate's LDS reads
-    // are issued into the freed staging set before this gate's FMAs (their latency hides under them)
-    double S_[8];
-    if (NG > 0) load_u(Us, U);
-#define BORNVI_GATE_S(I_)                                                            \
-    if (NG > I_) {                                                                   \
-      _Pragma("unroll") for (int e_ = 0; e_ < 8; ++e_) S_[e_] = uniform_to_sgpr(U[e_]); \
-      if (NG > I_ + 1) load_u(Us + 4 * (I_ + 1), U);                                 \
-      op_u1_inplace_s<I_>(ar, ai, S_);                                               \
-    }
-    BORNVI_GATE_S(0) BORNVI_GATE_S(1) BORNVI_GATE_S(2) BORNVI_GATE_S(3)
-#undef BORNVI_GATE_S
-#else
     if (NG > 0) { load_u(Us, U); op_u1_inplace<0>(ar, ai, U); }
     if (NG > 1) { load_u(Us + 4, U); op_u1_inplace<1>(ar, ai, U); }
     if (NG > 2) { load_u(Us + 8, U); op_u1_inplace<2>(ar, ai, U); }
     if (NG > 3) { load_u(Us + 12, U); op_u1_inplace<3>(ar, ai, U); }
-#endif
   }
   if (POST) apply_sign_bits(my_sg >> 16, ar, ai);
   if (IO == 2) {
@@ -739,9 +669,6 @@ __device__ __forceinline__ void stage_dispatch(uint32_t kind, double2* __restric
     stage_body<NG, PRE, POST, IO, DEBUG, LT>(tile, Us, my_rw, my_sg, G, dbg, v, hbm_off, hbm_basis, hbm_base, fin, cross); break;
 #define BORNVI_STAGE_NG(PRE, POST) \
   BORNVI_STAGE(0, PRE, POST) BORNVI_STAGE(1, PRE, POST) BORNVI_STAGE(2, PRE, POST) BORNVI_STAGE(3, PRE, POST) BORNVI_STAGE(4, PRE, POST)
-#if BORNVI_TIMING_NO_GATES   /* experiment (wrong results): the stages' LDS round trips and signs without the gate arithmetic */
-  kind &= ~7u;
-#endif
   switch (kind) {
     BORNVI_STAGE_NG(0, 0)
     BORNVI_STAGE_NG(1, 0)
@@ -754,27 +681,6 @@ __device__ __forceinline__ void stage_dispatch(uint32_t kind, double2* __restric
 #undef BORNVI_STAGE_NG
 #undef BORNVI_STAGE
 }
-
-// In-kernel phase stamps (diagnostic build only, -DBORNVI_STAMPS=1, tools/probes/stamp_probe.py): wave 0 of every
-// workgroup adds up, per phase of a tile trip, the shader cycles (s_memtime) it spent there; totals go to a buffer that
-// nothing else reads.  In the production build every BORNVI_STAMP expands to nothing.
-#ifndef BORNVI_STAMPS
-#define BORNVI_STAMPS 0
-#endif
-#ifndef BORNVI_SPLIT_PREFETCH
-#define BORNVI_SPLIT_PREFETCH 1      // 0: never use the SPLIT instantiation (A/B against the round-1 form)
-#endif
-#if BORNVI_STAMPS
-__device__ unsigned long long g_stamp_totals[16];
-#define BORNVI_STAMP(PH_)                                                        \
-  do {                                                                           \
-    const unsigned long long now_ = __builtin_readcyclecounter();                \
-    stamp_acc[PH_] += now_ - stamp_last;                                         \
-    stamp_last = now_;                                                           \
-  } while (0)
-#else
-#define BORNVI_STAMP(PH_) do { } while (0)
-#endif
 
 template <bool DEBUG, bool SPLIT>
 __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
@@ -904,10 +810,6 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
   // the loads of the next one and works on its own.  With a second load site (a prologue) the compiler has to merge
   // two definitions of the in-flight registers at the loop header and may do it with register copies placed right
   // behind a load -- copies of registers whose data has not arrived (tools/check_async_regs.py looks for that).
-#if BORNVI_STAMPS
-  unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long stamp_last = __builtin_readcyclecounter();
-#endif
   uint32_t g_tab = 0xffffffffu;   // tile row whose stage tables are in LDS
   uint32_t parity = 1;            // matrix buffer of the current tile (trip -1 stages tile 0's matrices into buffer 0)
   const uint32_t* __restrict__ FS0 = F + FH_WORDS;
@@ -926,12 +828,12 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
   // start on the states the previous pass wrote last, i.e. on what the memory-side cache still holds)
   const long long walk_flip = total_tiles - 1;
   const bool walk_rev = (direct_mask & 4) != 0;
-  const bool zskip = BORNVI_SKIP_ZERO_TILES && !DEBUG && init && gbits > 0 && total_tiles < (1ll << 31);
+  const bool zskip = !DEBUG && init && gbits > 0 && total_tiles < (1ll << 31);
   // direct_mask bit 3: the launcher vouches that pass 0 and pass 1 of this batch both run with the direct first stage
   // on, so the masks of FH_ZINFO (plan.cpp: support of |0..0>) hold: an INIT pass leaves out the tiles nobody will
   // read (zgmask), the pass behind it does not load the slots known to be zero (zslots; v[] is zero from the start of
   // the kernel and those registers are never loaded, so the first stage finds zeros there)
-  const uint32_t zinfo = (BORNVI_SKIP_ZERO_TILES && !DEBUG && (direct_mask & 8)) ? F[FH_ZINFO] : 0u;
+  const uint32_t zinfo = (!DEBUG && (direct_mask & 8)) ? F[FH_ZINFO] : 0u;
   const uint32_t zgmask = zskip ? zinfo : 0u;
   const uint32_t zslots = (!init && direct_in) ? (zinfo & 0xffffu) : 0u;
   const uint32_t zs_nb = (uint32_t)(total_tiles >> gbits), zs_gm1 = (1u << gbits) - 1u;   // circuits; zero tiles per circuit
@@ -970,13 +872,11 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
       pdst = row < 0 ? share.trash : probs + ((long long)row << n);
     }
     void* hbm_base = fin ? (void*)pdst : (void*)dst;
-    BORNVI_STAMP(real ? 6 : 7);     // loop overhead / the pipeline-start trip
     if (real) {
       // ---- the tile has arrived in registers: all but this wave's 16 tile-out stores are done (after trip -1
       // nothing is outstanding) ----
       if (DEBUG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      BORNVI_STAMP(0);              // waiting for the prefetched tile
 #pragma unroll
       for (int i = 0; i < MAX_TILE_ITERS; ++i) asm volatile("" : "+v"(v[i]));
       // ---- registers -> LDS: the tile (head CNOTs of the pass folded into the slot), unless the first stage
@@ -995,14 +895,13 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
       if (direct_in) BORNVI_RUN_STAGE(0, 1);    // (the matrices were staged a trip ago)
       asm volatile("" ::: "memory");
     }
-    BORNVI_STAMP(1);                // tile -> LDS (or the direct first stage)
     if (SPLIT) {
     // ---- the registers are free: the next tile starts its trip from HBM.  Large tiles (one workgroup of >= 4 waves per
     // CU, all in step between barriers): the 16 loads are issued in two halves BETWEEN the stages, and the two halves of
     // the workgroup's waves (SIMD partners: wave w and w + nwaves/2 share a SIMD) issue theirs in alternate stages.  A
     // wave-level 1-KiB load takes ~100 cycles of the CU's memory pipe, so 16 of them issued back to back by all waves at
-    // once blocked every wave for 11 % of a trip at n = 20 with the VALU idle (in-kernel stamps,
-    // tools/probes/stamp_probe.py); now one partner computes while the other issues: -4 % at n = 20, L = 8, rows
+    // once blocked every wave for 11 % of a trip at n = 20 with the VALU idle (in-kernel phase stamps, DESIGN.md
+    // section 4.1); now one partner computes while the other issues: -4 % at n = 20, L = 8, rows
     // bit-identical.  2^11 tiles (four independent workgroups per CU already interleave their phases; measured
     // neutral to +2 %) issue all 16 before the first stage as before.  Either way there is ONE load site per in-flight
     // register (inside the loop below, which always runs at least once) and all loads precede the trip's 16 stores:
@@ -1021,15 +920,11 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
       if (tt_ < npieces && !next_zero) async_load16(mp, tw_mat[tt_], gates + bn_h * gate_stride);
     }
     const bool want_v = has_next && !init && !(dbg & 4);
-    BORNVI_STAMP(2);                // head of the prefetch (matrix piece)
     {
       const int s0 = (real && direct_in) ? 1 : 0;
       const int ns = (real && !zero_tile) ? nstages : 0;
       const int niter = (ns - s0 > 0) ? ns - s0 : 1;
-#ifndef BORNVI_SPLIT_STAGGER
-#define BORNVI_SPLIT_STAGGER 1
-#endif
-      const int wc = (BORNVI_SPLIT_STAGGER && 2u * (t >> 6) >= (T >> 6)) ? 1 : 0;     // second half of the workgroup's waves
+      const int wc = (2u * (t >> 6) >= (T >> 6)) ? 1 : 0;     // second half of the workgroup's waves
       for (int j = 0; j < niter; ++j) {
         const int s = s0 + j;
         const bool last = j == niter - 1;
@@ -1054,11 +949,7 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
             BORNVI_RUN_STAGE(s, 2);
           } else {
             BORNVI_RUN_STAGE(s, 0);
-#if BORNVI_TIMING_NO_STAGE_BARRIER   /* experiment (wrong results): what the workgroup-wide barrier between stages costs */
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
             __syncthreads();
-#endif
           }
         }
       }
@@ -1066,7 +957,6 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
     } else {
     // ---- the registers are free: the next tile starts its trip from HBM now (the only load site) ----
     if (has_next) BORNVI_PREFETCH(Tnext);
-    BORNVI_STAMP(2);                // issuing the prefetch
     if (real) {
       __syncthreads();                          // the tile (or the first stage's result) is in LDS
       for (int s = direct_in ? 1 : 0; s < (zero_tile ? 0 : nstages); ++s) {
@@ -1080,7 +970,6 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
     }
     }
     if (real) {
-      BORNVI_STAMP(3);              // the stages (LDS round trips, gates, barriers)
       // ---- tile out: LDS -> HBM in the next pass's bit order, or |psi|^2 in canonical order: exactly 16
       // vector-memory stores per wave (the vmcnt waits count them), here or in the last stage ----
       if (noop_tile) {
@@ -1109,7 +998,6 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
         }
       }
     }
-    BORNVI_STAMP(4);                // tile out (LDS reads + store issue)
     if (!has_next) break;
     // ---- stage tables of the NEXT tile's row -> LDS.  The launcher makes the grid a multiple of the tiles per
     // state whenever it can, so a workgroup keeps its row and this runs once, in trip -1, beside the first prefetch
@@ -1137,14 +1025,7 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
     asm volatile("" : "+v"(mp));
     if (t < npieces) mats_next[t] = make_double2(mp.x, mp.y);
     __syncthreads();   // the tile is overwritten by the next trip; its matrices are in place
-    BORNVI_STAMP(5);                // end of trip: wait for the matrices in flight, stage them, barrier
   }
-#if BORNVI_STAMPS
-  if (threadIdx.x == 0) {
-    for (int ph = 0; ph < 8; ++ph) atomicAdd(&g_stamp_totals[ph], stamp_acc[ph]);
-    atomicAdd(&g_stamp_totals[8], 1ull);
-  }
-#endif
 #undef BORNVI_RUN_STAGE
 #undef BORNVI_PREFETCH
 }
@@ -1414,7 +1295,7 @@ hipError_t prepare_circuit_kernel(size_t lds_bytes) {
 
 int circuit_fast_workgroups_per_cu(int threads, size_t lds) {
   int nb = 0;
-  const hipError_t e = (BORNVI_SPLIT_PREFETCH && threads >= 256)
+  const hipError_t e = threads >= 256
                            ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_fast_kernel<false, true>, threads, lds)
                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_fast_kernel<false, false>, threads, lds);
   if (e != hipSuccess) return 0;
@@ -1440,23 +1321,10 @@ hipError_t launch_circuit_pass_fast(const uint32_t* plan, uint32_t pass_off, con
                                                              (uint32_t)(lds_tab_off / 16), (uint32_t)(lds_mats2_off / 16), direct_mask, DBG_, share)
   // large tiles (one workgroup of >= 4 waves per CU): the instantiation that spreads the prefetch over the stages
   if (dbg) BORNVI_LAUNCH_FAST(true, false, dbg);
-  else if (BORNVI_SPLIT_PREFETCH && block.x >= 256) BORNVI_LAUNCH_FAST(false, true, 0);
+  else if (block.x >= 256) BORNVI_LAUNCH_FAST(false, true, 0);
   else BORNVI_LAUNCH_FAST(false, false, 0);
 #undef BORNVI_LAUNCH_FAST
   return hipGetLastError();
-}
-
-// diagnostic builds: read (and clear) the phase-stamp totals; zeros in the production build
-hipError_t read_circuit_stamps(unsigned long long* out16) {
-  for (int i = 0; i < 16; ++i) out16[i] = 0;
-#if BORNVI_STAMPS
-  hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stamp_totals), 16 * sizeof(unsigned long long));
-  if (e != hipSuccess) return e;
-  unsigned long long zero[16] = {0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_totals), zero, sizeof(zero));
-#else
-  return hipSuccess;
-#endif
 }
 
 hipError_t launch_circuit_pass(const uint32_t* plan, uint32_t pass_off, int n, int k, int threads, size_t lds, int batch,

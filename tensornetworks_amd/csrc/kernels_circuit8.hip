@@ -18,29 +18,6 @@
 
 namespace bornvi {
 
-// timing-only ablations (wrong results by construction; tools/probes/build_r3_variants.sh): what the parts of a stage cost
-#ifndef BORNVI_R3_NO_MATLOAD
-#define BORNVI_R3_NO_MATLOAD 0     // 1: the gates' matrices are not read from LDS
-#endif
-#ifndef BORNVI_R3_NO_STAGES
-#define BORNVI_R3_NO_STAGES 0      // 1: tile in, tile out, nothing in between (the HBM side of a pass alone)
-#endif
-#ifndef BORNVI_R3_STAGGER
-#define BORNVI_R3_STAGGER 0        // experiment: workgroups start 0 .. 3 quarters of this many 64-cycle ticks late (phase spread over the CUs)
-#endif
-#ifndef BORNVI_R3_MAT_UPFRONT
-#define BORNVI_R3_MAT_UPFRONT 1    // 1: the stage's matrices are requested together, ahead of the amplitude reads; 0: each one in front of its gate (A/B)
-#endif
-#ifndef BORNVI_R3_NO_LDS_READ
-#define BORNVI_R3_NO_LDS_READ 0    // 1: a stage does not read its amplitudes from LDS (what the read half of the round trip costs)
-#endif
-#ifndef BORNVI_R3_NO_LDS_WRITE
-#define BORNVI_R3_NO_LDS_WRITE 0   // 1: a stage does not write its results back to LDS
-#endif
-#ifndef BORNVI_R3_NO_GATES
-#define BORNVI_R3_NO_GATES 0       // 1: the stages' LDS round trips and signs without the gate arithmetic
-#endif
-
 namespace {
 
 // One gate on an amplitude pair, matrix as the pivot-normalised RECORD build_gates_kernel writes (kernels_circuit.hip):
@@ -69,14 +46,8 @@ __device__ __forceinline__ bool rec_swap(const double (&R)[8]) { return __double
 
 // the 2x2 complex matrix at a wave-uniform address: one 64-byte scalar load
 __device__ __forceinline__ void load_u8(const double* __restrict__ Um, double (&U)[8]) {
-#if BORNVI_R3_NO_MATLOAD
-  (void)Um;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) asm volatile("" : "=s"(U[e]));
-#else
 #pragma unroll
   for (int e = 0; e < 8; ++e) U[e] = Um[e];
-#endif
 }
 
 __device__ __forceinline__ uint32_t comb3(int j, const uint32_t (&B)[3]) {
@@ -123,11 +94,7 @@ __device__ __forceinline__ void put_slot(double xr, double xi, int jj, char* __r
     if (FIN) async_store8(ha, (xr * xr + xi * xi) * scale, hbm_base);
     else async_store16(ha, (d2_t){xr, xi}, hbm_base);
   } else {
-#if BORNVI_R3_NO_LDS_WRITE
-    asm volatile("" : : "v"(xr), "v"(xi), "v"(wa0 ^ comb3(jj, WB)));
-#else
     *reinterpret_cast<double2*>(lds + (wa0 ^ comb3(jj, WB))) = make_double2(xr, xi);
-#endif
   }
 }
 
@@ -168,10 +135,8 @@ __device__ __forceinline__ void stage8(char* __restrict__ lds, const char* __res
   // lgkmcnt(0) in front of the first gate covers both)
   // (two register sets: the third matrix is requested into the first set behind gate 0 and arrives under gate 1's FMAs)
   double Ua[8], Ub[8];
-#if BORNVI_R3_MAT_UPFRONT
   if (NG > 0) load_u8(reinterpret_cast<const double*>(gb + MAT[0]), Ua);
   if (NG > 1) load_u8(reinterpret_cast<const double*>(gb + MAT[1]), Ub);
-#endif
   if (IO == 1) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) { ar[j] = v[j].x; ai[j] = v[j].y; }
@@ -179,12 +144,8 @@ __device__ __forceinline__ void stage8(char* __restrict__ lds, const char* __res
     const uint32_t ra0 = (my_rw & 0xffffu) << 4;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-#if BORNVI_R3_NO_LDS_READ
-      asm volatile("" : "=v"(ar[j]), "=v"(ai[j]) : "v"(ra0 ^ comb3(j, RB)));
-#else
       const double2 x = *reinterpret_cast<const double2*>(lds + (ra0 ^ comb3(j, RB)));
       ar[j] = x.x; ai[j] = x.y;
-#endif
     }
     if (cross) {      // the read map took amplitudes from other threads' groups (plan.hpp: STAGE_CROSS_READ)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -193,18 +154,12 @@ __device__ __forceinline__ void stage8(char* __restrict__ lds, const char* __res
   }
   if (PRE) sign8(my_sg & 0xffu, ar, ai);
   uint32_t wa0 = (IO == 2) ? hbm_off : (my_rw >> 16) << 4;
-#if !BORNVI_R3_MAT_UPFRONT
-  if (NG > 0) load_u8(reinterpret_cast<const double*>(gb + MAT[0]), Ua);
-#endif
   // sig: bit i set = the results of register bit i's gate change places (the record's pivot sits in the other row): slot j
   // of the registers then holds the amplitude of slot j ^ sig -- folded into the write address and the post sign bits
   uint32_t sig = 0;
   if (NG > 1) {
     gate8<0>(ar, ai, Ua);
     sig |= rec_swap(Ua) ? 1u : 0u;
-#if !BORNVI_R3_MAT_UPFRONT
-    load_u8(reinterpret_cast<const double*>(gb + MAT[1]), Ub);
-#endif
     if (NG > 2) load_u8(reinterpret_cast<const double*>(gb + MAT[2]), Ua);
   }
   if (NG > 2) { gate8<1>(ar, ai, Ub); sig |= rec_swap(Ub) ? 2u : 0u; }
@@ -250,9 +205,6 @@ __device__ __forceinline__ void dispatch8(uint32_t kind, char* __restrict__ lds,
 #define BORNVI_ST8(NG, PRE, POST) \
   case (NG) | ((PRE) << 3) | ((POST) << 4): stage8<NG, PRE, POST, IO, FIN, DOT>(lds, gb, MAT, my_rw, my_sg, RB, WB, v, hbm_off, hb, hbm_base, cross, scale, W, acc); break;
 #define BORNVI_ST8_NG(PRE, POST) BORNVI_ST8(0, PRE, POST) BORNVI_ST8(1, PRE, POST) BORNVI_ST8(2, PRE, POST) BORNVI_ST8(3, PRE, POST)
-#if BORNVI_R3_NO_GATES
-  kind &= ~7u;
-#endif
   switch (kind) {
     BORNVI_ST8_NG(0, 0)
     BORNVI_ST8_NG(1, 0)
@@ -288,7 +240,7 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
   const int kt = k - 3;
   const uint32_t ksize = 1u << k;
   const int gbits = n - k;
-  const int nstages = BORNVI_R3_NO_STAGES ? 0 : (int)H[CH_NSTAGES];
+  const int nstages = (int)H[CH_NSTAGES];
   const uint32_t nrows = H[CH_NROWS], nsign = H[CH_NSIGN], NW = H[CH_NWAVES];
   const uint32_t sign_any = H[CH_SIGN_PRE] | H[CH_SIGN_POST];
   const bool init = flags & PASS_INIT, fin = flags & PASS_FINAL;
@@ -317,9 +269,6 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
   for (uint32_t i = t; i < nrows * 64u; i += T) lane_tab[i] = C[H[CH_LANE_OFF] + i];
   __syncthreads();
 
-#if BORNVI_R3_STAGGER
-  for (uint32_t q = 0; q < ((blockIdx.x >> 3) & 3u) * (BORNVI_R3_STAGGER / 4); ++q) __builtin_amdgcn_s_sleep(1);
-#endif
   double W[8];              // DOT: dL/dq at the thread's 8 outcomes of tile row g_w
   double acc = 0.0;
 #pragma unroll

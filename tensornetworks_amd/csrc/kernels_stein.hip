@@ -242,7 +242,6 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const double* __restrict
       const double* ri0 = Lt + (it * 16 + ar) * g.rowpitch;
       const double* ri1 = ri0 + 16 * g.rowpitch;
       d4_t a1 = {0.0, 0.0, 0.0, 0.0}, a2 = a1, a3 = a1, c1 = a1, c2 = a1, c3 = a1;
-#ifndef BORNVI_GRAM_NO_MFMA     // (timing-only ablations: tools/probes/build_gram_variants.sh)
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
         a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri0[4 * kk + ak], b1[kk], a1, 0, 0, 0);
@@ -252,9 +251,6 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const double* __restrict
         a3 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri0[2 * g.p + 4 * kk + ak], b3[kk], a3, 0, 0, 0);
         c3 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri1[2 * g.p + 4 * kk + ak], b3[kk], c3, 0, 0, 0);
       }
-#else
-      a1[0] = a1[1] = a1[2] = a1[3] = ri0[ak] + b1[0]; c1 = a2 = c2 = a3 = c3 = a1;
-#endif
       // D layout: row = (lane >> 4) + 4 r, col = lane & 15
       const long long ib = i_blk + it * 16 + ak;
       const double* al0 = Lt + (it * 16 + ak) * g.rowpitch + 3 * g.p;   // alpha of row ak + 4 r: + 4 r rowpitch
@@ -268,19 +264,11 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const double* __restrict
           e0[r] = al0[4 * r * g.rowpitch] + alpha_j;
           e1[r] = al0[(16 + 4 * r) * g.rowpitch] + alpha_j;
         }
-#ifdef BORNVI_GRAM_NO_STORE
-        double keep = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          keep += w0[r] * ((a1[r] + (a2[r] + a3[r])) + e0[r]) + w1[r] * ((c1[r] + (c2[r] + c3[r])) + e1[r]);
-        if (keep == 1.2345e-300) Kp[0] = keep;
-#else
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           __builtin_nontemporal_store(w0[r] * ((a1[r] + (a2[r] + a3[r])) + e0[r]), Kp + (long long)(4 * r) * ld);
           __builtin_nontemporal_store(w1[r] * ((c1[r] + (c2[r] + c3[r])) + e1[r]), Kp + (long long)(16 + 4 * r) * ld);
         }
-#endif
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -441,12 +429,8 @@ __device__ __forceinline__ void gram_tables_columns(const double* __restrict__ S
       const double Bj_rt = gram_v3_ph<n, NH - NV, NH>(G, I0 + rt, ph_hi) + alpha_j;
       const double* ri = Lt + (rt * 16 + ar) * PITCH + ak * KK;
       d4_t a1 = {0.0, 0.0, 0.0, 0.0};
-#ifndef BORNVI_GRAM_NO_MFMA
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri[kk], b1[kk], a1, 0, 0, 0);
-#else
-      a1[0] = a1[1] = a1[2] = a1[3] = ri[0] + b1[0];
-#endif
       const double* aj = AJ + rt * 16 + ak * 4;
       const double* plr = Lt + (rt * 16 + ak) * PITCH + L::OFF_PL + ar;      // PL(row ak + 4 r of the tile, c = ar)
       const double* wt = apow_s + __popcll((unsigned long long)((I0 + rt) ^ J));
@@ -455,16 +439,8 @@ __device__ __forceinline__ void gram_tables_columns(const double* __restrict__ S
       for (int r = 0; r < 4; ++r) {
         const double val = wt[wslot[r]] * ((a1[r] + (plr[4 * r * PITCH] + PLc[r])) + (aj[r] + Bj_rt));
         const long long i = i_blk + rt * 16 + ak + 4 * r;
-#ifdef BORNVI_GRAM_NO_STORE      // (timing-only ablation: tools/probes/build_gram_variants.sh)
-        if (val == 1.2345e-300)
-#else
         if (!GUARD || (i >= row_begin && i < row_end))
-#endif
-#ifdef BORNVI_GRAM_PLAIN_STORE
-          *reinterpret_cast<double*>(reinterpret_cast<char*>(rowp + (long long)(4 * r) * ld) + voff) = val;
-#else
           __builtin_nontemporal_store(val, reinterpret_cast<double*>(reinterpret_cast<char*>(rowp + (long long)(4 * r) * ld) + voff));
-#endif
       }
     }
     __builtin_amdgcn_wave_barrier();     // the scratch is rewritten by the next column tile
@@ -764,20 +740,9 @@ hipError_t launch_quadform(int n, const double* K, long long row_begin, long lon
 // bulk_start(S) = min(N, 512 (S / 2 + 1)) on -- right of the diagonal blocks of all its waves and a multiple of the
 // 512-column trip; the NEAR part of wave w are the columns [128-aligned start of its diagonal block, bulk_start).
 // ------------------------------------------------------------------------------------------------
-#ifndef BORNVI_SYM_ABLATE      // timing-only builds (tools/probes): 2 = no column part at all (results invalid)
-#define BORNVI_SYM_ABLATE 0
-#endif
-#ifndef BORNVI_SYM_STORE_NT
-#define BORNVI_SYM_STORE_NT 0      // 1: the column-partial stores non-temporal (A/B)
-#endif
-#ifndef BORNVI_SYM_DEFER_STORE
-#define BORNVI_SYM_DEFER_STORE 1   // 0: store a trip's column partial at once (A/B)
-#endif
-#ifndef BORNVI_SYM_WAVES
-#define BORNVI_SYM_WAVES 8     // measured on six 32 GiB allocations held at once: 2.66-2.82 ms (8 waves) vs 2.66-2.94 ms (4)
-#endif
 constexpr int SYM_ROWS = 32;                        // rows per wave (its row accumulators)
-constexpr int SYM_WAVES = BORNVI_SYM_WAVES;         // 4 or 8 waves per band
+// 4 or 8 waves per band; measured on six 32 GiB allocations held at once: 2.66-2.82 ms (8 waves) vs 2.66-2.94 ms (4)
+constexpr int SYM_WAVES = 8;
 constexpr int SYM_BAND = SYM_ROWS * SYM_WAVES;      // rows per workgroup: the unit of the strip-pair shard
 constexpr int SYM_BP = 512 / SYM_BAND;              // bands per 512-column trip width
 constexpr int SYM_NEAR = 512;                       // per-wave capacity of near-diagonal column partials (< 480 used)
@@ -837,22 +802,14 @@ __device__ __forceinline__ void sym_trip(__amdgpu_buffer_rsrc_t rsrc, long long 
     for (int u = 0; u < RB; ++u)
 #pragma unroll
       for (int c = 0; c < CH; ++c) kv[u][c] = sym_load16(rsrc, vlane, soff[c] + (unsigned)(r0 + u) * ld8);
-    if (PEND && r0 == 0) {
-#if BORNVI_SYM_STORE_NT
-      __builtin_nontemporal_store(pend, pend_ptr);
-#else
-      *pend_ptr = pend;
-#endif
-    }
+    if (PEND && r0 == 0) *pend_ptr = pend;
 #pragma unroll
     for (int u = 0; u < RB; ++u)
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         acc[r0 + u] = fma(kv[u][c].x, q4[c].x, fma(kv[u][c].y, q4[c].y, acc[r0 + u]));
-        if (BORNVI_SYM_ABLATE < 2) {
-          z[c][0] = fma(kv[u][c].x, qi[r0 + u], z[c][0]);
-          z[c][1] = fma(kv[u][c].y, qi[r0 + u], z[c][1]);
-        }
+        z[c][0] = fma(kv[u][c].x, qi[r0 + u], z[c][0]);
+        z[c][1] = fma(kv[u][c].y, qi[r0 + u], z[c][1]);
       }
   }
 }
@@ -882,7 +839,7 @@ __device__ __forceinline__ void quadform_sym_band(const double* __restrict__ Kb 
       q4[0] = (col >= i0) ? *reinterpret_cast<const double2*>(q + col) : make_double2(0.0, 0.0);   // (i0 is even)
       double z[1][2];
       sym_trip<1, 8>(rsrc, ld, vlane, cb, q4, acc, qi, z);
-      if (BORNVI_SYM_ABLATE < 2 && col >= i0 + SYM_ROWS) *reinterpret_cast<double2*>(Z1s + col) = make_double2(z[0][0], z[0][1]);
+      if (col >= i0 + SYM_ROWS) *reinterpret_cast<double2*>(Z1s + col) = make_double2(z[0][0], z[0][1]);
     }
   }
   // BULK: trips of 512 columns; the four waves' column partials are added through LDS (fixed order) and stored once
@@ -891,7 +848,7 @@ __device__ __forceinline__ void quadform_sym_band(const double* __restrict__ Kb 
   const long long t0 = (part * tp < ntrips) ? part * tp : ntrips;
   const long long t1 = (t0 + tp < ntrips) ? t0 + tp : ntrips;
   double* __restrict__ Z2s = Z2 + sym_z2_offset(S, N) - bulk0;            // Z2s[j]
-  constexpr bool DEFER = SYM_WAVES == 8 && BORNVI_SYM_ABLATE < 2 && BORNVI_SYM_DEFER_STORE;
+  constexpr bool DEFER = SYM_WAVES == 8;
   // (deferred store, see sym_trip: the first trip "stores" 0.0 to the address its own result goes to one trip later)
   double pend = 0.0;
   double* pend_ptr = Z2s + (bulk0 + t0 * 512) + (wave * 64 + lane);
@@ -903,32 +860,24 @@ __device__ __forceinline__ void quadform_sym_band(const double* __restrict__ Kb 
     for (int c = 0; c < 4; ++c) q4[c] = *reinterpret_cast<const double2*>(q + cb + c * 128 + lane * 2);
     double z[4][2];
     sym_trip<4, 8, DEFER>(rsrc, ld, vlane, cb, q4, acc, qi, z, pend, pend_ptr);
-    if (BORNVI_SYM_ABLATE < 2) {
-      const int buf = (int)((t - t0) & 1);
+    const int buf = (int)((t - t0) & 1);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) zbuf[buf][wave][c * 64 + lane] = (sym_d2){z[c][0], z[c][1]};
-      __syncthreads();
-      const int tid = wave * 64 + lane;                 // columns cb + 2 tid, cb + 2 tid + 1
-      if (SYM_WAVES == 4) {
-        const sym_d2 sum = (zbuf[buf][0][tid] + zbuf[buf][1][tid]) + (zbuf[buf][2][tid] + zbuf[buf][3][tid]);
-        *reinterpret_cast<double2*>(Z2s + cb + 2 * tid) = make_double2(sum.x, sum.y);
-      } else {                                          // 512 threads, one column each
-        const double* zb = reinterpret_cast<const double*>(&zbuf[buf][0][0]);
-        double sum = 0.0;
+    for (int c = 0; c < 4; ++c) zbuf[buf][wave][c * 64 + lane] = (sym_d2){z[c][0], z[c][1]};
+    __syncthreads();
+    const int tid = wave * 64 + lane;                 // columns cb + 2 tid, cb + 2 tid + 1
+    if (SYM_WAVES == 4) {
+      const sym_d2 sum = (zbuf[buf][0][tid] + zbuf[buf][1][tid]) + (zbuf[buf][2][tid] + zbuf[buf][3][tid]);
+      *reinterpret_cast<double2*>(Z2s + cb + 2 * tid) = make_double2(sum.x, sum.y);
+    } else {                                          // 512 threads, one column each
+      const double* zb = reinterpret_cast<const double*>(&zbuf[buf][0][0]);
+      double sum = 0.0;
 #pragma unroll
-        for (int w2 = 0; w2 < SYM_WAVES; w2 += 2) sum += zb[w2 * 512 + tid] + zb[(w2 + 1) * 512 + tid];
-        if (DEFER) { pend = sum; pend_ptr = Z2s + cb + tid; }
-        else Z2s[cb + tid] = sum;
-      }
+      for (int w2 = 0; w2 < SYM_WAVES; w2 += 2) sum += zb[w2 * 512 + tid] + zb[(w2 + 1) * 512 + tid];
+      if (DEFER) { pend = sum; pend_ptr = Z2s + cb + tid; }
+      else Z2s[cb + tid] = sum;
     }
   }
-  if (DEFER && t1 > t0) {
-#if BORNVI_SYM_STORE_NT
-    __builtin_nontemporal_store(pend, pend_ptr);
-#else
-    *pend_ptr = pend;
-#endif
-  }
+  if (DEFER && t1 > t0) *pend_ptr = pend;
   __syncthreads();      // the LDS buffers are reused by the next band of this workgroup
 #pragma unroll
   for (int r = 0; r < SYM_ROWS; ++r) {

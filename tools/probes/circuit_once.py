@@ -1,5 +1,5 @@
 """One parameter-shift batch (n = N_QUBITS, default 16; L = LAYERS, default 6) run three times: the target of PMC passes
-over the circuit engine (tools/gpu_session.sh pmc_circ)."""
+over the circuit engine (rocprofv3 --pmc ... -- python tools/probes/circuit_once.py)."""
 import os
 import sys
 import torch
