@@ -306,6 +306,28 @@ int bornvi_shots_histogram(bornvi_handle h, int n, int B, const double* probs, d
                            unsigned long long seed, const long long* epoch_dev, int include_base, int p_begin,
                            int p_stride, void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
+/* ---- classical Born machine, probability-table family (replaces get_probabilities / entropy of
+ * born_machine_classical_sim.py:74-99, :177-181 and the autograd chain of ksd_vi.py:112-145 down to the table or the
+ * logits of the conditional network).  w dev [rows, 2^n] float32 raw parameters; mode 0 (use_logits):
+ * q = softmax(w - max w), mode 1: q = |w| / sum |w|.  q32 dev [rows, 2^n] float32 = what get_probabilities returns,
+ * q64 dev [rows, 2^n] float64 = its exact upcast (the KSD is computed on q32.to(float64)); entropy dev [rows] float32 or
+ * NULL = -sum q log max(q, 1e-10) over q32.  0 <= n <= 30, 1 <= rows <= 65535.  Row reductions are fixed-order partials
+ * in the workspace (no atomics: bitwise reproducible); no allocation or synchronisation (capturable).  Workspace:
+ * bornvi_born_table_workspace_bytes(h, n, rows), valid for both calls. */
+size_t bornvi_born_table_workspace_bytes(bornvi_handle h, int n, int rows);
+int bornvi_born_table_probs(bornvi_handle h, int n, int rows, int mode, const float* w, float* q32, double* q64,
+                            float* entropy, void* workspace, size_t workspace_bytes, bornvi_stream stream);
+/* grad dev [rows, 2^n] float32 (may be a parameter's .grad) = d/dw of  sqrt(max(ksd2, 1e-12)) - entropy_weight * H  per
+ * row, as torch autograd computes it through the reference's graph: dL/dq = float32(y / loss) (0 while the clamp is
+ * active) + entropy_weight (log max(q, 1e-10) + [q >= 1e-10]); softmax VJP q (g - sum q g); mode 1
+ * sign(w) (g - sum q g) / sum |w| (sign(0) = 0).  q64 as returned by bornvi_born_table_probs; y dev [rows, 2^n]
+ * = K_p q (bornvi_stein_quadform_sym / _matvec_kron) or NULL (no KSD term); ksd2 dev [rows] = q^T K_p q, or NULL with y
+ * given: y is then dL/dq itself; entropy_weight = 0: no entropy term.  loss_out dev [rows] or NULL
+ * = sqrt(max(ksd2, 1e-12)) (needs ksd2). */
+int bornvi_born_table_vjp(bornvi_handle h, int n, int rows, int mode, const float* w, const double* q64,
+                          const double* y, const double* ksd2, double entropy_weight, float* grad,
+                          double* loss_out, void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
 /* Gradient hand-off to the optimiser (replaces the float cast of the parameter-shift VJP and
  * torch.nn.utils.clip_grad_norm_(params, gradient_clip_norm), ksd_vi_quantum.py:153): grad32 dev [P] float32 =
  * float32(grad64) * min(1, max_norm / (||float32(grad64)||_2 + 1e-6)); total_norm dev [1] float32 = that norm. */

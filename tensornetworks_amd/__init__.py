@@ -5,7 +5,8 @@ stein_utils) on a hand-written HIP backend (libbornvi_hip.so, C ABI in include/b
 """
 from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
-__all__ = ["QuantumBornMachine", "KSDVariationalInference", "generate_all_binary_outcomes", "calculate_tvd"]
+__all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "ClassicalKSDVariationalInference",
+           "generate_all_binary_outcomes", "calculate_tvd"]
 
 
 def __getattr__(name):
@@ -14,5 +15,11 @@ def __getattr__(name):
         return QuantumBornMachine
     if name == "KSDVariationalInference":
         from .ksd_vi_quantum import KSDVariationalInference
+        return KSDVariationalInference
+    if name == "ClassicalBornMachine":
+        from .born_machine_classical_sim import ClassicalBornMachine
+        return ClassicalBornMachine
+    if name == "ClassicalKSDVariationalInference":      # (the reference's ksd_vi.KSDVariationalInference)
+        from .ksd_vi import KSDVariationalInference
         return KSDVariationalInference
     raise AttributeError(name)

@@ -389,6 +389,78 @@ def born_probs(state, n):
     return probs
 
 
+# ---- classical Born machine (probability table) ------------------------------------------------------------
+BORN_TABLE_MAX_ROWS = 65535
+
+
+def _born_table_args(w, mode):
+    """(rows, n) of a raw-parameter table w [rows, 2^n]; every argument error is raised here, before any GPU call."""
+    if isinstance(mode, bool) or mode not in (0, 1):
+        raise BornviError(f"born-table mode must be 0 (softmax) or 1 (|w| / sum |w|), got {mode!r}")
+    if not torch.is_tensor(w) or w.dim() != 2:
+        raise BornviError(f"w: expected a [rows, 2^n] tensor, got {tuple(w.shape) if torch.is_tensor(w) else type(w)}")
+    rows, N = int(w.shape[0]), int(w.shape[1])
+    if N < 1 or N & (N - 1):
+        raise BornviError(f"w: row length {N} is not a power of two")
+    if not 1 <= rows <= BORN_TABLE_MAX_ROWS:
+        raise BornviError(f"w: 1 ... {BORN_TABLE_MAX_ROWS} rows per call, got {rows}")
+    n = N.bit_length() - 1
+    _chk_n(n, 0, 30)
+    return rows, n
+
+
+def born_table_probs(w, mode, want_entropy=True):
+    """Classical Born machine forward (bornvi_born_table_probs): raw parameters w float32 [rows, 2^n] on the GPU ->
+    (q32 float32 [rows, 2^n], q64 = its exact float64 upcast, H float32 [rows] or None).  mode 0: softmax(w - max w),
+    1: |w| / sum |w|; H = -sum q log max(q, 1e-10) over q32."""
+    rows, n = _born_table_args(w, mode)
+    dev = w.device
+    h = _ext.handle_for(dev)
+    _chk(w, torch.float32, dev, "w")
+    q32 = torch.empty(w.shape, dtype=torch.float32, device=dev)
+    q64 = torch.empty(w.shape, dtype=torch.float64, device=dev)
+    H = torch.empty(rows, dtype=torch.float32, device=dev) if want_entropy else None
+    ws = _ws(dev, _cached_size(h, "bornvi_born_table_workspace_bytes", n, rows), "born_table")
+    h.call("bornvi_born_table_probs", n, rows, int(mode), _ptr(w), _ptr(q32), _ptr(q64), _ptr(H) if H is not None else None,
+           _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return q32, q64, H
+
+
+def born_table_vjp(w, q64, mode, y=None, ksd2=None, entropy_weight=0.0, out=None, loss_out=None):
+    """Classical Born machine backward (bornvi_born_table_vjp): float32 [rows, 2^n] d/dw of
+    sqrt(max(ksd2, 1e-12)) - entropy_weight * H per row.  y float64 [rows, 2^n] = K_p q (None: no KSD term); ksd2 float64
+    [rows] (None with y given: y is dL/dq itself); entropy_weight 0: no entropy term.  out: destination (e.g. a
+    parameter's .grad); loss_out float64 [rows]: receives sqrt(max(ksd2, 1e-12))."""
+    rows, n = _born_table_args(w, mode)
+    try:
+        lam = float(entropy_weight)
+    except (TypeError, ValueError):
+        raise BornviError(f"entropy_weight must be a number, got {entropy_weight!r}") from None
+    if not np.isfinite(lam):
+        raise BornviError(f"entropy_weight must be finite, got {entropy_weight!r}")
+    if loss_out is not None and ksd2 is None:
+        raise BornviError("loss_out needs ksd2")
+    dev = w.device
+    h = _ext.handle_for(dev)
+    _chk(w, torch.float32, dev, "w")
+    _chk(q64, torch.float64, dev, "q64", w.numel())
+    if y is not None:
+        _chk(y, torch.float64, dev, "y", w.numel())
+    if ksd2 is not None:
+        _chk(ksd2, torch.float64, dev, "ksd2", rows)
+    if loss_out is not None:
+        _chk(loss_out, torch.float64, dev, "loss_out", rows)
+    if out is None:
+        out = torch.empty(w.shape, dtype=torch.float32, device=dev)
+    else:
+        _chk(out, torch.float32, dev, "out", w.numel())
+    ws = _ws(dev, _cached_size(h, "bornvi_born_table_workspace_bytes", n, rows), "born_table")
+    h.call("bornvi_born_table_vjp", n, rows, int(mode), _ptr(w), _ptr(q64), _ptr(y) if y is not None else None,
+           _ptr(ksd2) if ksd2 is not None else None, lam, _ptr(out), _ptr(loss_out) if loss_out is not None else None,
+           _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out
+
+
 # ---- finite shots -------------------------------------------------------------------------------------
 SHOTS_MAX = (1 << 31) - 1
 

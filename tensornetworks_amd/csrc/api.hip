@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1085,6 +1086,41 @@ int bornvi_shots_histogram(bornvi_handle h, int n, int B, const double* probs, d
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_shots_histogram(n, B, probs, freq, (int)shots, seed, epoch_dev, include_base ? 1 : 0, p_begin, p_stride,
                                    workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+static bool valid_born_table(int n, int rows, int mode) {
+  return n >= 0 && n <= 30 && rows >= 1 && rows <= 65535 && (mode == 0 || mode == 1);
+}
+
+size_t bornvi_born_table_workspace_bytes(bornvi_handle h, int n, int rows) {
+  if (!h) return 0;
+  if (!valid_born_table(n, rows, 0)) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  return born_table_workspace_bytes(n, rows);
+}
+
+int bornvi_born_table_probs(bornvi_handle h, int n, int rows, int mode, const float* w, float* q32, double* q64,
+                            float* entropy, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_born_table(n, rows, mode)) return fail(h, BORNVI_ERR_INVALID, "bad argument (0 <= n <= 30, 1 <= rows <= 65535, mode 0 or 1)");
+  if (!w || !q32 || !q64) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < born_table_workspace_bytes(n, rows)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_born_table_probs(n, rows, mode, w, q32, q64, entropy, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_born_table_vjp(bornvi_handle h, int n, int rows, int mode, const float* w, const double* q64, const double* y,
+                          const double* ksd2, double entropy_weight, float* grad, double* loss_out, void* workspace,
+                          size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_born_table(n, rows, mode)) return fail(h, BORNVI_ERR_INVALID, "bad argument (0 <= n <= 30, 1 <= rows <= 65535, mode 0 or 1)");
+  if (!w || !q64 || !grad) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (loss_out && !ksd2) return fail(h, BORNVI_ERR_INVALID, "loss_out needs ksd2");
+  if (!std::isfinite(entropy_weight)) return fail(h, BORNVI_ERR_INVALID, "entropy_weight must be finite");
+  if (!workspace || workspace_bytes < born_table_workspace_bytes(n, rows)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_born_table_vjp(n, rows, mode, w, q64, y, ksd2, entropy_weight, grad, loss_out, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

@@ -63,6 +63,13 @@ hipError_t launch_shots_histogram(int n, long long B, const double* probs, doubl
                                   const long long* epoch_dev, int include_base, int p_begin, int p_stride, void* ws,
                                   hipStream_t st);
 
+// ---- classical Born machine, probability-table family (kernels_born_table.hip) -------------------------
+size_t born_table_workspace_bytes(int n, long long rows);
+hipError_t launch_born_table_probs(int n, long long rows, int mode, const float* w, float* q32, double* q64, float* H,
+                                   void* ws, hipStream_t st);
+hipError_t launch_born_table_vjp(int n, long long rows, int mode, const float* w, const double* q64, const double* y,
+                                 const double* ksd2, double lam, float* grad, double* loss_out, void* ws, hipStream_t st);
+
 // ---- adjoint differentiation (kernels_adjoint.hip): gate-block walks over one / two states ------------
 struct AdjRotBlock {      // consecutive one-qubit gates of one wire, applied e = 0 first (kinds: plan.hpp GateKind)
   int wire, nrot;

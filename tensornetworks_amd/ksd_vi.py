@@ -1,0 +1,269 @@
+"""KSD variational inference with the classical Born machine on MI355X.
+
+Drop-in for the reference trainer ksd_vi.py: same constructor and `train` signatures, attributes, history keys
+(loss_ksd, tvd, grad_norm, entropy), printed messages, early stopping and restore of the best probabilities through
+set_fixed_probs.  What changed is where the arithmetic happens:
+
+  reference epoch (ksd_vi.py:102-157)                       here
+  ---------------------------------------------------       ---------------------------------------------------------
+  q = get_probabilities(); 4^n get_stein_kernel_kp_value    born_table_probs: q32, q64 and the entropy in one launch
+     calls in a Python double loop; entropy() forward       y = K_p q, ksd2 = q.y: the quantum trainer's contraction
+  loss.backward() through 4^n autograd nodes                born_table_vjp -> params.grad (float32)
+  clip_grad_norm_, optimizer.step(), scheduler.step()       the same torch objects
+
+S and K_p are built once per train() call by the quantum trainer's machinery (scores on the GPU; dense Gram up to
+DENSE_GRAM_MAX_N, matrix-free Kronecker mat-vec beyond), reused by composition (`_SteinPath`).  MLP mode
+(conditioning_dim > 0): the network stays stock torch.nn and makes the reference's forwards in its order and number
+(loss, entropy, TVD, best-probabilities snapshot: the same Dropout draws); logits -> q and the VJP back onto the logits
+are the kernels, once per term, and torch.autograd carries the two logit gradients into the network.
+"""
+from functools import partial
+
+import numpy as np
+import torch
+import torch.nn.utils as nn_utils
+import torch.optim as optim
+
+from . import backend
+from . import ksd_vi_quantum as _quantum
+from . import paramshift_shard as shard
+from .born_machine_classical_sim import ClassicalBornMachine
+from .stein_utils import base_hamming_kernel_torch, tvd_table
+from .utils import calculate_tvd, generate_all_binary_outcomes
+
+DENSE_GRAM_MAX_N = _quantum.DENSE_GRAM_MAX_N
+
+
+class _SteinPath:
+    """Scores and K_p of one observation on one GPU, and the contraction (ksd2, y = K_p q): the quantum trainer's
+    _prepare_stein / _place_gram / _stein_contract, used unchanged on this object's attributes."""
+    _prepare_stein = _quantum.KSDVariationalInference._prepare_stein
+    _place_gram = _quantum.KSDVariationalInference._place_gram
+    _stein_contract = _quantum.KSDVariationalInference._stein_contract
+    _use_dense = _quantum.KSDVariationalInference._use_dense
+    _key = _quantum.KSDVariationalInference._key
+    _timed = _quantum.KSDVariationalInference._timed
+
+    def __init__(self, bn, latent_vars_names, length_scale, device):
+        self.bn = bn
+        self.latent_vars_names = latent_vars_names
+        self.num_latent_vars = len(latent_vars_names)
+        self.pytorch_device = device
+        self.base_kernel_length_scale = length_scale
+        self.gram_mode = "auto"
+        self.symmetric_contraction = True
+        self.process_group = shard.SOLO
+        self.gram_placement_tries = 4
+        self.gram_placement = None
+        self.timers = None
+        self._S = self._K = self._K_rows = self._K_pairs = self._stein_key = None
+
+
+class KSDVariationalInference:
+    def __init__(self, bayesian_network, latent_vars_names, observed_vars_names,
+                 born_machine_config, base_kernel_length_scale=1.0, device='cpu'):
+        """Arguments as the reference's (ksd_vi.py:20-41)."""
+        self.bn = bayesian_network
+        self.latent_vars_names = latent_vars_names
+        self.observed_vars_names = observed_vars_names
+        self.num_latent_vars = len(latent_vars_names)
+        self.num_observed_vars = len(observed_vars_names)
+        self.device = device
+
+        # the reference forces this initialisation whatever the config says (ksd_vi.py:30)
+        born_machine_config = {**born_machine_config, 'init_method': 'small_random'}
+        self.born_machine = ClassicalBornMachine(num_latent_vars=self.num_latent_vars,
+                                                 **born_machine_config).to(device)
+
+        self._all_states = None
+        self.num_possible_latent_states = 2 ** self.num_latent_vars
+        self.base_kernel_func = partial(base_hamming_kernel_torch,
+                                        num_vars=self.num_latent_vars,
+                                        length_scale=base_kernel_length_scale)
+        self._score_function_cache = {}
+        self._stein = _SteinPath(bayesian_network, latent_vars_names, base_kernel_length_scale, device)
+
+    @property
+    def all_latent_states_tuples(self):
+        """Reference attribute, built on first use (2^n Python tuples)."""
+        if self._all_states is None:
+            self._all_states = generate_all_binary_outcomes(self.num_latent_vars)
+        return self._all_states
+
+    def _get_precomputed_s_p(self, z_tuple, x_dict):
+        """Score vector of one state (reference :43-53), served from the batched device result."""
+        if z_tuple in self._score_function_cache:
+            return self._score_function_cache[z_tuple]
+        st = self._stein
+        if st._S is None or st._stein_key != st._key(x_dict):
+            st._prepare_stein(x_dict, announce=False)
+        idx = 0
+        for b in z_tuple:
+            idx = (idx << 1) | int(b)
+        s = st._S[idx].to(self.device)
+        self._score_function_cache[z_tuple] = s
+        return s
+
+    def _precompute_all_s_p(self, x_dict):
+        """reference :55-60 -- one kernel launch for the scores, plus K_p (dense) once."""
+        self._score_function_cache.clear()
+        print("Precomputing score functions s_p(x,z)...")
+        self._stein._prepare_stein(x_dict, announce=False)
+        print("Score functions precomputed.")
+
+    def make_optimizer(self, lr_born_machine, num_epochs, use_lr_scheduler=True, optimizer_type="adam",
+                       adam_betas=(0.9, 0.999)):
+        """The optimiser and scheduler the reference builds (ksd_vi.py:84-93)."""
+        if optimizer_type == "adam":
+            optimizer_born = optim.Adam(self.born_machine.parameters(), lr=lr_born_machine, betas=adam_betas)
+        else:
+            optimizer_born = optim.SGD(self.born_machine.parameters(), lr=lr_born_machine, momentum=0.9)
+        scheduler = None
+        if use_lr_scheduler:
+            scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer_born, T_max=num_epochs, eta_min=lr_born_machine / 10)
+        return optimizer_born, scheduler
+
+    def loss_and_grads(self, x_condition, entropy_weight):
+        """Device part of one epoch: -> (loss_ksd [1] float64, entropy [1] float32, q [2^n] float32 of the loss forward,
+        grads): grads = [(tensor, its gradient), ...] for apply_grads.  Nothing is read back to the host."""
+        bm = self.born_machine
+        mode = bm.born_mode
+        st = self._stein
+        if bm.conditioning_dim == 0:
+            # table: the forwards draw nothing, so one launch serves the loss and the entropy
+            home = bm.params.device
+            w = bm.params.detach().to(backend.compute_device(home)).reshape(1, -1)
+            q32, q64, H = backend.born_table_probs(w, mode, want_entropy=True)
+            ksd2, y = st._stein_contract(q64[0])
+            loss = torch.empty(1, dtype=torch.float64, device=w.device)
+            g = backend.born_table_vjp(w, q64, mode, y=y.reshape(1, -1), ksd2=ksd2, entropy_weight=entropy_weight,
+                                       loss_out=loss)
+            return loss, H, q32[0], [(bm.params, g.reshape(bm.params.shape).to(home))]
+        # MLP: the reference's two forwards (loss, then entropy()) -- with Dropout active two different samples
+        w1, _ = bm.kernel_input(bm.raw_params(x_condition))
+        if w1.shape[0] != 1:
+            raise ValueError(f"Probabilities shape mismatch: {tuple(w1.shape)}")
+        q32, q64, _ = backend.born_table_probs(w1.detach(), mode, want_entropy=False)
+        ksd2, y = st._stein_contract(q64[0])
+        loss = torch.empty(1, dtype=torch.float64, device=w1.device)
+        g1 = backend.born_table_vjp(w1.detach(), q64, mode, y=y.reshape(1, -1), ksd2=ksd2, loss_out=loss)
+        w2, _ = bm.kernel_input(bm.raw_params(x_condition))
+        _, q64e, H = backend.born_table_probs(w2.detach(), mode, want_entropy=True)
+        g2 = backend.born_table_vjp(w2.detach(), q64e, mode, entropy_weight=entropy_weight)
+        return loss, H, q32[0], [(w1, g1), (w2, g2)]
+
+    @staticmethod
+    def apply_grads(grads):
+        """Puts the epoch's gradients into the parameters' .grad (what loss.backward() does in the reference)."""
+        if len(grads) == 1 and grads[0][0].is_leaf:
+            p, g = grads[0]
+            p.grad = g
+        else:
+            torch.autograd.backward([t for t, _ in grads], [g for _, g in grads])
+
+    def train(self, x_observation_dict, num_epochs, lr_born_machine,
+              verbose=True, true_posterior_for_tvd=None,
+              use_lr_scheduler=True, gradient_clip_norm=10.0,
+              optimizer_type="adam", adam_betas=(0.9, 0.999),
+              entropy_weight=0.01, patience=200):
+        """Same signature, history keys, messages and return value as the reference (ksd_vi.py:62-216).
+        true_posterior_for_tvd may also be a tensor (stein_utils.true_posterior_table): TVD then by tvd_table on the
+        device, no dict of 2^n tuples."""
+        if self.num_observed_vars > 0 and set(x_observation_dict.keys()) != set(self.observed_vars_names):
+            raise ValueError("Keys in x_observation_dict must match self.observed_vars_names.")
+
+        x_obs_list = [x_observation_dict[name] for name in self.observed_vars_names] if self.num_observed_vars > 0 else []
+        x_obs_tensor_for_bm = torch.tensor(x_obs_list, dtype=torch.float32, device=self.device)
+        bm = self.born_machine
+
+        born_machine_x_condition = None
+        if bm.conditioning_dim > 0:
+            if self.num_observed_vars == 0:
+                raise ValueError("Born machine is conditional but no observed vars specified.")
+            if bm.conditioning_dim != self.num_observed_vars:
+                raise ValueError("Born machine conditioning_dim must match num_observed_vars.")
+            born_machine_x_condition = x_obs_tensor_for_bm
+
+        self._precompute_all_s_p(x_observation_dict)
+        optimizer_born, scheduler = self.make_optimizer(lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type,
+                                                        adam_betas)
+
+        history = {'loss_ksd': [], 'tvd': [], 'grad_norm': [], 'entropy': []}
+        best_tvd = float('inf')
+        best_epoch = -1
+        best_probs = None
+        epochs_without_improvement = 0
+        grad_norm = None              # the reference's `'grad_norm' in locals()`: the last value set, 0.0 before
+        table = torch.is_tensor(true_posterior_for_tvd)
+        has_posterior = true_posterior_for_tvd is not None and len(true_posterior_for_tvd) > 0
+
+        def current_tvd():
+            if table:
+                with torch.no_grad():
+                    q_now = bm.get_probabilities(x_condition=born_machine_x_condition).detach().reshape(-1)
+                return float(tvd_table(true_posterior_for_tvd.to(q_now.device), q_now))
+            return calculate_tvd(true_posterior_for_tvd, bm.get_prob_dict(x_condition=born_machine_x_condition))
+
+        for epoch in range(num_epochs):
+            optimizer_born.zero_grad()
+            loss_t, entropy_t, q, grads = self.loss_and_grads(born_machine_x_condition, entropy_weight)
+            if q.shape[0] != self.num_possible_latent_states:
+                raise ValueError(f"Probabilities shape mismatch: {q.shape}")
+            ksd_value = float(loss_t.item())             # the epoch's host synchronisation (reference: loss.item())
+            entropy_value = float(entropy_t.item())
+            # the guard is on the total loss (ksd_vi.py:140-142)
+            total = ksd_value - float(np.float32(entropy_weight) * np.float32(entropy_value))
+            if np.isnan(total) or np.isinf(total):
+                print(f"Warning: NaN or Inf loss: {total}. Skipping update.")
+            else:
+                self.apply_grads(grads)
+                grad_norm = nn_utils.clip_grad_norm_(bm.parameters(), gradient_clip_norm)
+                optimizer_born.step()
+                if scheduler is not None:
+                    scheduler.step()
+
+            history['loss_ksd'].append(ksd_value)
+            history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
+            history['entropy'].append(entropy_value)
+
+            if true_posterior_for_tvd is not None:
+                tvd = current_tvd()
+                history['tvd'].append(tvd)
+                if tvd < best_tvd:
+                    best_tvd = tvd
+                    best_epoch = epoch
+                    epochs_without_improvement = 0
+                    with torch.no_grad():
+                        best_probs = bm.get_probabilities(x_condition=born_machine_x_condition).squeeze().clone()
+                    if verbose and tvd < 0.05:
+                        print(f"  -> New best TVD: {tvd:.6f} at epoch {epoch+1}")
+                else:
+                    epochs_without_improvement += 1
+                if epochs_without_improvement > patience and epoch > 300:
+                    if verbose:
+                        print(f"\nEarly stopping at epoch {epoch+1} (no improvement for {patience} epochs)")
+                    break
+            else:
+                history['tvd'].append(np.nan)
+
+            if verbose and (epoch % max(1, num_epochs // 20) == 0 or epoch == num_epochs - 1):
+                log_msg = f"Epoch {epoch+1}/{num_epochs} | KSD: {ksd_value:.6f}"
+                if scheduler is not None:
+                    log_msg += f" | LR: {scheduler.get_last_lr()[0]:.6f}"
+                log_msg += f" | Entropy: {entropy_value:.4f}"
+                if has_posterior and not np.isnan(history['tvd'][-1]):
+                    log_msg += f" | TVD: {history['tvd'][-1]:.6f}"
+                print(log_msg)
+
+        # unlike the quantum trainer, the best probabilities are restored whatever `verbose` is (ksd_vi.py:199-214)
+        if best_probs is not None:
+            if verbose:
+                print(f"\nRestoring best probabilities (TVD: {best_tvd:.6f} from epoch {best_epoch+1})")
+            bm.set_fixed_probs(best_probs)
+            final_tvd = current_tvd()
+            if abs(final_tvd - best_tvd) > 1e-6:
+                print(f"WARNING: Still have restoration issue! Expected TVD: {best_tvd:.6f}, Got: {final_tvd:.6f}")
+            elif verbose:
+                print(f"Successfully restored best probabilities! Final TVD: {final_tvd:.6f}")
+
+        return history
