@@ -19,6 +19,16 @@
  *   - a handle is bound to one device and is not thread-safe; distinct handles are.
  *   - outcome index i <-> bitstring bin(i).zfill(n): bit position 0 of the tuple is the MOST
  *     significant bit of i and is wire 0 of the circuit (utils.py:77-91).
+ *   - accepted n per entry point (anything else is refused with BORNVI_ERR_UNSUPPORTED or
+ *     BORNVI_ERR_INVALID before any launch):
+ *       circuits, parameter shift (probs, grad, fused dot), adjoint engine,
+ *       matrix-free Stein mat-vec ................................. 1 <= n <= 29
+ *         (plan tile and workgroup indices are 16 bits, tiles at most 2^13 amplitudes;
+ *          the 8-amplitude kernel runs n <= 27, the larger states the generic pass kernel);
+ *       dense Gram and quadratic forms ............................ 1 <= n <= 17;
+ *       score from CPTs, k_p pairs, gradient assembly, shots ....... 1 <= n <= 30;
+ *       probability-table Born machine ............................ 0 <= n <= 30;
+ *       un-fused gate application ................................. 1 <= n <= 40.
  */
 #ifndef BORNVI_H
 #define BORNVI_H

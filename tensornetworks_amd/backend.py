@@ -90,9 +90,14 @@ def _chk(t, dtype, dev, name, numel=None):
         raise BornviError(f"{name}: expected {int(numel)} elements, got {t.numel()} (shape {tuple(t.shape)})")
 
 
+# Largest n of the circuit engines (circuits, parameter shift, fused dot, adjoint) and of the matrix-free Stein mat-vec:
+# the planner's tile and workgroup indices are 16 bits and its tiles hold at most 2^13 amplitudes (include/bornvi.h).
+CIRCUIT_MAX_N = 29
+
+
 def _chk_n(n, lo=1, hi=30):
     if not (isinstance(n, (int, np.integer)) and lo <= int(n) <= hi):
-        raise BornviError(f"number of qubits / latent variables out of range: {n!r}")
+        raise BornviError(f"number of qubits / latent variables out of range: {n!r} (accepted: {lo} ... {hi})")
 
 
 def _ptr(t):
@@ -207,10 +212,10 @@ def cu_range_stream(dev, first_cu, num_cus):
 # ---- circuits -------------------------------------------------------------------------------------
 def circuit_probs(ansatz_type, n, layers, thetas):
     """thetas float64 [B, P] on a cuda device -> probs float64 [B, 2^n]."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
     dev = thetas.device
     h = _ext.handle_for(dev)
     aid = ansatz_id(ansatz_type)
-    _chk_n(n)
     P = num_params(ansatz_type, n, layers)
     if thetas.dim() != 2 or thetas.shape[1] != P:
         raise BornviError(f"thetas must be [batch, {P}]")
@@ -228,10 +233,10 @@ def paramshift_probs(ansatz_type, n, layers, theta, p_begin, p_end, include_base
                      p_stride=1):
     """theta float64 [P] -> probs [(1 if include_base) + 2 count, 2^n]: optional base row, then (+p, -p) rows for
     p = p_begin, p_begin + p_stride, ... < p_end (count of them; p_stride = 1: the range [p_begin, p_end))."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
     dev = theta.device
     h = _ext.handle_for(dev)
     aid = ansatz_id(ansatz_type)
-    _chk_n(n)
     _chk(theta, torch.float64, dev, "theta", num_params(ansatz_type, n, layers))
     count = len(range(p_begin, p_end, p_stride))
     B = (1 if include_base else 0) + 2 * count
@@ -251,22 +256,24 @@ def paramshift_probs(ansatz_type, n, layers, theta, p_begin, p_end, include_base
 
 
 def paramshift_dot_supported(ansatz_type, n, layers, dev, count):
-    """True when the fused path exists for this plan (multi-pass plan of the 8-amplitude kernel, no prefix sharing)."""
+    """True when the fused path exists for this plan (multi-pass plan of the 8-amplitude kernel, no prefix sharing) and
+    its workspace -- every shifted state at once, no chunks -- fits WORKSPACE_CAP; else the caller takes the chunked
+    path (paramshift_probs)."""
     h = _ext.handle_for(dev)
     key = (id(h), "dot_supported", ansatz_id(ansatz_type), int(n), int(layers), int(count))
     if key not in _size_cache:       # (a size of 0 is the library's "not available": no error)
         _size_cache[key] = int(_ext.lib().bornvi_paramshift_dot_workspace_bytes(h.h, ansatz_id(ansatz_type), int(n), int(layers), int(count)))
-    return _size_cache[key] > 0
+    return 0 < _size_cache[key] <= WORKSPACE_CAP    # (the cap is read on every call: it may change after the size was cached)
 
 
 def paramshift_dot_begin(ansatz_type, n, layers, theta, p_begin, p_end, p_stride=1, ws_tag="dot"):
     """First half of a parameter-shift step with the dot product fused into the last circuit pass: runs the base circuit
     and the shifted circuits of p = p_begin, p_begin + p_stride, ... < p_end up to their last pass, and the base circuit
     to the end.  Returns (q [2^n], token); give the token to paramshift_dot_finish once y = K_p q is known."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
     dev = theta.device
     h = _ext.handle_for(dev)
     aid = ansatz_id(ansatz_type)
-    _chk_n(n)
     _chk(theta, torch.float64, dev, "theta", num_params(ansatz_type, n, layers))
     count = len(range(p_begin, p_end, p_stride))
     need = int(_cached_size(h, "bornvi_paramshift_dot_workspace_bytes", aid, n, layers, count))
@@ -298,10 +305,10 @@ def paramshift_dot_finish(token, w, ksd2=None):
 def paramshift_grad(ansatz_type, n, layers, theta, dLdq, p_begin, p_end, p_stride=1, shots=None):
     """grad[i] = 1/2 dLdq . (q(theta + pi/2 e_p) - q(theta - pi/2 e_p)) for p = p_begin + i p_stride < p_end, float64.
     shots = (S, seed, epoch tensor): the shifted distributions are replaced by histograms of S draws (shots_histogram)."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
     dev = theta.device
     h = _ext.handle_for(dev)
     aid = ansatz_id(ansatz_type)
-    _chk_n(n)
     _chk(theta, torch.float64, dev, "theta", num_params(ansatz_type, n, layers))
     _chk(dLdq, torch.float64, dev, "dLdq", 1 << n)
     ns = len(range(p_begin, p_end, p_stride))
@@ -321,10 +328,10 @@ def paramshift_grad(ansatz_type, n, layers, theta, dLdq, p_begin, p_end, p_strid
 
 def adjoint_state(ansatz_type, n, layers, theta, want_probs=True):
     """OPT-IN adjoint engine, forward walk: theta float64 [P] -> (state complex128 [2^n], probs float64 [2^n] or None)."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
     dev = theta.device
     h = _ext.handle_for(dev)
     aid = ansatz_id(ansatz_type)
-    _chk_n(n)
     _chk(theta, torch.float64, dev, "theta", num_params(ansatz_type, n, layers))
     state = torch.empty(1 << n, dtype=torch.complex128, device=dev)
     probs = torch.empty(1 << n, dtype=torch.float64, device=dev) if want_probs else None
@@ -337,10 +344,10 @@ def adjoint_state(ansatz_type, n, layers, theta, want_probs=True):
 def adjoint_vjp(ansatz_type, n, layers, theta, state, dLdq):
     """OPT-IN adjoint engine, backward walk: grad[p] = d/dtheta_p sum_z dLdq[z] q_z(theta), float64 [P] -- the quantity
     paramshift_grad computes with 2P circuits, from one forward state and one backward walk."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
     dev = theta.device
     h = _ext.handle_for(dev)
     aid = ansatz_id(ansatz_type)
-    _chk_n(n)
     P = num_params(ansatz_type, n, layers)
     _chk(theta, torch.float64, dev, "theta", P)
     _chk(state, torch.complex128, dev, "state", 1 << n)
@@ -678,9 +685,9 @@ def stein_quadform_sym(K, q, n):
 
 def stein_matvec_kron(S, q, n, length_scale=1.0):
     """Matrix-free (ksd2 [1], y = K_p q [2^n])."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
     dev = S.device
     h = _ext.handle_for(dev)
-    _chk_n(n)
     _chk(S, torch.float64, dev, "S", n << n)
     _chk(q, torch.float64, dev, "q", 1 << n)
     y = torch.empty(1 << n, dtype=torch.float64, device=dev)

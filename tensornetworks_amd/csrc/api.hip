@@ -407,7 +407,7 @@ int circuit_batch(bornvi_handle h, int ansatz, int n, int layers, long long batc
 bool build_adj_plan(int ansatz, int n, int layers, AdjPlan& out, std::string& msg) {
   std::vector<Gate> gates;
   if (!build_gate_list(ansatz, n, layers, gates)) { msg = "unknown ansatz"; return false; }
-  if (n < 1 || n > 30) { msg = "adjoint engine supports 1 <= n <= 30"; return false; }
+  if (n < 1 || n > MAX_PLAN_QUBITS) { msg = "adjoint engine supports 1 <= n <= " + std::to_string(MAX_PLAN_QUBITS); return false; }
   out.n_params = num_params(ansatz, n, layers);
   std::vector<std::vector<Gate>> per_wire((size_t)n);     // one-qubit gates of the current segment, per wire (they commute across wires)
   std::vector<Gate> two;                                   // two-qubit gates of the current entangler
@@ -1004,7 +1004,7 @@ int bornvi_stein_quadform_sym_pairs(bornvi_handle h, int n, const double* K_lo, 
 }
 
 size_t bornvi_stein_matvec_kron_workspace_bytes(bornvi_handle h, int n) {
-  if (!h || n < 1 || n > 30) return 0;
+  if (!h || n < 1 || n > MAX_PLAN_QUBITS) return 0;
   DevPlan* dp = nullptr;
   if (get_plan(h, -1, n, 0, &dp)) return 0;
   const size_t npk = (size_t)(n + 2) / 2;

@@ -344,7 +344,7 @@ bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::
 }  // namespace
 
 bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan, std::string& msg) {
-  if (n < 1 || n > 30) { msg = "num qubits must be in [1, 30]"; return false; }
+  if (n < 1 || n > MAX_PLAN_QUBITS) { msg = "num qubits must be in [1, " + std::to_string(MAX_PLAN_QUBITS) + "]"; return false; }
   if (layers < 0) { msg = "layers must be >= 0"; return false; }
   std::vector<Gate> gates;
   if (!build_gate_list(ansatz, n, layers, gates)) { msg = "unknown ansatz id"; return false; }
@@ -380,7 +380,10 @@ bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan
     std::string m13;
     if (build_plan(spec, o13, p13, m13)) {
       FastTables ft;
-      if (build_fast_tables(p13, FAST_TABLE_MAX_BYTES, ft) && p13.fast_lds_bytes(ft.max_tab_rows) <= MAX_LDS_BYTES) {
+      // (2^11 tiles cannot address more than 2^27 amplitudes -- tile and workgroup indices are 16 bits: above that the
+      // 2^13-tile plan runs on the generic kernel)
+      if ((build_fast_tables(p13, FAST_TABLE_MAX_BYTES, ft) && p13.fast_lds_bytes(ft.max_tab_rows) <= MAX_LDS_BYTES) ||
+          n - o11.kmulti > 16) {
         plan = std::move(p13);
         return true;
       }
@@ -394,7 +397,7 @@ bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan
 // Wires are visited from the least significant physical bit upwards so that the first and the
 // last pass both hold the canonical low bits locally.
 bool make_kron_plan(int n, const PlanOptions& opt, Plan& plan, std::string& msg) {
-  if (n < 1 || n > 30) { msg = "num bits must be in [1, 30]"; return false; }
+  if (n < 1 || n > MAX_PLAN_QUBITS) { msg = "num bits must be in [1, " + std::to_string(MAX_PLAN_QUBITS) + "]"; return false; }
   BuildSpec spec;
   spec.n = n;
   Fused f; f.fill(0xffffffffu); f[0] = 0; f[1] = 0;
@@ -402,6 +405,11 @@ bool make_kron_plan(int n, const PlanOptions& opt, Plan& plan, std::string& msg)
   for (int w = n - 1; w >= 0; --w) spec.ops.push_back({K_U1, w, -1, 0});
   spec.in_state = spec.out_state = true;
   spec.n_gates = n;
+  if (opt.kmulti == 0 && n - 12 > 16 && opt.kmax >= 13) {   // (the default 2^12 tiles leave a 17-bit workgroup index at n = 29)
+    PlanOptions o13 = opt;
+    o13.kmulti = 13;
+    return build_plan(spec, o13, plan, msg);
+  }
   return build_plan(spec, opt, plan, msg);
 }
 

@@ -265,6 +265,9 @@ struct CompactTables {
 // 2^22 of them per row, a fixed sample beyond)
 bool build_compact_tables(const Plan& plan, CompactTables& out, std::string& msg);
 
+// Largest state a plan can address: tile and workgroup indices are 16 bits each and tiles hold at most 2^13 amplitudes,
+// so n - 13 <= 16.
+constexpr int MAX_PLAN_QUBITS = 29;
 // Returns false (with msg) on unsupported sizes.
 bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& out, std::string& msg);
 // Program applying one shared 2x2 matrix to every bit of a canonical-order vector (state in,

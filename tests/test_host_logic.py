@@ -419,3 +419,53 @@ def test_cosine_schedule_table_follows_torch():
         got = cosine_annealing_lr(np.arange(len(want)), lr0, T, eta)
         np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-15)
         assert cosine_annealing_lr(0, lr0, T, eta) == lr0
+
+
+@pytest.mark.parametrize("aid", [-1, 0, 1, 2])
+def test_every_accepted_n_has_a_plan(aid):
+    """The route get_plan takes yields a plan for every n the backend accepts for circuits and the kron mat-vec, and
+    none above: the 8-amplitude plan (compact tables) up to n = 27, the 4-wire plan (fast or generic kernel) beyond.
+    2^11 tiles leave a 17-bit workgroup index at n = 28, so the 4-wire fallback must keep 2^13 tiles there."""
+    from tensornetworks_amd import _ext, backend
+    lib = _ext.lib()
+    assert backend.CIRCUIT_MAX_N == 29
+
+    def compact(n, L):
+        return lib.bornvi_plan_compact_describe(aid, n, L, _ext.R3, None, 0, None, 0)
+
+    for n in range(17, 31):
+        for L in ((0,) if aid == -1 else (0, 1, 2)):
+            if n <= 27:
+                st = pe.plan_stats(_ext.plan_words(aid, n, L, _ext.R3))
+                assert st["k"] <= 13 and n - st["k"] <= 16, (aid, n, L, st["k"])
+                # (the compact tables take seconds per plan at n >= 24: built at both ends of their range only)
+                if n in (17, 27) and L <= 1:
+                    assert compact(n, L) > 0, (aid, n, L)
+            elif n <= backend.CIRCUIT_MAX_N:
+                W = _ext.plan_words(aid, n, L, 0)
+                st = pe.plan_stats(W)
+                assert st["k"] <= 13 and n - st["k"] <= 16 and int(W[1]) == n, (aid, n, L, st["k"])
+                if aid >= 0:
+                    assert st["k"] == 13 and st["gates"] == lib.bornvi_num_gates(aid, n, L)
+                assert compact(n, L) == 0        # (the 8-amplitude route refuses it: get_plan takes this plan)
+            else:
+                with pytest.raises(_ext.BornviError):
+                    _ext.plan_words(aid, n, L, 0)
+                assert compact(n, L) == -1
+
+
+def test_circuit_entry_points_refuse_n_above_the_planner_range():
+    """n = 30 is refused by the argument checks, before a handle or a GPU is needed."""
+    import torch
+    from tensornetworks_amd import _ext, backend
+    t = torch.zeros(1, dtype=torch.float64)
+    calls = [lambda: backend.circuit_probs("basic", 30, 1, t.reshape(1, 1)),
+             lambda: backend.paramshift_probs("basic", 30, 1, t, 0, 1),
+             lambda: backend.paramshift_dot_begin("basic", 30, 1, t, 0, 1),
+             lambda: backend.paramshift_grad("basic", 30, 1, t, t, 0, 1),
+             lambda: backend.adjoint_state("basic", 30, 1, t),
+             lambda: backend.adjoint_vjp("basic", 30, 1, t, t, t),
+             lambda: backend.stein_matvec_kron(t, t, 30)]
+    for f in calls:
+        with pytest.raises(_ext.BornviError, match="out of range"):
+            f()
