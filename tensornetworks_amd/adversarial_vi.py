@@ -112,8 +112,7 @@ class AdversarialVariationalInference:
 
     # ---- one classifier step / one Born-machine step, device-resident (no host read-back inside) ----------------------
     def _spans(self, name):
-        from .ksd_vi_quantum import _EventSpan
-        return _EventSpan(self.timers if torch.device(self.device).type == "cuda" else None, name)
+        return backend.EventSpan(self.timers if torch.device(self.device).type == "cuda" else None, name)
 
     def _clf_inputs(self, z, x_obs_tensor, with_x):
         if with_x:

@@ -71,7 +71,7 @@ def fresh_workspace(dev, nbytes):
 
 def set_workspace(dev, tag, buf):
     """Makes `buf` the cached workspace `tag` of the current stream (the trainer places the symmetric contraction's
-    workspace by measurement: KSDVariationalInference._place_gram)."""
+    workspace by measurement: SteinOperator._place_gram)."""
     key = _ws_key(dev, tag)
     _ws_windows.pop(key, None)
     _workspaces[key] = buf
@@ -207,6 +207,33 @@ def cu_range_stream(dev, first_cu, num_cus):
         h.call("bornvi_stream_create_cu_range", int(first_cu), int(num_cus), C.byref(st))
         _cu_streams[key] = torch.cuda.ExternalStream(st.value, device=dev)
     return _cu_streams[key]
+
+
+_ROCTX = os.environ.get("BORNVI_ROCTX", "0") == "1"
+
+
+class EventSpan:
+    """`with` block that records a (start, end) torch.cuda.Event pair on the current stream -- the
+    stream every bornvi kernel of the block is launched on -- when timers are enabled."""
+
+    def __init__(self, timers, name):
+        self.timers, self.name = timers, name
+
+    def __enter__(self):
+        if _ROCTX:                       # BORNVI_ROCTX=1: named ranges for rocprofv3 --marker-trace / roctx consumers
+            torch.cuda.nvtx.range_push(f"bornvi:{self.name}")
+        if self.timers is not None:
+            self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            self.ev[0].record()
+        return self
+
+    def __exit__(self, *exc):
+        if _ROCTX:
+            torch.cuda.nvtx.range_pop()
+        if self.timers is not None:
+            self.ev[1].record()
+            self.timers.setdefault(self.name, []).append(self.ev)
+        return False
 
 
 # ---- circuits -------------------------------------------------------------------------------------

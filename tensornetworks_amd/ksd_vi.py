@@ -11,8 +11,8 @@ set_fixed_probs.  What changed is where the arithmetic happens:
   loss.backward() through 4^n autograd nodes                born_table_vjp -> params.grad (float32)
   clip_grad_norm_, optimizer.step(), scheduler.step()       the same torch objects
 
-S and K_p are built once per train() call by the quantum trainer's machinery (scores on the GPU; dense Gram up to
-DENSE_GRAM_MAX_N, matrix-free Kronecker mat-vec beyond), reused by composition (`_SteinPath`).  MLP mode
+S and K_p are built once per train() call by a `stein_operator.SteinOperator` of this trainer's own, the one the quantum
+trainer derives from (scores on the GPU; dense Gram up to DENSE_GRAM_MAX_N, matrix-free Kronecker mat-vec beyond).  MLP mode
 (conditioning_dim > 0): the network stays stock torch.nn and makes the reference's forwards in its order and number
 (loss, entropy, TVD, best-probabilities snapshot: the same Dropout draws); logits -> q and the VJP back onto the logits
 are the kernels, once per term, and torch.autograd carries the two logit gradients into the network.
@@ -25,38 +25,11 @@ import torch.nn.utils as nn_utils
 import torch.optim as optim
 
 from . import backend
-from . import ksd_vi_quantum as _quantum
 from . import paramshift_shard as shard
 from .born_machine_classical_sim import ClassicalBornMachine
+from .stein_operator import DENSE_GRAM_MAX_N, SteinOperator      # noqa: F401  (DENSE_GRAM_MAX_N: exported from here too)
 from .stein_utils import base_hamming_kernel_torch, tvd_table
-from .utils import calculate_tvd, generate_all_binary_outcomes
-
-DENSE_GRAM_MAX_N = _quantum.DENSE_GRAM_MAX_N
-
-
-class _SteinPath:
-    """Scores and K_p of one observation on one GPU, and the contraction (ksd2, y = K_p q): the quantum trainer's
-    _prepare_stein / _place_gram / _stein_contract, used unchanged on this object's attributes."""
-    _prepare_stein = _quantum.KSDVariationalInference._prepare_stein
-    _place_gram = _quantum.KSDVariationalInference._place_gram
-    _stein_contract = _quantum.KSDVariationalInference._stein_contract
-    _use_dense = _quantum.KSDVariationalInference._use_dense
-    _key = _quantum.KSDVariationalInference._key
-    _timed = _quantum.KSDVariationalInference._timed
-
-    def __init__(self, bn, latent_vars_names, length_scale, device):
-        self.bn = bn
-        self.latent_vars_names = latent_vars_names
-        self.num_latent_vars = len(latent_vars_names)
-        self.pytorch_device = device
-        self.base_kernel_length_scale = length_scale
-        self.gram_mode = "auto"
-        self.symmetric_contraction = True
-        self.process_group = shard.SOLO
-        self.gram_placement_tries = 4
-        self.gram_placement = None
-        self.timers = None
-        self._S = self._K = self._K_rows = self._K_pairs = self._stein_key = None
+from .utils import calculate_tvd
 
 
 class KSDVariationalInference:
@@ -75,41 +48,27 @@ class KSDVariationalInference:
         self.born_machine = ClassicalBornMachine(num_latent_vars=self.num_latent_vars,
                                                  **born_machine_config).to(device)
 
-        self._all_states = None
         self.num_possible_latent_states = 2 ** self.num_latent_vars
         self.base_kernel_func = partial(base_hamming_kernel_torch,
                                         num_vars=self.num_latent_vars,
                                         length_scale=base_kernel_length_scale)
-        self._score_function_cache = {}
-        self._stein = _SteinPath(bayesian_network, latent_vars_names, base_kernel_length_scale, device)
+        # scores and K_p of one observation on one GPU, and the contraction (ksd2, y = K_p q)
+        self._stein = SteinOperator(bayesian_network, latent_vars_names, base_kernel_length_scale, device,
+                                    process_group=shard.SOLO)
+        self._score_function_cache = self._stein._score_function_cache
 
     @property
     def all_latent_states_tuples(self):
         """Reference attribute, built on first use (2^n Python tuples)."""
-        if self._all_states is None:
-            self._all_states = generate_all_binary_outcomes(self.num_latent_vars)
-        return self._all_states
+        return self._stein.all_latent_states_tuples
 
     def _get_precomputed_s_p(self, z_tuple, x_dict):
         """Score vector of one state (reference :43-53), served from the batched device result."""
-        if z_tuple in self._score_function_cache:
-            return self._score_function_cache[z_tuple]
-        st = self._stein
-        if st._S is None or st._stein_key != st._key(x_dict):
-            st._prepare_stein(x_dict, announce=False)
-        idx = 0
-        for b in z_tuple:
-            idx = (idx << 1) | int(b)
-        s = st._S[idx].to(self.device)
-        self._score_function_cache[z_tuple] = s
-        return s
+        return self._stein._get_precomputed_s_p(z_tuple, x_dict)
 
     def _precompute_all_s_p(self, x_dict):
         """reference :55-60 -- one kernel launch for the scores, plus K_p (dense) once."""
-        self._score_function_cache.clear()
-        print("Precomputing score functions s_p(x,z)...")
-        self._stein._prepare_stein(x_dict, announce=False)
-        print("Score functions precomputed.")
+        self._stein._precompute_all_s_p(x_dict)
 
     def make_optimizer(self, lr_born_machine, num_epochs, use_lr_scheduler=True, optimizer_type="adam",
                        adam_betas=(0.9, 0.999)):

@@ -20,7 +20,6 @@ Finite shots (qbm_shots=S): the base and the 2P shifted distributions of a step 
 each (backend.shots_histogram, every row its own draws) before the contraction; loss sqrt(max(q^T K_p q^, 1e-12)) and
 gradient 1/2 dL/dq^ . (q^+_p - q^-_p) are the plug-in estimates PennyLane's parameter-shift rule gives under shots.
 """
-import os
 import time
 from functools import partial
 
@@ -32,35 +31,9 @@ import torch.optim as optim
 from . import backend
 from . import paramshift_shard as shard
 from .quantum_born_machine import QuantumBornMachine
-from .stein_utils import base_hamming_kernel_torch, score_matrix, stein_gram_matrix, tvd_table
-from .utils import calculate_tvd, generate_all_binary_outcomes
-
-_ROCTX = os.environ.get("BORNVI_ROCTX", "0") == "1"
-DENSE_GRAM_MAX_N = 16     # 8 * 4^16 bytes = 32 GiB of the 288 GB HBM; beyond that the matrix-free form
-
-
-class _EventSpan:
-    """`with` block that records a (start, end) torch.cuda.Event pair on the current stream -- the
-    stream every bornvi kernel of the block is launched on -- when timers are enabled."""
-
-    def __init__(self, timers, name):
-        self.timers, self.name = timers, name
-
-    def __enter__(self):
-        if _ROCTX:                       # BORNVI_ROCTX=1: named ranges for rocprofv3 --marker-trace / roctx consumers
-            torch.cuda.nvtx.range_push(f"bornvi:{self.name}")
-        if self.timers is not None:
-            self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            self.ev[0].record()
-        return self
-
-    def __exit__(self, *exc):
-        if _ROCTX:
-            torch.cuda.nvtx.range_pop()
-        if self.timers is not None:
-            self.ev[1].record()
-            self.timers.setdefault(self.name, []).append(self.ev)
-        return False
+from .stein_operator import DENSE_GRAM_MAX_N, SteinOperator      # noqa: F401  (DENSE_GRAM_MAX_N: exported from here too)
+from .stein_utils import base_hamming_kernel_torch, tvd_table
+from .utils import calculate_tvd
 
 
 def cosine_annealing_lr(epoch, base_lr, T_max, eta_min):
@@ -142,7 +115,7 @@ class DeviceAdam:
         return self.lr_at(self.epochs)
 
 
-class KSDVariationalInference:
+class KSDVariationalInference(SteinOperator):
     def __init__(self,
                  bayesian_network,
                  latent_vars_names: list,
@@ -170,17 +143,10 @@ class KSDVariationalInference:
             # qbm_num_latent_vars qubits: the device kernels would index one with the other's sizes
             raise ValueError(f"qbm_num_latent_vars ({qbm_num_latent_vars}) must equal len(latent_vars_names) "
                              f"({len(latent_vars_names)})")
-        self.bn = bayesian_network
-        self.latent_vars_names = latent_vars_names
+        super().__init__(bayesian_network, latent_vars_names, base_kernel_length_scale, pytorch_device, gram_mode, process_group)
         self.observed_vars_names = observed_vars_names
-        self.num_latent_vars = qbm_num_latent_vars
         self.num_observed_vars = len(observed_vars_names)
         self.pytorch_device = pytorch_device
-        self.base_kernel_length_scale = base_kernel_length_scale
-        if gram_mode not in ("auto", "dense", "kron"):
-            raise ValueError("gram_mode must be 'auto', 'dense' or 'kron'")
-        self.gram_mode = gram_mode
-        self.process_group = process_group
 
         self.born_machine = QuantumBornMachine(
             num_latent_vars=self.num_latent_vars,
@@ -194,21 +160,12 @@ class KSDVariationalInference:
         ).to(pytorch_device)
         self.born_machine.process_group = process_group
 
-        self._all_states = None
         self.num_possible_latent_states = 2 ** self.num_latent_vars
 
         self.base_kernel_func = partial(base_hamming_kernel_torch,
                                         num_vars=self.num_latent_vars,
                                         length_scale=base_kernel_length_scale)
 
-        self._score_function_cache = {}
-        self._S = None          # scores [2^n, n] on the GPU
-        self._K = None          # dense Gram (dense mode): all rows, or this rank's row block when sharded
-        self._K_rows = None     # (row_begin, row_end) held in self._K (row shard)
-        self._K_pairs = None    # (pair_begin, pair_end, rows of the lower block) held in self._K (strip-pair shard)
-        self._stein_key = None
-        self.timers = None      # optional {name: [(start_event, end_event), ...]} filled by ksd_and_grad
-        self.symmetric_contraction = True   # dense mode: contract with the upper triangle of K_p only
         # How the shifted circuits and the contraction of a step share the GPU (they need nothing from each other):
         #   False        in sequence on the current stream
         #   True         contraction on a second plain stream: paid with the one-workgroup-per-tile circuit kernel; the
@@ -231,179 +188,7 @@ class KSDVariationalInference:
         # same gradient to rounding; taken where the library offers it (multi-pass plans of the 8-amplitude kernel),
         # else the probabilities are written and dotted as before.  False: always the un-fused path (A/B).
         self.fused_dot = True
-        # A dense K_p >= 1 GiB is placed by measurement: up to this many copies are built (each in fresh memory while the
-        # earlier ones are held), the contraction is timed on each, the fastest stays (_place_gram).  The contraction's
-        # rate depends on where the driver put K_p RELATIVE to the workspace its partial sums go to -- 2.55 or 2.78 ms
-        # at n = 16 for the same kernel and matrix, stable for the life of the allocations, equal alone and inside the
-        # training step (tools/probes/step_placement_probe.py, ws_place_probe.py, ws_far_probe.py) -- and a process
-        # cannot see physical addresses.  One-time cost: ~50 ms and 2^(2n+3) bytes per extra copy, freed at once; the
-        # search stops at the first pair that streams at 83 % of the HBM peak.  1 = take the first copy.
-        self.gram_placement_tries = 4
-        self.gram_placement = None          # {"contraction_ms_per_pair": [[copy, workspace, ms], ...], "kept": [copy, workspace]}
         self._aux_stream = None
-
-    # ---- reference attribute kept lazily (2^n Python tuples) -------------------------------------------
-    @property
-    def all_latent_states_tuples(self):
-        if self._all_states is None:
-            self._all_states = generate_all_binary_outcomes(self.num_latent_vars)
-        return self._all_states
-
-    def _get_precomputed_s_p(self, z_tuple, x_dict):
-        """Score vector of one state (reference :58-68), served from the batched device result."""
-        if z_tuple in self._score_function_cache:
-            return self._score_function_cache[z_tuple]
-        if self._S is None or self._stein_key != self._key(x_dict):
-            self._prepare_stein(x_dict, announce=False)
-        idx = 0
-        for b in z_tuple:
-            idx = (idx << 1) | int(b)
-        s = self._S[idx].to(self.pytorch_device)
-        self._score_function_cache[z_tuple] = s
-        return s
-
-    def _precompute_all_s_p(self, x_dict):
-        """reference :70-75 -- one kernel launch instead of 2^n * (n+1) network enumerations."""
-        self._score_function_cache.clear()
-        print("Precomputing score functions s_p(x,z)...")
-        self._prepare_stein(x_dict, announce=False)
-        print("Score functions precomputed.")
-
-    def _key(self, x_dict):
-        return tuple(sorted((x_dict or {}).items()))
-
-    def _use_dense(self):
-        if self.gram_mode == "dense":
-            return True
-        if self.gram_mode == "kron":
-            return False
-        return self.num_latent_vars <= DENSE_GRAM_MAX_N
-
-    def _prepare_stein(self, x_dict, announce=True):
-        """Scores and (dense mode) the Gram matrix, once per observation.  With W > 1 ranks each rank
-        builds and keeps only its block of N/W rows of K_p (row shard of the quadratic form)."""
-        dev = backend.compute_device(self.pytorch_device)
-        n = self.num_latent_vars
-        S_new = score_matrix(self.bn, x_dict, self.latent_vars_names, device=dev)
-        # K_p is a function of (S, n, length scale) only: a second train() on the same observation and network keeps the
-        # matrix it has (32 GiB and a placement search at n = 16) -- the scores themselves are recomputed like the
-        # reference does (one launch)
-        sig = (float(self.base_kernel_length_scale), self._use_dense(), bool(self.symmetric_contraction),
-               shard.world(self.process_group), int(self.gram_placement_tries))
-        if (self._use_dense() and getattr(self, "_K", None) is not None and getattr(self, "_K_sig", None) == sig
-                and self._S is not None and self._S.shape == S_new.shape and torch.equal(self._S, S_new)):
-            self._S = S_new
-            self._stein_key = self._key(x_dict)
-            return
-        self._S = S_new
-        self._K_sig = sig
-        self._K = None
-        self._K_rows = None
-        self._K_pairs = None
-        if self._use_dense():
-            rank, ws = shard.world(self.process_group)
-            sp = backend.sym_pair_shard(n, rank, ws) if (ws > 1 and self.symmetric_contraction) else None
-            if sp is not None:
-                # strip-pair shard of the symmetric contraction: this rank keeps two row blocks of K_p (a long and
-                # a short part of the upper triangle) and reads only 1/W of the triangle per step
-                (pa, pb), (l0, l1), (h0, h1) = sp
-                self._K_pairs = (pa, pb, l1 - l0)
-
-                def build():
-                    # (padded row pitch: backend.gram_ld -- the strips' row streams must not share an HBM channel)
-                    K = torch.empty(((l1 - l0) + (h1 - h0), backend.gram_ld(n)), dtype=torch.float64, device=dev)[:, : 1 << n]
-                    if l1 > l0:
-                        backend.stein_gram(self._S, n, self.base_kernel_length_scale, rows=(l0, l1), out=K[: l1 - l0])
-                        backend.stein_gram(self._S, n, self.base_kernel_length_scale, rows=(h0, h1), out=K[l1 - l0:])
-                    return K
-
-                def contract(K, q):
-                    return backend.stein_quadform_sym_pairs(K[: l1 - l0], K[l1 - l0:], pa, pb, q, n)
-            else:
-                self._K_rows = shard.shard_range(1 << n, rank, ws)
-                r0, r1 = self._K_rows
-
-                def build():
-                    # one GPU, symmetric contraction: padded row pitch (backend.gram_ld); the full-matrix and row-shard
-                    # kernels read contiguous rows
-                    pad = ws == 1 and self.symmetric_contraction
-                    return backend.stein_gram(self._S, n, self.base_kernel_length_scale, rows=self._K_rows,
-                                              ld=backend.gram_ld(n) if pad else None)
-
-                def contract(K, q):
-                    if ws == 1:
-                        return backend.stein_quadform_sym(K, q, n) if self.symmetric_contraction else backend.stein_quadform(K, q, n, want_y=True)
-                    return backend.stein_quadform_rows(K, r0, r1, q, n)
-            sym = self.symmetric_contraction and (ws == 1 or sp is not None)
-            self._K = self._place_gram(build, contract, backend.stein_sym_workspace_bytes(dev, n) if sym else 0)
-        self._stein_key = self._key(x_dict)
-
-    def _place_gram(self, build, contract, ws_bytes=0):
-        """Builds K_p and, for large matrices, picks a well-placed copy.  The contraction streams the matrix from HBM
-        and its rate depends on where the driver put it relative to the contraction's workspace: round 2, same kernel,
-        same box, n = 16: 2.55 ms or 2.78 ms, stable for the life of the two allocations, the same alone and inside the
-        training step, following the (K_p, workspace) PAIR -- a workspace inside K_p's own allocation is always the
-        slow case (tools/probes/ws_in_kp_probe.py), one 64+ GiB further on usually the fast one (ws_far_probe.py).
-        (Round 1's 2.84 / 3.32 ms were the same effect amplified by 8x more partial-sum stores.)
-        So: build up to `gram_placement_tries` copies (each in fresh memory while the earlier ones are still held), and
-        behind each a fresh workspace (`ws_bytes` > 0: the symmetric contraction's, which then lies one matrix further
-        on than the last), time the contraction on every (copy, workspace) pair, keep the fastest pair, free the rest.
-        Same matrix, same results; stops as soon as one pair streams at 83 % of the HBM peak (about every second first
-        copy does: then nothing extra is built); at worst `gram_placement_tries` copies are held at once for ~0.2 s."""
-        K = build()
-        nbytes = K.numel() * K.element_size()
-        tries = int(self.gram_placement_tries)
-        self.gram_placement = None
-        if tries <= 1 or nbytes < (1 << 30):
-            return K
-        dev = K.device
-        free_b, _ = torch.cuda.mem_get_info(dev)
-        q = torch.full((1 << self.num_latent_vars,), 1.0 / (1 << self.num_latent_vars), dtype=torch.float64, device=dev)
-
-        def clock(Kc):
-            contract(Kc, q)
-            torch.cuda.synchronize(dev)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(3):
-                contract(Kc, q)
-            b.record()
-            torch.cuda.synchronize(dev)
-            return a.elapsed_time(b) / 3
-
-        Ks = [K]
-        Ws = [backend.fresh_workspace(dev, ws_bytes)] if ws_bytes else [None]
-        took = {}
-
-        def time_new_pairs():
-            for i, Kc in enumerate(Ks):
-                for j, w in enumerate(Ws):
-                    if (i, j) not in took:
-                        if w is not None:
-                            backend.set_workspace(dev, "qfsym", w)
-                        took[(i, j)] = clock(Kc)
-
-        # good enough = the upper triangle (half of these rows) at 83 % of the MI355X's 8 TB/s: what the kernel reaches on
-        # a well-placed pair (n = 16: 2.59 ms; fast pairs run 2.555-2.58, the rest 2.61-2.80).  A first copy that is
-        # already there costs nothing extra -- no second copy is built.
-        good_ms = (nbytes / 2) / (0.83 * 8e12) * 1e3
-        time_new_pairs()
-        while len(Ks) < tries and free_b > (len(Ks) + 1) * (nbytes + ws_bytes) + (8 << 30):
-            if min(took.values()) <= good_ms:
-                break
-            Ks.append(build())
-            if ws_bytes:
-                Ws.append(backend.fresh_workspace(dev, ws_bytes))
-            time_new_pairs()
-        bi, bj = min(took, key=took.get)
-        K = Ks[bi]
-        if Ws[bj] is not None:
-            backend.set_workspace(dev, "qfsym", Ws[bj])
-        self.gram_placement = {"contraction_ms_per_pair": [[i, j, round(t, 4)] for (i, j), t in sorted(took.items())],
-                               "kept": [bi, bj], "note": "[K_p copy, workspace, ms]"}
-        del Ks, Ws
-        torch.cuda.empty_cache()
-        return K
 
     def choose_overlap(self, reps=4):
         """Decides by measurement whether the circuits and the contraction of a step take turns on the whole chip or
@@ -436,41 +221,6 @@ class KSDVariationalInference:
         self.overlap_choice = {"sequential_ms": round(took[False], 4), "partition_ms": round(took["partition"], 4),
                                "chosen": "partition" if self.overlap_streams else "sequential"}
 
-    def _timed(self, name):
-        return _EventSpan(self.timers, name)
-
-    def _stein_contract(self, q):
-        """(ksd2 [1], y = K_p q [2^n]) for the current q, on the GPU."""
-        n = self.num_latent_vars
-        if self._K is None:
-            return backend.stein_matvec_kron(self._S, q, n, self.base_kernel_length_scale)
-        rank, ws = shard.world(self.process_group)
-        if self._K_pairs is not None:
-            # every rank adds its share of (K q, q.y); one all-reduce of 2^n + 1 doubles
-            pa, pb, nlo = self._K_pairs
-            msg = backend.stein_quadform_sym_pairs(self._K[:nlo], self._K[nlo:], pa, pb, q, n)
-            with self._timed("allreduce"):
-                shard.all_reduce_sum(msg, self.process_group)
-            return msg[1 << n:], msg[: 1 << n]
-        r0, r1 = self._K_rows
-        if ws == 1:
-            if self.symmetric_contraction:      # K_p from our builder is bitwise symmetric: read half of it
-                return backend.stein_quadform_sym(self._K, q, n)
-            ksd2, Y = backend.stein_quadform(self._K, q, n, want_y=True)
-            return ksd2, Y[0]
-        # row shard: every rank contributes its rows of K q plus its partial of q.y in one all-gather
-        chunk = -(-(1 << n) // ws)
-        msg = torch.zeros(chunk + 1, dtype=torch.float64, device=q.device)
-        part = backend.stein_quadform_rows(self._K, r0, r1, q, n)
-        msg[: r1 - r0] = part[:-1]
-        msg[chunk] = part[-1]
-        full = torch.empty((ws, chunk + 1), dtype=torch.float64, device=q.device)
-        with self._timed("allreduce"):          # (an all-gather here: the row shard's exchange of K q rows)
-            shard.all_gather_flat(full.view(-1), msg, self.process_group)
-        y = full[:, :chunk].reshape(-1)[: 1 << n].contiguous()
-        ksd2 = full[:, chunk].sum().reshape(1)      # fixed rank order: identical on every rank
-        return ksd2, y
-
     # ---- one KSD-gradient step on the device -------------------------------------------------------------
     def ksd_and_grad(self, theta64=None):
         """Runs the device part of one epoch for the current theta: returns (loss [1] float64 on the GPU,
@@ -501,38 +251,10 @@ class KSDVariationalInference:
         if overlap is None:
             overlap = False
         if overlap == "partition":
-            main = torch.cuda.current_stream(dev)
             ncu = torch.cuda.get_device_properties(dev).multi_processor_count
             nc = ncu // 2
             sc, sa = backend.cu_range_stream(dev, 0, nc), backend.cu_range_stream(dev, nc, ncu - nc)
-            start = torch.cuda.Event()
-            start.record(main)                      # theta64 is produced on the main stream
-            try:
-                with torch.cuda.stream(sa):
-                    sa.wait_event(start)
-                    backend.set_engine_option(dev, "circuit_cus", ncu - nc)
-                    with self._timed("base_circuit"):
-                        q = backend.paramshift_probs(at, n, L, theta64, 0, 0, include_base=True, ws_tag="base")[0]
-                    with self._timed("stein"):
-                        ksd2, y = self._stein_contract(q)
-                    stein_done = torch.cuda.Event()
-                    stein_done.record(sa)
-                with torch.cuda.stream(sc):
-                    sc.wait_event(start)
-                    backend.set_engine_option(dev, "circuit_cus", nc)
-                    with self._timed("circuits"):
-                        shifted = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=False, p_stride=step,
-                                                           ws_tag="part")
-                    circ_done = torch.cuda.Event()
-                    circ_done.record(sc)
-            finally:
-                backend.set_engine_option(dev, "circuit_cus", 0)
-            main.wait_event(stein_done)
-            main.wait_event(circ_done)
-            for tns in (ksd2, y, q, shifted):
-                tns.record_stream(main)
-            theta64.record_stream(sa)
-            theta64.record_stream(sc)
+            q, ksd2, y, shifted = self._overlapped(theta64, lo, hi, step, sa, sc, cus=(ncu - nc, nc))
         elif not overlap and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
             # The dot product with dL/dq fused into the shifted circuits' last pass (kernels_circuit8.hip): base circuit
             # and all but the last pass of the shifted ones -> q -> contraction -> last pass of the shifted circuits with
@@ -557,31 +279,60 @@ class KSDVariationalInference:
             # The contraction needs only q of the base circuit, the shifted circuits need neither: the base
             # circuit and then the contraction run on a second HIP stream while the 2P shifted circuits run on
             # the main one (they are bound by different resources: HBM vs LDS/FMA + HBM).
-            main = torch.cuda.current_stream(dev)
             if self._aux_stream is None:
                 self._aux_stream = torch.cuda.Stream(device=dev)
-            aux = self._aux_stream
-            start = torch.cuda.Event()
-            start.record(main)                      # theta64 is produced on the main stream
-            with torch.cuda.stream(aux):
-                aux.wait_event(start)
-                with self._timed("base_circuit"):
-                    q = backend.paramshift_probs(at, n, L, theta64, 0, 0, include_base=True, ws_tag="base")[0]
-                with self._timed("stein"):
-                    ksd2, y = self._stein_contract(q)
-                stein_done = torch.cuda.Event()
-                stein_done.record(aux)
-            with self._timed("circuits"):
-                shifted = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=False, p_stride=step)
-            main.wait_event(stein_done)
-            for tns in (ksd2, y, q):
-                tns.record_stream(main)
-            theta64.record_stream(aux)
+            q, ksd2, y, shifted = self._overlapped(theta64, lo, hi, step, self._aux_stream)
         with self._timed("finish"):
             loss, grad_local, _ = backend.ksd_grad_finish(n, shifted, n_local, y, ksd2)
             with self._timed("allgather"):
                 grad = shard.all_gather_grad(grad_local, P, self.process_group)
         return loss, grad, q
+
+    def _overlapped(self, theta64, lo, hi, step, side, circ=None, cus=None):
+        """The two halves of a step that need nothing from each other, side by side: base circuit, then contraction, on the
+        stream `side`; the shifted circuits on the current stream or on `circ`; both after what the current stream holds and
+        joined on it again.  cus = ("circuit_cus" of `side`, of `circ`) for two CU-masked streams.  -> (q, ksd2, y, shifted)."""
+        bm = self.born_machine
+        n, L, at = self.num_latent_vars, bm.ansatz_layers, bm.ansatz_type
+        dev = theta64.device
+        main = torch.cuda.current_stream(dev)
+        start = torch.cuda.Event()
+        start.record(main)                      # theta64 is produced on the main stream
+        try:
+            with torch.cuda.stream(side):
+                side.wait_event(start)
+                if cus is not None:
+                    backend.set_engine_option(dev, "circuit_cus", cus[0])
+                with self._timed("base_circuit"):
+                    q = backend.paramshift_probs(at, n, L, theta64, 0, 0, include_base=True, ws_tag="base")[0]
+                with self._timed("stein"):
+                    ksd2, y = self._stein_contract(q)
+                stein_done = torch.cuda.Event()
+                stein_done.record(side)
+            if circ is None:
+                with self._timed("circuits"):
+                    shifted = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=False, p_stride=step)
+            else:
+                with torch.cuda.stream(circ):
+                    circ.wait_event(start)
+                    backend.set_engine_option(dev, "circuit_cus", cus[1])
+                    with self._timed("circuits"):
+                        shifted = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=False, p_stride=step,
+                                                           ws_tag="part")
+                    circ_done = torch.cuda.Event()
+                    circ_done.record(circ)
+        finally:
+            if cus is not None:
+                backend.set_engine_option(dev, "circuit_cus", 0)
+        main.wait_event(stein_done)
+        for tns in (ksd2, y, q):
+            tns.record_stream(main)
+        theta64.record_stream(side)
+        if circ is not None:
+            main.wait_event(circ_done)
+            shifted.record_stream(main)
+            theta64.record_stream(circ)
+        return q, ksd2, y, shifted
 
     def _ksd_and_grad_shots(self, theta64, lo, hi, step, n_local):
         """ksd_and_grad with finite shots: the un-fused batch (base row, then the (+p, -p) rows of this rank's parameters),

@@ -266,7 +266,7 @@ def test_async_step_equals_sync_step_and_guards_on_device(dev):
     runs = []
     for use_async in (False, True):
         vi = make_vi(bn, ['C', 'S', 'R'], ['W'], 3, 2, "hardware_efficient", "cuda:0", seed=11)
-        vi._prepare_stein(x, announce=False) if 'announce' in vi._prepare_stein.__code__.co_varnames else vi._prepare_stein(x)
+        vi._prepare_stein(x)
         params, opt, sched = vi.make_optimizer(0.05, 5, True, "adam", (0.9, 0.999))
         losses, norms = [], []
         for _ in range(5):

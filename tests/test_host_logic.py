@@ -369,6 +369,53 @@ def test_trainer_rejects_mismatched_latent_count():
         KSDVariationalInference(get_sprinkler_network(False), ['C', 'S', 'R'], ['W'], qbm_num_latent_vars=4)
 
 
+@pytest.mark.parametrize("mode,n,dense", [("auto", 1, True), ("auto", 12, True), ("auto", 16, True), ("auto", 17, False),
+                                          ("auto", 29, False), ("dense", 12, True), ("dense", 17, True), ("kron", 3, False),
+                                          ("kron", 16, False)])
+def test_gram_layout_from_plain_values(mode, n, dense):
+    """The form of K_p that _prepare_stein settles and the contraction follows, for every rank of 1 ... 8: "auto" is dense
+    up to n = 16, "dense" / "kron" override; one rank: symmetric or full; several ranks: strip pairs exactly where
+    backend.sym_pair_shard cuts 2^n into whole pairs (symmetric contraction only), else row blocks."""
+    from tensornetworks_amd import backend
+    from tensornetworks_amd.stein_operator import gram_layout
+    for symmetric in (True, False):
+        for W in (1, 2, 3, 4, 8):
+            for rank in range(W):
+                if not dense:
+                    want = "kron"
+                elif W == 1:
+                    want = "sym" if symmetric else "full"
+                elif symmetric and backend.sym_pair_shard(n, rank, W) is not None:
+                    want = "pairs"
+                else:
+                    want = "rows"
+                assert gram_layout(mode, n, symmetric, rank, W) == want, (symmetric, rank, W)
+
+
+def test_stein_state_is_set_by_the_constructors():
+    """Every attribute the Stein path reads exists right after construction, without a GPU: on a SteinOperator of its
+    own, on the quantum trainer (which derives from it) and on the classical trainer's operator."""
+    from tensornetworks_amd.bayesian_network import get_sprinkler_network
+    from tensornetworks_amd.ksd_vi import KSDVariationalInference as ClassicalKSD
+    from tensornetworks_amd.ksd_vi_quantum import KSDVariationalInference as QuantumKSD
+    from tensornetworks_amd.stein_operator import SteinOperator
+    bn, lat, obs = get_sprinkler_network(False), ['C', 'S', 'R'], ['W']
+    classical = ClassicalKSD(bn, lat, obs, born_machine_config={'use_logits': True, 'conditioning_dim': 0})
+    quantum = QuantumKSD(bn, lat, obs, qbm_num_latent_vars=3)
+    assert isinstance(quantum, SteinOperator) and type(classical._stein) is SteinOperator
+    for op in (SteinOperator(bn, lat, 1.0, "cpu"), quantum, classical._stein):
+        state = vars(op)
+        for name in ("_S", "_K", "_K_rows", "_K_pairs", "_K_sig", "_stein_key", "gram_placement", "timers"):
+            assert name in state and state[name] is None, name
+        assert state["gram_placement_tries"] == 4 and state["symmetric_contraction"] is True
+        assert state["_score_function_cache"] == {} and state["num_latent_vars"] == 3
+        assert op.gram_mode == "auto" and op.base_kernel_length_scale == 1.0 and op.latent_vars_names == lat
+    with pytest.raises(ValueError, match="gram_mode must be 'auto', 'dense' or 'kron'"):
+        SteinOperator(bn, lat, 1.0, "cpu", gram_mode="sparse")
+    with pytest.raises(ValueError, match="gram_mode must be 'auto', 'dense' or 'kron'"):
+        QuantumKSD(bn, lat, obs, qbm_num_latent_vars=3, gram_mode="sparse")
+
+
 def test_bench_refuses_a_world_size_that_is_not_gpus(monkeypatch):
     """bench.py --gpus N under a launcher that started a different number of ranks exits non-zero (before any GPU call)
     instead of measuring the wrong job with a note on stderr."""

@@ -40,7 +40,7 @@ def measure(n, epochs, warmup):
     torch.manual_seed(0)
     bn, lat, obs, x = synthetic_network(n, 0)
     vi = KSDVariationalInference(bn, lat, obs, {'use_logits': True, 'conditioning_dim': 0}, device="cuda:0")
-    vi._stein._prepare_stein(x, announce=False)
+    vi._stein._prepare_stein(x)
     opt, sched = vi.make_optimizer(0.01, epochs + warmup)
     params = list(vi.born_machine.parameters())
 

@@ -1,6 +1,6 @@
 """Per-kernel averages over the TRAINING STEPS of a rocprofv3 --kernel-trace CSV.  rocprofv3 --stats averages over every
-dispatch of the process, i.e. also the contractions _place_gram times on the K_p copies it does not keep; this lists,
-per kernel, the dispatches that sit between the first circuit pass of a step and its optimiser update:
+dispatch of the process, i.e. also the contractions SteinOperator._place_gram times on the K_p copies it does not keep;
+this lists, per kernel, the dispatches that sit between the first circuit pass of a step and its optimiser update:
   python tools/trace_step_stats.py 'gpurun_out/prof_x/**/*kernel_trace.csv' > profiles/..._kernel_stats_in_step.csv"""
 import csv
 import glob
