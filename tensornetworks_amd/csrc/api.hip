@@ -5,7 +5,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -516,10 +515,6 @@ int bornvi_create(int device_ordinal, bornvi_handle* out) {
   bornvi_ctx* h = new (std::nothrow) bornvi_ctx();
   if (!h) { g_create_error = "out of host memory"; return BORNVI_ERR_INVALID; }
   h->device = device_ordinal;
-  // (A/B switches for whole test / bench runs; bornvi_set_option "reg_wires" / "read_map" are the per-handle form)
-  if (const char* e = std::getenv("BORNVI_REG_WIRES")) { if (e[0] == '3' || e[0] == '4') h->opt.r = e[0] - '0'; }
-  if (const char* e = std::getenv("BORNVI_CONTIG_OUT")) h->opt.contig_out = e[0] != '0';
-  if (const char* e = std::getenv("BORNVI_READ_MAP")) h->opt.read_map = e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1);
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0)
     h->num_cus = prop.multiProcessorCount;

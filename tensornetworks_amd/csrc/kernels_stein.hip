@@ -5,10 +5,8 @@
 //
 // Index convention: outcome index i <-> tuple z with z[b] = (i >> (n-1-b)) & 1 (utils.py:77-91).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 
 #include <cmath>
-#include <type_traits>
 
 #include "kernels.hpp"
 
@@ -132,175 +130,35 @@ static hipError_t launch_gram_nb(const double* S, double* K, const PowTable& apo
 // ------------------------------------------------------------------------------------------------
 // dense Gram on the matrix cores (n >= 8).  The bracket of the closed form above is a rank-(3n+2) bilinear
 // form in (i, j): with U_ib = T_ib (1 - 2 i_b) and alpha_i = -c_same sum_b T_ib - dc sum_b i_b T_ib,
-//   bracket = sum_b S_ib S_jb  +  sum_b (-dc U_ib) j_b  +  sum_b i_b (-dc U_jb)  +  (alpha_i + alpha_j)
-// i.e. three small GEMMs, run as chains of v_mfma_f64_16x16x4_f64 on 16 x 16 tiles.  They are kept in three
-// separate accumulators and combined as (acc1 + (acc2 + acc3)) + (alpha_i + alpha_j): acc1 is symmetric term
-// by term and acc2(i, j) == acc3(j, i) operation by operation, so K stays BITWISE symmetric (the symmetric
-// contraction relies on it).  a^d is applied in the epilogue.  HBM-write bound: 8 * 4^n bytes.
-// Workgroup = 4 waves, GM_ROWS rows x GM_COLS columns; the row factors sit in LDS for the whole workgroup, each
-// wave walks over 16-column tiles of its share, whose column factors it builds in its own LDS scratch.
+//   bracket = sum_b S_ib S_jb  +  sum_b (-dc U_ib) j_b  +  sum_b i_b (-dc U_jb)  +  (alpha_i + alpha_j).
+// Only the first product runs on the matrix cores (chains of v_mfma_f64_16x16x4_f64 on 16 x 16 tiles); a^d is
+// applied in the epilogue.
 // Fragment layout of the f64 MFMA (cdna_hip_programming.md, section 3): A[row = lane & 15][k = lane >> 4],
 // B[k = lane >> 4][col = lane & 15], D[row = (lane >> 4) + 4 r][col = lane & 15], r = 0..3.
 // ------------------------------------------------------------------------------------------------
 constexpr int GM_ROWS = 64, GM_COLS = 2048, GM_MAXN = 17;
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
-struct GramFactorPitch {
-  int np, p, rowpitch;   // padded K of each of the three products; LDS pitch of one factor row; of one outcome
-};
-__host__ __device__ constexpr GramFactorPitch gram_pitch(int n) {
-  GramFactorPitch g{};
-  g.np = (n + 3) / 4 * 4;
-  g.p = g.np + 2;              // pitch = 2 (mod 4): the 16 rows x 2 k's a half-wave reads hit 32 distinct 8-byte banks
-  g.rowpitch = 3 * g.p + 4;    // F1 | F2 | F3 | alpha, again 2 (mod 4)
-  return g;
-}
-
-// the n scores of outcome z, all loads issued together (the column side fetches them one tile ahead)
+// the n scores of outcome z, all loads issued together
 template <int n>
 __device__ __forceinline__ void gram_load_scores(const double* __restrict__ S, long long z, double (&sv)[GM_MAXN]) {
 #pragma unroll
   for (int b = 0; b < GM_MAXN; ++b) sv[b] = (b < n) ? S[z * n + b] : 0.0;
 }
 
-// factors of one outcome index z into its LDS row: F1 = S_z,  F2 = -dc U_z,  F3 = bits(z) (each padded with zeros),
-// then alpha_z.  Row side and column side use this same function: alpha_z must be the same bits on both sides.
-template <int n>
-__device__ __forceinline__ void gram_factors(const double (&sv)[GM_MAXN], long long z, double c_same, double dc,
-                                             double* __restrict__ row) {
-  constexpr GramFactorPitch g = gram_pitch(n);
-  double rt = 0.0, ab = 0.0;
-#pragma unroll
-  for (int b = 0; b < g.np; ++b) {
-    if (b < n) {
-      const double t = sv[b] - 1.0;
-      const int bit = (int)((z >> (n - 1 - b)) & 1ll);
-      rt += t;
-      ab += bit ? t : 0.0;
-      row[b] = sv[b];
-      row[g.p + b] = -dc * (bit ? -t : t);
-      row[2 * g.p + b] = bit ? 1.0 : 0.0;
-    } else {
-      row[b] = 0.0; row[g.p + b] = 0.0; row[2 * g.p + b] = 0.0;
-    }
-  }
-  row[3 * g.p] = -c_same * rt - dc * ab;
-}
-
-template <int n>
-__global__ __launch_bounds__(256) void gram_mfma_kernel(const double* __restrict__ S, double* __restrict__ K,
-                                                        PowTable apow, double c_same, double dc, long long row_begin,
-                                                        long long row_end, long long ld) {
-  extern __shared__ double gm_lds[];
-  __shared__ double apow_s[33];
-  constexpr GramFactorPitch g = gram_pitch(n);
-  constexpr int KK = g.np / 4;                          // MFMAs per product and tile
-  const long long N = 1ll << n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double* __restrict__ Lt = gm_lds;                      // [GM_ROWS][rowpitch]
-  double* __restrict__ Rt = gm_lds + GM_ROWS * g.rowpitch + wave * 16 * g.rowpitch;   // this wave's [16][rowpitch]
-  if (threadIdx.x < 33) apow_s[threadIdx.x] = apow.v[threadIdx.x];
-  const long long i_blk = row_begin + (long long)blockIdx.y * GM_ROWS;
-  if (threadIdx.x < GM_ROWS) {
-    const long long i = i_blk + threadIdx.x;
-    double* r = Lt + threadIdx.x * g.rowpitch;
-    if (i < row_end) {
-      double sv[GM_MAXN];
-      gram_load_scores<n>(S, i, sv);
-      gram_factors<n>(sv, i, c_same, dc, r);
-    } else {
-      for (int b = 0; b < g.rowpitch; ++b) r[b] = 0.0;
-    }
-  }
-  __syncthreads();
-  const long long j_chunk = (long long)blockIdx.x * GM_COLS;
-  const long long j_chunk_end = (j_chunk + GM_COLS < N) ? j_chunk + GM_COLS : N;
-  const int ar = lane & 15, ak = lane >> 4;
-  double svn[GM_MAXN];     // scores of the NEXT column tile (lanes 0..15), in flight during this tile's MFMAs
-  long long j0 = j_chunk + wave * 16;
-  if (lane < 16 && j0 < j_chunk_end) gram_load_scores<n>(S, j0 + lane, svn);
-  for (; j0 < j_chunk_end; j0 += 64) {
-    // column factors of this 16-column tile -> the wave's scratch (lanes 0..15 one column each)
-    if (lane < 16) {
-      gram_factors<n>(svn, j0 + lane, c_same, dc, Rt + lane * g.rowpitch);
-      if (j0 + 64 < j_chunk_end) gram_load_scores<n>(S, j0 + 64 + lane, svn);
-    }
-    __builtin_amdgcn_wave_barrier();
-    // B fragments of the three products (column side), kept in registers across the row tiles
-    double b1[KK], b2[KK], b3[KK];
-    const double* rj = Rt + ar * g.rowpitch;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      b1[kk] = rj[4 * kk + ak];
-      b2[kk] = rj[2 * g.p + 4 * kk + ak];   // pairs with the row side's F2: bits(j)
-      b3[kk] = rj[g.p + 4 * kk + ak];       // pairs with the row side's F3: -dc U_j
-    }
-    const double alpha_j = rj[3 * g.p];
-    const long long j = j0 + ar;
-#pragma unroll 1
-    for (int it = 0; it < GM_ROWS / 16; it += 2) {   // two row tiles at a time: six independent MFMA chains
-      const double* ri0 = Lt + (it * 16 + ar) * g.rowpitch;
-      const double* ri1 = ri0 + 16 * g.rowpitch;
-      d4_t a1 = {0.0, 0.0, 0.0, 0.0}, a2 = a1, a3 = a1, c1 = a1, c2 = a1, c3 = a1;
-#pragma unroll
-      for (int kk = 0; kk < KK; ++kk) {
-        a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri0[4 * kk + ak], b1[kk], a1, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri1[4 * kk + ak], b1[kk], c1, 0, 0, 0);
-        a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri0[g.p + 4 * kk + ak], b2[kk], a2, 0, 0, 0);
-        c2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri1[g.p + 4 * kk + ak], b2[kk], c2, 0, 0, 0);
-        a3 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri0[2 * g.p + 4 * kk + ak], b3[kk], a3, 0, 0, 0);
-        c3 = __builtin_amdgcn_mfma_f64_16x16x4f64(ri1[2 * g.p + 4 * kk + ak], b3[kk], c3, 0, 0, 0);
-      }
-      // D layout: row = (lane >> 4) + 4 r, col = lane & 15
-      const long long ib = i_blk + it * 16 + ak;
-      const double* al0 = Lt + (it * 16 + ak) * g.rowpitch + 3 * g.p;   // alpha of row ak + 4 r: + 4 r rowpitch
-      double* __restrict__ Kp = K + (ib - row_begin) * ld + j;
-      if (i_blk + GM_ROWS <= row_end) {     // whole row block inside the range (wave-uniform): no per-row tests
-        double w0[4], w1[4], e0[4], e1[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          w0[r] = apow_s[__popcll((unsigned long long)((ib + 4 * r) ^ j))];
-          w1[r] = apow_s[__popcll((unsigned long long)((ib + 16 + 4 * r) ^ j))];
-          e0[r] = al0[4 * r * g.rowpitch] + alpha_j;
-          e1[r] = al0[(16 + 4 * r) * g.rowpitch] + alpha_j;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          __builtin_nontemporal_store(w0[r] * ((a1[r] + (a2[r] + a3[r])) + e0[r]), Kp + (long long)(4 * r) * ld);
-          __builtin_nontemporal_store(w1[r] * ((c1[r] + (c2[r] + c3[r])) + e1[r]), Kp + (long long)(16 + 4 * r) * ld);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long long i = ib + 4 * r;
-          if (i < row_end)
-            K[(i - row_begin) * ld + j] = apow_s[__popcll((unsigned long long)(i ^ j))] *
-                                         ((a1[r] + (a2[r] + a3[r])) + (al0[4 * r * g.rowpitch] + alpha_j));
-          if (i + 16 < row_end)
-            K[(i + 16 - row_begin) * ld + j] = apow_s[__popcll((unsigned long long)((i + 16) ^ j))] *
-                                              ((c1[r] + (c2[r] + c3[r])) + (al0[(16 + 4 * r) * g.rowpitch] + alpha_j));
-        }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();     // the scratch is rewritten by the next tile
-  }
-}
-
-// ---- the shipped form: ONE matrix product per tile, the two bit products from tables ------------------------------
 // Measured on gfx950 (tools/probes/mfma64_probe.hip): v_mfma_f64_16x16x4_f64 holds the SIMD's vector ALU for its 64
 // cycles -- no vector instruction of ANY wave on that SIMD issues beside it (6 MFMAs + 96 v_add_u32 on a second wave
-// take the sum of their times, not the maximum).  So gram_mfma_kernel's time is its 12 MFMAs (768 cycles per tile)
-// PLUS its epilogue (timing-only builds: 6.1 + 3.9 of 10.2 ms at n = 16), software pipelining changes nothing (built,
-// measured, bit-identical, 10.1 ms), and the way down is fewer vector-pipe cycles per tile.  The two products with the
-// 0/1 matrices need no matrix instruction: with the outcome index split into its tile part T (bits >= 4) and its
-// in-tile part c (low 4 bits),
+// take the sum of their times, not the maximum).  So running all three products on the matrix cores cost 12 MFMAs
+// (768 cycles per tile) PLUS the epilogue (6.1 + 3.9 of 10.2 ms at n = 16), software pipelining changed nothing, and
+// the way down is fewer vector-pipe cycles per tile.  The two products with the 0/1 matrices need no matrix
+// instruction: with the outcome index split into its tile part T (bits >= 4) and its in-tile part c (low 4 bits),
 //     X(z, t) := sum_b G_zb t_b = PH(z, T) + PL(z, c),        G_zb = -dc U_zb,
 // PH(z, T) is one number per (outcome, 16-wide tile of the other index) and PL(z, c) one of 16 per outcome, and
 //     K(i, j) = a^d(i,j) * ( (acc1 + (PL(i, c_j) + PL(j, c_i))) + (A(i, T_j) + A(j, T_i)) ),   A(z, T) = PH(z, T) + alpha_z.
 // Every term is either symmetric in (i, j) or one of a pair added commutatively, and PH / PL / alpha are computed by
 // the same instruction sequence whichever side z is on: K stays BITWISE symmetric.  Per tile: 4 MFMAs (acc1) and
 // ~60 vector instructions instead of 12 and ~75; HBM-write bound from here (8 * 4^n bytes).
-// Workgroup = 4 waves x (64 aligned rows) x GM_COLS columns; rows outside [row_begin, row_end) are computed and not stored.
+// Workgroup = 4 waves x (GM_ROWS aligned rows) x GM_COLS columns; rows outside [row_begin, row_end) are computed and not stored.
 template <int n>
 struct GramV3 {
   static constexpr int NP = (n + 3) / 4 * 4;            // scores padded to the MFMA's k = 4
@@ -375,9 +233,8 @@ __device__ __forceinline__ double gram_v3_pl(const double (&G)[GM_MAXN], double 
   return __builtin_fma(G[n - 1], m0, acc);
 }
 
-// the walk of one wave over its column tiles (R rows per workgroup; GUARD: the block sticks out of [row_begin, row_end):
-// per-row store tests)
-template <int n, int R, bool GUARD>
+// the walk of one wave over its column tiles (GUARD: the block sticks out of [row_begin, row_end): per-row store tests)
+template <int n, bool GUARD>
 __device__ __forceinline__ void gram_tables_columns(const double* __restrict__ S, const double* __restrict__ GA,
                                                     const double* __restrict__ Lt_, double* __restrict__ AJ,
                                                     const double* __restrict__ apow_s, int lane, const int (&wslot)[4],
@@ -386,9 +243,9 @@ __device__ __forceinline__ void gram_tables_columns(const double* __restrict__ S
                                                     long long row_begin, long long row_end, int ar, int ak) {
   using L = GramV3<n>;
   constexpr int KK = L::KK, NH = L::NH, PITCH = L::PITCH;
-  constexpr int RT = R / 16;                            // row tiles of the block
-  constexpr int NV = RT == 8 ? 3 : (RT == 4 ? 2 : 1);   // tile bits that differ between them
-  static_assert(RT == 8 || RT == 4, "64 or 128 rows per workgroup");
+  constexpr int RT = GM_ROWS / 16;                      // row tiles of the block
+  constexpr int NV = 2;                                 // tile bits that differ between them
+  static_assert(RT == 1 << NV, "the block's row tiles differ in their last NV tile bits");
   // two register sets for the column factors: a tile works on one while the next tile's loads land in the other (a
   // single set rotated through copies cost 44 register moves per column tile)
   double Ga[GM_MAXN], Gb[GM_MAXN], alpha_a, alpha_b, ba[KK], bb[KK];
@@ -409,10 +266,10 @@ __device__ __forceinline__ void gram_tables_columns(const double* __restrict__ S
     double PLc[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) PLc[r] = gram_v3_pl<n>(G, (r & 2) ? 1.0 : 0.0, (r & 1) ? 1.0 : 0.0, mk1, mk0);
-    // row side: A(row, J) of the lane's own rows (lane, lane + 64, ...: their G from LDS), handed to the lanes that need
-    // them through the wave's scratch
+    // row side: A(row, J) of the lane's own rows (row = lane: its G from LDS), handed to the lanes that need them through
+    // the wave's scratch (one trip at 64 rows; written as a loop, which the compiler schedules differently from the bare body)
 #pragma unroll
-    for (int h = 0; h < R / 64; ++h) {
+    for (int h = 0; h < GM_ROWS / 64; ++h) {
       const int row = lane + 64 * h;
       const double* gr = Lt + row * PITCH + L::OFF_G;
       double Gr[GM_MAXN];
@@ -459,7 +316,7 @@ __device__ __forceinline__ void gram_tables_columns(const double* __restrict__ S
   }
 }
 
-template <int n, int R>
+template <int n>
 __global__ __launch_bounds__(256, 2) void gram_tables_kernel(const double* __restrict__ S, double* __restrict__ K,
                                                             const double* __restrict__ GA, PowTable apow, double c_same,
                                                             double dc, long long row_begin, long long row_end, long long ld) {
@@ -470,11 +327,11 @@ __global__ __launch_bounds__(256, 2) void gram_tables_kernel(const double* __res
   const long long N = 1ll << n;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  double* __restrict__ Lt = gm_lds;                        // [R][PITCH]
-  double* __restrict__ AJ = gm_lds + R * PITCH + wave * R;   // this wave's A(row, J), in [row tile][ak][r] order
+  double* __restrict__ Lt = gm_lds;                        // [GM_ROWS][PITCH]
+  double* __restrict__ AJ = gm_lds + GM_ROWS * PITCH + wave * GM_ROWS;   // this wave's A(row, J), in [row tile][ak][r] order
   if (threadIdx.x < 40) apow_s[threadIdx.x] = threadIdx.x < 33 ? apow.v[threadIdx.x] : 0.0;
-  const long long i_blk = (row_begin & ~(long long)(R - 1)) + (long long)blockIdx.y * R;   // R-aligned
-  if (threadIdx.x < R) {
+  const long long i_blk = (row_begin & ~(long long)(GM_ROWS - 1)) + (long long)blockIdx.y * GM_ROWS;   // GM_ROWS-aligned
+  if (threadIdx.x < GM_ROWS) {
     const long long i = i_blk + threadIdx.x;
     double sv[GM_MAXN], G[GM_MAXN], alpha;
     gram_load_scores<n>(S, i, sv);
@@ -500,69 +357,39 @@ __global__ __launch_bounds__(256, 2) void gram_tables_kernel(const double* __res
   for (int r = 0; r < 4; ++r) wslot[r] = __popc((unsigned)((ak + 4 * r) ^ ar));
   const double mk1 = (ak & 2) ? 1.0 : 0.0, mk0 = (ak & 1) ? 1.0 : 0.0;     // low bits of this lane's rows ak + 4 r
   const unsigned voff = (unsigned)(((long long)ak * ld + ar) * 8);
-  const bool whole = i_blk >= row_begin && i_blk + R <= row_end;            // (uniform) no per-row tests
+  const bool whole = i_blk >= row_begin && i_blk + GM_ROWS <= row_end;      // (uniform) no per-row tests
   const long long I0 = i_blk >> 4;                     // tile index of row tile 0
   double* __restrict__ Kblk = K + (i_blk - row_begin) * ld;                 // (not dereferenced for rows outside the range)
   if (whole)
-    gram_tables_columns<n, R, false>(S, GA, Lt, AJ, apow_s, lane, wslot, mk1, mk0, voff, i_blk, I0, Kblk, ld, j0, j_chunk_end,
-                                     row_begin, row_end, ar, ak);
+    gram_tables_columns<n, false>(S, GA, Lt, AJ, apow_s, lane, wslot, mk1, mk0, voff, i_blk, I0, Kblk, ld, j0, j_chunk_end,
+                                  row_begin, row_end, ar, ak);
   else
-    gram_tables_columns<n, R, true>(S, GA, Lt, AJ, apow_s, lane, wslot, mk1, mk0, voff, i_blk, I0, Kblk, ld, j0, j_chunk_end,
-                                    row_begin, row_end, ar, ak);
+    gram_tables_columns<n, true>(S, GA, Lt, AJ, apow_s, lane, wslot, mk1, mk0, voff, i_blk, I0, Kblk, ld, j0, j_chunk_end,
+                                 row_begin, row_end, ar, ak);
 }
 
 template <int NB>
-static hipError_t launch_gram_mfma_nb(const double* S, double* K, const PowTable& apow, double c_same, double dc,
-                                      long long row_begin, long long row_end, long long ld, hipStream_t st) {
+static hipError_t launch_gram_tables_nb(const double* S, double* K, const PowTable& apow, double c_same, double dc,
+                                        long long row_begin, long long row_end, long long ld, hipStream_t st) {
   const long long N = 1ll << NB;
   if (row_end <= row_begin) return hipSuccess;
-  constexpr GramFactorPitch g = gram_pitch(NB);
-  const size_t lds = (size_t)(GM_ROWS + 4 * 16) * g.rowpitch * sizeof(double);
-  {   // (per device and cheap: set on every launch rather than behind a process-wide flag)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gram_mfma_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  // (64 rows per workgroup: 128 halves the column side's work per tile and measured the same at n = 16 -- 6.9 ms both:
+  // with the tables the kernel waits for its stores, 6.9 ms without the MFMAs too, 6.1 ms without the stores -- and
+  // slower for small matrices, n = 9: 47 against 37 us)
   const long long cols = N < GM_COLS ? N : GM_COLS;
-  // BORNVI_GRAM_TABLES=0: the three-product kernel (A/B; one process builds every matrix with one of the two -- their
-  // roundings differ, and K's two triangles must come from the same arithmetic)
-  static const bool tables = [] { const char* e = getenv("BORNVI_GRAM_TABLES"); return !(e && e[0] == '0'); }();
-  if (tables) {
-    // rows per workgroup: 64.  128 (BORNVI_GRAM_ROWS=128, A/B) halves the column side's work per tile and measures the
-    // same at n = 16 (6.9 ms both: with the tables the kernel waits for its stores -- 6.9 ms without the MFMAs too, 6.1 ms
-    // without the stores) and slower for small matrices (n = 9: 47 against 37 us)
-    static const bool rows64 = [] { const char* e = getenv("BORNVI_GRAM_ROWS"); return !(e && e[0] == '1'); }();
-    double* GA = nullptr;                 // stream-ordered scratch: (n + 1) 2^n doubles (8.9 MB at n = 16)
-    hipError_t e = hipMallocAsync((void**)&GA, (size_t)(NB + 1) * (size_t)N * sizeof(double), st);
-    if (e != hipSuccess) return e;
-    gram_prep_kernel<NB><<<(unsigned)((N + 255) / 256), 256, 0, st>>>(S, c_same, dc, GA);
-    auto run = [&](auto rows_tag) -> hipError_t {
-      constexpr int R = decltype(rows_tag)::value;
-      const size_t lds3 = (size_t)(R * GramV3<NB>::PITCH + 4 * R) * sizeof(double);
-      hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(gram_tables_kernel<NB, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      if (e1 != hipSuccess) return e1;
-      const long long first = row_begin & ~(long long)(R - 1);
-      dim3 grid((unsigned)((N + cols - 1) / cols), (unsigned)((row_end - first + R - 1) / R));
-      gram_tables_kernel<NB, R><<<grid, 256, lds3, st>>>(S, K, GA, apow, c_same, dc, row_begin, row_end, ld);
-      return hipGetLastError();
-    };
-    e = (rows64 || NB < 9) ? run(std::integral_constant<int, 64>{}) : run(std::integral_constant<int, 128>{});
-    hipError_t e2 = hipFreeAsync(GA, st);
-    return e != hipSuccess ? e : e2;
-  }
-  dim3 grid((unsigned)((N + cols - 1) / cols), (unsigned)((row_end - row_begin + GM_ROWS - 1) / GM_ROWS));
-  gram_mfma_kernel<NB><<<grid, 256, lds, st>>>(S, K, apow, c_same, dc, row_begin, row_end, ld);
-  return hipGetLastError();
-}
-
-static hipError_t launch_gram_mfma(int n, const double* S, double* K, const PowTable& apow, double c_same, double dc,
-                                   long long row_begin, long long row_end, long long ld, hipStream_t st) {
-  switch (n) {
-#define BORNVI_GM_CASE(NB) case NB: return launch_gram_mfma_nb<NB>(S, K, apow, c_same, dc, row_begin, row_end, ld, st);
-    BORNVI_GM_CASE(8) BORNVI_GM_CASE(9) BORNVI_GM_CASE(10) BORNVI_GM_CASE(11) BORNVI_GM_CASE(12) BORNVI_GM_CASE(13)
-    BORNVI_GM_CASE(14) BORNVI_GM_CASE(15) BORNVI_GM_CASE(16) BORNVI_GM_CASE(17)
-#undef BORNVI_GM_CASE
-    default: return hipErrorInvalidValue;
-  }
+  const size_t lds = (size_t)(GM_ROWS * GramV3<NB>::PITCH + 4 * GM_ROWS) * sizeof(double);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gram_tables_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  double* GA = nullptr;                 // stream-ordered scratch: (n + 1) 2^n doubles (8.9 MB at n = 16)
+  e = hipMallocAsync((void**)&GA, (size_t)(NB + 1) * (size_t)N * sizeof(double), st);
+  if (e != hipSuccess) return e;
+  gram_prep_kernel<NB><<<(unsigned)((N + 255) / 256), 256, 0, st>>>(S, c_same, dc, GA);
+  const long long first = row_begin & ~(long long)(GM_ROWS - 1);
+  dim3 grid((unsigned)((N + cols - 1) / cols), (unsigned)((row_end - first + GM_ROWS - 1) / GM_ROWS));
+  gram_tables_kernel<NB><<<grid, 256, lds, st>>>(S, K, GA, apow, c_same, dc, row_begin, row_end, ld);
+  e = hipGetLastError();
+  hipError_t e2 = hipFreeAsync(GA, st);
+  return e != hipSuccess ? e : e2;
 }
 
 hipError_t launch_gram_build(int n, double length_scale, const double* S, double* K, long long row_begin,
@@ -573,16 +400,16 @@ hipError_t launch_gram_build(int n, double length_scale, const double* S, double
   const double a = apow.v[1];
   const double c_same = 1.0 - a, c_diff = 1.0 - 1.0 / a;
   const double dc = c_diff - c_same;
-  // matrix-core path for n >= 8 (2^n >= 256: whole 16 x 16 tiles); BORNVI_GRAM_VALU=1 keeps the VALU kernel (A/B)
-  static const bool force_valu = [] { const char* e = getenv("BORNVI_GRAM_VALU"); return e && e[0] == '1'; }();
-  if (n >= 8 && n <= GM_MAXN && !force_valu) return launch_gram_mfma(n, S, K, apow, c_same, dc, row_begin, row_end, ld, st);
+  // matrix-core path for n = 8 .. GM_MAXN (2^n >= 256: whole 16 x 16 tiles), the VALU kernel below that
   switch (n) {
 #define BORNVI_GRAM_CASE(NB) case NB: return launch_gram_nb<NB>(S, K, apow, c_same, dc, row_begin, row_end, ld, st);
     BORNVI_GRAM_CASE(1) BORNVI_GRAM_CASE(2) BORNVI_GRAM_CASE(3) BORNVI_GRAM_CASE(4) BORNVI_GRAM_CASE(5)
-    BORNVI_GRAM_CASE(6) BORNVI_GRAM_CASE(7) BORNVI_GRAM_CASE(8) BORNVI_GRAM_CASE(9) BORNVI_GRAM_CASE(10)
-    BORNVI_GRAM_CASE(11) BORNVI_GRAM_CASE(12) BORNVI_GRAM_CASE(13) BORNVI_GRAM_CASE(14) BORNVI_GRAM_CASE(15)
-    BORNVI_GRAM_CASE(16) BORNVI_GRAM_CASE(17)
+    BORNVI_GRAM_CASE(6) BORNVI_GRAM_CASE(7)
 #undef BORNVI_GRAM_CASE
+#define BORNVI_GM_CASE(NB) case NB: return launch_gram_tables_nb<NB>(S, K, apow, c_same, dc, row_begin, row_end, ld, st);
+    BORNVI_GM_CASE(8) BORNVI_GM_CASE(9) BORNVI_GM_CASE(10) BORNVI_GM_CASE(11) BORNVI_GM_CASE(12) BORNVI_GM_CASE(13)
+    BORNVI_GM_CASE(14) BORNVI_GM_CASE(15) BORNVI_GM_CASE(16) BORNVI_GM_CASE(17)
+#undef BORNVI_GM_CASE
     default: return hipErrorInvalidValue;
   }
 }
@@ -996,8 +823,7 @@ hipError_t launch_quadform_sym_pairs(int n, const double* K_lo, const double* K_
   double* Z2 = Z1 + nb * SYM_WAVES * SYM_NEAR;
   const long long npairs = pair_end - pair_begin;
   int parts_log2 = 0;                                       // enough column pieces for two workgroups per CU
-  static const int min_wgs = [] { const char* e = getenv("BORNVI_SYM_MIN_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-  while ((1 << parts_log2) < SYM_MAX_PARTS && (npairs << parts_log2) < min_wgs * 4 / SYM_WAVES) ++parts_log2;
+  while ((1 << parts_log2) < SYM_MAX_PARTS && (npairs << parts_log2) < 512 * 4 / SYM_WAVES) ++parts_log2;
   const int nparts = 1 << parts_log2;
   if (npairs > 0) {
     quadform_sym_kernel<<<(unsigned)(npairs << parts_log2), 64 * SYM_WAVES, 0, st>>>(K_lo, K_hi, ld, pair_begin, pair_end, q, yrow,

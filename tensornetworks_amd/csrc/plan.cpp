@@ -1,7 +1,5 @@
 // Circuit execution planner -- see plan.hpp for the model.
 #include "plan.hpp"
-#include <cstdio>
-#include <cstdlib>
 
 #include <algorithm>
 #include <array>
@@ -666,17 +664,6 @@ bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::
       StageSel sel;
       stage_select(ops, pool, n, r, sel, rest, defer_cx3, opt.use_read_map());
       if (sel.count() == 0) { msg = "stage planner made no progress"; return false; }
-      if (getenv("BORNVI_PLAN_DEBUG")) {
-        auto show = [&](const char* nm, const std::vector<int>& v) {
-          fprintf(stderr, " %s[", nm);
-          for (int idx : v) fprintf(stderr, "%s%d%s ", ops[idx].kind == K_U1 ? "U" : (ops[idx].kind == K_CX ? "X" : "Z"), ops[idx].a,
-                                    ops[idx].b >= 0 ? (std::string(">") + std::to_string(ops[idx].b)).c_str() : "");
-          fprintf(stderr, "]");
-        };
-        fprintf(stderr, "pass %d stage %u:", i, nstages);
-        show("cx0", sel.pre_cx); show("cz1", sel.pre_cz); show("u", sel.us); show("cx3", sel.post_cx); show("cz4", sel.post_cz);
-        fprintf(stderr, "  rest %zu\n", rest.size());
-      }
       // register wires: targets, padded with local wires (highest LDS bits first)
       std::vector<char> isr(n, 0);
       std::vector<int> regw;   // wires carrying a fused U first (the fast kernel's stage kinds count them)

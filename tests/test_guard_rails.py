@@ -5,9 +5,11 @@
     cross-compiles here) and fails if the compiler touches a register whose load is still in flight;
   * the planner (plan.cpp) compiled with g++ -fsanitize=address,undefined and run over a sweep of configurations,
     its plans and fast tables compared word-hash for word-hash with the production library's;
-  * every stage kind the planner hands to the fast kernel is one the kernel has a specialised body for.
+  * every stage kind the planner hands to the fast kernel is one the kernel has a specialised body for;
+  * the library reads no environment variable: its results depend only on its arguments and its handle's options.
 """
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -26,6 +28,21 @@ def test_async_register_check_is_clean():
                        timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "0 problem(s)" in r.stdout and "prefetch loads checked" in r.stdout
+
+
+def test_library_reads_no_environment():
+    """No source of libbornvi_hip.so calls getenv: a variable in a job's environment must not change what the library
+    computes (per-handle settings go through bornvi_set_option)."""
+    calls = []
+    for root, dirs, files in os.walk(CSRC):
+        dirs[:] = [d for d in dirs if not d.startswith(("_", "."))]
+        for f in sorted(files):
+            if f.endswith((".hip", ".cpp", ".hpp")):
+                path = os.path.join(root, f)
+                for i, line in enumerate(open(path, encoding="utf-8"), 1):
+                    if re.search(r"getenv\s*\(", line):
+                        calls.append(f"{os.path.relpath(path, REPO)}:{i}: {line.strip()}")
+    assert not calls, "getenv in the library's sources:\n" + "\n".join(calls)
 
 
 def _fnv(words):
@@ -99,7 +116,7 @@ def test_fast_stage_kinds_are_the_kernels_twenty(ansatz, n, L, kb):
 
 def test_hot_kernels_stay_inside_their_register_budget():
     """The compiler's resource remarks of the last build (kept beside the objects by csrc/build.py): no scratch and no
-    VGPR spills in the contraction kernels, at most the set-up code's 20 bytes in the circuit engine.  A small source edit
+    VGPR spills in the contraction kernels and the Gram builder, at most the set-up code's 20 bytes in the circuit engine.  A small source edit
     has turned a 2.6 ms kernel into a 6.6 ms one this way, with identical results -- only the build can see it."""
     from tensornetworks_amd.csrc import build as b
     objs = [os.path.join(b.OBJ, s + ".o") for s in b.SOURCES]

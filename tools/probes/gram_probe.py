@@ -31,4 +31,4 @@ sym = bool(torch.equal(K[:4096, :4096], K[:4096, :4096].T)) and bool(torch.equal
 f = timed(lambda: buf.fill_(1.0))
 gb = N * N * 8 / 1e9
 print(f"lib={os.environ.get('BORNVI_LIB', 'shipped')} n={n} ld={ld} gram ms {[round(x, 3) for x in t]} -> {gb / min(t) * 1e3:.0f} GB/s"
-      f" | digest {digest} tables={os.environ.get('BORNVI_GRAM_TABLES', '1')} | fill ms {[round(x, 3) for x in f]} -> {N * ld * 8 / 1e9 / min(f) * 1e3:.0f} GB/s | sym {sym}")
+      f" | digest {digest} | fill ms {[round(x, 3) for x in f]} -> {N * ld * 8 / 1e9 / min(f) * 1e3:.0f} GB/s | sym {sym}")
