@@ -338,6 +338,26 @@ int bornvi_born_table_vjp(bornvi_handle h, int n, int rows, int mode, const floa
                           const double* y, const double* ksd2, double entropy_weight, float* grad,
                           double* loss_out, void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
+/* ---- classical Born machine, REINFORCE step of the adversarial (KL) trainer (replaces adversarial_vi.py:200-222 for
+ * one observation: raw reward, running baseline, log q of the samples, the loss with its entropy bonus, and the part of
+ * loss_q.backward() from the loss down to q, whose index-gather gradient is a scatter-add over the samples).
+ * idx dev [B] int64 sampled outcome indices; logit dev [B] float32 classifier logits of the samples; log_p dev [2^n]
+ * float32 = log p(x_obs | z) (may hold +-inf); q32 dev [2^n] float32 = the Born machine's probabilities.
+ *   raw_b = logit_b - log_p[idx_b];  mean = (1/B) sum raw_b;  baseline (dev [1] float64, in/out) = mean if first, else
+ *   baseline_decay * baseline + (1 - baseline_decay) * mean;  w_b = raw_b - baseline + entropy_coef;
+ *   loss dev [1] float32 = (1/B) sum_b log max(q32[idx_b], q_floor) * w_b;
+ *   dLdq dev [2^n] float64 = [q32[i] >= q_floor] * (sum of w_b over idx_b = i) / (B * q32[i]), 0 where no sample fell:
+ * the y of bornvi_born_table_vjp(..., ksd2 = NULL).  found_inf dev [1] float32 = 1 if the loss is NaN or +-Inf (then
+ * loss = NaN and dLdq = 0), else 0: the flag torch's fused optimisers consume.  The per-outcome sums are 64-bit
+ * fixed-point integer sums (kernels_reinforce.hip states the scale and its error bound) and the means fixed-order
+ * partials in the workspace: bitwise reproducible.  An index outside [0, 2^n) is not dereferenced and counts as a sample
+ * of reward 0 on no outcome.  1 <= n <= 30, 1 <= B <= 2^24.  No allocation or synchronisation (capturable). */
+size_t bornvi_reinforce_workspace_bytes(bornvi_handle h, int n, long long B);
+int bornvi_reinforce_step(bornvi_handle h, int n, long long B, const long long* idx, const float* logit,
+                          const float* log_p, const float* q32, double* baseline, int first, double baseline_decay,
+                          double entropy_coef, double q_floor, double* dLdq, float* loss, float* found_inf,
+                          void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
 /* Gradient hand-off to the optimiser (replaces the float cast of the parameter-shift VJP and
  * torch.nn.utils.clip_grad_norm_(params, gradient_clip_norm), ksd_vi_quantum.py:153): grad32 dev [P] float32 =
  * float32(grad64) * min(1, max_norm / (||float32(grad64)||_2 + 1e-6)); total_norm dev [1] float32 = that norm. */

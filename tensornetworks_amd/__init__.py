@@ -6,6 +6,7 @@ stein_utils) on a hand-written HIP backend (libbornvi_hip.so, C ABI in include/b
 from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "ClassicalKSDVariationalInference",
+           "ClassicalAdversarialVariationalInference",
            "generate_all_binary_outcomes", "calculate_tvd"]
 
 
@@ -22,4 +23,7 @@ def __getattr__(name):
     if name == "ClassicalKSDVariationalInference":      # (the reference's ksd_vi.KSDVariationalInference)
         from .ksd_vi import KSDVariationalInference
         return KSDVariationalInference
+    if name == "ClassicalAdversarialVariationalInference":      # (the reference's adversarial_vi.AdversarialVariationalInference)
+        from .adversarial_vi_classical import AdversarialVariationalInference
+        return AdversarialVariationalInference
     raise AttributeError(name)

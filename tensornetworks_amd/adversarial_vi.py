@@ -43,8 +43,7 @@ class AdversarialVariationalInference:
         self.device = device
 
         born_machine_config = {**born_machine_config, 'init_method': 'small_random'}
-        self.born_machine = QuantumBornMachine(num_latent_vars=self.num_latent_vars,
-                                               **born_machine_config).to(device)
+        self.born_machine = self._make_born_machine(born_machine_config).to(device)
 
         classifier_input_dim = self.num_latent_vars
         if born_machine_config.get('conditioning_dim', 0) > 0:
@@ -65,6 +64,32 @@ class AdversarialVariationalInference:
         self._label_cache = None
         self._baseline = None
         self.timers = None      # optional {phase: [(start, end) events]} filled by the steps (bench.py)
+
+    # ---- what depends on the variational family (adversarial_vi_classical.py overrides these) ---------------------------
+    def _make_born_machine(self, born_machine_config):
+        return QuantumBornMachine(num_latent_vars=self.num_latent_vars, **born_machine_config)
+
+    def _sample_from_born(self, batch_size, x_obs_tensor):
+        """Bit rows [batch, n] of `batch_size` draws from q_theta (no gradient)."""
+        q = self.born_machine.get_probabilities().detach()
+        return self._bits(torch.multinomial(q / q.sum(), batch_size, replacement=True).to(self.device))
+
+    def _current_tvd(self, true_posterior_for_tvd, x_obs_tensor):
+        if torch.is_tensor(true_posterior_for_tvd):   # array form (stein_utils.true_posterior_table): stays on the device
+            from .stein_utils import tvd_table
+            q_now = self.born_machine.get_probabilities().detach()
+            return float(tvd_table(true_posterior_for_tvd.to(q_now.device), q_now))
+        return calculate_tvd(true_posterior_for_tvd, self.born_machine.get_prob_dict())
+
+    def _graph_by_default(self):
+        return True
+
+    def _begin_training(self):
+        """Device scalars of one train() call (a captured epoch reads and writes these tensors in place)."""
+        self._baseline = torch.zeros((), device=self.device)
+        self._found_inf = torch.zeros((), dtype=torch.float32, device=self.device)
+        self._last_good_norm = torch.zeros((), dtype=torch.float32, device=self.device)
+        self._label_cache = None
 
     # reference attributes kept lazily (2^n Python objects)
     @property
@@ -124,8 +149,7 @@ class AdversarialVariationalInference:
         optimizer_classifier.zero_grad()
         with self._spans("sample"):
             with torch.no_grad():
-                q = self.born_machine.get_probabilities().detach()
-                z_from_born = self._bits(torch.multinomial(q / q.sum(), batch_size, replacement=True).to(self.device))
+                z_from_born = self._sample_from_born(batch_size, x_obs_tensor)
             z_from_prior = self._sample_from_prior_z(batch_size)
         with self._spans("classifier"):
             all_inputs = torch.cat((self._clf_inputs(z_from_born, x_obs_tensor, with_x),
@@ -227,7 +251,7 @@ class AdversarialVariationalInference:
 
         on_gpu = torch.device(self.device).type == "cuda"
         fused = {"fused": True} if on_gpu else {}
-        want_graph = (graph_epochs if graph_epochs is not None else True) and on_gpu and optimizer_type == "adam" \
+        want_graph = (graph_epochs if graph_epochs is not None else self._graph_by_default()) and on_gpu and optimizer_type == "adam" \
             and self.timers is None and num_epochs > 3
         if optimizer_type == "adam":
             lr_b, lr_c = lr_born_machine, lr_classifier
@@ -247,10 +271,7 @@ class AdversarialVariationalInference:
             scheduler_classifier = optim.lr_scheduler.CosineAnnealingLR(optimizer_classifier, T_max=num_epochs, eta_min=lr_classifier / 10)
 
         criterion_classifier = nn.BCEWithLogitsLoss()
-        self._baseline = torch.zeros((), device=self.device)
-        self._found_inf = torch.zeros((), dtype=torch.float32, device=self.device)
-        self._last_good_norm = torch.zeros((), dtype=torch.float32, device=self.device)
-        self._label_cache = None
+        self._begin_training()
         self._log_p_active = self._log_p_table(x_obs_tensor)   # built once, outside the epochs (its key is a host read-back)
         self.graph_error = None
         dev_hist = {'loss_classifier': [], 'loss_born_machine': [], 'grad_norm_born': [], 'grad_norm_classifier': []}
@@ -266,7 +287,6 @@ class AdversarialVariationalInference:
         loss_d = grad_norm_d = None
         skipped_seen = 0
         skipped = torch.zeros((), dtype=torch.int64, device=self.device)
-        tvd_on_device = torch.is_tensor(true_posterior_for_tvd)
 
         def epoch_body(first):
             """(loss_d, grad_norm_d, loss_q [NaN where the update was skipped], grad_norm_q, number of skipped updates)"""
@@ -335,12 +355,7 @@ class AdversarialVariationalInference:
                 scheduler_classifier.step()
 
             if true_posterior_for_tvd is not None:
-                if tvd_on_device:                     # array form (stein_utils.true_posterior_table): stays on the device
-                    from .stein_utils import tvd_table
-                    q_now = self.born_machine.get_probabilities().detach()
-                    tvd = float(tvd_table(true_posterior_for_tvd.to(q_now.device), q_now))
-                else:
-                    tvd = calculate_tvd(true_posterior_for_tvd, self.born_machine.get_prob_dict())
+                tvd = self._current_tvd(true_posterior_for_tvd, x_obs_tensor)
                 tvds.append(tvd)
                 if tvd < best_tvd:
                     best_tvd = tvd

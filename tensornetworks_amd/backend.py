@@ -495,6 +495,55 @@ def born_table_vjp(w, q64, mode, y=None, ksd2=None, entropy_weight=0.0, out=None
     return out
 
 
+REINFORCE_MAX_BATCH = 1 << 24
+
+
+def reinforce_step(idx, logit, log_p, q32, baseline, first, baseline_decay, entropy_coef=0.01, q_floor=1e-10, out=None,
+                   loss_out=None, found_out=None):
+    """REINFORCE step of the table family (bornvi_reinforce_step): idx int64 [B] sampled outcomes, logit float32 [B]
+    classifier logits of the samples, log_p float32 [2^n] = log p(x_obs | z), q32 float32 [2^n] the Born probabilities,
+    baseline float64 [1] running baseline (updated in place: the first call's mean reward, then the exponential average)
+    -> (dLdq float64 [2^n] = d loss_q / d q, the y of born_table_vjp(ksd2=None); loss float32 [1]; found_inf float32 [1],
+    1.0 when the loss is NaN or +-Inf).  out / loss_out / found_out: destinations to write into."""
+    dev = q32.device
+    h = _ext.handle_for(dev)
+    N = int(q32.numel())
+    if N < 2 or N & (N - 1):
+        raise BornviError(f"q32: {N} entries is not 2^n with n >= 1")
+    n = N.bit_length() - 1
+    _chk_n(n)
+    B = int(idx.numel())
+    if not 1 <= B <= REINFORCE_MAX_BATCH:
+        raise BornviError(f"idx: 1 ... 2^24 samples per call, got {B}")
+    for name, v in (("baseline_decay", baseline_decay), ("entropy_coef", entropy_coef), ("q_floor", q_floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise BornviError(f"{name} must be a finite number, got {v!r}")
+    if q_floor < 0:
+        raise BornviError(f"q_floor must not be negative, got {q_floor!r}")
+    _chk(idx, torch.int64, dev, "idx")
+    _chk(logit, torch.float32, dev, "logit", B)
+    _chk(log_p, torch.float32, dev, "log_p", N)
+    _chk(q32, torch.float32, dev, "q32")
+    _chk(baseline, torch.float64, dev, "baseline", 1)
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", N)
+    if loss_out is None:
+        loss_out = torch.empty(1, dtype=torch.float32, device=dev)
+    else:
+        _chk(loss_out, torch.float32, dev, "loss_out", 1)
+    if found_out is None:
+        found_out = torch.empty(1, dtype=torch.float32, device=dev)
+    else:
+        _chk(found_out, torch.float32, dev, "found_out", 1)
+    ws = _ws(dev, _cached_size(h, "bornvi_reinforce_workspace_bytes", n, B), "reinforce")
+    h.call("bornvi_reinforce_step", n, B, _ptr(idx), _ptr(logit), _ptr(log_p), _ptr(q32), _ptr(baseline), 1 if first else 0,
+           float(baseline_decay), float(entropy_coef), float(q_floor), _ptr(out), _ptr(loss_out), _ptr(found_out),
+           _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out, loss_out, found_out
+
+
 # ---- finite shots -------------------------------------------------------------------------------------
 SHOTS_MAX = (1 << 31) - 1
 

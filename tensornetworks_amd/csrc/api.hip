@@ -1119,6 +1119,30 @@ int bornvi_born_table_vjp(bornvi_handle h, int n, int rows, int mode, const floa
   return BORNVI_OK;
 }
 
+static bool valid_reinforce(int n, long long B) { return n >= 1 && n <= 30 && B >= 1 && B <= (1ll << 24); }
+
+size_t bornvi_reinforce_workspace_bytes(bornvi_handle h, int n, long long B) {
+  if (!h) return 0;
+  if (!valid_reinforce(n, B)) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  return reinforce_workspace_bytes(n, B);
+}
+
+int bornvi_reinforce_step(bornvi_handle h, int n, long long B, const long long* idx, const float* logit, const float* log_p,
+                          const float* q32, double* baseline, int first, double baseline_decay, double entropy_coef,
+                          double q_floor, double* dLdq, float* loss, float* found_inf, void* workspace,
+                          size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_reinforce(n, B)) return fail(h, BORNVI_ERR_INVALID, "bad argument (1 <= n <= 30, 1 <= B <= 2^24)");
+  if (!idx || !logit || !log_p || !q32 || !baseline || !dLdq || !loss || !found_inf) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!std::isfinite(baseline_decay) || !std::isfinite(entropy_coef) || !(q_floor >= 0.0) || !std::isfinite(q_floor))
+    return fail(h, BORNVI_ERR_INVALID, "baseline_decay, entropy_coef and q_floor must be finite, q_floor >= 0");
+  if (!workspace || workspace_bytes < reinforce_workspace_bytes(n, B)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_reinforce_step(n, B, idx, logit, log_p, q32, baseline, first ? 1 : 0, baseline_decay, entropy_coef, q_floor,
+                                  dLdq, loss, found_inf, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 int bornvi_clip_cast_grad(bornvi_handle h, int P, const double* grad64, double max_norm, float* grad32,
                           float* total_norm, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;

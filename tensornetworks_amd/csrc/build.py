@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "plan.cpp"]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "plan.cpp"]
 HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
@@ -34,6 +34,10 @@ RESOURCE_BUDGET = {
     "born_table_entropy_kernel": (0, 0),
     "born_table_vjp_stats_kernel": (0, 0),
     "born_table_vjp_kernel": (0, 0),
+    "reinforce_stats_kernel": (0, 0),             # REINFORCE step of the classical adversarial trainer (kernels_reinforce.hip)
+    "reinforce_scatter_kernel": (0, 0),
+    "reinforce_finish_kernel": (0, 0),
+    "reinforce_loss_kernel": (0, 0),
     "circuit_pass_r3_kernelILb1": (24, 4),        # its fused-dot instantiation (last pass only): 8 weights more per thread; the few
                                                   # spilled address words are reloaded at the end of a trip, not inside the stages
 }

@@ -70,6 +70,12 @@ hipError_t launch_born_table_probs(int n, long long rows, int mode, const float*
 hipError_t launch_born_table_vjp(int n, long long rows, int mode, const float* w, const double* q64, const double* y,
                                  const double* ksd2, double lam, float* grad, double* loss_out, void* ws, hipStream_t st);
 
+// ---- classical Born machine, REINFORCE step of the adversarial trainer (kernels_reinforce.hip) ---------
+size_t reinforce_workspace_bytes(int n, long long B);
+hipError_t launch_reinforce_step(int n, long long B, const long long* idx, const float* logit, const float* log_p,
+                                 const float* q32, double* baseline, int first, double decay, double coef, double q_floor,
+                                 double* dLdq, float* loss, float* found_inf, void* ws, hipStream_t st);
+
 // ---- adjoint differentiation (kernels_adjoint.hip): gate-block walks over one / two states ------------
 struct AdjRotBlock {      // consecutive one-qubit gates of one wire, applied e = 0 first (kinds: plan.hpp GateKind)
   int wire, nrot;

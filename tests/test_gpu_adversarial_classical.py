@@ -1,0 +1,343 @@
+"""Adversarial (KL) variational inference with the classical Born machine on the MI355X: the fused REINFORCE step
+(bornvi_reinforce_step) against a float64 NumPy evaluation of its documented formulas and against gradients recorded
+inside the reference's own train(); its repeatability; and the trainer (adversarial_vi_classical.py) -- API, equality with
+the torch restatement of the epoch (adversarial_mirror.py), skipped updates, convergence to the posterior, the HIP-graph
+replay, the large shapes and the example script."""
+import contextlib
+import io
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import adversarial_mirror as mirror
+from conftest import REPO, golden
+from tensornetworks_amd import backend
+from tensornetworks_amd.bayesian_network import get_sprinkler_network, synthetic_network
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+LAT, OBS, X = ['C', 'S', 'R'], ['W'], {'W': 1}
+DECAY = 0.9
+
+
+def make(bn, lat, obs, cfg, device=DEV, seed=0, **clf):
+    from tensornetworks_amd.adversarial_vi_classical import AdversarialVariationalInference
+    torch.manual_seed(seed)
+    return AdversarialVariationalInference(bn, lat, obs, born_machine_config=cfg, classifier_config=clf, device=device)
+
+
+def quiet_train(vi, *a, **kw):
+    with contextlib.redirect_stdout(io.StringIO()):
+        return vi.train(*a, **kw)
+
+
+# ---- kernel level ----------------------------------------------------------------------------------------------
+def step_inputs(n, B, kind, seed):
+    """(idx int64 [B], logit float32 [B], log_p float32 [2^n], q32 float32 [2^n]) with the cases the kernel documents:
+    sampled outcomes whose q is below 1e-10 (one at 1e-12, one at exactly 0), outcomes no sample hits (the upper half
+    of the table and more), negative logits and logits of magnitude ~50; kind 'one': every sample on one outcome."""
+    rng = np.random.default_rng(seed)
+    N = 1 << n
+    q = rng.random(N) ** 4 + 1e-6
+    q[0] = 1e-12 * q.sum()
+    if N > 2:
+        q[1] = 0.0
+    q32 = (q / q.sum()).astype(np.float32)
+    assert q32[0] < 1e-10
+    if kind == "one":
+        idx = np.full(B, N - 1, dtype=np.int64)
+    else:
+        idx = rng.integers(0, max(1, N // 2), size=B).astype(np.int64)
+        idx[0] = 0
+        if B > 2 and N > 2:
+            idx[1] = 1
+            idx[2] = N - 1
+    logit = (rng.standard_normal(B) * 5.0).astype(np.float32)
+    big = rng.random(B) < 0.1
+    logit[big] = (np.sign(rng.standard_normal(big.sum())) * (50.0 + rng.random(big.sum()))).astype(np.float32)
+    log_p = (rng.standard_normal(N) * 3.0 - 5.0).astype(np.float32)
+    return idx, logit, log_p, q32
+
+
+def run_step(idx, logit, log_p, q32, baseline, first, decay=DECAY):
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)      # noqa: E731
+    base = torch.tensor([baseline], dtype=torch.float64, device=DEV)
+    d, loss, found = backend.reinforce_step(t(idx), t(logit), t(log_p), t(q32), base, first, decay)
+    return d, loss, found, base
+
+
+def assert_step_close(d, loss, base, d_ref, loss_ref, base_ref, what):
+    """dLdq to 1e-6 of its largest entry, loss and baseline to 1e-6 relative.  The kernel's own error is far below: the
+    per-outcome sums are exact sums of weights rounded to 2^-44 of their bound (B = 65,536; kernels_reinforce.hip), the
+    means float64, the loss rounded to float32 once (6e-8)."""
+    d = d.cpu().numpy()
+    err = np.abs(d - d_ref).max()
+    print(f"{what}: dLdq err {err:.3e} (max {np.abs(d_ref).max():.3e}), loss {float(loss):.9g} vs {loss_ref:.9g}, "
+          f"baseline {float(base):.17g} vs {base_ref:.17g}")
+    assert err <= 1e-6 * np.abs(d_ref).max()
+    assert np.all(d[d_ref == 0.0] == 0.0)                      # never sampled, or q below the floor: exact zeros
+    assert abs(float(loss) - loss_ref) <= 1e-6 * abs(loss_ref)
+    assert abs(float(base) - base_ref) <= 1e-6 * abs(base_ref)
+
+
+@pytest.mark.parametrize("first", [True, False])
+@pytest.mark.parametrize("B", [1, 64, 65536])
+@pytest.mark.parametrize("n", [1, 3, 8, 12, 16, 20])
+@pytest.mark.parametrize("kind", ["mixed", "one"])
+def test_reinforce_step_against_numpy(kind, n, B, first):
+    idx, logit, log_p, q32 = step_inputs(n, B, kind, seed=100 * n + B % 97 + first)
+    d_ref, loss_ref, base_ref = mirror.reinforce_numpy(idx, logit, log_p, q32, 0.7, first, DECAY)
+    d, loss, found, base = run_step(idx, logit, log_p, q32, 0.7, first)
+    assert float(found) == 0.0
+    assert_step_close(d, loss, base, d_ref, loss_ref, base_ref, f"{kind} n={n} B={B} first={first}")
+    if kind == "mixed":     # q[0] is below the floor; no sample falls in [N / 2, N - 1)
+        assert d[0].item() == 0.0 and torch.count_nonzero(d[(1 << n) // 2:-1]).item() == 0
+
+
+@pytest.mark.parametrize("tag", ["logits", "abs"])
+def test_reinforce_step_and_vjp_against_the_reference_trace(tag):
+    """reinforce_step + born_table_vjp on the inputs recorded inside the reference's train() (Sprinkler, B = 64, 4
+    epochs) reproduce the reference's params.grad before clipping to 1e-5 of its largest entry, its running baseline to
+    1e-6 and loss_q to 1e-6 of max(1, |loss_q|) (the form test_host_logic.py's reinforce trace test uses: the reference's
+    loss is a float32 mean of terms of magnitude ~1)."""
+    g = golden("adversarial_classical_trace.npz")
+    mode = 0 if tag == "logits" else 1
+    base = torch.zeros(1, dtype=torch.float64, device=DEV)
+    log_p = torch.from_numpy(g[f"{tag}_log_p_table"]).to(DEV)
+    for e in range(4):
+        idx = torch.from_numpy(g[f"{tag}_idx"][e]).to(DEV)
+        logit = torch.from_numpy(g[f"{tag}_logits"][e]).to(DEV)
+        w = torch.from_numpy(g[f"{tag}_w"][e]).to(DEV).reshape(1, -1)
+        q32, q64, _ = backend.born_table_probs(w, mode, want_entropy=False)
+        np.testing.assert_allclose(q32[0].cpu().numpy(), g[f"{tag}_q"][e], rtol=1e-6, atol=1e-9)
+        d, loss, found = backend.reinforce_step(idx, logit, log_p, q32[0], base, e == 0, float(g["baseline_decay"]))
+        grad = backend.born_table_vjp(w, q64, mode, y=d.reshape(1, -1))[0].cpu().numpy().astype(np.float64)
+        ref = g[f"{tag}_grad"][e].astype(np.float64)
+        err = np.abs(grad - ref).max() / np.abs(ref).max()
+        print(f"{tag} epoch {e}: grad err {err:.3e} of max; baseline {float(base):.9g} vs {g[f'{tag}_baseline'][e]:.9g}; "
+              f"loss {float(loss):.9g} vs {g[f'{tag}_loss_q'][e]:.9g}")
+        assert float(found) == 0.0
+        assert err <= 1e-5
+        assert abs(float(base) - g[f"{tag}_baseline"][e]) <= 1e-6 * abs(g[f"{tag}_baseline"][e])
+        assert abs(float(loss) - g[f"{tag}_loss_q"][e]) <= 1e-6 * max(1.0, abs(g[f"{tag}_loss_q"][e]))
+
+
+def test_reinforce_step_is_bitwise_repeatable_and_order_independent():
+    """n = 16, B = 65,536.  Two calls on the same inputs give the same bits in dLdq, loss and baseline: the per-outcome sums
+    are 64-bit integer sums of weights rounded once to a fixed power-of-two step, so the order in which the adds arrive
+    cannot change them, and the means are two-level float64 sums in a fixed order over sample positions.
+    Permuting the samples (idx and logit together) is NOT guaranteed bitwise: the mean, hence the baseline, is summed in
+    sample order, so its last bits may move, and every weight with them.  Given the baseline's bits the design is
+    order-free.  (Differences of float32 values of bounded range are short float64 numbers, so at this size the partial
+    sums are usually exact and the bits usually agree; that is printed, not required.)  The permuted call must agree with
+    the unpermuted one within the tolerances of the NumPy comparison."""
+    idx, logit, log_p, q32 = step_inputs(16, 65536, "mixed", seed=5)
+    outs = [run_step(idx, logit, log_p, q32, 0.3, False) for _ in range(2)]
+    for a, b in zip(outs[0], outs[1]):
+        assert torch.equal(a, b)
+    perm = np.random.default_rng(6).permutation(65536)
+    d, loss, found, base = run_step(idx[perm], logit[perm], log_p, q32, 0.3, False)
+    d0, loss0, _, base0 = outs[0]
+    assert_step_close(d, loss, base, d0.cpu().numpy(), float(loss0), float(base0), "permuted")
+    print("bitwise under permutation:", torch.equal(d, d0), torch.equal(loss, loss0), torch.equal(base, base0))
+
+
+def test_reinforce_step_flags_non_finite_input():
+    """log p(x|z) = +inf / -inf under sampled outcomes (the reference's rule for p(z) < 1e-9) is legal input: the call
+    succeeds and raises the flag the optimiser reads; finite input leaves it down."""
+    idx, logit, log_p, q32 = step_inputs(8, 64, "mixed", seed=9)
+    _, loss, found, _ = run_step(idx, logit, log_p, q32, 0.0, True)
+    assert float(found) == 0.0 and np.isfinite(float(loss))
+    bad = log_p.copy()
+    bad[idx[3]] = np.inf
+    bad[idx[4]] = -np.inf if idx[4] != idx[3] else np.inf
+    d, loss, found, _ = run_step(idx, logit, bad, q32, 0.0, True)
+    torch.cuda.synchronize()
+    assert float(found) == 1.0 and not np.isfinite(float(loss))
+
+
+def test_reinforce_step_rejects_bad_arguments():
+    idx, logit, log_p, q32 = step_inputs(3, 8, "mixed", seed=1)
+    t = lambda a: torch.from_numpy(a).to(DEV)      # noqa: E731
+    base = torch.zeros(1, dtype=torch.float64, device=DEV)
+    with pytest.raises(backend.BornviError):
+        backend.reinforce_step(t(idx), t(logit).double(), t(log_p), t(q32), base, True, 0.9)
+    with pytest.raises(backend.BornviError):
+        backend.reinforce_step(t(idx), t(logit), t(log_p)[:7], t(q32), base, True, 0.9)
+    with pytest.raises(backend.BornviError):
+        backend.reinforce_step(t(idx), t(logit), t(log_p), t(q32), base.float(), True, 0.9)
+    with pytest.raises(backend.BornviError):
+        backend.reinforce_step(t(idx), t(logit), t(log_p), t(q32), base, True, float('nan'))
+
+
+# ---- trainer level ---------------------------------------------------------------------------------------------
+def test_api_history_and_messages():
+    import tensornetworks_amd
+    from tensornetworks_amd.adversarial_vi_classical import AdversarialVariationalInference
+    assert tensornetworks_amd.ClassicalAdversarialVariationalInference is AdversarialVariationalInference
+    bn = get_sprinkler_network(False)
+    post, _ = bn.get_true_posterior(LAT, X)
+    # a reference-style configuration: the initialisation is overridden (adversarial_vi.py:27), the rest is taken
+    vi = make(bn, LAT, OBS, {'use_logits': True, 'conditioning_dim': 1, 'init_method': 'uniform'})
+    assert vi.born_machine.conditioning_dim == 1 and vi.classifier.network[0].in_features == 4
+    tab = make(bn, LAT, OBS, {'use_logits': False, 'conditioning_dim': 0, 'init_method': 'uniform'}, seed=2)
+    torch.manual_seed(2)
+    assert torch.equal(tab.born_machine.params.detach().cpu(), 0.1 * torch.randn(8))       # 'small_random'
+    for m in (vi, tab):
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            hist = m.train(X, num_epochs=6, batch_size=64, lr_born_machine=0.01, lr_classifier=0.01, verbose=True,
+                           true_posterior_for_tvd=post)
+        assert set(hist) == {'loss_classifier', 'loss_born_machine', 'tvd', 'grad_norm_born', 'grad_norm_classifier'}
+        assert all(len(v) == 6 for v in hist.values()) and all(np.all(np.isfinite(v)) for v in hist.values())
+        out = buf.getvalue()
+        assert "Loss D:" in out and "Loss G:" in out and "LR_G:" in out and "Restoring best parameters" in out
+    with pytest.raises(ValueError, match="Keys in x_observation_dict must match"):
+        vi.train({'Q': 1}, 1, 8, 0.01, 0.01, verbose=False)
+    with pytest.raises(ValueError, match="Born machine is conditional but no observed vars specified"):
+        make(bn, ['C', 'S', 'R', 'W'], [], {'conditioning_dim': 1}).train({}, 1, 8, 0.01, 0.01, verbose=False)
+    with pytest.raises(ValueError, match="conditioning_dim must match num_observed_vars"):
+        make(bn, ['C', 'S'], ['R', 'W'], {'conditioning_dim': 1}).train({'R': 1, 'W': 1}, 1, 8, 0.01, 0.01, verbose=False)
+    odd = make(bn, LAT, OBS, {'conditioning_dim': 0})
+    odd.classifier = type(odd.classifier)(input_dim=7).to(DEV)
+    with pytest.raises(ValueError, match="Classifier input dimension mismatch"):
+        odd.train(X, 1, 8, 0.01, 0.01, verbose=False)
+    # the tensor form of the posterior
+    from tensornetworks_amd.stein_utils import true_posterior_table
+    table, _ = true_posterior_table(bn, X, LAT, device=DEV)
+    hist = quiet_train(tab, X, num_epochs=2, batch_size=64, lr_born_machine=0.01, lr_classifier=0.01, verbose=False,
+                       true_posterior_for_tvd=table)
+    q = tab.born_machine.get_prob_dict()
+    assert hist['tvd'][-1] == pytest.approx(0.5 * sum(abs(post[z] - q[z]) for z in post), abs=1e-6)
+
+
+@pytest.mark.parametrize("case", ["table_n6", "table_abs_n6", "mlp_n3"])
+def test_eager_epochs_equal_the_torch_mirror(case):
+    """Five eager epochs, same torch seed: the trainer (kernels) and adversarial_mirror.train (torch ops and autograd, same
+    multinomial / Dropout calls in the same order) give the same histories to 1e-5 relative and the same parameters to
+    1e-5 absolute.  MLP mode runs with Dropout active."""
+    if case == "mlp_n3":
+        bn, lat, obs, x = get_sprinkler_network(False), LAT, OBS, X
+        cfg = {'use_logits': True, 'conditioning_dim': 1}
+    else:
+        bn, lat, obs, x = synthetic_network(6, 3, p_low=0.25, p_high=0.75)
+        cfg = {'use_logits': case == "table_n6", 'conditioning_dim': 0}
+    kw = dict(num_epochs=5, batch_size=4096, lr_born_machine=0.01, lr_classifier=0.02, k_classifier_steps=2)
+    a = make(bn, lat, obs, cfg, seed=21)
+    ha = quiet_train(a, x, verbose=False, graph_epochs=False, **kw)
+    b = make(bn, lat, obs, cfg, seed=21)
+    assert b.born_machine.training
+    hb = mirror.train(b, x, **kw)
+    for key in hb:
+        print(case, key, ha[key], hb[key])
+        np.testing.assert_allclose(ha[key], hb[key], rtol=1e-5, atol=0)
+    for pa, pb in zip(a.born_machine.parameters(), b.born_machine.parameters()):
+        assert (pa - pb).abs().max().item() <= 1e-5
+    if cfg['conditioning_dim'] == 0:
+        qa, qb = a.born_machine.get_probabilities().detach(), b.born_machine.get_probabilities().detach()
+        assert (qa - qb).abs().max().item() <= 1e-5
+
+
+def test_skipped_born_updates_keep_the_last_applied_norm():
+    """From epoch 2 on log p(x|z) is +inf on a state the machine samples: the loss of those epochs is NaN in the history,
+    the update is skipped on the device (parameters stay finite and stop moving), and history['grad_norm_born'] keeps
+    the norm of the last update that was applied.  (The running baseline is infinite from then on, as the reference's
+    Python float would be.)"""
+    bn, lat, obs, x = synthetic_network(5, 3, p_low=0.25, p_high=0.75)
+    vi = make(bn, lat, obs, {'use_logits': True, 'conditioning_dim': 0}, seed=3)
+    orig = vi._born_step
+    calls = {"n": 0, "params": []}
+
+    def step(*a, **kw):
+        if calls["n"] == 2:
+            vi._log_p_active = torch.full_like(vi._log_p_active, float('inf'))     # every state: surely a sampled one
+        calls["n"] += 1
+        calls["params"].append(vi.born_machine.params.detach().clone())
+        return orig(*a, **kw)
+
+    vi._born_step = step
+    hist = quiet_train(vi, x, num_epochs=5, batch_size=256, lr_born_machine=0.01, lr_classifier=0.01, verbose=False,
+                       graph_epochs=False)
+    lb, gn = hist['loss_born_machine'], hist['grad_norm_born']
+    assert np.all(np.isfinite(lb[:2])) and np.all(np.isnan(lb[2:]))
+    assert gn[0] > 0 and gn[1] > 0 and gn[2] == gn[1] and gn[3] == gn[1] and gn[4] == gn[1]
+    assert torch.isfinite(vi.born_machine.params).all()
+    assert not torch.equal(calls["params"][1], calls["params"][2])
+    assert torch.equal(calls["params"][3], calls["params"][4]) and torch.equal(calls["params"][4], vi.born_machine.params.detach())
+
+
+SPRINKLER_KW = dict(num_epochs=300, batch_size=100, k_classifier_steps=5, k_born_steps=1, gradient_clip_norm=5.0,
+                    baseline_decay=0.95, adam_betas=(0.5, 0.999), verbose=False)
+
+
+@pytest.mark.parametrize("device,seed", [(DEV, 0), (DEV, 1), (DEV, 2), ("cpu", 0)])
+def test_table_training_moves_to_the_posterior(device, seed):
+    """Sprinkler W = 1, table mode, lr 0.03 / 0.03, 300 epochs: min TVD <= 0.25 TVD[0].  (The reference on these settings:
+    TVD[0] 0.52-0.56, minimum 0.020-0.025 on seeds 0, 1, 2.)  Seed 0 also with the parameters on the CPU."""
+    bn = get_sprinkler_network(False)
+    post, _ = bn.get_true_posterior(LAT, X)
+    vi = make(bn, LAT, OBS, {'use_logits': True, 'conditioning_dim': 0}, device=device, seed=seed)
+    hist = quiet_train(vi, X, lr_born_machine=0.03, lr_classifier=0.03, true_posterior_for_tvd=post, **SPRINKLER_KW)
+    print(f"table {device} seed {seed}: tvd[0] {hist['tvd'][0]:.4f} min {min(hist['tvd']):.4f} last {hist['tvd'][-1]:.4f} "
+          f"graphed {vi.graphed_epochs} {vi.graph_error}")
+    assert min(hist['tvd']) <= 0.25 * hist['tvd'][0]
+    if device != "cpu":
+        assert vi.graph_error is None and vi.graphed_epochs == 298
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_mlp_training_moves_to_the_posterior(seed):
+    """The reference run script's configuration (MLP of x, lr 0.003 / 0.03), 300 epochs: min TVD <= 0.5 TVD[0].  (The
+    reference: minima 0.014, 0.017, 0.103 from 0.52-0.55.)"""
+    bn = get_sprinkler_network(False)
+    post, _ = bn.get_true_posterior(LAT, X)
+    vi = make(bn, LAT, OBS, {'use_logits': True, 'conditioning_dim': 1, 'init_method': 'uniform'}, seed=seed,
+              hidden_dims=[32, 16], use_batch_norm=False)
+    hist = quiet_train(vi, X, lr_born_machine=0.003, lr_classifier=0.03, true_posterior_for_tvd=post, **SPRINKLER_KW)
+    print(f"mlp seed {seed}: tvd[0] {hist['tvd'][0]:.4f} min {min(hist['tvd']):.4f} last {hist['tvd'][-1]:.4f}")
+    assert min(hist['tvd']) <= 0.5 * hist['tvd'][0]
+
+
+def test_graphed_epochs_run_the_same_training():
+    """train(graph_epochs=True), table mode: after two eager epochs the epoch body -- sampling, classifier step,
+    born_table_probs, reinforce_step, born_table_vjp, clip, the guarded Adam step -- is captured once and replayed."""
+    bn, lat, obs, x = synthetic_network(6, 3, p_low=0.25, p_high=0.75)
+    runs = {}
+    for mode in (False, True):
+        vi = make(bn, lat, obs, {'use_logits': True, 'conditioning_dim': 0}, seed=11)
+        h = quiet_train(vi, x, num_epochs=8, batch_size=4096, lr_born_machine=0.01, lr_classifier=0.02, verbose=False,
+                        graph_epochs=mode)
+        runs[mode] = (h, vi.born_machine.params.detach().cpu().numpy().copy(), vi.graphed_epochs, vi.graph_error)
+    assert runs[False][2] == 0
+    assert runs[True][3] is None and runs[True][2] == 6, runs[True][2:]
+    for key in ("loss_classifier", "loss_born_machine", "grad_norm_born", "grad_norm_classifier"):
+        assert len(runs[True][0][key]) == 8 and np.all(np.isfinite(runs[True][0][key]))
+    assert np.all(np.isfinite(runs[True][1])) and not np.array_equal(runs[True][1], runs[False][1] * 0)
+    np.testing.assert_allclose(runs[True][0]["loss_classifier"][:2], runs[False][0]["loss_classifier"][:2], rtol=1e-6)
+    np.testing.assert_allclose(runs[True][0]["loss_born_machine"][:2], runs[False][0]["loss_born_machine"][:2], rtol=1e-5, atol=1e-7)
+
+
+@pytest.mark.parametrize("n", [12, 20])
+def test_large_shapes_run(n):
+    """REINFORCE batch 65,536 against 2^12 and 2^20 table parameters, two epochs.  CPTs in U(0.4, 0.6): every p(z) is at
+    least 0.4^20 = 1.1e-8, above the 1e-9 below which the reference's rule makes log p(x|z) infinite."""
+    bn, lat, obs, x = synthetic_network(n, 0, p_low=0.4, p_high=0.6)
+    vi = make(bn, lat, obs, {'use_logits': True, 'conditioning_dim': 0})
+    hist = quiet_train(vi, x, num_epochs=2, batch_size=65536, lr_born_machine=0.003, lr_classifier=0.03,
+                       k_classifier_steps=5, k_born_steps=1, verbose=False, adam_betas=(0.5, 0.999))
+    assert all(np.all(np.isfinite(hist[k])) for k in ('loss_classifier', 'loss_born_machine', 'grad_norm_born'))
+    assert hist['grad_norm_born'][-1] > 0
+    g = vi.born_machine.params.grad
+    assert g is not None and g.shape == (1 << n,) and torch.isfinite(g).all()
+
+
+def test_example_script_runs():
+    env = dict(os.environ, PYTHONPATH=REPO)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "examples", "run_sprinkler_adversarial.py"), "--epochs", "60",
+                        "--quiet"], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "Final TVD:" in r.stdout and "Best TVD during training:" in r.stdout
