@@ -14,7 +14,6 @@ from . import _ext
 from ._ext import ANSATZ_IDS, BornviError
 
 _workspaces = {}
-_ws_windows = {}     # key -> (byte offset, bytes): tools/probes place a workspace inside another buffer through this
 
 # Cap for the circuit workspace (bytes); larger batches are processed in chunks by the library.
 WORKSPACE_CAP = int(os.environ.get("BORNVI_WORKSPACE_CAP", str(48 << 30)))
@@ -51,12 +50,6 @@ def _ws(dev, nbytes, tag="main"):
     launch on auxiliary / CU-masked streams)."""
     key = _ws_key(dev, tag)
     buf = _workspaces.get(key)
-    win = _ws_windows.get(key)
-    if buf is not None and win is not None:        # (probes only: a chosen window of a larger buffer)
-        if win[1] >= nbytes:
-            return buf[win[0]: win[0] + win[1]]
-        del _ws_windows[key]
-        buf = None
     if buf is None or buf.numel() < nbytes:
         _workspaces[key] = None
         buf = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
@@ -72,14 +65,11 @@ def fresh_workspace(dev, nbytes):
 def set_workspace(dev, tag, buf):
     """Makes `buf` the cached workspace `tag` of the current stream (the trainer places the symmetric contraction's
     workspace by measurement: SteinOperator._place_gram)."""
-    key = _ws_key(dev, tag)
-    _ws_windows.pop(key, None)
-    _workspaces[key] = buf
+    _workspaces[_ws_key(dev, tag)] = buf
 
 
 def release_workspaces():
     _workspaces.clear()
-    _ws_windows.clear()
 
 
 def _chk(t, dtype, dev, name, numel=None):

@@ -72,7 +72,6 @@ struct bornvi_ctx {
   std::map<std::tuple<int, int, int>, std::unique_ptr<AdjPlan>> adj_plans;
   size_t max_lds_prepared = 0;
   size_t max_r3_lds_prepared = 0;
-  int debug_flags = 0;  // timing-only ablations of circuit_pass_kernel (results are WRONG when non-zero)
   int num_cus = 256;    // multiProcessorCount
   int circuit_cus = 0;  // > 0: size the persistent circuit grid for this many CUs (the caller launches on a CU-masked stream)
   int wgs_per_cu = 0;   // generic kernel: > 0 = persistent grid of num_cus * wgs_per_cu workgroups; 0 = one per tile
@@ -243,9 +242,12 @@ int run_passes(bornvi_handle h, DevPlan* dp, int bc, const void* in0, void* bufA
   for (int i = pass_begin; i < pass_end; ++i) {
     const bool last = (i == p.n_passes - 1);
     void* out = last ? final_state : ((in == bufA) ? bufB : bufA);
-    if (dp->d_compact) {
+    const bool fast16 = !dp->d_compact && dp->d_fast && h->fast_path && dp->fast_workgroups > 0;
+    if (dp->d_compact || fast16) {
+      // the two persistent kernels (8 and 16 amplitudes per thread) are launched alike
       const int cus = h->circuit_cus > 0 ? h->circuit_cus : h->num_cus;
-      const int wgs = h->fast_wgs_per_cu > 0 ? h->fast_wgs_per_cu * cus : dp->r3_workgroups / h->num_cus * cus;
+      const int wgs = h->fast_wgs_per_cu > 0 ? h->fast_wgs_per_cu * cus
+                                             : (fast16 ? dp->fast_workgroups : dp->r3_workgroups) / h->num_cus * cus;
       PrefixShare ps;
       int nb = bc;
       if (share) {
@@ -254,35 +256,23 @@ int run_passes(bornvi_handle h, DevPlan* dp, int bc, const void* in0, void* bufA
         ps.row_map = share->d_tab + share->bc;
         ps.trash = trash;
       }
-      HIPCHK(h, launch_circuit_pass_r3(dp->d_words, p.pass_off[i], dp->d_compact, dp->compact.pass_off[i], p.n, p.k, dp->r3_lds, nb, in,
-                                       out, final_probs, gates, gate_stride, wgs,
-                                       (((h->direct_stages >> 2) && (h->direct_stages >> 2) - 1 != i) ? 0 : (h->direct_stages & 3)) |
-                                           ((h->alternate_walk && (i & 1)) ? 4 : 0) |
-                                           ((pass_begin == 0 && in0 == nullptr && h->direct_stages == 3 && h->zero_support) ? 8 : 0),
-                                       ps, last ? wdot : nullptr, last ? partials : nullptr, st));
-    } else if (dp->d_fast && h->fast_path && dp->fast_workgroups > 0) {
-      const int cus = h->circuit_cus > 0 ? h->circuit_cus : h->num_cus;
-      const int wgs = h->fast_wgs_per_cu > 0 ? h->fast_wgs_per_cu * cus : dp->fast_workgroups / h->num_cus * cus;
-      PrefixShare ps;
-      int nb = bc;
-      if (share) {
-        nb = share->active[i];
-        ps.fresh_begin = share->fresh[i];
-        ps.row_map = share->d_tab + share->bc;
-        ps.trash = trash;
-      }
-      HIPCHK(h, launch_circuit_pass_fast(dp->d_words, p.pass_off[i], dp->d_fast, dp->fast.pass_off[i], p.n, p.k,
-                                         p.fast_lds_bytes(dp->fast.max_tab_rows), nb, in, out, final_probs, gates, gate_stride, wgs,
-                                         p.fast_lds_tab_off(), p.fast_lds_mats2_off(dp->fast.max_tab_rows),
-                                         (((h->direct_stages >> 2) && (h->direct_stages >> 2) - 1 != i) ? 0 : (h->direct_stages & 3)) |
-                                             ((h->alternate_walk && (i & 1)) ? 4 : 0) |
-                                             // (the zero-support masks of passes 0 and 1 assume both run with their direct
-                                             // first stage on and without debug ablations: plan.cpp FH_ZINFO)
-                                             ((in0 == nullptr && h->direct_stages == 3 && h->debug_flags == 0 && h->zero_support) ? 8 : 0),
-                                         h->debug_flags, ps, st));
+      // bit 3: the zero-support masks of passes 0 and 1 assume both run with their direct first stage on (plan.cpp
+      // FH_ZINFO).  The 16-amplitude branch used to test `in0 == nullptr` without `pass_begin == 0`; the two are the same
+      // there: only the fused dot (dot_supported: 8-amplitude plans) calls with pass_begin > 0, and with a non-null in0.
+      const int direct_mask = (((h->direct_stages >> 2) && (h->direct_stages >> 2) - 1 != i) ? 0 : (h->direct_stages & 3)) |
+                              ((h->alternate_walk && (i & 1)) ? 4 : 0) |
+                              ((pass_begin == 0 && in0 == nullptr && h->direct_stages == 3 && h->zero_support) ? 8 : 0);
+      if (fast16)
+        HIPCHK(h, launch_circuit_pass_fast(dp->d_words, p.pass_off[i], dp->d_fast, dp->fast.pass_off[i], p.n, p.k,
+                                           p.fast_lds_bytes(dp->fast.max_tab_rows), nb, in, out, final_probs, gates, gate_stride, wgs,
+                                           p.fast_lds_tab_off(), p.fast_lds_mats2_off(dp->fast.max_tab_rows), direct_mask, ps, st));
+      else
+        HIPCHK(h, launch_circuit_pass_r3(dp->d_words, p.pass_off[i], dp->d_compact, dp->compact.pass_off[i], p.n, p.k, dp->r3_lds, nb, in,
+                                         out, final_probs, gates, gate_stride, wgs, direct_mask, ps, last ? wdot : nullptr,
+                                         last ? partials : nullptr, st));
     } else {
       if (share) return fail(h, BORNVI_ERR_INVALID, "prefix sharing needs the fast circuit kernel");
-      HIPCHK(h, launch_circuit_pass(dp->d_words, p.pass_off[i], p.n, p.k, p.threads, p.lds_bytes(), bc, in, out, final_probs, gates, gate_stride, h->wgs_per_cu * h->num_cus, h->debug_flags, st));
+      HIPCHK(h, launch_circuit_pass(dp->d_words, p.pass_off[i], p.n, p.k, p.threads, p.lds_bytes(), bc, in, out, final_probs, gates, gate_stride, h->wgs_per_cu * h->num_cus, st));
     }
     in = out;
   }
@@ -533,7 +523,6 @@ const char* bornvi_last_error(bornvi_handle h) { return h ? h->err.c_str() : g_c
 
 int bornvi_set_option(bornvi_handle h, const char* name, long long value) {
   if (!h || !name) return BORNVI_ERR_INVALID;
-  if (!std::strcmp(name, "debug_flags")) { h->debug_flags = (int)value; return BORNVI_OK; }
   if (!std::strcmp(name, "workgroups_per_cu")) {
     if (value < 0 || value > 16) return fail(h, BORNVI_ERR_INVALID, "option value out of range");
     h->wgs_per_cu = (int)value;

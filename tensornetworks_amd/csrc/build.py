@@ -25,7 +25,7 @@ RESOURCE_BUDGET = {
     "quadform_batched_kernel": (0, 0),
     "quadform_kernel": (0, 0),
     "gram_tables_kernel": (0, 0),                 # the Gram builder: up to 163 VGPRs (n = 16), no scratch
-    "circuit_pass_fast_kernelILb0": (20, 0),      # (20 bytes: spilled SGPRs of the set-up code, outside the tile loop)
+    "circuit_pass_fast_kernelILb": (0, 0),        # 16 amplitudes per thread, both instantiations: no scratch
     "circuit_pass_r3_kernelILb0": (0, 0),         # 8 amplitudes per thread: <= 128 VGPRs (four waves per SIMD) without scratch
     "shots_mass_kernel": (0, 0),                  # finite-shot sampler (kernels_shots.hip): no scratch anywhere
     "shots_draw_kernel": (0, 0),

@@ -26,13 +26,13 @@ hipError_t launch_normalise_gates(double* gates, int count, hipStream_t st);   /
 hipError_t prepare_circuit_kernel(size_t lds_bytes);
 hipError_t launch_circuit_pass(const uint32_t* plan, uint32_t pass_off, int n, int k, int threads, size_t lds, int batch,
                                const void* in, void* out, double* probs, const double* gates,
-                               long long gate_stride, int max_workgroups, int dbg, hipStream_t st);
+                               long long gate_stride, int max_workgroups, hipStream_t st);
 // fast path (plan.hpp: build_fast_tables); persistent grid of at most max_workgroups workgroups
 int circuit_fast_workgroups_per_cu(int threads, size_t lds);
 hipError_t launch_circuit_pass_fast(const uint32_t* plan, uint32_t pass_off, const uint32_t* fast, uint32_t fast_off,
                                     int n, int k, size_t lds, int batch, const void* in, void* out, double* probs,
                                     const double* gates, long long gate_stride, int max_workgroups, size_t lds_tab_off,
-                                    size_t lds_mats2_off, int direct_mask, int dbg, const PrefixShare& share, hipStream_t st);
+                                    size_t lds_mats2_off, int direct_mask, const PrefixShare& share, hipStream_t st);
 // 8 amplitudes per thread, compact tables (kernels_circuit8.hip; plan.hpp: CompactTables)
 hipError_t prepare_circuit_r3_kernel(size_t lds_bytes);
 int circuit_r3_workgroups_per_cu(int threads, size_t lds);

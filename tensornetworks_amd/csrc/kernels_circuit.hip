@@ -236,14 +236,11 @@ constexpr int MAX_TILE_ITERS = 16;  // tile elements per thread in the HBM <-> L
 // grid = (2^(n-k) tiles, circuits); block = plan threads; dynamic LDS = 2^k * 16 bytes.
 // FULL = every thread moves exactly MAX_TILE_ITERS tile elements (k >= 10: threads = 2^(k-4)), which lets
 // all loads of the tile stay in registers; the generic instantiation handles small tiles.
-template <bool FULL, bool DEBUG>
+template <bool FULL>
 __global__ __launch_bounds__(512) void circuit_pass_kernel(
     const uint32_t* __restrict__ plan, uint32_t pass_off, const double2* __restrict__ in,
     double2* __restrict__ out, double* __restrict__ probs, const double* __restrict__ gates,
-    long long gate_stride, long long state_stride, long long total_tiles, int dbg_arg) {
-  // timing-only ablation flags exist only in the DEBUG instantiation: in the production kernel every
-  // `dbg` test folds away (as run-time tests they cost a scalar branch per LDS access)
-  const int dbg = DEBUG ? dbg_arg : 0;
+    long long gate_stride, long long state_stride, long long total_tiles) {
   extern __shared__ double2 tile[];
   const uint32_t* __restrict__ P = plan + pass_off;
   uint32_t H[PW_HEADER_WORDS];   // whole pass header with two wide scalar loads
@@ -282,7 +279,7 @@ __global__ __launch_bounds__(512) void circuit_pass_kernel(
   // ---- this circuit's fused matrices for every stage of the pass -> LDS (one 16-byte piece per thread;
   // they were written by build_gates_kernel on other CUs, i.e. they come from far memory: fetch them once,
   // under the tile loads, instead of stalling every stage on them)
-  for (uint32_t piece = t; piece < (uint32_t)nstages * 16u && !(dbg & 32); piece += T) {
+  for (uint32_t piece = t; piece < (uint32_t)nstages * 16u; piece += T) {
     const uint32_t sm = piece >> 2;                               // (stage, register bit)
     const uint32_t w = P[PW_MATS + (sm >> 1)];
     const uint32_t f = (sm & 1u) ? (w >> 16) : (w & 0xffffu);
@@ -293,7 +290,7 @@ __global__ __launch_bounds__(512) void circuit_pass_kernel(
   // ---- tile in: HBM (pass-specific bit order) -> LDS, or |0...0> ---------------------------------
   if (flags & PASS_INIT) {
     for (uint32_t u = t; u < ksize; u += T) tile[u] = make_double2((u == 0 && g == 0) ? 1.0 : 0.0, 0.0);
-  } else if (t < ksize && !(dbg & 4)) {
+  } else if (t < ksize) {
     const uint32_t gin = deposit16(g, 0, n - k, in_gphys);
     const double2* __restrict__ src = in + b * state_stride + gin;
     const uint32_t thr = (t & ((1u << lo_in) - 1u)) | deposit16(t, lo_in, kt, in_phys);
@@ -343,7 +340,7 @@ __global__ __launch_bounds__(512) void circuit_pass_kernel(
     const uint32_t npay0 = (((hdr0 >> 8) & STAGE_SIGN_PRE) ? SIGNQ_WORDS : 0) + (((hdr0 >> 8) & STAGE_SIGN_POST) ? SIGNQ_WORDS : 0);
     if (nstages > 0 && t < (1u << (k - (int)(hdr0 & 0xffu)))) base_word = S[STAGE_HDR_WORDS + npay0 + t];
   }
-  for (int s = 0; s < nstages && !(dbg & 64); ++s) {
+  for (int s = 0; s < nstages; ++s) {
     uint32_t G[STAGE_HDR_WORDS];     // stage header with three wide scalar loads
 #pragma unroll
     for (int i = 0; i < STAGE_HDR_WORDS; ++i) G[i] = S[i];
@@ -394,37 +391,29 @@ __global__ __launch_bounds__(512) void circuit_pass_kernel(
       wbase = pb ^ sflip;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        if ((FULL || j < nreg) && !(dbg & 2)) { const double2 x = tile[rbase ^ G[16 + j]]; ar[j] = x.x; ai[j] = x.y; }
+        if (FULL || j < nreg) { const double2 x = tile[rbase ^ G[16 + j]]; ar[j] = x.x; ai[j] = x.y; }
         else { ar[j] = (double)(rbase + j); ai[j] = 0.0; }
       }
       const uint32_t* __restrict__ Q = S + STAGE_HDR_WORDS;
-      if ((sflags & STAGE_SIGN_PRE) && !(dbg & 128)) { apply_sign(Q, e, n, ar, ai); Q += SIGNQ_WORDS; }
-      if (!(dbg & 1)) {
-        if (fi[0] != 0xffffu) op_u1<0>(ar, ai, Us);
-        if (fi[1] != 0xffffu) op_u1<1>(ar, ai, Us + 4);
-        if (fi[2] != 0xffffu) op_u1<2>(ar, ai, Us + 8);
-        if (fi[3] != 0xffffu) op_u1<3>(ar, ai, Us + 12);
-      }
-      if ((sflags & STAGE_SIGN_POST) && !(dbg & 128)) apply_sign(Q, e2, n, ar, ai);
+      if (sflags & STAGE_SIGN_PRE) { apply_sign(Q, e, n, ar, ai); Q += SIGNQ_WORDS; }
+      if (fi[0] != 0xffffu) op_u1<0>(ar, ai, Us);
+      if (fi[1] != 0xffffu) op_u1<1>(ar, ai, Us + 4);
+      if (fi[2] != 0xffffu) op_u1<2>(ar, ai, Us + 8);
+      if (fi[3] != 0xffffu) op_u1<3>(ar, ai, Us + 12);
+      if (sflags & STAGE_SIGN_POST) apply_sign(Q, e2, n, ar, ai);
     }
     if (sflags & STAGE_CROSS_READ) __syncthreads();
     if (stage_active) {
 #pragma unroll
       for (int j = 0; j < 16; ++j)
-        if ((FULL || j < nreg) && !(dbg & 2)) tile[wbase ^ G[32 + j]] = make_double2(ar[j], ai[j]);
-      if (dbg & 2) {   // timing-only build of the stage without LDS traffic: keep the values alive
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc += ar[j] + ai[j];
-        if (acc == 1.2345e300) tile[0] = make_double2(acc, acc);
-      }
+        if (FULL || j < nreg) tile[wbase ^ G[32 + j]] = make_double2(ar[j], ai[j]);
     }
-    if (!(dbg & 16)) __syncthreads();
+    __syncthreads();
     S += nwords;
   }
 
   // ---- tile out: LDS -> HBM in the next pass's bit order, or |psi|^2 in canonical order ---------------
-  if (t < ksize && !(dbg & 8)) {
+  if (t < ksize) {
     // phys-out address: GF(2)-linear in the out-enumeration index and the tile index (plan.hpp: PW_OUT_COL)
     const uint32_t gout = xor_cols(g, n - k, P + PW_OUT_GCOL);
     const uint32_t thr_l = xor_map16(t, kt, out_mask) ^ xor_map16(g, n - k, out_gmask);   // tail CNOTs folded in
@@ -563,15 +552,15 @@ __device__ __forceinline__ void op_u1_last_and_store(double (&ar)[16], double (&
 // body folds the write-back into the last gate and keeps the next gate's matrix in flight.  Measured at n = 20, L = 8:
 // -2.4 % (early write-back) and -5.2 % (both) on top of the split prefetch; at 2^11 tiles (four independent
 // workgroups per CU) neutral within noise, so those keep the round-1 body.  Same operations: bit-identical rows.
-template <int NG, bool PRE, bool POST, int IO, bool DEBUG, bool LT>
+template <int NG, bool PRE, bool POST, int IO, bool LT>
 __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const double2* __restrict__ Us, uint32_t my_rw,
-                                           uint32_t my_sg, const uint32_t (&G)[10], int dbg, d2_t (&v)[16],
+                                           uint32_t my_sg, const uint32_t (&G)[10], d2_t (&v)[16],
                                            uint32_t hbm_off, const uint32_t (&hbm_basis)[4], void* hbm_base, bool fin,
                                            bool cross) {
   double ar[16], ai[16];
   // (first: LDS returns in order, so the first gate can start as soon as ITS amplitudes have arrived behind the matrix)
   double Ua[8], Ub[8];
-  constexpr bool EARLY = LT && !DEBUG && NG > 0;
+  constexpr bool EARLY = LT && NG > 0;
   if (EARLY) {
     load_u(Us, Ua);
     if (NG > 1) load_u(Us + 4, Ub);
@@ -586,10 +575,8 @@ __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const dou
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const uint32_t ra = ra0 ^ (((j & 1) ? G[FS_RB] : 0u) ^ ((j & 2) ? G[FS_RB + 1] : 0u) ^ ((j & 4) ? G[FS_RB + 2] : 0u) ^ ((j & 8) ? G[FS_RB + 3] : 0u));
-      if (!(DEBUG && (dbg & 2))) {
-        const double2 x = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(tile) + ra);
-        ar[j] = x.x; ai[j] = x.y;
-      } else { ar[j] = (double)(ra + j); ai[j] = 0.0; }
+      const double2 x = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(tile) + ra);
+      ar[j] = x.x; ai[j] = x.y;
     }
   }
   if (IO != 1 && cross) {
@@ -623,20 +610,17 @@ __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const dou
     return;
 #undef BORNVI_LAST_GATE
   }
-  if (!(DEBUG && (dbg & 1))) {
-    double U[8];
-    if (NG > 0) { load_u(Us, U); op_u1_inplace<0>(ar, ai, U); }
-    if (NG > 1) { load_u(Us + 4, U); op_u1_inplace<1>(ar, ai, U); }
-    if (NG > 2) { load_u(Us + 8, U); op_u1_inplace<2>(ar, ai, U); }
-    if (NG > 3) { load_u(Us + 12, U); op_u1_inplace<3>(ar, ai, U); }
-  }
+  double U[8];
+  if (NG > 0) { load_u(Us, U); op_u1_inplace<0>(ar, ai, U); }
+  if (NG > 1) { load_u(Us + 4, U); op_u1_inplace<1>(ar, ai, U); }
+  if (NG > 2) { load_u(Us + 8, U); op_u1_inplace<2>(ar, ai, U); }
+  if (NG > 3) { load_u(Us + 12, U); op_u1_inplace<3>(ar, ai, U); }
   if (POST) apply_sign_bits(my_sg >> 16, ar, ai);
   if (IO == 2) {
     uint32_t ha0 = hbm_off;
     asm volatile("" : "+v"(ha0));     // addresses are formed here, after the gates
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-      if (DEBUG && (dbg & 8)) continue;
       const uint32_t ha = ha0 ^ (((j & 1) ? hbm_basis[0] : 0u) ^ ((j & 2) ? hbm_basis[1] : 0u) ^ ((j & 4) ? hbm_basis[2] : 0u) ^ ((j & 8) ? hbm_basis[3] : 0u));
       if (fin) async_store8(ha, ar[j] * ar[j] + ai[j] * ai[j], hbm_base);
       else async_store16(ha, (d2_t){ar[j], ai[j]}, hbm_base);
@@ -647,26 +631,20 @@ __device__ __forceinline__ void stage_body(double2* __restrict__ tile, const dou
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const uint32_t wa = wa0 ^ (((j & 1) ? G[FS_WB] : 0u) ^ ((j & 2) ? G[FS_WB + 1] : 0u) ^ ((j & 4) ? G[FS_WB + 2] : 0u) ^ ((j & 8) ? G[FS_WB + 3] : 0u));
-      if (!(DEBUG && (dbg & 2))) *reinterpret_cast<double2*>(reinterpret_cast<char*>(tile) + wa) = make_double2(ar[j], ai[j]);
+      *reinterpret_cast<double2*>(reinterpret_cast<char*>(tile) + wa) = make_double2(ar[j], ai[j]);
     }
-  }
-  if (DEBUG && (dbg & 2)) {
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc += ar[j] + ai[j];
-    if (acc == 1.2345e300) tile[0] = make_double2(acc, acc);
   }
 }
 
 // all (gate count, pre sign, post sign) kinds of one IO mode behind one scalar switch
-template <int IO, bool DEBUG, bool LT>
+template <int IO, bool LT>
 __device__ __forceinline__ void stage_dispatch(uint32_t kind, double2* __restrict__ tile, const double2* __restrict__ Us,
-                                               uint32_t my_rw, uint32_t my_sg, const uint32_t (&G)[10], int dbg,
+                                               uint32_t my_rw, uint32_t my_sg, const uint32_t (&G)[10],
                                                d2_t (&v)[16], uint32_t hbm_off, const uint32_t (&hbm_basis)[4],
                                                void* hbm_base, bool fin, bool cross) {
 #define BORNVI_STAGE(NG, PRE, POST) \
   case (NG) | ((PRE) << 3) | ((POST) << 4): \
-    stage_body<NG, PRE, POST, IO, DEBUG, LT>(tile, Us, my_rw, my_sg, G, dbg, v, hbm_off, hbm_basis, hbm_base, fin, cross); break;
+    stage_body<NG, PRE, POST, IO, LT>(tile, Us, my_rw, my_sg, G, v, hbm_off, hbm_basis, hbm_base, fin, cross); break;
 #define BORNVI_STAGE_NG(PRE, POST) \
   BORNVI_STAGE(0, PRE, POST) BORNVI_STAGE(1, PRE, POST) BORNVI_STAGE(2, PRE, POST) BORNVI_STAGE(3, PRE, POST) BORNVI_STAGE(4, PRE, POST)
   switch (kind) {
@@ -682,14 +660,13 @@ __device__ __forceinline__ void stage_dispatch(uint32_t kind, double2* __restric
 #undef BORNVI_STAGE
 }
 
-template <bool DEBUG, bool SPLIT>
+template <bool SPLIT>
 __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
     const uint32_t* __restrict__ plan, uint32_t pass_off, const uint32_t* __restrict__ fast, uint32_t fast_off,
     const double2* __restrict__ in, double2* __restrict__ out, double* __restrict__ probs,
     const double* __restrict__ gates, long long gate_stride, long long state_stride, long long total_tiles,
-    uint32_t lds_tab_off /* double2 units */, uint32_t lds_mats2_off /* double2 units */, int direct_mask, int dbg_arg,
+    uint32_t lds_tab_off /* double2 units */, uint32_t lds_mats2_off /* double2 units */, int direct_mask,
     PrefixShare share) {
-  const int dbg = DEBUG ? dbg_arg : 0;
   extern __shared__ double2 tile[];
   const uint32_t* __restrict__ P = plan + pass_off;
   const uint32_t* __restrict__ F = fast + fast_off;
@@ -791,7 +768,7 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
       tw_in[tt_] = fast[in_tab + (gn_ << kt) + tt_];                                                 \
     }                                                                                                \
     if (tt_ < npieces && !next_zero) async_load16(mp, tw_mat[tt_], gsrc_);                           \
-    if (!init && !(dbg & 4)) {                                                                       \
+    if (!init) {                                                                                     \
       /* one per-thread base offset, 16 wave-uniform offsets xor-ed in (both maps are bitwise disjoint or   \
          GF(2)-linear); the empty asm keeps the 16 sums from being hoisted out of the tile loop and spilled */ \
       const uint32_t base_ = tw_in[tt_];                                                             \
@@ -821,19 +798,19 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
     const uint32_t kind_ = FS_[FS_KIND];   /* fused gates (register bits 0 .. ng-1) | pre sign << 3 | post sign << 4 */ \
     const uint32_t rw_ = tab_rw[(uint32_t)(S_) * T + t];                                                        \
     const uint32_t sg_ = (kind_ >> 3) ? tab_sg[(uint32_t)__popc(sign_any & ((1u << (S_)) - 1u)) * T + t] : 0u;  \
-    stage_dispatch<IO_, DEBUG, SPLIT>(kind_, tile, mats + (S_) * 16, rw_, sg_, G_, dbg, v, (IO_) == 2 ? tw_out[t] : 0u, \
+    stage_dispatch<IO_, SPLIT>(kind_, tile, mats + (S_) * 16, rw_, sg_, G_, v, (IO_) == 2 ? tw_out[t] : 0u,             \
                                out_basis, hbm_base, fin, FS_[FS_CROSS] != 0u);                                  \
   } while (0)
   // (direct_mask bit 2: this launch walks the tiles from the last to the first -- alternate passes in opposite directions
   // start on the states the previous pass wrote last, i.e. on what the memory-side cache still holds)
   const long long walk_flip = total_tiles - 1;
   const bool walk_rev = (direct_mask & 4) != 0;
-  const bool zskip = !DEBUG && init && gbits > 0 && total_tiles < (1ll << 31);
+  const bool zskip = init && gbits > 0 && total_tiles < (1ll << 31);
   // direct_mask bit 3: the launcher vouches that pass 0 and pass 1 of this batch both run with the direct first stage
   // on, so the masks of FH_ZINFO (plan.cpp: support of |0..0>) hold: an INIT pass leaves out the tiles nobody will
   // read (zgmask), the pass behind it does not load the slots known to be zero (zslots; v[] is zero from the start of
   // the kernel and those registers are never loaded, so the first stage finds zeros there)
-  const uint32_t zinfo = (!DEBUG && (direct_mask & 8)) ? F[FH_ZINFO] : 0u;
+  const uint32_t zinfo = (direct_mask & 8) ? F[FH_ZINFO] : 0u;
   const uint32_t zgmask = zskip ? zinfo : 0u;
   const uint32_t zslots = (!init && direct_in) ? (zinfo & 0xffffu) : 0u;
   const uint32_t zs_nb = (uint32_t)(total_tiles >> gbits), zs_gm1 = (1u << gbits) - 1u;   // circuits; zero tiles per circuit
@@ -875,8 +852,7 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
     if (real) {
       // ---- the tile has arrived in registers: all but this wave's 16 tile-out stores are done (after trip -1
       // nothing is outstanding) ----
-      if (DEBUG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
 #pragma unroll
       for (int i = 0; i < MAX_TILE_ITERS; ++i) asm volatile("" : "+v"(v[i]));
       // ---- registers -> LDS: the tile (head CNOTs of the pass folded into the slot), unless the first stage
@@ -884,7 +860,7 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
       if (init) {
         if (!zero_tile)
           for (uint32_t u = t; u < ksize; u += T) tile[u] = make_double2((u == 0 && g == 0) ? 1.0 : 0.0, 0.0);
-      } else if (!direct_in && !(dbg & 4)) {
+      } else if (!direct_in) {
         const uint32_t slot_t = (tw_slots[t] & 0xffffu) ^ xor_map16(g, gbits, in_gmask);
 #pragma unroll
         for (int i = 0; i < MAX_TILE_ITERS; ++i) {
@@ -919,7 +895,7 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
       }
       if (tt_ < npieces && !next_zero) async_load16(mp, tw_mat[tt_], gates + bn_h * gate_stride);
     }
-    const bool want_v = has_next && !init && !(dbg & 4);
+    const bool want_v = has_next && !init;
     {
       const int s0 = (real && direct_in) ? 1 : 0;
       const int ns = (real && !zero_tile) ? nstages : 0;
@@ -992,7 +968,6 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
           const uint32_t it_l = ((i & 1) ? lpos[0] : 0u) ^ ((i & 2) ? lpos[1] : 0u) ^ ((i & 4) ? lpos[2] : 0u) ^ ((i & 8) ? lpos[3] : 0u);
           const uint32_t it_p = gout ^ ((i & 1) ? pcol[0] : 0u) ^ ((i & 2) ? pcol[1] : 0u) ^ ((i & 4) ? pcol[2] : 0u) ^ ((i & 8) ? pcol[3] : 0u);
           const double2 x = tile[thr_l ^ it_l];
-          if (DEBUG && (dbg & 8)) continue;
           if (fin) async_store8(thr_out ^ it_p, x.x * x.x + x.y * x.y, pdst);
           else async_store16(thr_out ^ it_p, (d2_t){x.x, x.y}, dst);
         }
@@ -1019,7 +994,7 @@ __global__ __launch_bounds__(512) void circuit_pass_fast_kernel(
     }
     // ---- the next tile's matrices (the oldest loads in flight: everything but the 16 amplitude loads and the 16
     // stores behind them is done after vmcnt(32); trip -1 and INIT passes have fewer ops in flight) -> the other buffer ----
-    if (DEBUG || !real) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!real) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if (init || zslots) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // (fewer than 16 loads in flight: all but the stores)
     else asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
     asm volatile("" : "+v"(mp));
@@ -1275,17 +1250,10 @@ hipError_t launch_normalise_gates(double* gates, int count, hipStream_t st) {
 }
 
 hipError_t prepare_circuit_kernel(size_t lds_bytes) {
-  const void* fns[6] = {reinterpret_cast<const void*>(circuit_pass_kernel<true, false>),
-                        reinterpret_cast<const void*>(circuit_pass_kernel<false, false>),
-                        reinterpret_cast<const void*>(circuit_pass_kernel<true, true>),
-                        reinterpret_cast<const void*>(circuit_pass_kernel<false, true>),
-                        reinterpret_cast<const void*>(circuit_pass_fast_kernel<false, false>),
-                        reinterpret_cast<const void*>(circuit_pass_fast_kernel<true, false>)};
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(circuit_pass_fast_kernel<false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
+  const void* fns[4] = {reinterpret_cast<const void*>(circuit_pass_kernel<true>),
+                        reinterpret_cast<const void*>(circuit_pass_kernel<false>),
+                        reinterpret_cast<const void*>(circuit_pass_fast_kernel<true>),
+                        reinterpret_cast<const void*>(circuit_pass_fast_kernel<false>)};
   for (const void* f : fns) {
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
@@ -1296,8 +1264,8 @@ hipError_t prepare_circuit_kernel(size_t lds_bytes) {
 int circuit_fast_workgroups_per_cu(int threads, size_t lds) {
   int nb = 0;
   const hipError_t e = threads >= 256
-                           ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_fast_kernel<false, true>, threads, lds)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_fast_kernel<false, false>, threads, lds);
+                           ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_fast_kernel<true>, threads, lds)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_fast_kernel<false>, threads, lds);
   if (e != hipSuccess) return 0;
   return nb;
 }
@@ -1305,7 +1273,7 @@ int circuit_fast_workgroups_per_cu(int threads, size_t lds) {
 hipError_t launch_circuit_pass_fast(const uint32_t* plan, uint32_t pass_off, const uint32_t* fast, uint32_t fast_off,
                                     int n, int k, size_t lds, int batch, const void* in, void* out, double* probs,
                                     const double* gates, long long gate_stride, int max_workgroups, size_t lds_tab_off,
-                                    size_t lds_mats2_off, int direct_mask, int dbg, const PrefixShare& share, hipStream_t st) {
+                                    size_t lds_mats2_off, int direct_mask, const PrefixShare& share, hipStream_t st) {
   const long long total_tiles = (long long)batch << (n - k);
   if (total_tiles == 0) return hipSuccess;
   long long wgs = (max_workgroups > 0 && total_tiles > max_workgroups) ? max_workgroups : total_tiles;
@@ -1315,33 +1283,30 @@ hipError_t launch_circuit_pass_fast(const uint32_t* plan, uint32_t pass_off, con
   if (wgs > per_state) wgs -= wgs % per_state;
   dim3 grid((unsigned)wgs);
   const dim3 block(1u << (k - 4));
-#define BORNVI_LAUNCH_FAST(D_, S_, DBG_)                                                                                 \
-  circuit_pass_fast_kernel<D_, S_><<<grid, block, lds, st>>>(plan, pass_off, fast, fast_off, (const double2*)in, (double2*)out, \
-                                                             probs, gates, gate_stride, 1ll << n, total_tiles,            \
-                                                             (uint32_t)(lds_tab_off / 16), (uint32_t)(lds_mats2_off / 16), direct_mask, DBG_, share)
+#define BORNVI_LAUNCH_FAST(S_)                                                                                       \
+  circuit_pass_fast_kernel<S_><<<grid, block, lds, st>>>(plan, pass_off, fast, fast_off, (const double2*)in, (double2*)out, \
+                                                         probs, gates, gate_stride, 1ll << n, total_tiles,            \
+                                                         (uint32_t)(lds_tab_off / 16), (uint32_t)(lds_mats2_off / 16), direct_mask, share)
   // large tiles (one workgroup of >= 4 waves per CU): the instantiation that spreads the prefetch over the stages
-  if (dbg) BORNVI_LAUNCH_FAST(true, false, dbg);
-  else if (block.x >= 256) BORNVI_LAUNCH_FAST(false, true, 0);
-  else BORNVI_LAUNCH_FAST(false, false, 0);
+  if (block.x >= 256) BORNVI_LAUNCH_FAST(true);
+  else BORNVI_LAUNCH_FAST(false);
 #undef BORNVI_LAUNCH_FAST
   return hipGetLastError();
 }
 
 hipError_t launch_circuit_pass(const uint32_t* plan, uint32_t pass_off, int n, int k, int threads, size_t lds, int batch,
                                const void* in, void* out, double* probs, const double* gates,
-                               long long gate_stride, int max_workgroups, int dbg, hipStream_t st) {
+                               long long gate_stride, int max_workgroups, hipStream_t st) {
   const long long total_tiles = (long long)batch << (n - k);
   dim3 grid((unsigned)((max_workgroups > 0 && total_tiles > max_workgroups) ? max_workgroups : total_tiles));
   int tau = 0;
   while ((1 << tau) < threads) ++tau;
   const bool full = (k - tau) == 4;   // 16 tile elements per thread
-#define BORNVI_LAUNCH_PASS(F, D)                                                     \
-  circuit_pass_kernel<F, D><<<grid, dim3(threads), lds, st>>>(                       \
-      plan, pass_off, (const double2*)in, (double2*)out, probs, gates, gate_stride, 1ll << n, total_tiles, dbg)
-  if (full && !dbg) BORNVI_LAUNCH_PASS(true, false);
-  else if (full) BORNVI_LAUNCH_PASS(true, true);
-  else if (!dbg) BORNVI_LAUNCH_PASS(false, false);
-  else BORNVI_LAUNCH_PASS(false, true);
+#define BORNVI_LAUNCH_PASS(F)                                                        \
+  circuit_pass_kernel<F><<<grid, dim3(threads), lds, st>>>(                          \
+      plan, pass_off, (const double2*)in, (double2*)out, probs, gates, gate_stride, 1ll << n, total_tiles)
+  if (full) BORNVI_LAUNCH_PASS(true);
+  else BORNVI_LAUNCH_PASS(false);
 #undef BORNVI_LAUNCH_PASS
   return hipGetLastError();
 }

@@ -59,7 +59,7 @@ class SteinOperator:
         # earlier ones are held), the contraction is timed on each, the fastest stays (_place_gram).  The contraction's
         # rate depends on where the driver put K_p RELATIVE to the workspace its partial sums go to -- 2.55 or 2.78 ms
         # at n = 16 for the same kernel and matrix, stable for the life of the allocations, equal alone and inside the
-        # training step (tools/probes/step_placement_probe.py, ws_place_probe.py, ws_far_probe.py) -- and a process
+        # training step (tools/probes/ws_place_probe.py) -- and a process
         # cannot see physical addresses.  One-time cost: ~50 ms and 2^(2n+3) bytes per extra copy, freed at once; the
         # search stops at the first pair that streams at 83 % of the HBM peak.  1 = take the first copy.
         self.gram_placement_tries = 4
@@ -152,7 +152,7 @@ class SteinOperator:
         and its rate depends on where the driver put it relative to the contraction's workspace: round 2, same kernel,
         same box, n = 16: 2.55 ms or 2.78 ms, stable for the life of the two allocations, the same alone and inside the
         training step, following the (K_p, workspace) PAIR -- a workspace inside K_p's own allocation is always the
-        slow case (tools/probes/ws_in_kp_probe.py), one 64+ GiB further on usually the fast one (ws_far_probe.py).
+        slow case, one 64+ GiB further on usually the fast one.
         (Round 1's 2.84 / 3.32 ms were the same effect amplified by 8x more partial-sum stores.)
         So: build up to `gram_placement_tries` copies (each in fresh memory while the earlier ones are still held), and
         behind each a fresh workspace (`ws_bytes` > 0: the symmetric contraction's, which then lies one matrix further
