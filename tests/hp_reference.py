@@ -1,0 +1,500 @@
+"""Extended-precision reference of the Stein path and its per-entry error bounds (test infrastructure, not under test).
+
+Plain and slow on purpose.  Every function restates a formula that oracle/stein.py (fp64) already restates and cites the
+same reference lines; where it can, it takes another route than the oracle's closed forms.  Arithmetic is x87
+``np.longdouble`` (eps 1.08e-19) where the platform has it, else mpmath at 40 digits on object arrays (small cases only:
+``MAX_N`` says how far).  Each ``*_terms`` / bound output is the same sum with every term replaced by its absolute
+value: a correct fp64 evaluation is wrong by a small multiple of ``EPS64 * bound`` PER ENTRY, however the magnitudes of
+the entries differ, so the tests assert ``ratio(got, ref, bound) <= C`` with no global maximum anywhere.
+
+Index convention as everywhere: outcome index i <-> tuple z, z[b] = (i >> (n-1-b)) & 1 (utils.py:77-91).
+"""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+LD = np.longdouble
+HAVE_LONGDOUBLE = bool(np.finfo(LD).eps < 2e-19)
+EPS64 = float(np.finfo(np.float64).eps)          # 2^-52: the unit every ratio is expressed in
+TINY64 = 2.0 ** -1074                            # smallest fp64 subnormal: the underflow floor's unit
+THREADS = max(1, min(16, os.cpu_count() or 1))
+
+
+class _LongDouble:
+    name = "longdouble"
+    max_n = 16
+
+    @staticmethod
+    def arr(x):
+        return np.asarray(x, dtype=np.float64).astype(LD)
+
+    num = staticmethod(LD)
+    exp = staticmethod(np.exp)
+    sqrt = staticmethod(np.sqrt)
+
+    @staticmethod
+    def zeros(shape):
+        return np.zeros(shape, LD)
+
+
+class _MpMath:
+    """40-digit mpmath numbers in object arrays: NumPy's +, *, abs, sum, @ and where all work on them."""
+    name = "mpmath-40"
+    max_n = 5
+
+    def __init__(self):
+        import mpmath
+        self.mp = mpmath.mp.clone()
+        self.mp.dps = 40
+
+    def num(self, x):
+        return self.mp.mpf(x if isinstance(x, (int, str)) else float(x))
+
+    def arr(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        out = np.empty(x.shape, dtype=object)
+        flat = out.reshape(-1)
+        for k, v in enumerate(x.reshape(-1)):
+            flat[k] = self.mp.mpf(float(v))      # float -> mpf is exact
+        return out
+
+    def exp(self, x):
+        return self.mp.exp(x)
+
+    def sqrt(self, x):
+        return self.mp.sqrt(x)
+
+    def zeros(self, shape):
+        out = np.empty(shape, dtype=object)
+        out.reshape(-1)[:] = [self.mp.mpf(0)] * out.size
+        return out
+
+
+def arithmetic(kind=None):
+    """The arithmetic the references run in: long double if it has a 64-bit mantissa, else mpmath."""
+    if kind is None:
+        kind = "longdouble" if HAVE_LONGDOUBLE else "mpmath"
+    if kind == "longdouble":
+        assert HAVE_LONGDOUBLE, "np.longdouble has no 64-bit mantissa on this machine"
+        return _LongDouble
+    return _MpMath()
+
+
+def unavailable(n, X=None):
+    """None, or the reason a case of size n is left out (printed by the test that skips it)."""
+    X = X or arithmetic()
+    if n > X.max_n:
+        return f"long double unavailable (np.longdouble eps {np.finfo(LD).eps:.3g}); {X.name} covers n <= {X.max_n} only"
+    return None
+
+
+def to_f64(x):
+    return np.asarray(x).astype(np.float64)
+
+
+def popcount(x):
+    x = np.array(x, dtype=np.int64)
+    c = np.zeros_like(x)
+    while x.any():
+        c += x & 1
+        x >>= 1
+    return c
+
+
+def ratio(got, ref, bound, floor=0.0, X=None):
+    """|got - ref| / (EPS64 * bound + floor) per entry, as float64.  Where the bound is exactly 0 (every term of the
+    entry is 0) only got == ref is accepted: the ratio is 0 or inf there."""
+    X = X or arithmetic()
+    got = np.atleast_1d(np.asarray(got, dtype=np.float64))
+    err = np.abs(X.arr(got) - np.atleast_1d(ref))
+    den = np.atleast_1d(bound) * X.num(EPS64) + X.arr(np.asarray(floor, dtype=np.float64))
+    zero = to_f64(den) == 0.0 if den.dtype != object else np.array([d == 0 for d in den.reshape(-1)]).reshape(den.shape)
+    safe = np.where(zero, X.num(1), den)
+    r = to_f64(err / safe)
+    exact = to_f64(err) == 0.0
+    return np.where(zero, np.where(exact, 0.0, np.inf), r)
+
+
+def worst(r):
+    """(worst ratio, its index tuple) of a ratio array; NaN counts as the worst."""
+    r = np.asarray(r, dtype=np.float64)
+    r = np.where(np.isnan(r), np.inf, r)
+    k = np.unravel_index(int(np.argmax(r)), r.shape)
+    return float(r[k]), tuple(int(v) for v in k)
+
+
+def measured_constant(oracle_ratio, derived):
+    """C of an N-term sum: max(16, 8 x what NumPy fp64 achieves on the same inputs), never above the derived worst case.
+    8: the kernels add in other orders than NumPy (wave butterflies, strips, transposed partials); rounding errors of
+    an N-term sum grow like sqrt(N), so a small integer factor separates correct orders from each other, while a
+    dropped or misplaced term shows up as 1e3 ... 1e15."""
+    return float(min(max(16.0, 8.0 * float(oracle_ratio)), float(derived)))
+
+
+# ------------------------------------------------------------------------------------------------ Gram
+def gram_constant(n, d):
+    """Derived C of one Gram entry, in units of EPS64 * B_ij: the n-term dot of three-term addends (3 roundings per
+    bit: product, c_b * (..), the running sum -> 3n), a^d as d multiplications of a rounded a or one table product of
+    that accuracy (d), and 12 for what is done once per entry or per operand: rounding a and forming c_b = 1 - a,
+    1 - 1/a from it (the dominant part: a / (1 - a) ~ n l half-units at l = 1, inside the 3n above that),
+    S - 1, the sums of the two sides, the final product."""
+    return 3 * n + np.asarray(d) + 12
+
+
+def _pairs(n, rows, cols):
+    N = 1 << n
+    rows = np.arange(N) if rows is None else np.asarray(rows, dtype=np.int64)
+    cols = np.arange(N) if cols is None else np.asarray(cols, dtype=np.int64)
+    return rows, cols, rows[:, None] ^ cols[None, :]
+
+
+def gram_bound(S, n, length_scale=1.0, rows=None, cols=None, X=None):
+    """(K, B, d) from the closed form (oracle/stein.py gram_closed_form), bit by bit so that no
+    [R, C, n] array is formed:  K_ij = a^d sum_b [S_ib S_jb - c_b (S_ib + S_jb) + 2 c_b],
+    B_ij = a^d sum_b (|S_ib S_jb| + |c_b| (|S_ib| + |S_jb|) + 2 |c_b|);  a = exp(-1/(n l)) in extended precision."""
+    X = X or arithmetic()
+    rows, cols, x = _pairs(n, rows, cols)
+    one = X.num(1)
+    a = X.exp(-one / (X.num(n) * X.num(float(length_scale))))
+    c_same, c_diff = one - a, one - one / a
+    Sr, Sc = X.arr(np.asarray(S)[rows]), X.arr(np.asarray(S)[cols])
+    T, Bt = X.zeros(x.shape), X.zeros(x.shape)
+    for b in range(n):
+        bit = ((x >> (n - 1 - b)) & 1).astype(bool)
+        c = np.where(bit, c_diff, c_same)
+        si, sj = Sr[:, b][:, None], Sc[:, b][None, :]
+        T = T + (si * sj - c * (si + sj) + 2 * c)
+        Bt = Bt + (np.abs(si * sj) + np.abs(c) * (np.abs(si) + np.abs(sj)) + 2 * np.abs(c))
+    d = popcount(x)
+    pw = np.empty(n + 1, dtype=Sr.dtype)
+    for k in range(n + 1):
+        pw[k] = a ** k
+    return pw[d] * T, pw[d] * Bt, d
+
+
+def gram_four_terms(S, n, length_scale=1.0, rows=None, cols=None, X=None):
+    """K_ij from the four-term definition (stein_utils.py:138-197, Eq. 13; oracle/stein.py stein_kernel_value) with the
+    Hamming base kernel k = exp(-d / (n l)) evaluated separately at every flipped pair -- no c_b, no a^d."""
+    X = X or arithmetic()
+    rows, cols, x = _pairs(n, rows, cols)
+    nl = X.num(n) * X.num(float(length_scale))
+    Sr, Sc = X.arr(np.asarray(S)[rows]), X.arr(np.asarray(S)[cols])
+    tab = np.empty(n + 2, dtype=Sr.dtype)
+    for k in range(n + 2):
+        tab[k] = X.exp(-X.num(k) / nl)
+    d = popcount(x)
+    k0 = tab[d]
+    K = X.zeros(x.shape)
+    for b in range(n):
+        bit = ((x >> (n - 1 - b)) & 1).astype(bool)
+        kb = tab[np.where(bit, d - 1, d + 1)]      # k(z1, flip_b z2) = k(flip_b z1, z2); k(flip_b z1, flip_b z2) = k
+        si, sj = Sr[:, b][:, None], Sc[:, b][None, :]
+        K = K + (si * sj * k0 - si * (k0 - kb) - (k0 - kb) * sj + (k0 - kb - kb + k0))
+    return K
+
+
+def gram_terms(S, n, length_scale=1.0, rows=None, cols=None, X=None):
+    """(K, B): K from the four-term definition for n <= 6, from the closed form above that (test_hp_reference.py shows
+    that the two agree in extended precision); B always from the closed form's absolute terms."""
+    K, B, _ = gram_bound(S, n, length_scale, rows, cols, X)
+    if n <= 6:
+        K = gram_four_terms(S, n, length_scale, rows, cols, X)
+    return K, B
+
+
+# ------------------------------------------------------------------------------------------------ contractions
+def matvec(K64, q, rows=None, cols=None, X=None, chunk=256):
+    """From the fp64 matrix the kernel was given (any strided view): y = K q, Yb_i = sum_j |K_ij| |q_j|, and
+    k2 = sum_i q_i y_i, K2b = sum_i |q_i| Yb_i.  q is [N] or [m, N] (then y, Yb are [m, R] and k2, K2b [m]).
+    K64 may be a block of the matrix: ``rows`` names the R row indices it holds (default: all, in order) and ``cols`` the
+    column indices (default: all) -- q is always the whole vector, and k2, K2b then sum over the rows present only.
+    Row chunks run on up to 16 threads."""
+    X = X or arithmetic()
+    q2 = np.atleast_2d(np.asarray(q, dtype=np.float64))
+    R = K64.shape[0]
+    rows = np.arange(R) if rows is None else np.asarray(rows, dtype=np.int64)
+    ql = X.arr(q2)
+    qa = np.abs(ql)
+    qc, qca = (ql, qa) if cols is None else (ql[:, np.asarray(cols)], qa[:, np.asarray(cols)])
+    assert K64.shape == (len(rows), qc.shape[1]), "K64 must be [len(rows), len(cols)]"
+
+    def part(r0):
+        Kl = X.arr(np.asarray(K64[r0:r0 + chunk]))
+        return r0, Kl @ qc.T, np.abs(Kl) @ qca.T
+
+    y = np.empty((q2.shape[0], R), dtype=ql.dtype)
+    Yb = np.empty_like(y)
+    starts = range(0, R, chunk)
+    if X.name == "longdouble" and R > chunk:
+        with ThreadPoolExecutor(THREADS) as ex:
+            parts = list(ex.map(part, starts))
+    else:
+        parts = [part(r0) for r0 in starts]
+    for r0, yy, bb in parts:
+        y[:, r0:r0 + chunk] = yy.T
+        Yb[:, r0:r0 + chunk] = bb.T
+    k2 = (ql[:, rows] * y).sum(axis=1)
+    K2b = (qa[:, rows] * Yb).sum(axis=1)
+    if np.ndim(q) == 1:
+        return y[0], Yb[0], k2[0], K2b[0]
+    return y, Yb, k2, K2b
+
+
+def dense_constants(N):
+    """Derived worst case of an N-term fp64 dot product, units of EPS64 * sum |terms|: N roundings of products and
+    sums on the longest path (gamma_N) + 2; the quadratic form is a second such dot of the first's results."""
+    return float(N + 2), float(2 * N + 4)
+
+
+def _kbase(v, n, a):
+    """K_base v, K_base = M^{(x) n}, M = [[1, a], [a, 1]] (oracle/stein.py kbase_apply)."""
+    v = v.reshape((2,) * n)
+    for ax in range(n):
+        v0, v1 = np.take(v, 0, axis=ax), np.take(v, 1, axis=ax)
+        v = np.stack([v0 + a * v1, a * v0 + v1], axis=ax)
+    return v.reshape(-1)
+
+
+def _flip(v, n, b):
+    return np.flip(v.reshape((2,) * n), axis=b).reshape(-1)
+
+
+def kron(S, q, n, length_scale=1.0, X=None):
+    """(y, Yb, k2, K2b) of the matrix-free recipe (oracle/stein.py stein_matvec_kron): n butterfly
+    passes, then sum_b s_b w_b - s_b du_b - dw_b + 2 du_b.  Yb: the same recipe on |q| and |S| with every subtraction an
+    addition -- what the recipe's own intermediates add up to, larger than the dense form's sum_j |K_ij| |q_j|."""
+    X = X or arithmetic()
+    one = X.num(1)
+    a = X.exp(-one / (X.num(n) * X.num(float(length_scale))))
+    Sl, ql = X.arr(S), X.arr(q)
+    Sa, qa = np.abs(Sl), np.abs(ql)
+    u, ub = _kbase(ql, n, a), _kbase(qa, n, a)
+    y, Yb = X.zeros(ql.shape), X.zeros(ql.shape)
+    for b in range(n):
+        sb, sab = Sl[:, b], Sa[:, b]
+        w, wb = _kbase(sb * ql, n, a), _kbase(sab * qa, n, a)
+        du, dw = u - _flip(u, n, b), w - _flip(w, n, b)
+        dub, dwb = ub + _flip(ub, n, b), wb + _flip(wb, n, b)
+        y = y + (sb * w - sb * du - dw + 2 * du)
+        Yb = Yb + (sab * wb + sab * dub + dwb + 2 * dub)
+    return y, Yb, (ql * y).sum(), (qa * Yb).sum()
+
+
+def kron_constant(n):
+    """Derived worst case of the recipe against its own term bound, units of EPS64: per butterfly pass at most 4
+    roundings (a or a normalised gate entry, the product, the sum, a rescale) = 2 units, n passes; s_b q, the two
+    differences, the four-term combination and the n-term accumulation over bits: n + 8 more."""
+    return float(3 * n + 8), float(3 * n + 8 + (1 << n) + 2)
+
+
+# ------------------------------------------------------------------------------------------------ scores
+def score_packed(packed, n, X=None):
+    """(S, pxz, Sb, zeroed) from the arrays the score kernel is given (bayesian_network.pack_network):
+    p(x, z) = sum over hidden nodes of the product of CPT entries (stein_utils.py:58-112, bayesian_network.py:111-146),
+    s_b = 1 - p(x, flip_b z) / p(x, z), a zero row where |p(x, z)| < 1e-12 (stein_utils.py:115-136).
+    Sb = 1 + |p'/p| (0 on zeroed rows); every term of p is non-negative, so p is its own bound."""
+    X = X or arithmetic()
+    role = np.asarray(packed["role"])
+    V = len(role)
+    hidden = [v for v in range(V) if role[v] == -3]
+    H = len(hidden)
+    z = np.arange(1 << n, dtype=np.int64)[:, None]
+    h = np.arange(1 << H, dtype=np.int64)[None, :]
+    val = []
+    for v in range(V):
+        if role[v] >= 0:
+            val.append(((z >> (n - 1 - int(role[v]))) & 1) + 0 * h)
+        elif role[v] == -1:
+            val.append(0 * z + 0 * h)
+        elif role[v] == -2:
+            val.append(0 * z + 0 * h + 1)
+        else:
+            val.append(((h >> (H - 1 - hidden.index(v))) & 1) + 0 * z)
+    cpt = X.arr(packed["cpt"])
+    prob = None
+    for v in range(V):
+        cfg = 0 * z + 0 * h
+        for p in range(int(packed["n_parents"][v])):
+            cfg = cfg * 2 + val[int(packed["parents"][v][p])]
+        f = cpt[int(packed["cpt_off"][v]) + 2 * cfg + val[v]]
+        prob = f if prob is None else prob * f
+    pxz = prob.sum(axis=1)
+    zeroed = np.array([abs(p) < 1e-12 for p in pxz])
+    S, Sb = X.zeros((1 << n, n)), X.zeros((1 << n, n))
+    safe = np.where(zeroed, X.num(1), pxz)
+    for b in range(n):
+        r = pxz[np.arange(1 << n) ^ (1 << (n - 1 - b))] / safe
+        S[:, b] = np.where(zeroed, X.num(0), 1 - r)
+        Sb[:, b] = np.where(zeroed, X.num(0), 1 + np.abs(r))
+    return S, pxz, Sb, zeroed
+
+
+def score(bn, x, latent, X=None):
+    from tensornetworks_amd.bayesian_network import pack_network
+    return score_packed(pack_network(bn, latent, x), len(latent), X)
+
+
+def score_constants(packed):
+    """Derived C: p is a sum of 2^h products of V factors, all non-negative: V + 2^h roundings + 2.  s = 1 - p'/p: both
+    sums, the quotient and the subtraction, against 1 + |p'/p|: 2 (V + 2^h) + 2."""
+    V = len(packed["role"])
+    A = 1 << int((np.asarray(packed["role"]) == -3).sum())
+    return float(V + A + 2), float(2 * (V + A) + 2)
+
+
+# ------------------------------------------------------------------------------------------------ finish
+def finish(shifted, y, ksd2, X=None):
+    """bornvi_ksd_grad_finish (ksd_vi_quantum.py:144-150): loss = sqrt(max(ksd2, 1e-12)); dL/dq = y / loss, 0 where
+    ksd2 < 1e-12 (the clamp's zero gradient); grad_p = sum_z y_z (q+_p(z) - q-_p(z)) / (2 loss) likewise.  grad_bound:
+    sum_z |y_z| |q+ - q-| / (2 loss): the kernel rounds each difference once, relative to itself.  The comparison with
+    1e-12 is exact here as in fp64: both see the same fp64 ksd2."""
+    X = X or arithmetic()
+    k2 = float(np.asarray(ksd2).reshape(-1)[0])
+    clamped = k2 < 1e-12
+    loss = X.sqrt(X.num(1e-12 if clamped else k2))
+    yl = X.arr(y)
+    inv = X.num(0) if clamped else 1 / loss
+    out = {"loss": loss, "clamped": clamped, "dldq": yl * inv, "dldq_bound": np.abs(yl) * inv}
+    if shifted is not None and len(shifted):
+        sh = X.arr(shifted)
+        diff = sh[0::2] - sh[1::2]
+        out["grad"] = (diff * yl[None, :]).sum(axis=1) * inv / 2
+        out["grad_bound"] = (np.abs(diff) * np.abs(yl)[None, :]).sum(axis=1) * inv / 2
+    return out
+
+
+FINISH_DERIVED_C = 3.0      # loss: sqrt; dL/dq: sqrt, reciprocal, product -- three roundings, units of EPS64 (each 1/2)
+KSD2_EDGE_VALUES = (-1e-13, 0.0, 1e-13, float(np.nextafter(1e-12, 0.0)), 1e-12, float(np.nextafter(1e-12, 1.0)), 3.7e-3)
+
+
+# ------------------------------------------------------------------------------------------------ input families
+SCORE_FAMILIES = ("mild", "wide", "wide-cols", "spiky", "zero-rows")
+Q_FAMILIES = ("dirichlet", "onehot", "strip", "band", "odd", "subnormal", "signed")
+
+
+def spiky_rows(n, rng):
+    """About 1 % of the rows, placed on the first and last row of a 64-row Gram block, a 32-row wave strip, a 256-row
+    band, and on rows 0 and 2^n - 1."""
+    N = 1 << n
+    edges = [0, N - 1]
+    for w in (32, 64, 256):
+        if N > w:
+            k = int(rng.integers(0, N // w))
+            edges += [k * w, k * w + w - 1, w - 1, w, N - w]
+    extra = rng.integers(0, N, max(0, N // 100 - len(edges)))
+    return np.unique(np.concatenate([np.asarray(edges, dtype=np.int64), extra]))
+
+
+def scores(family, n, seed=0):
+    """Score matrices S [2^n, n] float64 of one family (seeded)."""
+    rng = np.random.default_rng([seed, n, SCORE_FAMILIES.index(family)])
+    N = 1 << n
+    S = rng.uniform(-1.0, 1.0, (N, n))
+    if family == "wide":
+        S *= 10.0 ** rng.uniform(-6, 6, (N, 1))
+    elif family == "wide-cols":
+        S *= 10.0 ** rng.uniform(-6, 6, (1, n))
+    elif family == "spiky":
+        r = spiky_rows(n, rng)
+        S[r] *= 10.0 ** rng.uniform(9, 11, (len(r), 1))
+    elif family == "zero-rows":
+        r = np.unique(np.concatenate([[0, N - 1], rng.integers(0, N, max(1, N // 8))]))
+        S[r] = 0.0
+        S[r[::2]] = -0.0
+    return np.ascontiguousarray(S)
+
+
+def qvec(family, n, seed=0):
+    """Vectors q [2^n] float64 of one family (seeded)."""
+    rng = np.random.default_rng([seed, n, 100 + Q_FAMILIES.index(family)])
+    N = 1 << n
+    if family == "dirichlet":
+        q = rng.dirichlet(np.full(N, 0.05))
+    elif family == "onehot":
+        q = np.full(N, 1e-30)
+        q[int(rng.integers(0, N))] = 1.0 - 1e-9
+    elif family in ("strip", "band", "odd"):
+        q = np.zeros(N)
+        if family == "strip":
+            k = int(rng.integers(0, max(1, N // 32)))
+            idx = np.arange(k * 32, min(N, k * 32 + 32))
+        elif family == "band":
+            idx = np.arange(max(0, N - 256), N)
+        else:
+            idx = np.arange(1, N, 2)
+        q[idx] = rng.random(len(idx)) + 1e-3
+        q /= q.sum()
+    elif family == "subnormal":
+        q = np.full(N, 1e-310)
+    elif family == "signed":
+        u, v = rng.random(N), rng.random(N)
+        q = 1.0 * u / u.sum() - 0.7 * v / v.sum()
+    else:
+        raise KeyError(family)
+    return np.ascontiguousarray(q, dtype=np.float64)
+
+
+def underflow_floor(family, nterms):
+    """Additive floor of a bound under the ``subnormal`` q: products underflow there, and each of the nterms terms may
+    lose up to one unit of the subnormal grid (a relative bound cannot hold for a correct implementation either)."""
+    return nterms * TINY64 if family == "subnormal" else 0.0
+
+
+def sharpen(bn, seed, expected_rows=6.0):
+    """Pushes about ``expected_rows`` CPT rows of a network (each row with the same probability, at most 1/2) to
+    {t, 1 - t}, t = 10^U(-9, -5): near-deterministic tables beside ordinary ones.  Flipping a bit across such a row
+    gives scores of 1e5 ... 1e9 beside O(1) ones; an outcome that meets two tiny entries falls under the 1e-12 cut and
+    gets a zero row, one that meets at most one keeps its scores (sharp_network asserts that enough do)."""
+    rng = np.random.default_rng([seed, 77])
+    total = sum(len(bn.cpts[name]) for name in bn.nodes)
+    prob = min(0.5, expected_rows / total)
+    for name in bn.nodes:
+        for cfg, row in bn.cpts[name].items():
+            if rng.random() >= prob:
+                continue
+            t = float(10.0 ** rng.uniform(-9, -5))
+            p1 = t if rng.random() < 0.5 else 1.0 - t
+            bn.cpts[name][cfg] = {0: 1.0 - p1, 1: p1}
+    return bn
+
+
+def sharp_network(n, seed):
+    from tensornetworks_amd.bayesian_network import synthetic_network
+    bn, lat, obs, x = synthetic_network(n, seed)
+    return sharpen(bn, seed), lat, obs, x
+
+
+def surviving_rows(zeroed, S):
+    """(rows that keep a score, rows among them with a score above 1e4 in magnitude): what a bn-sharp case exercises."""
+    kept = ~np.asarray(zeroed)
+    big = kept & (np.abs(to_f64(S)).max(axis=1) > 1e4)
+    return int(kept.sum()), int(big.sum())
+
+
+def cut_network():
+    """Three latents and one observed leaf with p(x, z = 110) = 1e-12 (1 + 1e-3) and p(x, z = 111) = 1e-12 (1 - 1e-3):
+    the score kernel must zero exactly the rows the reference zeroes (1e-3 is 1e13 roundings away from the cut)."""
+    from tensornetworks_amd.bayesian_network import BayesianNetwork
+    bn = BayesianNetwork()
+    row = lambda p1: {0: 1.0 - p1, 1: p1}
+    bn.add_node("Z0", cpt={(): row(2e-6)})
+    bn.add_node("Z1", cpt={(): row(1e-6 * (1 + 1e-3))})
+    bn.add_node("Z2", cpt={(): row(0.5)})
+    bn.add_node("X", cpt={(0,): row(1.0 - 1e-9), (1,): row((1 - 1e-3) / (1 + 1e-3))}, parent_names=["Z2"])
+    return bn, ["Z0", "Z1", "Z2"], ["X"], {"X": 1}
+
+
+def sample_rows(n, seed, count=96):
+    """Row indices for the sampled Gram checks: the edges of 64-row blocks, 32-row strips and 256-row bands, rows 0 and
+    2^n - 1, filled up with random rows."""
+    N = 1 << n
+    rng = np.random.default_rng([seed, n, 9])
+    r = [0, 1, N - 2, N - 1]
+    for w in (16, 32, 64, 256):
+        k = int(rng.integers(1, max(2, N // w - 1)))
+        r += [w - 1, w, k * w - 1, k * w, k * w + w - 1, N - w, N - w - 1]
+    r = np.unique(np.clip(np.asarray(r, dtype=np.int64), 0, N - 1))
+    more = rng.integers(0, N, 4 * count)
+    r = np.unique(np.concatenate([r, more[: max(0, count - len(r))]]))
+    return r[:count] if len(r) > count else r

@@ -89,6 +89,7 @@ def test_quadform_and_kron_match_oracle(be, dev, n, seed):
     Qt = torch.as_tensor(Q, device=dev)
     ksd2, Y = be.stein_quadform(K, Qt, n)
     scale = np.abs(Kn).max()
+    # (a global scale guards indexing; accuracy is bounded per entry in test_gpu_stein_precision.py)
     np.testing.assert_allclose(Y.cpu().numpy(), Q @ Kn.T, rtol=0, atol=1e-13 * scale)
     for b in range(3):
         ref = Q[b] @ Kn @ Q[b]
@@ -114,7 +115,7 @@ def test_symmetric_quadform_equals_full(be, dev, n):
     q /= q.sum()
     k_full, Y = be.stein_quadform(K, q, n)
     k_sym, y_sym = be.stein_quadform_sym(K, q, n)
-    scale = (K.abs() @ q).max().item()
+    scale = (K.abs() @ q).max().item()       # (global: per-entry bounds are in test_gpu_stein_precision.py)
     assert (Y[0] - y_sym).abs().max().item() <= 1e-13 * scale
     assert abs(k_full.item() - k_sym.item()) <= 1e-13 * float((q[:, None] * q[None, :] * K).abs().sum())
     # the reference value: dense NumPy product
@@ -240,6 +241,7 @@ def test_full_size_gram_properties(be, dev):
     assert abs(k2d.item() - k2s.item()) <= 1e-12 * abs(k2d.item())
     assert (yd[0] - ys).abs().max().item() <= 1e-12 * yd.abs().max().item()
     k2k, yk = be.stein_matvec_kron(S, q, n, 1.0)
+    # (looser than the forms' own bounds: test_gpu_stein_precision.py::test_kron_per_entry, ::test_full_size_once)
     assert abs(k2d.item() - k2k.item()) <= 1e-9 * abs(k2d.item())
     assert (yd[0] - yk).abs().max().item() <= 1e-10 * yd.abs().max().item()
     idx = torch.randint(0, 2 ** n, (4096,), generator=g).to(dev)
