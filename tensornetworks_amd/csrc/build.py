@@ -38,8 +38,9 @@ RESOURCE_BUDGET = {
     "reinforce_scatter_kernel": (0, 0),
     "reinforce_finish_kernel": (0, 0),
     "reinforce_loss_kernel": (0, 0),
-    "circuit_pass_r3_kernelILb1": (24, 4),        # its fused-dot instantiation (last pass only): 8 weights more per thread; the few
-                                                  # spilled address words are reloaded at the end of a trip, not inside the stages
+    "circuit_pass_r3_kernelILb1": (0, 0),         # its fused-dot instantiation (last pass only): 8 weights more per thread, exactly
+                                                  # 128 VGPRs; a scratch reload is a vector-memory load, and its wait is a wait for the
+                                                  # whole prefetched tile (vmcnt retires in issue order)
 }
 
 

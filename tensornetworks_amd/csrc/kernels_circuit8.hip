@@ -247,10 +247,9 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
   const int out_shift = fin ? 3 : 4;
   // ---- LDS: tile | LANE rows | UNI rows of one tile row | MASK ----
   char* __restrict__ lds = reinterpret_cast<char*>(tile);
-  uint32_t* __restrict__ lane_tab = reinterpret_cast<uint32_t*>(tile + ksize);
-  uint32_t* __restrict__ uni_tab = lane_tab + nrows * 64u;
-  uint32_t* __restrict__ mask_tab = uni_tab + nrows * NW;
-  double* __restrict__ red_tab = reinterpret_cast<double*>(lane_tab + (((nrows * 64u + nrows * NW + (nsign ? nsign : 1u) * NW) + 1u) & ~1u));   // [NW] wave sums (DOT)
+  // (byte offsets: the tile loop forms the table pointers from per-trip copies of them)
+  const uint32_t lane_off = ksize << 4, uni_off = lane_off + nrows * 256u, mask_off = uni_off + nrows * NW * 4u;
+  const uint32_t red_off = lane_off + ((((nrows * 64u + nrows * NW + (nsign ? nsign : 1u) * NW) + 1u) & ~1u) << 2);
   // (direct_mask: bit 0 / 1 allow the direct first / last stage; bit 2: walk the tiles backwards; bit 3: support of |0..0>)
   const bool direct_in = (H[CH_DIRECT] & 1u) && !init && nstages > 0 && (direct_mask & 1);
   const bool direct_out = (H[CH_DIRECT] & 2u) && nstages > 1 && (direct_mask & 2);
@@ -266,7 +265,7 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
   const uint32_t* __restrict__ UNI = C + H[CH_UNI_OFF];
   const uint32_t* __restrict__ MASK = C + H[CH_MASK_OFF];
   // tile-row independent tables -> LDS (trip -1 already reads them for the first prefetch)
-  for (uint32_t i = t; i < nrows * 64u; i += T) lane_tab[i] = C[H[CH_LANE_OFF] + i];
+  for (uint32_t i = t; i < nrows * 64u; i += T) reinterpret_cast<uint32_t*>(lds + lane_off)[i] = C[H[CH_LANE_OFF] + i];
   __syncthreads();
 
   double W[8];              // DOT: dL/dq at the thread's 8 outcomes of tile row g_w
@@ -321,6 +320,15 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
     uint32_t lane_t = lane, wv_t = wv;
     asm volatile("" : "+v"(lane_t), "+v"(wv_t));
     const uint32_t t_t = (wv_t << 6) | lane_t;
+    // (DOT sits at 128 VGPRs: per-trip scalar copies of the table offsets as well, or their wave-uniform LDS addresses are
+    // hoisted into VGPRs, spilled, and reloaded from scratch behind the prefetch burst -- a vector-memory load whose wait
+    // is a wait for the whole next tile)
+    uint32_t lane_o = lane_off, uni_o = uni_off, mask_o = mask_off, red_o = red_off;
+    if (DOT) asm volatile("" : "+s"(lane_o), "+s"(uni_o), "+s"(mask_o), "+s"(red_o));
+    uint32_t* __restrict__ lane_tab = reinterpret_cast<uint32_t*>(lds + lane_o);
+    uint32_t* __restrict__ uni_tab = reinterpret_cast<uint32_t*>(lds + uni_o);
+    uint32_t* __restrict__ mask_tab = reinterpret_cast<uint32_t*>(lds + mask_o);
+    double* __restrict__ red_tab = reinterpret_cast<double*>(lds + red_o);     // [NW] wave sums (DOT)
     // (tiles below 2^9: only the first 2^(k-3) lanes of the one wave hold amplitudes; the fused-dot instantiation is
     // offered for tiles of whole waves only)
     const bool active = DOT ? true : t_t < (ksize >> 3);
@@ -374,6 +382,10 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
                                        : (lane_tab[row_out_n * 64u + lane_t] ^ uni_tab[row_out_n * NW + wv_t]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) W[j] = wdot[(o_ ^ (direct_out ? comb3(j, out_step_d) : comb3(j, out_step_n))) >> 3];
+        // (read here, so the compiler waits for the weights in this branch: left pending, their vmcnt waits land in the dot
+        // at the end of every trip, where in issue order they are waits for the next tile's loads)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(W[j]));
       }
       acc = 0.0;
 #pragma unroll
@@ -398,6 +410,10 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
       if (!init && gn_ != g_pref) {   // rare: compiler-tracked load, waited for inside this branch
         g_pref = gn_;
         in_uni = UNI[((size_t)gn_ * nrows + row_in) * NW + (tt_ >> 6)];
+        // (the empty asm reads the word HERE, so the compiler's wait for it sits in this branch.  Without it the word is
+        // still "pending" on the path round the branch, and every conditional prefetch load below, each a block of its
+        // own, got an s_waitcnt vmcnt(0) in front of its address xor: the eight loads went out one round trip apart)
+        asm volatile("" : "+v"(in_uni));
       }
       if (!init && active) {
         const uint32_t base_ = lane_tab[row_in * 64u + (tt_ & 63u)] ^ in_uni;
