@@ -73,19 +73,11 @@ void bornvi_destroy(bornvi_handle h);
  * for errors of bornvi_create. */
 const char* bornvi_last_error(bornvi_handle h);
 
-/* A HIP stream restricted to the compute units [first_cu, first_cu + num_cus) of the device
- * (hipExtStreamCreateWithCUMask): lets the instruction-bound circuit passes and the HBM-bound contraction of one
- * step run side by side on disjoint halves of the chip instead of taking turns.  Launch the
- * circuit entry points on such a stream with the option "circuit_cus" = num_cus so that the persistent grid is
- * sized for it.  No reference counterpart. */
-int bornvi_stream_create_cu_range(bornvi_handle h, int first_cu, int num_cus, bornvi_stream* out);
-int bornvi_stream_destroy(bornvi_handle h, bornvi_stream stream);
-
 /* Tuning knobs of the circuit planner (clears the plan cache): "tile_bits" (4..13, amplitudes per
  * LDS tile = 2^tile_bits, for every n), "tile_bits_multi" (tile size used only when the state needs
  * several tiles; default 0 = chosen per plan: 13 wherever the persistent kernel can run such tiles, else 11), "low_bits" (0..8, contiguous 16-byte elements per HBM run =
  * 2^low_bits), "max_threads" (64..1024).  Engine switches (no effect on results): "fast_path",
- * "fast_workgroups_per_cu", "workgroups_per_cu", "direct_stages", "circuit_cus", "zero_support" (default 1: the first two passes of a circuit from |0..0> leave out what the support of that state makes
+ * "fast_workgroups_per_cu", "workgroups_per_cu", "direct_stages", "zero_support" (default 1: the first two passes of a circuit from |0..0> leave out what the support of that state makes
  * known zeros -- tiles nobody reads are not written, slots known to be zero are not loaded), "reg_wires" (default 3: plans with 8 amplitudes per thread for the pass kernel that holds four waves per SIMD, wherever
  * such a plan is eligible; 4: 16 amplitudes per thread, two waves per SIMD -- also the fallback; clears the plan cache),
  * "read_map" (default -1 = by the kernel: the planner may fold phase-0 CNOTs on thread-held wires into a stage's read map --

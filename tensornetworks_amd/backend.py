@@ -46,8 +46,8 @@ def _ws_key(dev, tag):
 
 def _ws(dev, nbytes, tag="main"):
     """Cached workspace, one per (device, purpose, STREAM): a buffer is only ever used on the stream it was allocated
-    on, so the caching allocator's stream-ordered reuse stays valid when a workspace is re-grown (the overlap modes
-    launch on auxiliary / CU-masked streams)."""
+    on, so the caching allocator's stream-ordered reuse stays valid when a workspace is re-grown (the graphed step
+    warms up and captures on a side stream, and the probes launch on several streams)."""
     key = _ws_key(dev, tag)
     buf = _workspaces.get(key)
     if buf is None or buf.numel() < nbytes:
@@ -178,25 +178,8 @@ def get_option(dev, name):
 
 
 def set_engine_option(dev, name, value):
-    """Options that do not change plans or workspace sizes (e.g. "circuit_cus"): no cache invalidation."""
+    """Options that do not change plans or workspace sizes (e.g. "batched_quadform"): no cache invalidation."""
     _ext.handle_for(dev).call("bornvi_set_option", name.encode(), int(value))
-
-
-_cu_streams = {}
-
-
-def cu_range_stream(dev, first_cu, num_cus):
-    """A stream restricted to the CUs [first_cu, first_cu + num_cus) (bornvi_stream_create_cu_range), as a
-    torch.cuda.ExternalStream so that torch events / allocator bookkeeping work with it.  Cached for the process."""
-    dev = torch.device(dev)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(first_cu), int(num_cus))
-    if key not in _cu_streams:
-        import ctypes as C
-        h = _ext.handle_for(dev)
-        st = C.c_void_p()
-        h.call("bornvi_stream_create_cu_range", int(first_cu), int(num_cus), C.byref(st))
-        _cu_streams[key] = torch.cuda.ExternalStream(st.value, device=dev)
-    return _cu_streams[key]
 
 
 _ROCTX = os.environ.get("BORNVI_ROCTX", "0") == "1"
@@ -283,7 +266,7 @@ def paramshift_dot_supported(ansatz_type, n, layers, dev, count):
     return 0 < _size_cache[key] <= WORKSPACE_CAP    # (the cap is read on every call: it may change after the size was cached)
 
 
-def paramshift_dot_begin(ansatz_type, n, layers, theta, p_begin, p_end, p_stride=1, ws_tag="dot"):
+def paramshift_dot_begin(ansatz_type, n, layers, theta, p_begin, p_end, p_stride=1):
     """First half of a parameter-shift step with the dot product fused into the last circuit pass: runs the base circuit
     and the shifted circuits of p = p_begin, p_begin + p_stride, ... < p_end up to their last pass, and the base circuit
     to the end.  Returns (q [2^n], token); give the token to paramshift_dot_finish once y = K_p q is known."""
@@ -296,7 +279,7 @@ def paramshift_dot_begin(ansatz_type, n, layers, theta, p_begin, p_end, p_stride
     need = int(_cached_size(h, "bornvi_paramshift_dot_workspace_bytes", aid, n, layers, count))
     if need == 0:
         raise BornviError("the fused parameter-shift dot is not available for this plan (see paramshift_dot_supported)")
-    ws = _ws(dev, need, ws_tag)
+    ws = _ws(dev, need, "dot")
     q = torch.empty(1 << n, dtype=torch.float64, device=dev)
     h.call("bornvi_paramshift_dot_begin", aid, n, layers, _ptr(theta), int(p_begin), int(count), int(p_stride), _ptr(q), _ptr(ws),
            ws.numel(), _ext.stream_ptr(dev))
@@ -538,7 +521,7 @@ def reinforce_step(idx, logit, log_p, q32, baseline, first, baseline_decay, entr
 SHOTS_MAX = (1 << 31) - 1
 
 
-def shots_histogram(probs, n, shots, seed, epoch, include_base=True, p_begin=0, p_stride=1, out=None, ws_tag="shots"):
+def shots_histogram(probs, n, shots, seed, epoch, include_base=True, p_begin=0, p_stride=1, out=None):
     """Finite-shot measurement of B Born distributions (bornvi_shots_histogram): probs float64 [B, 2^n] on the GPU ->
     frequencies counts / shots [B, 2^n] of `shots` exact multinomial draws per row.  Row r is circuit id 0 (base) if
     include_base and r == 0, else 2p + 1 / 2p + 2 for the (+p, -p) rows of p = p_begin, p_begin + p_stride, ... -- the
@@ -566,7 +549,7 @@ def shots_histogram(probs, n, shots, seed, epoch, include_base=True, p_begin=0, 
                 raise BornviError("shots_histogram: out overlaps probs without being the same buffer")
     if B == 0:
         return out
-    ws = _ws(dev, _cached_size(h, "bornvi_shots_workspace_bytes", int(n), int(B)), ws_tag)
+    ws = _ws(dev, _cached_size(h, "bornvi_shots_workspace_bytes", int(n), int(B)), "shots")
     h.call("bornvi_shots_histogram", int(n), int(B), _ptr(probs), _ptr(out), int(shots), int(seed) & ((1 << 64) - 1),
            _ptr(epoch), 1 if include_base else 0, int(p_begin), int(p_stride), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
     return out

@@ -20,7 +20,6 @@ Finite shots (qbm_shots=S): the base and the 2P shifted distributions of a step 
 each (backend.shots_histogram, every row its own draws) before the contraction; loss sqrt(max(q^T K_p q^, 1e-12)) and
 gradient 1/2 dL/dq^ . (q^+_p - q^-_p) are the plug-in estimates PennyLane's parameter-shift rule gives under shots.
 """
-import time
 from functools import partial
 
 import numpy as np
@@ -136,8 +135,8 @@ class KSDVariationalInference(SteinOperator):
         paramshift_shard.SOLO = never shard); qbm_shots = S: finite-shot training (every circuit evaluation of a step
         is a histogram of S draws; QuantumBornMachine(shots=...)), shot_seed = the draws' seed (None: one draw from
         torch's global CPU generator; pass the same seed, or seed torch alike, on every rank).  With shots the step
-        always runs the un-fused, sequential path (overlap_streams and fused_dot do not apply: the fused dot has no
-        probabilities to sample); the TVD and best-parameter snapshot of train() use the exact q_theta."""
+        always runs the un-fused path (fused_dot does not apply: the fused dot has no probabilities to sample); the
+        TVD and best-parameter snapshot of train() use the exact q_theta."""
         if int(qbm_num_latent_vars) != len(latent_vars_names):
             # the scores are [2^len(latent_vars_names), len(latent_vars_names)] while the circuit has
             # qbm_num_latent_vars qubits: the device kernels would index one with the other's sizes
@@ -166,18 +165,6 @@ class KSDVariationalInference(SteinOperator):
                                         num_vars=self.num_latent_vars,
                                         length_scale=base_kernel_length_scale)
 
-        # How the shifted circuits and the contraction of a step share the GPU (they need nothing from each other):
-        #   False        in sequence on the current stream
-        #   True         contraction on a second plain stream: paid with the one-workgroup-per-tile circuit kernel; the
-        #                persistent one fills every CU's registers and LDS, so the contraction's waves only get in
-        #                between passes (5.4-6.3 ms against 5.5 ms in sequence at n = 16)
-        #   "partition"  two CU-masked streams: the instruction-bound circuit passes on one half of the CUs, the
-        #                HBM-bound contraction on the other half (bornvi_stream_create_cu_range)
-        #                (measured on the MI355X at n = 16: 5.43 ms against 5.36 ms in sequence -- each kernel alone
-        #                keeps ~80 % of its speed on half the CUs, but together they contend for HBM; no gain)
-        #   None         = False.  `choose_overlap()` decides between False and "partition" by measurement.
-        self.overlap_streams = None
-        self.overlap_choice = None
         # Gradient engine.  "paramshift" (default) = the reference's rule: 2P shifted circuit evaluations
         # (diff_method="parameter-shift", quantum_born_machine.py:58).  "adjoint" = OPT-IN extra:
         # one forward and one backward walk over the gates (bornvi_adjoint_state / _vjp) -- the same gradient to
@@ -188,38 +175,19 @@ class KSDVariationalInference(SteinOperator):
         # same gradient to rounding; taken where the library offers it (multi-pass plans of the 8-amplitude kernel),
         # else the probabilities are written and dotted as before.  False: always the un-fused path (A/B).
         self.fused_dot = True
-        self._aux_stream = None
 
-    def choose_overlap(self, reps=4):
-        """Decides by measurement whether the circuits and the contraction of a step take turns on the whole chip or
-        run side by side on two halves of its CUs ("partition"); call after `_prepare_stein`.  Only where both are
-        sizeable: one GPU, dense Gram, circuits of several passes.  Runs 2 + `reps` gradient evaluations per mode at the current theta (no optimiser
-        step, nothing is kept); both modes produce the same numbers."""
-        rank, ws = shard.world(self.process_group)
-        n = self.num_latent_vars
-        self.overlap_streams = False
-        if ws != 1 or not self._use_dense() or n < 14 or self.born_machine.shots is not None:
-            return
-        dev = self._S.device
-        theta64 = self.born_machine.theta.detach().to(device=dev, dtype=torch.float64).contiguous()
-        timers, self.timers = self.timers, None
-        took = {}
-        try:
-            for mode in (False, "partition"):
-                self.overlap_streams = mode
-                for _ in range(2):
-                    self.ksd_and_grad(theta64)
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                for _ in range(reps):
-                    self.ksd_and_grad(theta64)
-                torch.cuda.synchronize(dev)
-                took[mode] = (time.perf_counter() - t0) / reps * 1e3
-        finally:
-            self.timers = timers
-        self.overlap_streams = "partition" if took["partition"] < 0.97 * took[False] else False
-        self.overlap_choice = {"sequential_ms": round(took[False], 4), "partition_ms": round(took["partition"], 4),
-                               "chosen": "partition" if self.overlap_streams else "sequential"}
+    # Both exist only because the benchmark record reads them: the overlap stream modes were retired.
+    overlap_choice = None
+
+    @property
+    def overlap_streams(self):
+        return False
+
+    @overlap_streams.setter
+    def overlap_streams(self, mode):
+        if mode is not None and mode is not False:
+            raise ValueError(f"overlap_streams = {mode!r}: the overlap stream modes were retired (they measured no gain, "
+                             "DESIGN.md section 4.1); commit 47ae535 is the last that has them")
 
     # ---- one KSD-gradient step on the device -------------------------------------------------------------
     def ksd_and_grad(self, theta64=None):
@@ -247,15 +215,7 @@ class KSDVariationalInference(SteinOperator):
             return loss, grad, q
         if self.grad_engine != "paramshift":
             raise ValueError("grad_engine must be 'paramshift' or 'adjoint'")
-        overlap = self.overlap_streams
-        if overlap is None:
-            overlap = False
-        if overlap == "partition":
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-            nc = ncu // 2
-            sc, sa = backend.cu_range_stream(dev, 0, nc), backend.cu_range_stream(dev, nc, ncu - nc)
-            q, ksd2, y, shifted = self._overlapped(theta64, lo, hi, step, sa, sc, cus=(ncu - nc, nc))
-        elif not overlap and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
+        if self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
             # The dot product with dL/dq fused into the shifted circuits' last pass (kernels_circuit8.hip): base circuit
             # and all but the last pass of the shifted ones -> q -> contraction -> last pass of the shifted circuits with
             # w = y.  Their probabilities are never written or re-read (8 GB each way at n = 20).
@@ -268,71 +228,17 @@ class KSDVariationalInference(SteinOperator):
                 with self._timed("allgather"):
                     grad = shard.all_gather_grad(grad_local, P, self.process_group)
             return loss, grad, q
-        elif not overlap:
-            with self._timed("circuits"):
-                probs = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=True, p_stride=step)
-            q = probs[0]
-            shifted = probs[1:]
-            with self._timed("stein"):
-                ksd2, y = self._stein_contract(q)
-        else:
-            # The contraction needs only q of the base circuit, the shifted circuits need neither: the base
-            # circuit and then the contraction run on a second HIP stream while the 2P shifted circuits run on
-            # the main one (they are bound by different resources: HBM vs LDS/FMA + HBM).
-            if self._aux_stream is None:
-                self._aux_stream = torch.cuda.Stream(device=dev)
-            q, ksd2, y, shifted = self._overlapped(theta64, lo, hi, step, self._aux_stream)
+        with self._timed("circuits"):
+            probs = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=True, p_stride=step)
+        q = probs[0]
+        shifted = probs[1:]
+        with self._timed("stein"):
+            ksd2, y = self._stein_contract(q)
         with self._timed("finish"):
             loss, grad_local, _ = backend.ksd_grad_finish(n, shifted, n_local, y, ksd2)
             with self._timed("allgather"):
                 grad = shard.all_gather_grad(grad_local, P, self.process_group)
         return loss, grad, q
-
-    def _overlapped(self, theta64, lo, hi, step, side, circ=None, cus=None):
-        """The two halves of a step that need nothing from each other, side by side: base circuit, then contraction, on the
-        stream `side`; the shifted circuits on the current stream or on `circ`; both after what the current stream holds and
-        joined on it again.  cus = ("circuit_cus" of `side`, of `circ`) for two CU-masked streams.  -> (q, ksd2, y, shifted)."""
-        bm = self.born_machine
-        n, L, at = self.num_latent_vars, bm.ansatz_layers, bm.ansatz_type
-        dev = theta64.device
-        main = torch.cuda.current_stream(dev)
-        start = torch.cuda.Event()
-        start.record(main)                      # theta64 is produced on the main stream
-        try:
-            with torch.cuda.stream(side):
-                side.wait_event(start)
-                if cus is not None:
-                    backend.set_engine_option(dev, "circuit_cus", cus[0])
-                with self._timed("base_circuit"):
-                    q = backend.paramshift_probs(at, n, L, theta64, 0, 0, include_base=True, ws_tag="base")[0]
-                with self._timed("stein"):
-                    ksd2, y = self._stein_contract(q)
-                stein_done = torch.cuda.Event()
-                stein_done.record(side)
-            if circ is None:
-                with self._timed("circuits"):
-                    shifted = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=False, p_stride=step)
-            else:
-                with torch.cuda.stream(circ):
-                    circ.wait_event(start)
-                    backend.set_engine_option(dev, "circuit_cus", cus[1])
-                    with self._timed("circuits"):
-                        shifted = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=False, p_stride=step,
-                                                           ws_tag="part")
-                    circ_done = torch.cuda.Event()
-                    circ_done.record(circ)
-        finally:
-            if cus is not None:
-                backend.set_engine_option(dev, "circuit_cus", 0)
-        main.wait_event(stein_done)
-        for tns in (ksd2, y, q):
-            tns.record_stream(main)
-        theta64.record_stream(side)
-        if circ is not None:
-            main.wait_event(circ_done)
-            shifted.record_stream(main)
-            theta64.record_stream(circ)
-        return q, ksd2, y, shifted
 
     def _ksd_and_grad_shots(self, theta64, lo, hi, step, n_local):
         """ksd_and_grad with finite shots: the un-fused batch (base row, then the (+p, -p) rows of this rank's parameters),
@@ -632,8 +538,7 @@ class KSDVariationalInference(SteinOperator):
         n = self.num_latent_vars
         rank, ws = shard.world(self.process_group)
         use_graph = (optimizer_type == "adam" and n <= 13 and ws == 1 and self.timers is None and num_epochs > 4
-                     and not self.overlap_streams and true_posterior_for_tvd is None)   # (a TVD per epoch needs theta
-                                                                                          # after exactly that epoch)
+                     and true_posterior_for_tvd is None)   # (a TVD per epoch needs theta after exactly that epoch)
         params, optimizer_born, scheduler = self.make_optimizer(lr_born_machine, num_epochs, use_lr_scheduler,
                                                                 optimizer_type, adam_betas, capturable=use_graph)
         dev = theta.device

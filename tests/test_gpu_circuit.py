@@ -364,8 +364,8 @@ def test_strided_parameter_set(be, dev, n, L, kb):
 
 
 def test_argument_errors_of_the_shift_entry_points(be, dev):
-    """Out-of-range parameter sets, CU ranges and workspaces are refused with BORNVI_ERR_* (raised as BornviError), not
-    executed: the kernels index with these numbers."""
+    """Out-of-range parameter sets and workspaces are refused with BORNVI_ERR_* (raised as BornviError), not executed:
+    the kernels index with these numbers.  So is the retired option "circuit_cus" (an unknown option now)."""
     import ctypes as C
     from tensornetworks_amd import _ext
     ansatz, n, L = "hardware_efficient", 6, 2
@@ -388,17 +388,9 @@ def test_argument_errors_of_the_shift_entry_points(be, dev):
         o14 = torch.empty((3, 1 << 14), dtype=torch.float64, device=dev)
         h.call("bornvi_paramshift_probs", aid, 14, 1, C.c_void_p(t14.data_ptr()), 0, 1, 1, C.c_void_p(o14.data_ptr()),
                C.c_void_p(ws.data_ptr()), 4096, None)
-    st = C.c_void_p()
-    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-    for first, cnt in ((-1, 4), (0, 0), (ncu - 1, 2), (0, ncu + 1)):
-        with pytest.raises(_ext.BornviError):
-            h.call("bornvi_stream_create_cu_range", first, cnt, C.byref(st))
-    try:
-        h.call("bornvi_stream_create_cu_range", 0, ncu // 2, C.byref(st))
-    except _ext.BornviError as e:                             # a valid range: only the driver can refuse it
-        pytest.skip(f"hipExtStreamCreateWithCUMask unavailable: {e}")
-    assert st.value
-    h.call("bornvi_stream_destroy", st)
+    with pytest.raises(_ext.BornviError):                     # the retired CU-range option and entry point are gone
+        be.set_option(dev, "circuit_cus", 8)
+    assert not hasattr(_ext.lib(), "bornvi_stream_create_cu_range")
 
 
 def test_prefix_sharing_with_the_large_tile(be, dev):

@@ -300,37 +300,6 @@ def test_async_step_equals_sync_step_and_guards_on_device(dev):
         assert torch.equal(opt.state[params[0]][k], v), k
 
 
-def test_cu_partition_mode_gives_the_same_step(dev):
-    """overlap_streams = "partition": circuits and contraction on two CU-masked streams (bornvi_stream_create_cu_range)
-    -- same loss, gradient and q as the sequential step, bit for bit (independent computations, only placed differently)."""
-    import torch
-    from tensornetworks_amd.bayesian_network import synthetic_network
-    from tensornetworks_amd.ksd_vi_quantum import KSDVariationalInference
-    n, L = 14, 2
-    bn, lat, obs, x = synthetic_network(n, seed=1)
-    torch.manual_seed(0)
-    vi = KSDVariationalInference(bn, lat, obs, qbm_num_latent_vars=n, qbm_ansatz_layers=L, pytorch_device=str(dev),
-                                 gram_mode="dense")
-    vi._prepare_stein(x)
-    vi.overlap_streams = False
-    vi.fused_dot = False          # (the overlapped modes store the probabilities and dot them afterwards: compare like with like;
-    l0, g0, q0 = vi.ksd_and_grad()   # the fused dot sums in another order -- tests/test_gpu_r3.py holds it to 1e-12)
-    vi.overlap_streams = "partition"
-    try:
-        backend_mod = __import__("tensornetworks_amd.backend", fromlist=["backend"])
-        ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-        backend_mod.cu_range_stream(dev, 0, ncu // 2)
-    except Exception as e:                                    # CU masking refused by this driver / container
-        pytest.skip(f"hipExtStreamCreateWithCUMask unavailable: {e}")
-    l1, g1, q1 = vi.ksd_and_grad()
-    l2, g2, q2 = vi.ksd_and_grad()
-    torch.cuda.synchronize()
-    for a, b in ((l0, l1), (g0, g1), (q0, q1), (l0, l2), (g0, g2)):
-        assert torch.equal(a, b)
-    vi.choose_overlap(reps=2)
-    assert vi.overlap_choice["chosen"] in ("sequential", "partition")
-
-
 def test_gram_placement_keeps_an_identical_matrix(dev):
     """Large dense K_p: _prepare_stein builds several copies in fresh memory, keeps the one the contraction streams
     fastest (placement matters on this part) and records the timings; the kept matrix is the same bits."""

@@ -369,6 +369,24 @@ def test_trainer_rejects_mismatched_latent_count():
         KSDVariationalInference(get_sprinkler_network(False), ['C', 'S', 'R'], ['W'], qbm_num_latent_vars=4)
 
 
+def test_overlap_modes_are_retired():
+    """The overlap stream modes are gone: what the benchmark record still reads stays (overlap_streams is False and
+    takes False / None, overlap_choice is None), every other mode is refused, and there is no choose_overlap."""
+    from tensornetworks_amd.bayesian_network import get_sprinkler_network
+    from tensornetworks_amd.ksd_vi_quantum import KSDVariationalInference
+    vi = KSDVariationalInference(get_sprinkler_network(False), ['C', 'S', 'R'], ['W'], qbm_num_latent_vars=3)
+    assert vi.overlap_streams is False
+    for mode in (False, None):
+        vi.overlap_streams = mode
+        assert vi.overlap_streams is False
+    for mode in (True, "partition"):
+        with pytest.raises(ValueError, match="retired"):
+            vi.overlap_streams = mode
+        assert vi.overlap_streams is False
+    assert vi.overlap_choice is None
+    assert not hasattr(vi, "choose_overlap")
+
+
 @pytest.mark.parametrize("mode,n,dense", [("auto", 1, True), ("auto", 12, True), ("auto", 16, True), ("auto", 17, False),
                                           ("auto", 29, False), ("dense", 12, True), ("dense", 17, True), ("kron", 3, False),
                                           ("kron", 16, False)])
