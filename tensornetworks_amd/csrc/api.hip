@@ -30,6 +30,7 @@ struct DevPlan {
   // plans with 3 register wires (8 amplitudes per thread): compact tables + circuit_pass_r3_kernel
   CompactTables compact;
   uint32_t* d_compact = nullptr;
+  std::vector<uint32_t> compact_hdr;   // the passes' compact headers (CH_WORDS each), kept on the host: the launcher reads them
   size_t r3_lds = 0;
   int r3_workgroups = 0;
   // prefix sharing of parameter-shift batches (circuit_batch): device tables per (parameter range, chunk capacity)
@@ -170,6 +171,8 @@ int get_plan(bornvi_handle h, int ansatz, int n, int layers, DevPlan** out) {
     }
     dp->r3_workgroups = circuit_r3_workgroups_per_cu(dp->plan.threads, dp->r3_lds) * h->num_cus;
     if (dp->r3_workgroups <= 0) return fail(h, BORNVI_ERR_HIP, "circuit_pass_r3_kernel: no workgroup fits a CU");
+    for (uint32_t o : dp->compact.pass_off)
+      dp->compact_hdr.insert(dp->compact_hdr.end(), dp->compact.words.begin() + o, dp->compact.words.begin() + o + CH_WORDS);
     std::vector<uint32_t>().swap(dp->compact.words);
     { int rc_ = sync_uploads(h); if (rc_) return rc_; }
     *out = dp.get();
@@ -265,7 +268,8 @@ int run_passes(bornvi_handle h, DevPlan* dp, int bc, const void* in0, void* bufA
                                            p.fast_lds_bytes(dp->fast.max_tab_rows), nb, in, out, final_probs, gates, gate_stride, wgs,
                                            p.fast_lds_tab_off(), p.fast_lds_mats2_off(dp->fast.max_tab_rows), direct_mask, ps, st));
       else
-        HIPCHK(h, launch_circuit_pass_r3(dp->d_words, p.pass_off[i], dp->d_compact, dp->compact.pass_off[i], p.n, p.k, dp->r3_lds, nb, in,
+        HIPCHK(h, launch_circuit_pass_r3(dp->d_words, p.pass_off[i], dp->d_compact, dp->compact.pass_off[i],
+                                         dp->compact_hdr.data() + (size_t)i * CH_WORDS, p.n, p.k, dp->r3_lds, nb, in,
                                          out, final_probs, gates, gate_stride, wgs, direct_mask, ps, last ? wdot : nullptr,
                                          last ? partials : nullptr, st));
     } else {
@@ -575,6 +579,7 @@ int bornvi_get_option(bornvi_handle h, const char* name, long long* value) {
   else if (!std::strcmp(name, "zero_support")) *value = h->zero_support;
   else if (!std::strcmp(name, "alternate_walk")) *value = h->alternate_walk;
   else if (!std::strcmp(name, "batched_quadform")) *value = h->batched_quadform;
+  else if (!std::strcmp(name, "fast_workgroups_per_cu")) *value = h->fast_wgs_per_cu;
   else return fail(h, BORNVI_ERR_INVALID, std::string("unknown option ") + name);
   return BORNVI_OK;
 }

@@ -36,7 +36,8 @@ hipError_t launch_circuit_pass_fast(const uint32_t* plan, uint32_t pass_off, con
 // 8 amplitudes per thread, compact tables (kernels_circuit8.hip; plan.hpp: CompactTables)
 hipError_t prepare_circuit_r3_kernel(size_t lds_bytes);
 int circuit_r3_workgroups_per_cu(int threads, size_t lds);
-hipError_t launch_circuit_pass_r3(const uint32_t* plan, uint32_t pass_off, const uint32_t* ctab, uint32_t ct_off, int n, int k,
+hipError_t launch_circuit_pass_r3(const uint32_t* plan, uint32_t pass_off, const uint32_t* ctab, uint32_t ct_off,
+                                  const uint32_t* hdr_host /* the pass's compact header on the host */, int n, int k,
                                   size_t lds, int batch, const void* in, void* out, double* probs, const double* gates,
                                   long long gate_stride, int max_workgroups, int direct_mask, const PrefixShare& share,
                                   const double* wdot, double* partials, hipStream_t st);

@@ -12,6 +12,8 @@
 // broadcast ds_read (which was a third of the LDS traffic of a stage), 16 VGPRs less.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "circuit_dev.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -220,7 +222,7 @@ __device__ __forceinline__ void dispatch8(uint32_t kind, char* __restrict__ lds,
 
 // DOT (final pass of a multi-pass plan only): instead of the probabilities of circuit b, partials[b * tiles + g] = the
 // tile's share of  sum_z wdot[z] q_b(z)  (fixed summation order: deterministic); probs is not written.
-template <bool DOT>
+template <bool DOT, bool SPREAD>
 __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
     const uint32_t* __restrict__ plan, uint32_t pass_off, const uint32_t* __restrict__ ctab, uint32_t ct_off,
     const double2* __restrict__ in, double2* __restrict__ out, double* __restrict__ probs,
@@ -305,6 +307,32 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
       dispatch8<IO_, false>(kind_, lds, gb, MAT_, rw_, sg_, RB_, WB_, v, ho_, out_step_d, hbm_base, CS_[CS_CROSS] != 0u, 1.0, W, acc); \
   } while (0)
 
+  // One group of the next tile's loads (GRP_: wave-uniform slot mask).  The address base is formed again at every site
+  // from the lane row in LDS and the loop-carried wave word: nothing is held in registers across a peeled stage.
+#define BORNVI_PREFETCH_GROUP8(GRP_)                                                                            \
+  do {                                                                                                          \
+    if (!init && active) {                                                                                      \
+      uint32_t tg_ = t_t;                                                                                       \
+      asm volatile("" : "+v"(tg_));                                                                             \
+      const long long bg_ = Tnext >> gbits;                                                                     \
+      const uint32_t base_ = lane_tab[row_in * 64u + (tg_ & 63u)] ^ in_uni;                                     \
+      const double2* src_ = in + (bg_ >= share.fresh_begin ? 0ll : bg_) * state_stride;                         \
+      _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                             \
+        if (((GRP_) >> i) & 1u) async_load16(v[i], base_ ^ comb3(i, in_step), src_);                            \
+    }                                                                                                           \
+  } while (0)
+  // One stage that reads LDS: the last stage of a pass with a direct last stage stores to HBM, every other one writes
+  // LDS and ends in a barrier
+#define BORNVI_LDS_STAGE8(S_)                                                                                   \
+  do {                                                                                                          \
+    if ((S_) == nstages - 1 && direct_out) {                                                                    \
+      if (active) BORNVI_RUN_STAGE8(S_, 2);                                                                     \
+    } else {                                                                                                    \
+      if (active) BORNVI_RUN_STAGE8(S_, 0);                                                                     \
+      __syncthreads();                                                                                          \
+    }                                                                                                           \
+  } while (0)
+
   const long long walk_flip = total_tiles - 1;
   const bool walk_rev = (direct_mask & 4) != 0;
   const bool zskip = init && gbits > 0 && total_tiles < (1ll << 31);
@@ -312,6 +340,31 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
   const uint32_t zgmask = zskip ? zinfo : 0u;
   const uint32_t zslots = (!init && direct_in) ? (zinfo & 0xffu) : 0u;
   const uint32_t zs_nb = (uint32_t)(total_tiles >> gbits), zs_gm1 = (1u << gbits) - 1u;
+  // ---- the next tile's eight loads are spread over the first LDS stages (wave-uniform, from nstages) ----
+  // A CU's memory pipe takes a wave's 1-KiB load in tens of cycles and issue is in order within a wave, so a wave that
+  // issues all eight back to back sits at its loads -- and issues no gate arithmetic -- while the pipe drains the other
+  // fifteen waves' bursts: reads and stages take turns.  The stages s0 .. s0 + npeel - 1 (s0: the first stage that reads
+  // LDS) are therefore PEELED out of the run-time stage loop into straight-line code, and the loads go out in npeel + 1
+  // groups at fixed sites of the trip's top-level block: behind stage 0 (or the tile fill), behind peeled stage s0 and
+  // behind peeled stage s0 + 1.  No load site is inside a loop: the compiler never merges an in-flight destination register
+  // (tools/check_async_regs.py follows the straight line from every site to the wait at the top of the next trip).
+  // The LAST stage of a pass is never peeled (npeel <= nstages - s0 - 1), so every store of a trip -- the direct last
+  // stage's or the drain's -- is issued behind the last load group: the issue order of a trip is still
+  // "this trip's loads, then this trip's stores", and the hand-counted waits at the top of a trip hold as they were.
+  // A pass with too few stages (npeel == 0) keeps the single burst.
+  // SPREAD is a second instantiation, not a run-time choice: the three copies of the stage switch cost SGPR spill moves in
+  // every stage (measured: + 4-10 % vector instructions, passes with nothing to spread 2-7 % slower), so the launcher sends
+  // a pass here only when it has loads to spread (launch_circuit_pass_r3), and every other launch -- the INIT pass, the
+  // pass behind it with its zero slots, the fused dot, every single-pass plan -- runs the instantiation with one site.
+  // Results do not depend on that choice: npeel is formed here, from the pass's own header.
+  const int s0 = direct_in ? 1 : 0;
+  const int spare = nstages - s0 - 1;          // LDS stages in front of the last one
+  const int nloads = init ? 0 : 8 - (int)__popc(zslots);
+  const int npeel = (!SPREAD || nloads == 0 || spare < 1) ? 0 : (spare > 2 ? 2 : spare);
+  // slots of the three load groups (npeel = 0: 8 | 0 | 0, 1: 4 | 4 | 0, 2: 3 | 3 | 2), less the slots the pass does not load
+  const uint32_t grp_a = (npeel == 0 ? 0xffu : npeel == 1 ? 0x0fu : 0x07u) & ~zslots;
+  const uint32_t grp_b = (npeel == 0 ? 0x00u : npeel == 1 ? 0xf0u : 0x38u) & ~zslots;
+  const uint32_t grp_c = (npeel == 2 ? 0xc0u : 0x00u) & ~zslots;
   for (long long Scur = (long long)blockIdx.x - (long long)gridDim.x;; Scur += gridDim.x) {
     const bool real = Scur >= 0;
     const long long Snext = Scur + gridDim.x;
@@ -373,7 +426,10 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
     }
     void* hbm_base = fin ? (void*)pdst : (void*)dst;
     if (real) {
-      // the tile has arrived in registers: all but this wave's 8 tile-out stores are done (DOT: a trip issues no stores)
+      // the tile has arrived in registers: all but this wave's 8 tile-out stores are done (DOT: a trip issues no stores).
+      // Issue order of the previous trip, whatever its load groups: group a, [peeled stage], group b, [peeled stage], group c,
+      // the remaining stages, then its 8 stores -- the last stage is never peeled, so no store sits between two load groups
+      // and the 8 youngest vector-memory ops are exactly the stores
       if (DOT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       if (DOT && g != g_w && active) {      // the thread's 8 weights of this tile row (the grid keeps a workgroup on one row: once per launch)
@@ -401,10 +457,9 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
       if (direct_in && active) BORNVI_RUN_STAGE8(0, 1);
       asm volatile("" ::: "memory");
     }
-    // ---- the registers are free: the next tile starts its trip from HBM now (the only load site) ----
+    // ---- the registers are free: the next tile starts its trip from HBM now (first of the three load sites) ----
     if (has_next) {
       const uint32_t gn_ = (uint32_t)(Tnext & ((1ll << gbits) - 1));
-      const long long bn_ = Tnext >> gbits;
       uint32_t tt_ = t_t;
       asm volatile("" : "+v"(tt_));   // (nothing derived from the thread id is hoisted out of the loop)
       if (!init && gn_ != g_pref) {   // rare: compiler-tracked load, waited for inside this branch
@@ -415,24 +470,28 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
         // own, got an s_waitcnt vmcnt(0) in front of its address xor: the eight loads went out one round trip apart)
         asm volatile("" : "+v"(in_uni));
       }
-      if (!init && active) {
-        const uint32_t base_ = lane_tab[row_in * 64u + (tt_ & 63u)] ^ in_uni;
-        const double2* src_ = in + (bn_ >= share.fresh_begin ? 0ll : bn_) * state_stride;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (!((zslots >> i) & 1u)) async_load16(v[i], base_ ^ comb3(i, in_step), src_);
-      }
+      BORNVI_PREFETCH_GROUP8(grp_a);
     }
     if (real) {
       __syncthreads();                          // the tile (or the first stage's result) is in LDS
-      for (int s = direct_in ? 1 : 0; s < (zero_tile ? 0 : nstages); ++s) {
-        if (s == nstages - 1 && direct_out) {
-          if (active) BORNVI_RUN_STAGE8(s, 2);
-        } else {
-          if (active) BORNVI_RUN_STAGE8(s, 0);
-          __syncthreads();
-        }
+      // first peeled stage (never the last stage of the pass: LDS -> LDS; an INIT pass's zero tiles run no stages)
+      if (SPREAD && npeel > 0 && !zero_tile) {
+        if (active) BORNVI_RUN_STAGE8(s0, 0);
+        __syncthreads();
       }
+    }
+    // ---- second load site ----
+    if (SPREAD && has_next) BORNVI_PREFETCH_GROUP8(grp_b);
+    if (real) {
+      if (SPREAD && npeel > 1 && !zero_tile) {           // second peeled stage
+        if (active) BORNVI_RUN_STAGE8(s0 + 1, 0);
+        __syncthreads();
+      }
+    }
+    // ---- third load site ----
+    if (SPREAD && has_next) BORNVI_PREFETCH_GROUP8(grp_c);
+    if (real) {
+      for (int s = s0 + npeel; s < (zero_tile ? 0 : nstages); ++s) BORNVI_LDS_STAGE8(s);
       // ---- tile out: exactly 8 vector-memory stores per wave (the vmcnt waits count them), here or in the last stage ----
       if (noop_tile || !active) {
       } else if (zero_tile) {
@@ -485,25 +544,45 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
     if (!real) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();   // the tile is overwritten by the next trip; the table rows are in place
   }
+#undef BORNVI_LDS_STAGE8
+#undef BORNVI_PREFETCH_GROUP8
 #undef BORNVI_RUN_STAGE8
 }
 
 hipError_t prepare_circuit_r3_kernel(size_t lds_bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(circuit_pass_r3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds_bytes);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(circuit_pass_r3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)lds_bytes);
+  const void* ks[3] = {reinterpret_cast<const void*>(circuit_pass_r3_kernel<false, false>),
+                       reinterpret_cast<const void*>(circuit_pass_r3_kernel<false, true>),
+                       reinterpret_cast<const void*>(circuit_pass_r3_kernel<true, false>)};
+  for (const void* kf : ks) {
+    hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 int circuit_r3_workgroups_per_cu(int threads, size_t lds) {
-  int nb = 0, nd = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_r3_kernel<false>, threads, lds) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nd, circuit_pass_r3_kernel<true>, threads, lds) != hipSuccess) return 0;
-  return nb < nd ? nb : nd;
+  int nb = 0, ns = 0, nd = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, circuit_pass_r3_kernel<false, false>, threads, lds) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ns, circuit_pass_r3_kernel<false, true>, threads, lds) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nd, circuit_pass_r3_kernel<true, false>, threads, lds) != hipSuccess) return 0;
+  return std::min(nb, std::min(ns, nd));
 }
 
-hipError_t launch_circuit_pass_r3(const uint32_t* plan, uint32_t pass_off, const uint32_t* ctab, uint32_t ct_off, int n, int k,
+// Does the pass have loads worth spreading over peeled stages?  hdr: the pass's compact header ON THE HOST.  Same derivation
+// as the kernel's (direct_in, zslots, spare); the cut-off "more than three slots to load" is a measured choice: with the
+// support of |0..0> on, pass 1 loads one slot, and with its stages peeled it ran 325 us against 315 us at n = 16 (DESIGN
+// 4.1a).  The fused dot keeps the single burst as well: its reads-only trips did not move (224 -> 226 us).
+static bool pass_spreads(const uint32_t* hdr, bool has_input, int direct_mask, bool dot) {
+  if (!hdr || !has_input || dot) return false;
+  const int nstages = (int)hdr[CH_NSTAGES];
+  const bool direct_in = (hdr[CH_DIRECT] & 1u) && nstages > 0 && (direct_mask & 1);
+  const uint32_t zslots = (direct_in && (direct_mask & 8)) ? (hdr[CH_ZINFO] & 0xffu) : 0u;
+  const int spare = nstages - (direct_in ? 1 : 0) - 1;
+  return spare >= 1 && 8 - __builtin_popcount(zslots) > 3;
+}
+
+hipError_t launch_circuit_pass_r3(const uint32_t* plan, uint32_t pass_off, const uint32_t* ctab, uint32_t ct_off,
+                                  const uint32_t* hdr_host, int n, int k,
                                   size_t lds, int batch, const void* in, void* out, double* probs, const double* gates,
                                   long long gate_stride, int max_workgroups, int direct_mask, const PrefixShare& share,
                                   const double* wdot, double* partials, hipStream_t st) {
@@ -512,12 +591,17 @@ hipError_t launch_circuit_pass_r3(const uint32_t* plan, uint32_t pass_off, const
   long long wgs = (max_workgroups > 0 && total_tiles > max_workgroups) ? max_workgroups : total_tiles;
   const long long per_state = 1ll << (n - k);
   if (wgs > per_state) wgs -= wgs % per_state;      // a workgroup keeps its tile row: its table rows stay in LDS
+  const dim3 grid((unsigned)wgs), block(k >= 9 ? 1u << (k - 3) : 64u);
   if (wdot)
-    circuit_pass_r3_kernel<true><<<dim3((unsigned)wgs), dim3(k >= 9 ? 1u << (k - 3) : 64u), lds, st>>>(
+    circuit_pass_r3_kernel<true, false><<<grid, block, lds, st>>>(
         plan, pass_off, ctab, ct_off, (const double2*)in, (double2*)out, probs, gates, gate_stride, 1ll << n, total_tiles,
         direct_mask, share, wdot, partials);
+  else if (pass_spreads(hdr_host, in != nullptr, direct_mask, false))
+    circuit_pass_r3_kernel<false, true><<<grid, block, lds, st>>>(
+        plan, pass_off, ctab, ct_off, (const double2*)in, (double2*)out, probs, gates, gate_stride, 1ll << n, total_tiles,
+        direct_mask, share, nullptr, nullptr);
   else
-    circuit_pass_r3_kernel<false><<<dim3((unsigned)wgs), dim3(k >= 9 ? 1u << (k - 3) : 64u), lds, st>>>(
+    circuit_pass_r3_kernel<false, false><<<grid, block, lds, st>>>(
         plan, pass_off, ctab, ct_off, (const double2*)in, (double2*)out, probs, gates, gate_stride, 1ll << n, total_tiles,
         direct_mask, share, nullptr, nullptr);
   return hipGetLastError();

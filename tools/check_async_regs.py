@@ -40,7 +40,15 @@ def check(asm_text, prefix="_ZN6bornvi24circuit_pass_fast_kernel"):
     top of the next trip as the compiler laid it out after it; branches are not followed.  (A path-exact version
     needs the loop invariants the vmcnt counts rest on -- "a pass with a direct last stage has more than one stage",
     "every stage kind is one of the twenty" -- and flags infeasible paths without them; the multi-trip parity test
-    tests/test_gpu_circuit.py::test_persistent_tile_loop is the check on the hardware.)"""
+    tests/test_gpu_circuit.py::test_persistent_tile_loop is the check on the hardware.)
+    circuit_pass_r3_kernel<false, true> has THREE load sites in a trip, with a conditionally run peeled stage between
+    two of them.  All three are straight-line code of the trip's top-level block, which the compiler lays out in source
+    order (site, peeled stage's switch, site, peeled stage's switch, site, stage loop), so the file-order scan walks from
+    each site through everything that can run behind it up to the end of the kernel with that site's registers in flight:
+    the peeled stages and the stage loop are covered for every group.  What the scan does NOT cover, with one site or with
+    three: the instructions between the loop header and the hand-written wait at the top of the next trip (they lie in front
+    of the sites in file order), and any layout in which the compiler moved a block that runs behind a site to a place in
+    front of it.  tests/test_gpu_r3_spread.py is the check of those on the hardware."""
     problems = []
     kernels = re.split(r"\n(?=" + re.escape(prefix) + r"[^\n]*:\s*;)", asm_text)
     n_sites = 0
