@@ -26,7 +26,8 @@
  *         (plan tile and workgroup indices are 16 bits, tiles at most 2^13 amplitudes;
  *          the 8-amplitude kernel runs n <= 27, the larger states the generic pass kernel);
  *       dense Gram and quadratic forms ............................ 1 <= n <= 17;
- *       score from CPTs, k_p pairs, gradient assembly, shots ....... 1 <= n <= 30;
+ *       score from CPTs, k_p pairs, gradient assembly, shots,
+ *       ELBO weights .............................................. 1 <= n <= 30;
  *       probability-table Born machine ............................ 0 <= n <= 30;
  *       un-fused gate application ................................. 1 <= n <= 40.
  */
@@ -348,6 +349,25 @@ int bornvi_reinforce_step(bornvi_handle h, int n, long long B, const long long* 
                           const float* log_p, const float* q32, double* baseline, int first, double baseline_decay,
                           double entropy_coef, double q_floor, double* dLdq, float* loss, float* found_inf,
                           void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
+/* ---- exact ELBO / reverse KL of a Born distribution (no reference counterpart: the reference estimates this quantity
+ * through a classifier and REINFORCE, adversarial_vi.py:200-222).  With the log-joint of one observation tabulated,
+ *   L = sum_z q_z (log q_z - log p(x, z)) = KL(q || p(.|x)) - log p(x)
+ * is exact in O(2^n).  q dev [rows, 2^n] float64; log_p dev [2^n] float64, finite, shared by all rows.  Per row, with
+ * l_z = log max(q_z, q_floor):
+ *   w dev [rows, 2^n] or NULL:  w_z = l_z - log_p_z + [q_z >= q_floor] = dL/dq_z -- the derivative of q log max(q, floor),
+ *     the convention of bornvi_born_table_vjp's entropy term; the weight vector of bornvi_paramshift_dot_finish
+ *     (ksd2 = NULL), the dLdq of bornvi_adjoint_vjp and the y of bornvi_born_table_vjp (ksd2 = NULL);
+ *   neg_elbo dev [rows] = sum_z q_z (l_z - log_p_z), a term with q_z == 0 being exactly 0;
+ *   entropy dev [rows] or NULL = -sum_z q_z l_z.
+ * A non-finite log_p entry is not refused: it reaches neg_elbo (unless its q_z is 0), where the optimiser hand-off's
+ * guard (bornvi_clip_cast_grad_guard, bornvi_clip_adam_step) skips the update.  The sums are fixed-order partials in the
+ * workspace (no atomics: bitwise reproducible); no allocation or synchronisation (capturable).  1 <= n <= 30,
+ * 1 <= rows <= 65535, q_floor > 0.  Workspace: bornvi_elbo_workspace_bytes(h, n, rows). */
+size_t bornvi_elbo_workspace_bytes(bornvi_handle h, int n, int rows);
+int bornvi_elbo_weights(bornvi_handle h, int n, int rows, const double* q, const double* log_p,
+                        double q_floor, double* w, double* neg_elbo, double* entropy,
+                        void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
 /* Gradient hand-off to the optimiser (replaces the float cast of the parameter-shift VJP and
  * torch.nn.utils.clip_grad_norm_(params, gradient_clip_norm), ksd_vi_quantum.py:153): grad32 dev [P] float32 =

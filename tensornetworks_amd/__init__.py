@@ -6,7 +6,7 @@ stein_utils) on a hand-written HIP backend (libbornvi_hip.so, C ABI in include/b
 from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "ClassicalKSDVariationalInference",
-           "ClassicalAdversarialVariationalInference",
+           "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
            "generate_all_binary_outcomes", "calculate_tvd"]
 
 
@@ -26,4 +26,10 @@ def __getattr__(name):
     if name == "ClassicalAdversarialVariationalInference":      # (the reference's adversarial_vi.AdversarialVariationalInference)
         from .adversarial_vi_classical import AdversarialVariationalInference
         return AdversarialVariationalInference
+    if name == "ELBOVariationalInference":
+        from .elbo_vi_quantum import ELBOVariationalInference
+        return ELBOVariationalInference
+    if name == "ClassicalELBOVariationalInference":
+        from .elbo_vi import ELBOVariationalInference
+        return ELBOVariationalInference
     raise AttributeError(name)

@@ -319,9 +319,23 @@ def paramshift_grad(ansatz_type, n, layers, theta, dLdq, p_begin, p_end, p_strid
     if shots is not None:
         S, seed, epoch = shots
         shots_histogram(shifted, n, S, seed, epoch, include_base=False, p_begin=p_begin, p_stride=p_stride, out=shifted)
-    # dot products on the device: reuse the finishing kernel with ksd2 = 1 (loss = 1, scale = 1/2)
+    return shifted_dot(n, shifted, ns, dLdq, out=grad)
+
+
+def shifted_dot(n, shifted, n_shift, dLdq, out=None):
+    """grad[i] = 1/2 dLdq . (shifted[2 i] - shifted[2 i + 1]) over stored (+p, -p) rows [2 n_shift, 2^n], float64: the
+    finishing kernel with ksd2 = 1 (loss = 1, scale = 1/2)."""
+    dev = dLdq.device
+    h = _ext.handle_for(dev)
+    _chk_n(n)
+    _chk(dLdq, torch.float64, dev, "dLdq", 1 << n)
+    grad = out if out is not None else torch.empty(n_shift, dtype=torch.float64, device=dev)
+    _chk(grad, torch.float64, dev, "out", n_shift)
+    if n_shift == 0:
+        return grad
+    _chk(shifted, torch.float64, dev, "shifted", (2 * n_shift) << n)
     one = torch.ones(1, dtype=torch.float64, device=dev)
-    h.call("bornvi_ksd_grad_finish", n, _ptr(shifted), ns, _ptr(dLdq), _ptr(one), None, None, _ptr(grad),
+    h.call("bornvi_ksd_grad_finish", n, _ptr(shifted), int(n_shift), _ptr(dLdq), _ptr(one), None, None, _ptr(grad),
            _ext.stream_ptr(dev))
     return grad
 
@@ -515,6 +529,48 @@ def reinforce_step(idx, logit, log_p, q32, baseline, first, baseline_decay, entr
            float(baseline_decay), float(entropy_coef), float(q_floor), _ptr(out), _ptr(loss_out), _ptr(found_out),
            _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
     return out, loss_out, found_out
+
+
+# ---- exact ELBO ---------------------------------------------------------------------------------------
+ELBO_MAX_ROWS = 65535
+
+
+def elbo_weights(q, log_p, q_floor=1e-10, want_w=True, want_entropy=True, out=None):
+    """Exact ELBO of Born distributions against a log-joint table (bornvi_elbo_weights): q float64 [rows, 2^n] (or
+    [2^n]) on the GPU, log_p float64 [2^n] = log p(x, z), finite -> (neg_elbo [rows] = sum q (l - log_p), entropy [rows]
+    = -sum q l or None, w [rows, 2^n] = l - log_p + [q >= q_floor] = d neg_elbo / d q or None), l = log max(q, q_floor).
+    out: destination of w (same element count as q).  Every argument error is raised here, before any GPU call."""
+    if not torch.is_tensor(q) or not torch.is_tensor(log_p) or q.dim() not in (1, 2) or log_p.dim() != 1:
+        raise BornviError("elbo_weights: q must be a [rows, 2^n] or [2^n] tensor and log_p a [2^n] tensor")
+    N = int(log_p.numel())
+    if N < 2 or N & (N - 1):
+        raise BornviError(f"log_p: {N} entries is not 2^n with n >= 1")
+    n = N.bit_length() - 1
+    _chk_n(n)
+    if q.shape[-1] != N:
+        raise BornviError(f"q: rows of {int(q.shape[-1])} entries against a log_p of {N}")
+    rows = int(q.numel()) // N
+    if not 1 <= rows <= ELBO_MAX_ROWS:
+        raise BornviError(f"q: 1 ... {ELBO_MAX_ROWS} rows per call, got {rows}")
+    if isinstance(q_floor, bool) or not isinstance(q_floor, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(q_floor) or not q_floor > 0:
+        raise BornviError(f"q_floor must be a positive finite number, got {q_floor!r}")
+    if out is not None and not want_w:
+        raise BornviError("elbo_weights: out is the destination of w, which want_w=False leaves out")
+    dev = q.device
+    h = _ext.handle_for(dev)
+    _chk(q, torch.float64, dev, "q")
+    _chk(log_p, torch.float64, dev, "log_p")
+    w = None
+    if want_w:
+        w = out if out is not None else torch.empty(q.shape, dtype=torch.float64, device=dev)
+        _chk(w, torch.float64, dev, "out", q.numel())
+    neg_elbo = torch.empty(rows, dtype=torch.float64, device=dev)
+    entropy = torch.empty(rows, dtype=torch.float64, device=dev) if want_entropy else None
+    ws = _ws(dev, _cached_size(h, "bornvi_elbo_workspace_bytes", n, rows), "elbo")
+    h.call("bornvi_elbo_weights", n, rows, _ptr(q), _ptr(log_p), float(q_floor), _ptr(w) if w is not None else None,
+           _ptr(neg_elbo), _ptr(entropy) if entropy is not None else None, _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return neg_elbo, entropy, w
 
 
 # ---- finite shots -------------------------------------------------------------------------------------

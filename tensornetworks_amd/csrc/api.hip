@@ -1089,6 +1089,26 @@ int bornvi_born_table_vjp(bornvi_handle h, int n, int rows, int mode, const floa
   return BORNVI_OK;
 }
 
+static bool valid_elbo(int n, int rows) { return n >= 1 && n <= 30 && rows >= 1 && rows <= 65535; }
+
+size_t bornvi_elbo_workspace_bytes(bornvi_handle h, int n, int rows) {
+  if (!h) return 0;
+  if (!valid_elbo(n, rows)) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  return elbo_workspace_bytes(n, rows);
+}
+
+int bornvi_elbo_weights(bornvi_handle h, int n, int rows, const double* q, const double* log_p, double q_floor, double* w,
+                        double* neg_elbo, double* entropy, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_elbo(n, rows)) return fail(h, BORNVI_ERR_INVALID, "bad argument (1 <= n <= 30, 1 <= rows <= 65535)");
+  if (!(q_floor > 0.0) || !std::isfinite(q_floor)) return fail(h, BORNVI_ERR_INVALID, "q_floor must be positive and finite");
+  if (!q || !log_p || !neg_elbo) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < elbo_workspace_bytes(n, rows)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_elbo_weights(n, rows, q, log_p, q_floor, w, neg_elbo, entropy, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 static bool valid_reinforce(int n, long long B) { return n >= 1 && n <= 30 && B >= 1 && B <= (1ll << 24); }
 
 size_t bornvi_reinforce_workspace_bytes(bornvi_handle h, int n, long long B) {

@@ -71,6 +71,11 @@ hipError_t launch_born_table_probs(int n, long long rows, int mode, const float*
 hipError_t launch_born_table_vjp(int n, long long rows, int mode, const float* w, const double* q64, const double* y,
                                  const double* ksd2, double lam, float* grad, double* loss_out, void* ws, hipStream_t st);
 
+// ---- exact ELBO of a Born distribution against a log-joint table (kernels_elbo.hip) --------------------
+size_t elbo_workspace_bytes(int n, long long rows);
+hipError_t launch_elbo_weights(int n, long long rows, const double* q, const double* log_p, double q_floor, double* w,
+                               double* neg_elbo, double* entropy, void* ws, hipStream_t st);
+
 // ---- classical Born machine, REINFORCE step of the adversarial trainer (kernels_reinforce.hip) ---------
 size_t reinforce_workspace_bytes(int n, long long B);
 hipError_t launch_reinforce_step(int n, long long B, const long long* idx, const float* logit, const float* log_p,

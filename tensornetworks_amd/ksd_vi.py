@@ -70,6 +70,13 @@ class KSDVariationalInference:
         """reference :55-60 -- one kernel launch for the scores, plus K_p (dense) once."""
         self._stein._precompute_all_s_p(x_dict)
 
+    # what train() knows of the objective: a trainer with another loss (elbo_vi.py) overrides these and loss_and_grads
+    _loss_name = "KSD"           # in the log lines
+    _loss_key = 'loss_ksd'       # history key of the loss
+
+    def _prepare_observation(self, x_dict):
+        self._precompute_all_s_p(x_dict)
+
     def make_optimizer(self, lr_born_machine, num_epochs, use_lr_scheduler=True, optimizer_type="adam",
                        adam_betas=(0.9, 0.999)):
         """The optimiser and scheduler the reference builds (ksd_vi.py:84-93)."""
@@ -143,11 +150,11 @@ class KSDVariationalInference:
                 raise ValueError("Born machine conditioning_dim must match num_observed_vars.")
             born_machine_x_condition = x_obs_tensor_for_bm
 
-        self._precompute_all_s_p(x_observation_dict)
+        self._prepare_observation(x_observation_dict)
         optimizer_born, scheduler = self.make_optimizer(lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type,
                                                         adam_betas)
 
-        history = {'loss_ksd': [], 'tvd': [], 'grad_norm': [], 'entropy': []}
+        history = {self._loss_key: [], 'tvd': [], 'grad_norm': [], 'entropy': []}
         best_tvd = float('inf')
         best_epoch = -1
         best_probs = None
@@ -181,7 +188,7 @@ class KSDVariationalInference:
                 if scheduler is not None:
                     scheduler.step()
 
-            history['loss_ksd'].append(ksd_value)
+            history[self._loss_key].append(ksd_value)
             history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
             history['entropy'].append(entropy_value)
 
@@ -206,7 +213,7 @@ class KSDVariationalInference:
                 history['tvd'].append(np.nan)
 
             if verbose and (epoch % max(1, num_epochs // 20) == 0 or epoch == num_epochs - 1):
-                log_msg = f"Epoch {epoch+1}/{num_epochs} | KSD: {ksd_value:.6f}"
+                log_msg = f"Epoch {epoch+1}/{num_epochs} | {self._loss_name}: {ksd_value:.6f}"
                 if scheduler is not None:
                     log_msg += f" | LR: {scheduler.get_last_lr()[0]:.6f}"
                 log_msg += f" | Entropy: {entropy_value:.4f}"

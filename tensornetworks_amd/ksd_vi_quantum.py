@@ -189,6 +189,22 @@ class KSDVariationalInference(SteinOperator):
             raise ValueError(f"overlap_streams = {mode!r}: the overlap stream modes were retired (they measured no gain, "
                              "DESIGN.md section 4.1); commit 47ae535 is the last that has them")
 
+    # ---- what the epoch loop below knows of the objective: a trainer with another loss (elbo_vi_quantum.py) overrides these
+    _loss_name = "KSD"           # in the log lines and warnings
+    _loss_key = 'loss_ksd'       # history key of the loss
+    _extra_keys = ()             # history keys of further per-epoch device scalars (_step_extras)
+
+    def _prepare_observation(self, x_dict):
+        self._precompute_all_s_p(x_dict)
+
+    def _objective_and_grad(self, **kw):
+        """The device part of one epoch -> (loss [1] float64, grad [P] float64, q [2^n])."""
+        return self.ksd_and_grad(**kw)
+
+    def _step_extras(self):
+        """Device scalars of the step just enqueued, one per _extra_keys entry."""
+        return ()
+
     # ---- one KSD-gradient step on the device -------------------------------------------------------------
     def ksd_and_grad(self, theta64=None):
         """Runs the device part of one epoch for the current theta: returns (loss [1] float64 on the GPU,
@@ -313,7 +329,7 @@ class KSDVariationalInference(SteinOperator):
         if not (theta.is_cuda and theta.dtype == torch.float32 and len(params) == 1 and optimizer_born.defaults.get("fused")):
             raise backend.BornviError("training_step_async needs a float32 theta on the GPU and a fused torch optimiser")
         optimizer_born.zero_grad()
-        loss_t, grad64, q = self.ksd_and_grad()
+        loss_t, grad64, q = self._objective_and_grad()
         g32, grad_norm, found_inf = backend.clip_cast_grad_guard(grad64, gradient_clip_norm, loss_t)
         theta.grad = g32
         optimizer_born.found_inf = found_inf
@@ -323,7 +339,7 @@ class KSDVariationalInference(SteinOperator):
             del optimizer_born.found_inf
         if scheduler is not None:
             scheduler.step()
-        return loss_t, grad_norm, q
+        return (loss_t, grad_norm, q) + tuple(self._step_extras())
 
     @staticmethod
     def _device_adam_for(theta, optimizer_born, scheduler):
@@ -367,11 +383,11 @@ class KSDVariationalInference(SteinOperator):
         adam = self._device_adam_for(theta, optimizer_born, scheduler) if device_adam else None
 
         def own_body():
-            loss_t, grad64, q = self.ksd_and_grad(theta64=adam.theta64)
-            return loss_t, adam.step(grad64, loss_t, gradient_clip_norm), q
+            loss_t, grad64, q = self._objective_and_grad(theta64=adam.theta64)
+            return (loss_t, adam.step(grad64, loss_t, gradient_clip_norm), q) + tuple(self._step_extras())
 
         def torch_body():
-            loss_t, grad64, q = self.ksd_and_grad()
+            loss_t, grad64, q = self._objective_and_grad()
             # (the clipped gradient and the guard flag are written straight into theta.grad and the flag tensor the fused
             # Adam kernel reads: no copy nodes in the graph)
             _, grad_norm, _ = backend.clip_cast_grad_guard(grad64, gradient_clip_norm, loss_t,
@@ -381,7 +397,7 @@ class KSDVariationalInference(SteinOperator):
                 optimizer_born.step()
             finally:
                 del optimizer_born.found_inf
-            return loss_t, grad_norm, q
+            return (loss_t, grad_norm, q) + tuple(self._step_extras())
 
         body = own_body if adam is not None else torch_body
 
@@ -421,7 +437,7 @@ class KSDVariationalInference(SteinOperator):
         """One epoch body (reference :111-161) without the logging: device step, NaN/Inf guard, clip,
         optimiser and scheduler step.  Returns (loss_value, grad_norm or None if skipped, q)."""
         optimizer_born.zero_grad()
-        loss_t, grad64, q = self.ksd_and_grad()
+        loss_t, grad64, q = self._objective_and_grad()
         loss_value = float(loss_t.item())        # the epoch's one host sync (reference: loss.item(), :163)
         if np.isnan(loss_value) or np.isinf(loss_value):
             return loss_value, None, q
@@ -460,12 +476,12 @@ class KSDVariationalInference(SteinOperator):
             x_obs_list_for_qbm = [x_observation_dict[name] for name in self.observed_vars_names]
             qbm_x_condition_input = torch.tensor(x_obs_list_for_qbm, dtype=torch.float32, device=self.pytorch_device)
 
-        self._precompute_all_s_p(x_observation_dict)
+        self._prepare_observation(x_observation_dict)
 
         params, optimizer_born, scheduler = self.make_optimizer(lr_born_machine, num_epochs, use_lr_scheduler,
                                                                 optimizer_type, adam_betas)
 
-        history = {'loss_ksd': [], 'tvd': [], 'grad_norm': []}
+        history = {self._loss_key: [], 'tvd': [], 'grad_norm': [], **{k: [] for k in self._extra_keys}}
         best_tvd = float('inf')
         best_params = None
         grad_norm = None
@@ -483,14 +499,16 @@ class KSDVariationalInference(SteinOperator):
                 raise ValueError(f"Probabilities from Born machine have unexpected shape")
 
             if step_norm is None:
-                print(f"Warning: NaN or Inf KSD loss: {loss_value}. Skipping update.")
+                print(f"Warning: NaN or Inf {self._loss_name} loss: {loss_value}. Skipping update.")
             else:
                 grad_norm = step_norm
                 if verbose and epoch % log_every == 0:
                     print(f"  Epoch {epoch+1} Grad Norm (after clipping): {grad_norm:.4f}")
 
-            history['loss_ksd'].append(loss_value)
+            history[self._loss_key].append(loss_value)
             history['grad_norm'].append(grad_norm if grad_norm is not None else 0.0)
+            for k, v in zip(self._extra_keys, self._step_extras()):
+                history[k].append(float(v))
 
             if true_posterior_for_tvd is not None:
                 if torch.is_tensor(true_posterior_for_tvd):
@@ -513,7 +531,7 @@ class KSDVariationalInference(SteinOperator):
                 history['tvd'].append(np.nan)
 
             if verbose and (epoch % max(1, num_epochs // 20) == 0 or epoch == num_epochs - 1):
-                log_msg = f"Epoch {epoch+1}/{num_epochs} | KSD: {loss_value:.6f}"
+                log_msg = f"Epoch {epoch+1}/{num_epochs} | {self._loss_name}: {loss_value:.6f}"
                 if scheduler is not None:
                     log_msg += f" | LR: {scheduler.get_last_lr()[0]:.6f}"
                 if true_posterior_for_tvd is not None and len(true_posterior_for_tvd) and not np.isnan(history['tvd'][-1]):
@@ -534,7 +552,7 @@ class KSDVariationalInference(SteinOperator):
         theta = self.born_machine.theta
         if not (theta.is_cuda and theta.dtype == torch.float32):
             raise backend.BornviError("train(host_sync=False) needs a float32 theta on the GPU (pytorch_device='cuda:N')")
-        self._precompute_all_s_p(x_observation_dict)
+        self._prepare_observation(x_observation_dict)
         n = self.num_latent_vars
         rank, ws = shard.world(self.process_group)
         use_graph = (optimizer_type == "adam" and n <= 13 and ws == 1 and self.timers is None and num_epochs > 4
@@ -542,13 +560,13 @@ class KSDVariationalInference(SteinOperator):
         params, optimizer_born, scheduler = self.make_optimizer(lr_born_machine, num_epochs, use_lr_scheduler,
                                                                 optimizer_type, adam_betas, capturable=use_graph)
         dev = theta.device
-        losses, norms, tvds, first4 = [], [], [], {}
+        losses, norms, tvds, extras = [], [], [], []
         log_every = (num_epochs // 10 if num_epochs >= 10 else 1)
         tvd_table_dev = None
         if true_posterior_for_tvd is not None:
             tvd_table_dev = (true_posterior_for_tvd if torch.is_tensor(true_posterior_for_tvd)
                              else torch.tensor([true_posterior_for_tvd.get(o, 0.0) for o in self.all_latent_states_tuples],
-                                               dtype=torch.float64)).to(self._S.device)
+                                               dtype=torch.float64)).to(dev)
         step = None
         seen = 0                              # epochs whose warnings / values have been reported
 
@@ -564,7 +582,7 @@ class KSDVariationalInference(SteinOperator):
                 vals = torch.stack([l.reshape(()) for l in losses[seen:upto]]).cpu().tolist()
             for v in vals:
                 if np.isnan(v) or np.isinf(v):
-                    print(f"Warning: NaN or Inf KSD loss: {v}. Skipping update.")
+                    print(f"Warning: NaN or Inf {self._loss_name} loss: {v}. Skipping update.")
             seen = upto
             return vals[-1]
 
@@ -575,13 +593,15 @@ class KSDVariationalInference(SteinOperator):
                 pending = rec                 # epochs 0 and 1 are the graph's two eager warm-up steps
                 adam = step.adam
             if use_graph and epoch < 2:
-                loss_t, gn, q = pending[epoch]
+                loss_t, gn, q, *ex = pending[epoch]
             elif use_graph and adam is not None:
-                loss_t, gn, q = step()        # graph-owned: read below, before the next replay, or not at all
+                loss_t, gn, q, *ex = step()   # graph-owned: read below, before the next replay, or not at all
             elif use_graph:
-                loss_t, gn, q = (t.clone() for t in step())
+                loss_t, gn, q, *ex = (t.clone() for t in step())
             else:
-                loss_t, gn, q = self.training_step_async(params, optimizer_born, scheduler, gradient_clip_norm)
+                loss_t, gn, q, *ex = self.training_step_async(params, optimizer_born, scheduler, gradient_clip_norm)
+            if ex:
+                extras.append(torch.stack([e.reshape(()) for e in ex]))      # (a copy: the next step overwrites them)
             if q.shape[0] != self.num_possible_latent_states:
                 raise ValueError(f"Probabilities from Born machine have unexpected shape")
             if adam is None:
@@ -597,7 +617,7 @@ class KSDVariationalInference(SteinOperator):
             if verbose and (epoch % max(1, num_epochs // 20) == 0 or epoch == num_epochs - 1):
                 last = report(epoch + 1)
                 last = float(loss_t) if last is None else last
-                log_msg = f"Epoch {epoch+1}/{num_epochs} | KSD: {last:.6f}"
+                log_msg = f"Epoch {epoch+1}/{num_epochs} | {self._loss_name}: {last:.6f}"
                 if scheduler is not None:
                     lr_now = (step.adam.lr_at(epoch + 1) if step is not None and step.adam is not None
                               else float(scheduler.get_last_lr()[0]))
@@ -619,7 +639,10 @@ class KSDVariationalInference(SteinOperator):
                 last_good = gv
             grad_h.append(last_good if last_good is not None else 0.0)
         tvd_h = (torch.stack([t.reshape(()) for t in tvds]).cpu().tolist() if tvds else [np.nan] * num_epochs)
-        history = {'loss_ksd': loss_h, 'tvd': tvd_h, 'grad_norm': grad_h}
+        history = {self._loss_key: loss_h, 'tvd': tvd_h, 'grad_norm': grad_h}
+        if extras:
+            for k, col in zip(self._extra_keys, torch.stack(extras).t().cpu().tolist()):
+                history[k] = col
         if tvds and verbose:
             print(f"\nRestoring best parameters (TVD: {min(tvd_h):.6f})")     # (a no-op in the reference too: quirk Q3)
         return history
