@@ -27,7 +27,7 @@
  *          the 8-amplitude kernel runs n <= 27, the larger states the generic pass kernel);
  *       dense Gram and quadratic forms ............................ 1 <= n <= 17;
  *       score from CPTs, k_p pairs, gradient assembly, shots,
- *       ELBO weights .............................................. 1 <= n <= 30;
+ *       ELBO weights, Fisher matrix ............................... 1 <= n <= 30;
  *       probability-table Born machine ............................ 0 <= n <= 30;
  *       un-fused gate application ................................. 1 <= n <= 40.
  */
@@ -368,6 +368,31 @@ size_t bornvi_elbo_workspace_bytes(bornvi_handle h, int n, int rows);
 int bornvi_elbo_weights(bornvi_handle h, int n, int rows, const double* q, const double* log_p,
                         double q_floor, double* w, double* neg_elbo, double* entropy,
                         void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
+/* ---- natural gradient (no reference counterpart: the reference steps theta with Adam on the raw gradient).
+ * bornvi_fisher_gram: the classical Fisher information matrix of the Born distribution from the stored parameter-shift
+ * rows.  shifted dev [2 n_shift, 2^n] float64, rows (+p, -p) as bornvi_paramshift_probs lays them out; q dev [2^n]; both
+ * 16-byte aligned.  F dev [n_shift, n_shift] row-major:
+ *   F_ab = sum_z d_a(z) d_b(z) r_z,  d_a = 1/2 (row_{2a} - row_{2a+1}),  r_z = 1 / q_z where q_z >= q_floor, else 0
+ * (the library's floor convention: a state under the floor contributes nothing).  A split-K SYRK on the fp64 matrix
+ * cores; slab partials go to the workspace and a finishing launch adds them in a fixed order (no atomics: two calls are
+ * bitwise equal); only tiles on or above the diagonal are computed and the lower triangle is the bitwise mirror
+ * (F == F^T exactly).  No allocation or synchronisation (capturable).  1 <= n <= 30, 1 <= n_shift <= 1024, q_floor > 0.
+ * Workspace: bornvi_fisher_workspace_bytes(h, n, n_shift). */
+size_t bornvi_fisher_workspace_bytes(bornvi_handle h, int n, int n_shift);
+int bornvi_fisher_gram(bornvi_handle h, int n, const double* shifted, int n_shift, const double* q,
+                       double q_floor, double* F, void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
+/* bornvi_spd_solve: (A + damping I) x = b by Cholesky, one launch of one workgroup, fixed operation order (bitwise
+ * reproducible), no allocation or synchronisation (capturable).  A dev [P, P] symmetric: its upper triangle is read and A
+ * is left untouched (the factor lives in the workspace); b, x dev [P]; info dev [1] int32: 0 on success.  If pivot k
+ * (counted from 0) is non-positive or non-finite, info = k + 1; if b holds a non-finite entry, info = P + 1 (tested
+ * first); if the solution is not finite, info = P + 2; in each of these cases x = b bit for bit, so that a caller which
+ * steps along x falls back to the plain gradient: nothing non-finite is written into x on behalf of the factorisation.
+ * 1 <= P <= 1024, damping >= 0.  Workspace: bornvi_spd_solve_workspace_bytes(h, P). */
+size_t bornvi_spd_solve_workspace_bytes(bornvi_handle h, int P);
+int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, const double* b, double* x, int* info,
+                     void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
 /* Gradient hand-off to the optimiser (replaces the float cast of the parameter-shift VJP and
  * torch.nn.utils.clip_grad_norm_(params, gradient_clip_norm), ksd_vi_quantum.py:153): grad32 dev [P] float32 =

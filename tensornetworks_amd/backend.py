@@ -573,6 +573,77 @@ def elbo_weights(q, log_p, q_floor=1e-10, want_w=True, want_entropy=True, out=No
     return neg_elbo, entropy, w
 
 
+# ---- natural gradient ---------------------------------------------------------------------------------
+FISHER_MAX_PARAMS = 1024
+
+
+def _chk_positive(v, name, allow_zero=False):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
+            or not (v >= 0 if allow_zero else v > 0):
+        raise BornviError(f"{name} must be a finite number {'>= 0' if allow_zero else '> 0'}, got {v!r}")
+
+
+def fisher_gram(shifted, q, q_floor=1e-10, out=None):
+    """Classical Fisher matrix of a Born distribution from stored parameter-shift rows (bornvi_fisher_gram): shifted
+    float64 [2 P, 2^n] on the GPU, rows (+p, -p) as paramshift_probs lays them out; q float64 [2^n] -> F float64 [P, P],
+    F_ab = sum_z d_a d_b / q_z over the states with q_z >= q_floor, d_a = 1/2 (row_2a - row_2a+1).  F == F.T bitwise; two
+    calls are bitwise equal; capturable once the stream's workspace exists."""
+    if not torch.is_tensor(shifted) or not torch.is_tensor(q) or shifted.dim() != 2 or q.dim() != 1:
+        raise BornviError("fisher_gram: shifted must be a [2 P, 2^n] tensor and q a [2^n] tensor")
+    N = int(q.numel())
+    if N < 2 or N & (N - 1):
+        raise BornviError(f"q: {N} entries is not 2^n with n >= 1")
+    n = N.bit_length() - 1
+    _chk_n(n)
+    if shifted.shape[1] != N or shifted.shape[0] % 2:
+        raise BornviError(f"shifted: shape {tuple(shifted.shape)} is not [2 P, {N}]")
+    P = int(shifted.shape[0]) // 2
+    if not 1 <= P <= FISHER_MAX_PARAMS:
+        raise BornviError(f"shifted: 1 ... {FISHER_MAX_PARAMS} parameters per call, got {P}")
+    _chk_positive(q_floor, "q_floor")
+    dev = q.device
+    h = _ext.handle_for(dev)
+    _chk(shifted, torch.float64, dev, "shifted")
+    _chk(q, torch.float64, dev, "q")
+    if out is None:
+        out = torch.empty((P, P), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", P * P)
+    ws = _ws(dev, _cached_size(h, "bornvi_fisher_workspace_bytes", n, P), "fisher")
+    h.call("bornvi_fisher_gram", n, _ptr(shifted), P, _ptr(q), float(q_floor), _ptr(out), _ptr(ws), ws.numel(),
+           _ext.stream_ptr(dev))
+    return out
+
+
+def spd_solve(A, b, damping=0.0, out=None, info=None):
+    """(A + damping I) x = b by Cholesky on the device (bornvi_spd_solve): A float64 [P, P] symmetric (its upper triangle
+    is read, A is left untouched), b float64 [P] -> (x float64 [P], info int32 [1]).  info is 0 on success, k + 1 when
+    pivot k is non-positive or non-finite, P + 1 when b is not finite, P + 2 when the solution is not finite; in those
+    cases x = b.  Bitwise reproducible; capturable once the stream's workspace exists."""
+    if not torch.is_tensor(A) or not torch.is_tensor(b) or A.dim() != 2 or A.shape[0] != A.shape[1] or b.dim() != 1:
+        raise BornviError("spd_solve: A must be a [P, P] tensor and b a [P] tensor")
+    P = int(A.shape[0])
+    if not 1 <= P <= FISHER_MAX_PARAMS:
+        raise BornviError(f"A: 1 ... {FISHER_MAX_PARAMS} rows, got {P}")
+    _chk_positive(damping, "damping", allow_zero=True)
+    dev = A.device
+    h = _ext.handle_for(dev)
+    _chk(A, torch.float64, dev, "A")
+    _chk(b, torch.float64, dev, "b", P)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", P)
+    if info is None:
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(info, torch.int32, dev, "info", 1)
+    ws = _ws(dev, _cached_size(h, "bornvi_spd_solve_workspace_bytes", P), "spd_solve")
+    h.call("bornvi_spd_solve", P, _ptr(A), float(damping), _ptr(b), _ptr(out), _ptr(info), _ptr(ws), ws.numel(),
+           _ext.stream_ptr(dev))
+    return out, info
+
+
 # ---- finite shots -------------------------------------------------------------------------------------
 SHOTS_MAX = (1 << 31) - 1
 

@@ -1109,6 +1109,45 @@ int bornvi_elbo_weights(bornvi_handle h, int n, int rows, const double* q, const
   return BORNVI_OK;
 }
 
+static bool valid_fisher(int n, int n_shift) { return n >= 1 && n <= 30 && n_shift >= 1 && n_shift <= 1024; }
+
+size_t bornvi_fisher_workspace_bytes(bornvi_handle h, int n, int n_shift) {
+  if (!h) return 0;
+  if (!valid_fisher(n, n_shift)) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  return fisher_workspace_bytes(n, n_shift);
+}
+
+int bornvi_fisher_gram(bornvi_handle h, int n, const double* shifted, int n_shift, const double* q, double q_floor, double* F,
+                       void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_fisher(n, n_shift)) return fail(h, BORNVI_ERR_INVALID, "bad argument (1 <= n <= 30, 1 <= n_shift <= 1024)");
+  if (!(q_floor > 0.0) || !std::isfinite(q_floor)) return fail(h, BORNVI_ERR_INVALID, "q_floor must be positive and finite");
+  if (!shifted || !q || !F) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if ((((uintptr_t)shifted) | ((uintptr_t)q)) & 15) return fail(h, BORNVI_ERR_INVALID, "shifted and q must be 16-byte aligned");
+  if (!workspace || workspace_bytes < fisher_workspace_bytes(n, n_shift)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_fisher_gram(n, shifted, n_shift, q, q_floor, F, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+size_t bornvi_spd_solve_workspace_bytes(bornvi_handle h, int P) {
+  if (!h) return 0;
+  if (P < 1 || P > 1024) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  return spd_solve_workspace_bytes(P);
+}
+
+int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, const double* b, double* x, int* info,
+                     void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (P < 1 || P > 1024) return fail(h, BORNVI_ERR_INVALID, "bad argument (1 <= P <= 1024)");
+  if (!(damping >= 0.0) || !std::isfinite(damping)) return fail(h, BORNVI_ERR_INVALID, "damping must be finite and >= 0");
+  if (!A || !b || !x || !info) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < spd_solve_workspace_bytes(P)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_spd_solve(P, A, damping, b, x, info, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 static bool valid_reinforce(int n, long long B) { return n >= 1 && n <= 30 && B >= 1 && B <= (1ll << 24); }
 
 size_t bornvi_reinforce_workspace_bytes(bornvi_handle h, int n, long long B) {

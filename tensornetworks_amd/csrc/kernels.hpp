@@ -76,6 +76,13 @@ size_t elbo_workspace_bytes(int n, long long rows);
 hipError_t launch_elbo_weights(int n, long long rows, const double* q, const double* log_p, double q_floor, double* w,
                                double* neg_elbo, double* entropy, void* ws, hipStream_t st);
 
+// ---- natural gradient: Fisher matrix of the stored parameter-shift rows, damped Cholesky solve (kernels_fisher.hip)
+size_t fisher_workspace_bytes(int n, int n_shift);
+hipError_t launch_fisher_gram(int n, const double* shifted, int n_shift, const double* q, double q_floor, double* F, void* ws,
+                              hipStream_t st);
+size_t spd_solve_workspace_bytes(int P);
+hipError_t launch_spd_solve(int P, const double* A, double damping, const double* b, double* x, int* info, void* ws, hipStream_t st);
+
 // ---- classical Born machine, REINFORCE step of the adversarial trainer (kernels_reinforce.hip) ---------
 size_t reinforce_workspace_bytes(int n, long long B);
 hipError_t launch_reinforce_step(int n, long long B, const long long* idx, const float* logit, const float* log_p,

@@ -40,13 +40,15 @@ class ELBOVariationalInference(KSDVariationalInference):
                  qbm_ansatz_type: str = "hardware_efficient",
                  qbm_init_method: str = "small_random",
                  pytorch_device: str = 'cpu',
-                 *, p_floor: float = 1e-30, process_group=None):
+                 *, p_floor: float = 1e-30, process_group=None, natural_gradient=None):
         """The KSD quantum trainer's arguments without the kernel's length scale, the Gram mode and the shots.
         p_floor: log p(x, z) is log max(p(x, z), p_floor) (states the network gives probability zero stay finite);
-        process_group: as there (the shifted circuits are sharded over its ranks)."""
+        process_group: as there (the shifted circuits are sharded over its ranks); natural_gradient: as there (the step
+        is (F + damping I)^-1 grad, the textbook optimiser for the KL; always the stored-rows route)."""
         super().__init__(bayesian_network, latent_vars_names, observed_vars_names, qbm_num_latent_vars, qbm_ansatz_layers,
                          qbm_conditioning_dim, qbm_pennylane_device_name, qbm_ansatz_type, qbm_init_method,
-                         pytorch_device=pytorch_device, gram_mode="kron", process_group=process_group)
+                         pytorch_device=pytorch_device, gram_mode="kron", process_group=process_group,
+                         natural_gradient=natural_gradient)
         self.objective = ElboObjective(bayesian_network, latent_vars_names, pytorch_device, p_floor=p_floor)
         self._entropy = None         # entropy [1] of the last elbo_and_grad (device)
 
@@ -60,7 +62,7 @@ class ELBOVariationalInference(KSDVariationalInference):
         return self.elbo_and_grad(**kw)
 
     def _step_extras(self):
-        return (self._entropy,)
+        return (self._entropy,) + self._natgrad_extras()
 
     def ksd_and_grad(self, theta64=None):
         raise backend.BornviError("the ELBO trainer has no Stein side: use elbo_and_grad")
@@ -101,7 +103,7 @@ class ELBOVariationalInference(KSDVariationalInference):
             return loss, grad, q
         if self.grad_engine != "paramshift":
             raise ValueError("grad_engine must be 'paramshift' or 'adjoint'")
-        if self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
+        if self.natural_gradient is None and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
             # base circuit and all but the last pass of the shifted ones -> q -> w -> the shifted circuits' last pass
             # dotted with w: their probabilities are never written or re-read
             with self._timed("circuits"):
@@ -118,6 +120,9 @@ class ELBOVariationalInference(KSDVariationalInference):
             loss, self._entropy, w = self.objective.weights(q)
         with self._timed("finish"):
             grad = backend.shifted_dot(n, probs[1:], n_local, w)
+        if self.natural_gradient is not None:       # (one rank: probs[1:] holds every parameter's rows)
+            with self._timed("natgrad"):
+                grad, self._natgrad_info = self.natural_gradient.precondition(probs[1:], q, grad)
         return loss, grad, q
 
     def train(self, x_observation_dict, num_epochs, lr_born_machine,
@@ -126,7 +131,7 @@ class ELBOVariationalInference(KSDVariationalInference):
               optimizer_type="adam", adam_betas=(0.9, 0.999), *, host_sync=True):
         """The KSD quantum trainer's train(): same arguments, messages (the loss is labelled ELBO) and read-back modes.
         History: loss_elbo (= L), kl (= L + log p(x) = KL(q || p(.|x)) before the epoch's update), entropy (of that q),
-        tvd, grad_norm."""
+        tvd, grad_norm; with natural_gradient also natgrad_info."""
         history = super().train(x_observation_dict, num_epochs, lr_born_machine, verbose, true_posterior_for_tvd,
                                 use_lr_scheduler, gradient_clip_norm, optimizer_type, adam_betas, host_sync=host_sync)
         history['kl'] = [v + self.objective.log_evidence for v in history['loss_elbo']]

@@ -29,6 +29,7 @@ import torch.optim as optim
 
 from . import backend
 from . import paramshift_shard as shard
+from .natural_gradient import MAX_PARAMS as NATGRAD_MAX_PARAMS, FisherPreconditioner
 from .quantum_born_machine import QuantumBornMachine
 from .stein_operator import DENSE_GRAM_MAX_N, SteinOperator      # noqa: F401  (DENSE_GRAM_MAX_N: exported from here too)
 from .stein_utils import base_hamming_kernel_torch, tvd_table
@@ -127,7 +128,7 @@ class KSDVariationalInference(SteinOperator):
                  qbm_init_method: str = "small_random",
                  base_kernel_length_scale: float = 1.0,
                  pytorch_device: str = 'cpu',
-                 *, gram_mode: str = "auto", process_group=None, qbm_shots=None, shot_seed=None):
+                 *, gram_mode: str = "auto", process_group=None, qbm_shots=None, shot_seed=None, natural_gradient=None):
         """Arguments up to `pytorch_device` are the reference's (ksd_vi_quantum.py:19-30).
         Keyword-only extras: gram_mode in {"auto", "dense", "kron"} (dense Gram matrix vs matrix-free
         Kronecker mat-vec; "auto" = dense up to n = 16); process_group = torch.distributed group over
@@ -136,7 +137,17 @@ class KSDVariationalInference(SteinOperator):
         is a histogram of S draws; QuantumBornMachine(shots=...)), shot_seed = the draws' seed (None: one draw from
         torch's global CPU generator; pass the same seed, or seed torch alike, on every rank).  With shots the step
         always runs the un-fused path (fused_dot does not apply: the fused dot has no probabilities to sample); the
-        TVD and best-parameter snapshot of train() use the exact q_theta."""
+        TVD and best-parameter snapshot of train() use the exact q_theta.
+        natural_gradient = True, a damping, or a natural_gradient.FisherPreconditioner: the step hands the optimiser
+        delta = (F + damping I)^-1 grad, F the classical Fisher matrix of q_theta built from the stored parameter-shift
+        rows (always the un-fused path: the fused dot never writes the rows); history['grad_norm'] is then the norm of
+        delta and history['natgrad_info'] the solve's status per epoch (0: solved; otherwise delta is the plain
+        gradient).  Not with the adjoint engine, finite shots, more than one rank or more than 1024 parameters."""
+        self.natural_gradient = FisherPreconditioner.coerce(natural_gradient)
+        self._natgrad_info = None    # int32 [1] of the last step (device)
+        if self.natural_gradient is not None and qbm_shots is not None:
+            raise ValueError("natural_gradient with qbm_shots: the Fisher matrix of histograms is biased and unbounded "
+                             "at empty bins")
         if int(qbm_num_latent_vars) != len(latent_vars_names):
             # the scores are [2^len(latent_vars_names), len(latent_vars_names)] while the circuit has
             # qbm_num_latent_vars qubits: the device kernels would index one with the other's sizes
@@ -170,11 +181,34 @@ class KSDVariationalInference(SteinOperator):
         # one forward and one backward walk over the gates (bornvi_adjoint_state / _vjp) -- the same gradient to
         # rounding from about three circuit evaluations; every rank computes it whole (nothing to shard).
         self.grad_engine = "paramshift"
+        if self.natural_gradient is not None:
+            P = self.born_machine.num_ansatz_params
+            if P > NATGRAD_MAX_PARAMS:
+                raise ValueError(f"natural_gradient: {P} parameters; the device solve holds at most {NATGRAD_MAX_PARAMS}")
+            if shard.world(process_group)[1] > 1:
+                raise ValueError("natural_gradient with a process group of more than one rank: the Fisher matrix needs "
+                                 "the cross terms between the ranks' rows")
+            self._extra_keys = tuple(type(self)._extra_keys) + ('natgrad_info',)
         # The parameter-shift dot product  sum_z dL/dq_z (q+ - q-)(z)  inside the shifted circuits' last pass instead of a
         # pass over their stored probabilities (bornvi_paramshift_dot_begin / _finish): still all 2P circuit evaluations,
         # same gradient to rounding; taken where the library offers it (multi-pass plans of the 8-amplitude kernel),
         # else the probabilities are written and dotted as before.  False: always the un-fused path (A/B).
         self.fused_dot = True
+
+    @property
+    def grad_engine(self):
+        return self._grad_engine
+
+    @grad_engine.setter
+    def grad_engine(self, engine):
+        if engine == "adjoint" and getattr(self, "natural_gradient", None) is not None:
+            raise ValueError("natural_gradient with grad_engine = 'adjoint': the adjoint engine has no parameter-shift "
+                             "rows to build the Fisher matrix from")
+        self._grad_engine = engine
+
+    def _natgrad_extras(self):
+        """The natural-gradient solve's status of the step just enqueued, as the history's float64 device scalar."""
+        return () if self.natural_gradient is None else (self._natgrad_info.to(torch.float64),)
 
     # Both exist only because the benchmark record reads them: the overlap stream modes were retired.
     overlap_choice = None
@@ -203,7 +237,7 @@ class KSDVariationalInference(SteinOperator):
 
     def _step_extras(self):
         """Device scalars of the step just enqueued, one per _extra_keys entry."""
-        return ()
+        return self._natgrad_extras()
 
     # ---- one KSD-gradient step on the device -------------------------------------------------------------
     def ksd_and_grad(self, theta64=None):
@@ -231,7 +265,7 @@ class KSDVariationalInference(SteinOperator):
             return loss, grad, q
         if self.grad_engine != "paramshift":
             raise ValueError("grad_engine must be 'paramshift' or 'adjoint'")
-        if self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
+        if self.natural_gradient is None and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
             # The dot product with dL/dq fused into the shifted circuits' last pass (kernels_circuit8.hip): base circuit
             # and all but the last pass of the shifted ones -> q -> contraction -> last pass of the shifted circuits with
             # w = y.  Their probabilities are never written or re-read (8 GB each way at n = 20).
@@ -254,6 +288,9 @@ class KSDVariationalInference(SteinOperator):
             loss, grad_local, _ = backend.ksd_grad_finish(n, shifted, n_local, y, ksd2)
             with self._timed("allgather"):
                 grad = shard.all_gather_grad(grad_local, P, self.process_group)
+        if self.natural_gradient is not None:       # (one rank: `shifted` holds every parameter's rows)
+            with self._timed("natgrad"):
+                grad, self._natgrad_info = self.natural_gradient.precondition(shifted, q, grad)
         return loss, grad, q
 
     def _ksd_and_grad_shots(self, theta64, lo, hi, step, n_local):
