@@ -394,6 +394,35 @@ size_t bornvi_spd_solve_workspace_bytes(bornvi_handle h, int P);
 int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, const double* b, double* x, int* info,
                      void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
+/* ---- quantum natural gradient: the Fubini-Study metric instead of the classical Fisher matrix (what PennyLane's
+ * QNGOptimizer preconditions with; no reference counterpart).  Every parameter enters exactly one gate exp(-i theta s / 2),
+ * so d_a psi = 1/2 psi(theta + pi e_a).
+ * bornvi_paramshift_states: states dev [include_base + p_count, 2^n] complex128 (re, im interleaved), row 0 (if
+ * include_base) U(theta)|0..0>, then U(theta + pi e_p)|0..0> for p = p_begin .. p_begin + p_count - 1; canonical order
+ * (wire 0 the most significant bit), WITH the correct phase and with the gates that end the circuit applied: a row
+ * agrees with bornvi_adjoint_state at the same parameters to rounding.  The batched engine runs a plan of its own with
+ * raw fused matrices (the pivot-normalised records of the 8-amplitude kernel drop a phase per circuit, so that kernel is
+ * not used here, whatever reg_wires says); a small kernel then applies the circuit-ending CNOTs and CZs on the way from
+ * the engine's buffer into `states`.  Circuits are processed in chunks of as many as the workspace holds (at least one).
+ * No allocation or synchronisation once the plan exists (capturable after one eager call).  Workspace:
+ * bornvi_paramshift_states_workspace_bytes(h, ansatz, n, layers, rows) holds `rows` circuits at once. */
+size_t bornvi_paramshift_states_workspace_bytes(bornvi_handle h, int ansatz, int n, int layers, int rows);
+int bornvi_paramshift_states(bornvi_handle h, int ansatz, int n, int layers, const double* theta, int p_begin,
+                             int p_count, int include_base, double* states, void* workspace, size_t workspace_bytes,
+                             bornvi_stream stream);
+
+/* bornvi_qfi_gram: the quantum Fisher information matrix (4 x the Fubini-Study metric, 4 x PennyLane's metric_tensor;
+ * Q >= F, the classical Fisher matrix, in the Loewner order) from the pi-shifted states.  phi dev [P, 2^n] complex128,
+ * psi dev [2^n] complex128, both 16-byte aligned; Q dev [P, P] float64 row-major:
+ *   Q_ab = Re<phi_a|phi_b> - Re(conj(c_a) c_b),  c_a = <psi|phi_a>.
+ * One real split-K SYRK on the fp64 matrix cores over the P + 2 rows (phi, psi, i psi) of 2^(n+1) doubles; slab partials
+ * go to the workspace and a finishing launch adds them in a fixed order, subtracts the projection term and writes Q_ab
+ * and Q_ba from the same value (no atomics: two calls are bitwise equal; Q == Q^T exactly).  No allocation or
+ * synchronisation (capturable).  1 <= n <= 30, 1 <= P <= 1024.  Workspace: bornvi_qfi_workspace_bytes(h, n, P). */
+size_t bornvi_qfi_workspace_bytes(bornvi_handle h, int n, int P);
+int bornvi_qfi_gram(bornvi_handle h, int n, int P, const double* phi, const double* psi, double* Q, void* workspace,
+                    size_t workspace_bytes, bornvi_stream stream);
+
 /* Gradient hand-off to the optimiser (replaces the float cast of the parameter-shift VJP and
  * torch.nn.utils.clip_grad_norm_(params, gradient_clip_norm), ksd_vi_quantum.py:153): grad32 dev [P] float32 =
  * float32(grad64) * min(1, max_norm / (||float32(grad64)||_2 + 1e-6)); total_norm dev [1] float32 = that norm. */

@@ -644,6 +644,69 @@ def spd_solve(A, b, damping=0.0, out=None, info=None):
     return out, info
 
 
+def paramshift_states_bytes(n, count, include_base=True):
+    """Bytes of the rows paramshift_states writes: 16 (count + base) 2^n."""
+    return 16 * (int(count) + (1 if include_base else 0)) << int(n)
+
+
+def paramshift_states(ansatz_type, n, layers, theta, p_begin, p_end, include_base=True, out=None):
+    """theta float64 [P] -> states complex128 [(1 if include_base) + (p_end - p_begin), 2^n]: optional base row
+    U(theta)|0..0>, then U(theta + pi e_p)|0..0> for p in [p_begin, p_end), phase-coherent and in canonical order
+    (bornvi_paramshift_states; a row equals adjoint_state at the same parameters to rounding).  The circuits run in
+    chunks when their workspace would exceed WORKSPACE_CAP.  Capturable after one eager call."""
+    _chk_n(n, 1, CIRCUIT_MAX_N)
+    dev = theta.device
+    h = _ext.handle_for(dev)
+    aid = ansatz_id(ansatz_type)
+    P = num_params(ansatz_type, n, layers)
+    _chk(theta, torch.float64, dev, "theta", P)
+    if not 0 <= p_begin <= p_end <= P:
+        raise BornviError(f"parameter range [{p_begin}, {p_end}) out of bounds (P = {P})")
+    count = int(p_end) - int(p_begin)
+    B = (1 if include_base else 0) + count
+    if out is None:
+        out = torch.empty((B, 1 << n), dtype=torch.complex128, device=dev)
+    else:
+        _chk(out, torch.complex128, dev, "out", B << n)
+    if B == 0:
+        return out
+    need = _cached_size(h, "bornvi_paramshift_states_workspace_bytes", aid, n, layers, B)
+    ws = _ws(dev, min(need, max(WORKSPACE_CAP, _cached_size(h, "bornvi_paramshift_states_workspace_bytes", aid, n, layers, 1))),
+             "states")
+    h.call("bornvi_paramshift_states", aid, n, layers, _ptr(theta), int(p_begin), count, 1 if include_base else 0, _ptr(out),
+           _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out
+
+
+def qfi_gram(phi, psi, out=None):
+    """Quantum Fisher information matrix (bornvi_qfi_gram): phi complex128 [P, 2^n] (the pi-shifted states), psi
+    complex128 [2^n] -> Q float64 [P, P], Q_ab = Re<phi_a|phi_b> - Re(conj(c_a) c_b), c_a = <psi|phi_a>: 4 x the
+    Fubini-Study metric.  Q == Q.T bitwise; two calls are bitwise equal; capturable once the stream's workspace exists."""
+    if not torch.is_tensor(phi) or not torch.is_tensor(psi) or phi.dim() != 2 or psi.dim() != 1:
+        raise BornviError("qfi_gram: phi must be a [P, 2^n] tensor and psi a [2^n] tensor")
+    N = int(psi.numel())
+    if N < 2 or N & (N - 1):
+        raise BornviError(f"psi: {N} entries is not 2^n with n >= 1")
+    n = N.bit_length() - 1
+    _chk_n(n)
+    P = int(phi.shape[0])
+    if phi.shape[1] != N:
+        raise BornviError(f"phi: shape {tuple(phi.shape)} is not [P, {N}]")
+    if not 1 <= P <= FISHER_MAX_PARAMS:
+        raise BornviError(f"phi: 1 ... {FISHER_MAX_PARAMS} parameters per call, got {P}")
+    dev = psi.device
+    h = _ext.handle_for(dev)
+    _chk(phi, torch.complex128, dev, "phi")
+    _chk(psi, torch.complex128, dev, "psi")
+    if out is None:
+        out = torch.empty((P, P), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", P * P)
+    ws = _ws(dev, _cached_size(h, "bornvi_qfi_workspace_bytes", n, P), "qfi")
+    h.call("bornvi_qfi_gram", n, P, _ptr(phi), _ptr(psi), _ptr(out), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out
+
+
 # ---- finite shots -------------------------------------------------------------------------------------
 SHOTS_MAX = (1 << 31) - 1
 

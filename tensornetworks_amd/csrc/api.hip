@@ -45,6 +45,8 @@ struct DevPlan {
     std::vector<ShareChunk> chunks;
   };
   std::vector<std::unique_ptr<ShareTables>> share_cache;
+  // state plans (get_plan with state_out): the gates that end the circuit, applied after the last pass (launch_state_tail)
+  StateTail tail;
 };
 
 
@@ -135,14 +137,47 @@ int sync_uploads(bornvi_handle h) {
   return fail(h, BORNVI_ERR_HIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
 }
 
-int get_plan(bornvi_handle h, int ansatz, int n, int layers, DevPlan** out) {
-  auto key = std::make_tuple(ansatz, n, layers);
+// CNOTs then CZs (every ansatz ends that way) -> out[y] = s(y) in[A y]: y = C_m .. C_1 x, so x = C_1 .. C_m y (a CNOT is
+// its own inverse): the CNOTs applied to y last one first; the CZs act on the final index.  Wire w is index bit n - 1 - w.
+bool build_state_tail(const std::vector<TailOp>& ops, int n, StateTail& T) {
+  std::vector<unsigned> expr(n);
+  for (int w = 0; w < n; ++w) expr[w] = 1u << (n - 1 - w);
+  for (int b = 0; b < 32; ++b) T.row[b] = T.cz[b] = 0;
+  bool seen_cz = false;
+  for (const TailOp& o : ops) {
+    if (o.is_cz) seen_cz = true;
+    else if (seen_cz) return false;
+  }
+  for (size_t q = ops.size(); q-- > 0;) {
+    const TailOp& o = ops[q];
+    if (o.is_cz) T.cz[n - 1 - o.a] ^= 1u << (n - 1 - o.b);     // (a pair given twice cancels, as two CZs do)
+    else expr[o.b] ^= expr[o.a];
+  }
+  for (int w = 0; w < n; ++w) T.row[n - 1 - w] = expr[w];
+  return true;
+}
+
+constexpr int STATE_PLAN_KEY = 0x100;    // plan-cache key of a state plan: ansatz | STATE_PLAN_KEY
+
+// state_out: the plan of bornvi_paramshift_states (make_state_plan): always the 16-amplitude / generic kernels, which
+// read raw matrices.
+int get_plan(bornvi_handle h, int ansatz, int n, int layers, DevPlan** out, bool state_out = false) {
+  auto key = std::make_tuple(state_out ? (ansatz | STATE_PLAN_KEY) : ansatz, n, layers);
   auto it = h->plans.find(key);
   if (it != h->plans.end()) { *out = it->second.get(); return BORNVI_OK; }
   auto dp = std::make_unique<DevPlan>();
   std::string msg;
   bool ok = false, use_r3 = false;
-  if (h->opt.r == 3) {
+  if (state_out) {
+    if (ansatz < 0) return fail(h, BORNVI_ERR_INVALID, "unknown ansatz id");
+    PlanOptions o4 = h->opt;
+    o4.r = 4;
+    if (o4.max_threads > 512) o4.max_threads = 512;
+    std::vector<TailOp> tail;
+    if (!make_state_plan(ansatz, n, layers, o4, dp->plan, tail, msg)) return fail(h, BORNVI_ERR_UNSUPPORTED, msg);
+    if (!build_state_tail(tail, n, dp->tail)) return fail(h, BORNVI_ERR_UNSUPPORTED, "a CNOT follows a CZ at the end of the circuit");
+    ok = true;
+  } else if (h->opt.r == 3) {
     // 8 amplitudes per thread where the plan is eligible for circuit_pass_r3_kernel (compact tables, tile and tables
     // within the CU's LDS); otherwise the 16-amplitude plan below
     std::string m3;
@@ -1145,6 +1180,83 @@ int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, co
   if (!workspace || workspace_bytes < spd_solve_workspace_bytes(P)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_spd_solve(P, A, damping, b, x, info, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+// ---- quantum natural gradient: coherent states of the pi-shifted circuits, quantum Fisher information ------------
+namespace {
+// workspace of `rows` circuits at once: [thetas | gates | stateA | stateB], each region 256-byte aligned
+size_t states_per_circuit_bytes(const Plan& p) { return (size_t)p.n_params * 8 + (size_t)gate_slots(p) * 64 + 2 * ((size_t)16 << p.n); }
+}  // namespace
+
+size_t bornvi_paramshift_states_workspace_bytes(bornvi_handle h, int ansatz, int n, int layers, int rows) {
+  if (!h || rows < 0) return 0;
+  DevPlan* dp = nullptr;
+  if (get_plan(h, ansatz, n, layers, &dp, true)) return 0;
+  const Plan& p = dp->plan;
+  const size_t r = (size_t)(rows > 0 ? rows : 1);
+  return 2048 + align_up(r * p.n_params * 8, 256) + align_up(r * gate_slots(p) * 64, 256) + 2 * align_up(r * ((size_t)16 << n), 256);
+}
+
+int bornvi_paramshift_states(bornvi_handle h, int ansatz, int n, int layers, const double* theta, int p_begin, int p_count,
+                             int include_base, double* states, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  const int P = num_params(ansatz, n, layers);
+  if (P < 0 || p_begin < 0 || p_count < 0 || (long long)p_begin + p_count > P) return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+  include_base = include_base ? 1 : 0;
+  const long long rows = (long long)include_base + p_count;
+  if (rows == 0) return BORNVI_OK;
+  if ((!theta && P > 0) || !states) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (((uintptr_t)states) & 15) return fail(h, BORNVI_ERR_INVALID, "states must be 16-byte aligned");
+  DevPlan* dp = nullptr;
+  int rc = get_plan(h, ansatz, n, layers, &dp, true);
+  if (rc) return rc;
+  const Plan& p = dp->plan;
+  if (!workspace || workspace_bytes < 2048) return fail(h, BORNVI_ERR_WORKSPACE, "workspace missing");
+  long long bc_max = (long long)((workspace_bytes - 2048) / states_per_circuit_bytes(p));   // (2048: the four regions' alignment)
+  if (bc_max > rows) bc_max = rows;
+  if (bc_max > 65535) bc_max = 65535;  // gridDim.y
+  if (bc_max < 1) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small for one circuit");
+  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  const size_t th_bytes = align_up((size_t)bc_max * p.n_params * 8, 256);
+  const size_t gates_bytes = align_up((size_t)bc_max * gate_slots(p) * 64, 256);
+  const size_t state_bytes = align_up((size_t)bc_max * ((size_t)16 << n), 256);
+  double* thetas = (double*)base;
+  double* gates = (double*)(base + th_bytes);
+  void* bufA = base + th_bytes + gates_bytes;
+  void* bufB = base + th_bytes + gates_bytes + state_bytes;
+  // run_passes ping-pongs A, B, A, ... from pass 0 on; the last pass writes where the ping-pong would have gone next
+  void* last = (p.n_passes % 2 == 1) ? bufA : bufB;
+  hipStream_t st = (hipStream_t)stream;
+  DEVICE_SCOPE(h);
+  for (long long c0 = 0; c0 < rows; c0 += bc_max) {
+    const int bc = (int)((rows - c0 < bc_max) ? rows - c0 : bc_max);
+    HIPCHK(h, launch_pi_shift_thetas(theta, P, (int)c0, include_base, p_begin, bc, thetas, st));
+    HIPCHK(h, launch_build_gates(dp->d_words, p.n_fused, thetas, P, 0, 0, 1, 0, 0, bc, gates, nullptr, gate_slots(p), 0, st));
+    rc = run_passes(h, dp, bc, nullptr, bufA, bufB, last, nullptr, gates, (long long)gate_slots(p) * 8, st);
+    if (rc) return rc;
+    HIPCHK(h, launch_state_tail((const double*)last, states + ((size_t)c0 << (n + 1)), n, bc, dp->tail, st));
+  }
+  return BORNVI_OK;
+}
+
+static bool valid_qfi(int n, int P) { return n >= 1 && n <= 30 && P >= 1 && P <= 1024; }
+
+size_t bornvi_qfi_workspace_bytes(bornvi_handle h, int n, int P) {
+  if (!h) return 0;
+  if (!valid_qfi(n, P)) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  return qfi_workspace_bytes(n, P);
+}
+
+int bornvi_qfi_gram(bornvi_handle h, int n, int P, const double* phi, const double* psi, double* Q, void* workspace,
+                    size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_qfi(n, P)) return fail(h, BORNVI_ERR_INVALID, "bad argument (1 <= n <= 30, 1 <= P <= 1024)");
+  if (!phi || !psi || !Q) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if ((((uintptr_t)phi) | ((uintptr_t)psi)) & 15) return fail(h, BORNVI_ERR_INVALID, "phi and psi must be 16-byte aligned");
+  if (!workspace || workspace_bytes < qfi_workspace_bytes(n, P)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_qfi_gram(n, P, phi, psi, Q, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

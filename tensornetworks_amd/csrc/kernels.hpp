@@ -83,6 +83,18 @@ hipError_t launch_fisher_gram(int n, const double* shifted, int n_shift, const d
 size_t spd_solve_workspace_bytes(int P);
 hipError_t launch_spd_solve(int P, const double* A, double damping, const double* b, double* x, int* info, void* ws, hipStream_t st);
 
+// ---- quantum natural gradient (kernels_qfi.hip): coherent states of pi-shifted circuits, quantum Fisher information
+// thetas[c][p] = theta[p] + pi where p is the parameter of row row0 + c (row < include_base: the base circuit, no shift)
+hipError_t launch_pi_shift_thetas(const double* theta, int P, int row0, int include_base, int p_begin, int bc, double* thetas,
+                                  hipStream_t st);
+struct StateTail {        // the gates that end a circuit: out[y] = s(y) in[A y] over the PHYSICAL index bits
+  unsigned row[32];       // bit b of x = parity(y & row[b])
+  unsigned cz[32];        // s(y) = (-1)^(sum_b y_b popcount(y & cz[b])): each CZ pair listed once
+};
+hipError_t launch_state_tail(const double* in, double* out, int n, int bc, const StateTail& T, hipStream_t st);
+size_t qfi_workspace_bytes(int n, int P);
+hipError_t launch_qfi_gram(int n, int P, const double* phi, const double* psi, double* Q, void* ws, hipStream_t st);
+
 // ---- classical Born machine, REINFORCE step of the adversarial trainer (kernels_reinforce.hip) ---------
 size_t reinforce_workspace_bytes(int n, long long B);
 hipError_t launch_reinforce_step(int n, long long B, const long long* idx, const float* logit, const float* log_p,

@@ -341,7 +341,23 @@ struct BuildSpec {
 bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::string& msg);
 }  // namespace
 
+namespace {
+bool make_plan_impl(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan, std::string& msg, std::vector<TailOp>* tail);
+}  // namespace
+
 bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan, std::string& msg) {
+  return make_plan_impl(ansatz, n, layers, opt, plan, msg, nullptr);
+}
+
+// The same passes as make_plan's, but the last one writes the state (PASS_FINAL_STATE) and no CNOT is folded into the
+// outcome index: the gates that end the circuit come back in `tail`, for the caller to apply (kernels_qfi.hip).
+bool make_state_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan, std::vector<TailOp>& tail, std::string& msg) {
+  tail.clear();
+  return make_plan_impl(ansatz, n, layers, opt, plan, msg, &tail);
+}
+
+namespace {
+bool make_plan_impl(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan, std::string& msg, std::vector<TailOp>* tail) {
   if (n < 1 || n > MAX_PLAN_QUBITS) { msg = "num qubits must be in [1, " + std::to_string(MAX_PLAN_QUBITS) + "]"; return false; }
   if (layers < 0) { msg = "layers must be >= 0"; return false; }
   std::vector<Gate> gates;
@@ -354,10 +370,13 @@ bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan
   {
     size_t last_u = spec.ops.size();
     while (last_u > 0 && spec.ops[last_u - 1].kind != K_U1) --last_u;
-    for (size_t q = last_u; q < spec.ops.size(); ++q)
-      if (spec.ops[q].kind == K_CX) spec.out_perm.push_back({spec.ops[q].a, spec.ops[q].b});
+    for (size_t q = last_u; q < spec.ops.size(); ++q) {
+      if (tail) tail->push_back({spec.ops[q].kind == K_CZ ? 1 : 0, spec.ops[q].a, spec.ops[q].b});
+      else if (spec.ops[q].kind == K_CX) spec.out_perm.push_back({spec.ops[q].a, spec.ops[q].b});
+    }
     spec.ops.resize(last_u);
   }
+  spec.out_state = tail != nullptr;
   spec.n_params = num_params(ansatz, n, layers);
   spec.n_gates = (int)gates.size();
   if (opt.kmulti == 0 && n > opt.kmax && opt.kmax >= 13) {
@@ -390,6 +409,7 @@ bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& plan
   }
   return build_plan(spec, opt, plan, msg);
 }
+}  // namespace
 
 // v -> (M (x) M (x) ... (x) M) v for one shared 2x2 matrix (fused gate 0): state in, state out.
 // Wires are visited from the least significant physical bit upwards so that the first and the

@@ -270,6 +270,11 @@ bool build_compact_tables(const Plan& plan, CompactTables& out, std::string& msg
 constexpr int MAX_PLAN_QUBITS = 29;
 // Returns false (with msg) on unsupported sizes.
 bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& out, std::string& msg);
+// The gates that end a circuit (everything after its last one-qubit gate), in program order: is_cz = 0: CNOT(a = control,
+// b = target), 1: CZ(a, b).  make_plan folds them away (|psi|^2 only needs the CNOTs, as a permutation of the outcome
+// index); make_state_plan hands them to the caller, and its plan's last pass writes the state before them.
+struct TailOp { int is_cz, a, b; };
+bool make_state_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& out, std::vector<TailOp>& tail, std::string& msg);
 // Program applying one shared 2x2 matrix to every bit of a canonical-order vector (state in,
 // state out); used by the matrix-free Stein mat-vec (K_base = M^{(x) n}).
 bool make_kron_plan(int n, const PlanOptions& opt, Plan& out, std::string& msg);

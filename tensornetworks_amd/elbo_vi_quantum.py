@@ -44,7 +44,8 @@ class ELBOVariationalInference(KSDVariationalInference):
         """The KSD quantum trainer's arguments without the kernel's length scale, the Gram mode and the shots.
         p_floor: log p(x, z) is log max(p(x, z), p_floor) (states the network gives probability zero stay finite);
         process_group: as there (the shifted circuits are sharded over its ranks); natural_gradient: as there (the step
-        is (F + damping I)^-1 grad, the textbook optimiser for the KL; always the stored-rows route)."""
+        is (F + damping I)^-1 grad, the textbook optimiser for the KL; always the stored-rows route -- or, with "quantum",
+        (Q + damping I)^-1 grad on whichever route the step takes)."""
         super().__init__(bayesian_network, latent_vars_names, observed_vars_names, qbm_num_latent_vars, qbm_ansatz_layers,
                          qbm_conditioning_dim, qbm_pennylane_device_name, qbm_ansatz_type, qbm_init_method,
                          pytorch_device=pytorch_device, gram_mode="kron", process_group=process_group,
@@ -100,10 +101,10 @@ class ELBOVariationalInference(KSDVariationalInference):
                 loss, self._entropy, w = self.objective.weights(q)
             with self._timed("finish"):
                 grad = backend.adjoint_vjp(at, n, L, theta64, state, w)
-            return loss, grad, q
+            return loss, self._quantum_precondition(theta64, grad), q
         if self.grad_engine != "paramshift":
             raise ValueError("grad_engine must be 'paramshift' or 'adjoint'")
-        if self.natural_gradient is None and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
+        if not self._rows_needed() and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
             # base circuit and all but the last pass of the shifted ones -> q -> w -> the shifted circuits' last pass
             # dotted with w: their probabilities are never written or re-read
             with self._timed("circuits"):
@@ -112,7 +113,7 @@ class ELBOVariationalInference(KSDVariationalInference):
                 loss, self._entropy, w = self.objective.weights(q)
             with self._timed("finish"):
                 _, grad = backend.paramshift_dot_finish(token, w)
-            return loss, grad, q
+            return loss, self._quantum_precondition(theta64, grad), q      # (one rank with a preconditioner: local = whole)
         with self._timed("circuits"):
             probs = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=True, p_stride=step)
         q = probs[0]
@@ -120,10 +121,10 @@ class ELBOVariationalInference(KSDVariationalInference):
             loss, self._entropy, w = self.objective.weights(q)
         with self._timed("finish"):
             grad = backend.shifted_dot(n, probs[1:], n_local, w)
-        if self.natural_gradient is not None:       # (one rank: probs[1:] holds every parameter's rows)
+        if self._rows_needed():       # (one rank: probs[1:] holds every parameter's rows)
             with self._timed("natgrad"):
                 grad, self._natgrad_info = self.natural_gradient.precondition(probs[1:], q, grad)
-        return loss, grad, q
+        return loss, self._quantum_precondition(theta64, grad), q
 
     def train(self, x_observation_dict, num_epochs, lr_born_machine,
               verbose=True, true_posterior_for_tvd=None,

@@ -142,7 +142,11 @@ class KSDVariationalInference(SteinOperator):
         delta = (F + damping I)^-1 grad, F the classical Fisher matrix of q_theta built from the stored parameter-shift
         rows (always the un-fused path: the fused dot never writes the rows); history['grad_norm'] is then the norm of
         delta and history['natgrad_info'] the solve's status per epoch (0: solved; otherwise delta is the plain
-        gradient).  Not with the adjoint engine, finite shots, more than one rank or more than 1024 parameters."""
+        gradient).  Not with the adjoint engine, finite shots, more than one rank or more than 1024 parameters.
+        natural_gradient = "quantum" or a natural_gradient.QuantumFisherPreconditioner: delta = (Q + damping I)^-1 grad
+        with Q the quantum Fisher information (4 x the Fubini-Study metric) built from the P + 1 statevectors; the step
+        keeps the gradient route it would take otherwise (fused dot, stored rows or the adjoint engine).  Not with
+        finite shots, more than one rank, more than 1024 parameters or statevectors beyond the workspace cap."""
         self.natural_gradient = FisherPreconditioner.coerce(natural_gradient)
         self._natgrad_info = None    # int32 [1] of the last step (device)
         if self.natural_gradient is not None and qbm_shots is not None:
@@ -188,6 +192,8 @@ class KSDVariationalInference(SteinOperator):
             if shard.world(process_group)[1] > 1:
                 raise ValueError("natural_gradient with a process group of more than one rank: the Fisher matrix needs "
                                  "the cross terms between the ranks' rows")
+            if self.natural_gradient.quantum:
+                self.natural_gradient.bind(self.born_machine.ansatz_type, self.num_latent_vars, self.born_machine.ansatz_layers, P)
             self._extra_keys = tuple(type(self)._extra_keys) + ('natgrad_info',)
         # The parameter-shift dot product  sum_z dL/dq_z (q+ - q-)(z)  inside the shifted circuits' last pass instead of a
         # pass over their stored probabilities (bornvi_paramshift_dot_begin / _finish): still all 2P circuit evaluations,
@@ -201,10 +207,23 @@ class KSDVariationalInference(SteinOperator):
 
     @grad_engine.setter
     def grad_engine(self, engine):
-        if engine == "adjoint" and getattr(self, "natural_gradient", None) is not None:
+        ng = getattr(self, "natural_gradient", None)
+        if engine == "adjoint" and ng is not None and not ng.quantum:
             raise ValueError("natural_gradient with grad_engine = 'adjoint': the adjoint engine has no parameter-shift "
                              "rows to build the Fisher matrix from")
         self._grad_engine = engine
+
+    def _rows_needed(self):
+        """True when the step must store the parameter-shift rows: the classical Fisher matrix is built from them."""
+        return self.natural_gradient is not None and not self.natural_gradient.quantum
+
+    def _quantum_precondition(self, theta64, grad):
+        """grad -> delta under the quantum metric (any gradient route); grad itself without that preconditioner."""
+        if self.natural_gradient is None or not self.natural_gradient.quantum:
+            return grad
+        with self._timed("natgrad"):
+            grad, self._natgrad_info = self.natural_gradient.precondition(theta64, grad)
+        return grad
 
     def _natgrad_extras(self):
         """The natural-gradient solve's status of the step just enqueued, as the history's float64 device scalar."""
@@ -262,10 +281,10 @@ class KSDVariationalInference(SteinOperator):
             with self._timed("finish"):
                 loss, _, dldq = backend.ksd_grad_finish(n, None, 0, y, ksd2, want_dldq=True)
                 grad = backend.adjoint_vjp(at, n, L, theta64, state, dldq)
-            return loss, grad, q
+            return loss, self._quantum_precondition(theta64, grad), q
         if self.grad_engine != "paramshift":
             raise ValueError("grad_engine must be 'paramshift' or 'adjoint'")
-        if self.natural_gradient is None and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
+        if not self._rows_needed() and self.fused_dot and backend.paramshift_dot_supported(at, n, L, dev, n_local):
             # The dot product with dL/dq fused into the shifted circuits' last pass (kernels_circuit8.hip): base circuit
             # and all but the last pass of the shifted ones -> q -> contraction -> last pass of the shifted circuits with
             # w = y.  Their probabilities are never written or re-read (8 GB each way at n = 20).
@@ -277,7 +296,7 @@ class KSDVariationalInference(SteinOperator):
                 loss, grad_local = backend.paramshift_dot_finish(token, y, ksd2)
                 with self._timed("allgather"):
                     grad = shard.all_gather_grad(grad_local, P, self.process_group)
-            return loss, grad, q
+            return loss, self._quantum_precondition(theta64, grad), q
         with self._timed("circuits"):
             probs = backend.paramshift_probs(at, n, L, theta64, lo, hi, include_base=True, p_stride=step)
         q = probs[0]
@@ -288,10 +307,10 @@ class KSDVariationalInference(SteinOperator):
             loss, grad_local, _ = backend.ksd_grad_finish(n, shifted, n_local, y, ksd2)
             with self._timed("allgather"):
                 grad = shard.all_gather_grad(grad_local, P, self.process_group)
-        if self.natural_gradient is not None:       # (one rank: `shifted` holds every parameter's rows)
+        if self._rows_needed():       # (one rank: `shifted` holds every parameter's rows)
             with self._timed("natgrad"):
                 grad, self._natgrad_info = self.natural_gradient.precondition(shifted, q, grad)
-        return loss, grad, q
+        return loss, self._quantum_precondition(theta64, grad), q
 
     def _ksd_and_grad_shots(self, theta64, lo, hi, step, n_local):
         """ksd_and_grad with finite shots: the un-fused batch (base row, then the (+p, -p) rows of this rank's parameters),
