@@ -29,6 +29,7 @@
  *       score from CPTs, k_p pairs, gradient assembly, shots,
  *       ELBO weights, Fisher matrix ............................... 1 <= n <= 30;
  *       probability-table Born machine ............................ 0 <= n <= 30;
+ *       matrix-product-state Born machine (bond 1 <= D <= 32) ..... 1 <= n <= 26;
  *       un-fused gate application ................................. 1 <= n <= 40.
  */
 #ifndef BORNVI_H
@@ -368,6 +369,29 @@ size_t bornvi_elbo_workspace_bytes(bornvi_handle h, int n, int rows);
 int bornvi_elbo_weights(bornvi_handle h, int n, int rows, const double* q, const double* log_p,
                         double q_floor, double* w, double* neg_elbo, double* entropy,
                         void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
+/* ---- matrix-product-state (tensor-train) Born machine (no reference counterpart: the reference's classical family is the
+ * 2^n-entry table of born_machine_classical_sim.py; these two calls take its place in a training step, the first that of
+ * bornvi_born_table_probs and the second that of bornvi_born_table_vjp with ksd2 = NULL).
+ *   psi(z) = e0^T A_1[z_1] A_2[z_2] ... A_n[z_n] e0,   Z = sum_z psi(z)^2,   q_z = psi(z)^2 / Z.
+ * cores dev [n, 2, D, D] float64 row-major: A_k[s][a][b], a the left bond, b the right bond, s the value of tuple position
+ * k - 1 (position 0 = the most significant bit of the outcome index).  Both boundary vectors are e0: only row 0 of site 1
+ * and column 0 of site n enter.  No rescaling between levels.
+ * bornvi_mps_probs: q64 dev [2^n] float64; q32 dev [2^n] float32 or NULL = float32(q64); psi dev [2^n] float64 or NULL;
+ * Z_out dev [1] float64.  If Z is 0 or not finite, every q is NaN (no error code: the trainers' NaN/Inf guard skips the
+ * step).  The call leaves in the workspace what bornvi_mps_vjp needs (the levels of the prefix-doubling sweep, psi, Z): the
+ * same workspace goes to both calls and is left alone in between, the convention of bornvi_paramshift_dot_begin/_finish.
+ * bornvi_mps_vjp: g dev [2^n] float64 = dL/dq; grad_cores dev [n, 2, D, D] float64 = dL/dcores, same cores as the probs
+ * call; the entries of the first and last core that do not enter psi get exactly 0.0.
+ * Z, sum q g and the sums over prefixes of the core gradients are fixed-order partials in the workspace plus a finishing
+ * step (no atomics: two calls are bitwise equal); no allocation or synchronisation (capturable).  1 <= n <= 26 and
+ * 1 <= D <= 32, anything else is BORNVI_ERR_UNSUPPORTED before any launch.  Workspace: bornvi_mps_workspace_bytes(h, n, D)
+ * (about 14 D 2^n bytes: the levels are stored, not recomputed). */
+size_t bornvi_mps_workspace_bytes(bornvi_handle h, int n, int D);
+int bornvi_mps_probs(bornvi_handle h, int n, int D, const double* cores, double* q64, float* q32, double* psi,
+                     double* Z_out, void* workspace, size_t workspace_bytes, bornvi_stream stream);
+int bornvi_mps_vjp(bornvi_handle h, int n, int D, const double* cores, const double* g, double* grad_cores,
+                   void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
 /* ---- natural gradient (no reference counterpart: the reference steps theta with Adam on the raw gradient).
  * bornvi_fisher_gram: the classical Fisher information matrix of the Born distribution from the stored parameter-shift

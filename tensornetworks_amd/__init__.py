@@ -5,7 +5,7 @@ stein_utils) on a hand-written HIP backend (libbornvi_hip.so, C ABI in include/b
 """
 from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
-__all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "ClassicalKSDVariationalInference",
+__all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
            "generate_all_binary_outcomes", "calculate_tvd"]
 
@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "ClassicalBornMachine":
         from .born_machine_classical_sim import ClassicalBornMachine
         return ClassicalBornMachine
+    if name == "MPSBornMachine":
+        from .born_machine_mps import MPSBornMachine
+        return MPSBornMachine
     if name == "ClassicalKSDVariationalInference":      # (the reference's ksd_vi.KSDVariationalInference)
         from .ksd_vi import KSDVariationalInference
         return KSDVariationalInference

@@ -108,6 +108,11 @@ _PROTOS = {
     "bornvi_elbo_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "bornvi_elbo_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bornvi_mps_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "bornvi_mps_probs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bornvi_mps_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
     "bornvi_fisher_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "bornvi_fisher_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),

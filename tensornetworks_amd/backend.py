@@ -573,6 +573,58 @@ def elbo_weights(q, log_p, q_floor=1e-10, want_w=True, want_entropy=True, out=No
     return neg_elbo, entropy, w
 
 
+# ---- matrix-product-state Born machine -------------------------------------------------------------------
+MPS_MAX_N = 26
+MPS_MAX_BOND = 32
+
+
+def _mps_args(cores):
+    """(n, D) of cores [n, 2, D, D]; every argument error is raised here, before any GPU call."""
+    if not torch.is_tensor(cores) or cores.dim() != 4 or cores.shape[1] != 2 or cores.shape[2] != cores.shape[3]:
+        raise BornviError(f"cores: expected an [n, 2, D, D] tensor, got {tuple(cores.shape) if torch.is_tensor(cores) else type(cores)}")
+    n, D = int(cores.shape[0]), int(cores.shape[2])
+    _chk_n(n, 1, MPS_MAX_N)
+    if not 1 <= D <= MPS_MAX_BOND:
+        raise BornviError(f"cores: bond dimension 1 ... {MPS_MAX_BOND}, got {D}")
+    return n, D
+
+
+def mps_probs(cores, want_q32=True, want_psi=False):
+    """MPS Born machine forward (bornvi_mps_probs): cores float64 [n, 2, D, D] on the GPU -> (q32 float32 [2^n] or None,
+    q64 float64 [2^n], psi float64 [2^n] or None, Z float64 [1]).  Leaves the sweep's levels, psi and Z in the cached
+    workspace for mps_vjp: call that next, with the same cores, before another mps_probs of this shape on this stream."""
+    n, D = _mps_args(cores)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    N = 1 << n
+    q64 = torch.empty(N, dtype=torch.float64, device=dev)
+    q32 = torch.empty(N, dtype=torch.float32, device=dev) if want_q32 else None
+    psi = torch.empty(N, dtype=torch.float64, device=dev) if want_psi else None
+    Z = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _ws(dev, _cached_size(h, "bornvi_mps_workspace_bytes", n, D), "mps")
+    h.call("bornvi_mps_probs", n, D, _ptr(cores), _ptr(q64), _ptr(q32) if q32 is not None else None,
+           _ptr(psi) if psi is not None else None, _ptr(Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return q32, q64, psi, Z
+
+
+def mps_vjp(cores, g, out=None):
+    """MPS Born machine backward (bornvi_mps_vjp): float64 [n, 2, D, D] = dL/dcores from g = dL/dq float64 [2^n], through
+    what the last mps_probs(cores) left in the cached workspace.  out: destination (e.g. a parameter's .grad)."""
+    n, D = _mps_args(cores)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(g, torch.float64, dev, "g", 1 << n)
+    if out is None:
+        out = torch.empty(cores.shape, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", cores.numel())
+    ws = _ws(dev, _cached_size(h, "bornvi_mps_workspace_bytes", n, D), "mps")
+    h.call("bornvi_mps_vjp", n, D, _ptr(cores), _ptr(g), _ptr(out), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out
+
+
 # ---- natural gradient ---------------------------------------------------------------------------------
 FISHER_MAX_PARAMS = 1024
 

@@ -1144,6 +1144,36 @@ int bornvi_elbo_weights(bornvi_handle h, int n, int rows, const double* q, const
   return BORNVI_OK;
 }
 
+static bool valid_mps(int n, int D) { return n >= 1 && n <= 26 && D >= 1 && D <= 32; }
+
+size_t bornvi_mps_workspace_bytes(bornvi_handle h, int n, int D) {
+  if (!h) return 0;
+  if (!valid_mps(n, D)) { fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 26, 1 <= D <= 32)"); return 0; }
+  return mps_workspace_bytes(n, D);
+}
+
+int bornvi_mps_probs(bornvi_handle h, int n, int D, const double* cores, double* q64, float* q32, double* psi, double* Z_out,
+                     void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps(n, D)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 26, 1 <= D <= 32)");
+  if (!cores || !q64 || !Z_out) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < mps_workspace_bytes(n, D)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_probs(n, D, cores, q64, q32, psi, Z_out, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_mps_vjp(bornvi_handle h, int n, int D, const double* cores, const double* g, double* grad_cores, void* workspace,
+                   size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps(n, D)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 26, 1 <= D <= 32)");
+  if (!cores || !g || !grad_cores) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < mps_workspace_bytes(n, D)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_vjp(n, D, cores, g, grad_cores, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 static bool valid_fisher(int n, int n_shift) { return n >= 1 && n <= 30 && n_shift >= 1 && n_shift <= 1024; }
 
 size_t bornvi_fisher_workspace_bytes(bornvi_handle h, int n, int n_shift) {

@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "plan.cpp"]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "plan.cpp"]
 HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
@@ -46,6 +46,14 @@ RESOURCE_BUDGET = {
     "qfi_gram_kernel": (0, 0),                    # quantum natural gradient (kernels_qfi.hip): no scratch anywhere
     "qfi_finish_kernel": (0, 0),
     "state_tail_kernel": (0, 0),
+    "mps_fwd_fused_kernel": (0, 0),               # MPS Born machine (kernels_mps.hip), every bond-size instantiation: a row of
+    "mps_fwd_level_kernel": (0, 0),               # up to 32 doubles per lane lives in registers, no scratch anywhere
+    "mps_psi_kernel": (0, 0),
+    "mps_q_kernel": (0, 0),
+    "mps_gstats_kernel": (0, 0),
+    "mps_bwd_fused_kernel": (0, 0),
+    "mps_bwd_level_kernel": (0, 0),
+    "mps_finish_kernel": (0, 0),
     "circuit_pass_r3_kernelILb1": (0, 0),         # its fused-dot instantiation (last pass only): 8 weights more per thread, exactly
                                                   # 128 VGPRs; a scratch reload is a vector-memory load, and its wait is a wait for the
                                                   # whole prefetched tile (vmcnt retires in issue order)

@@ -76,6 +76,12 @@ size_t elbo_workspace_bytes(int n, long long rows);
 hipError_t launch_elbo_weights(int n, long long rows, const double* q, const double* log_p, double q_floor, double* w,
                                double* neg_elbo, double* entropy, void* ws, hipStream_t st);
 
+// ---- matrix-product-state Born machine (kernels_mps.hip): cores [n, 2, D, D] -> q, and dL/dq -> dL/dcores ----------
+size_t mps_workspace_bytes(int n, int D);
+hipError_t launch_mps_probs(int n, int D, const double* cores, double* q64, float* q32, double* psi_out, double* Z_out, void* ws,
+                            hipStream_t st);
+hipError_t launch_mps_vjp(int n, int D, const double* cores, const double* g, double* grad_cores, void* ws, hipStream_t st);
+
 // ---- natural gradient: Fisher matrix of the stored parameter-shift rows, damped Cholesky solve (kernels_fisher.hip)
 size_t fisher_workspace_bytes(int n, int n_shift);
 hipError_t launch_fisher_gram(int n, const double* shifted, int n_shift, const double* q, double q_floor, double* F, void* ws,

@@ -9,12 +9,15 @@ log-joint table).  No reference counterpart: the reference's classical route to 
   objective.weights(q64): L, entropy, w = dL/dq           one pass over 2^n doubles, in place of the K_p contraction
   born_table_vjp(y = w, ksd2 = None) -> params.grad       y is then dL/dq itself
 
+With born_machine_config['family'] = 'mps' the two ends are mps_probs and mps_vjp (born_machine_mps.py) and q stays float64.
+
 train() -- optimiser, clip, guard, early stopping, restore of the best probabilities -- is the classical KSD trainer's
 own code (this class derives from it and overrides the objective hooks); its Stein side is never prepared.
 """
 import torch
 
 from . import backend
+from .born_machine_mps import MPSBornMachine
 from .elbo_objective import ElboObjective
 from .ksd_vi import KSDVariationalInference
 
@@ -41,6 +44,13 @@ class ELBOVariationalInference(KSDVariationalInference):
         L - entropy_weight * H (the KSD trainer's entropy bonus; L carries the entropy itself, so 0 is the ELBO).
         Nothing is read back to the host.  One forward per epoch, in MLP mode too."""
         bm = self.born_machine
+        if isinstance(bm, MPSBornMachine):
+            cores, q32, q64 = self.mps_forward()
+            loss, entropy, dldq = self.objective.weights(q64)
+            g = dldq.reshape(-1)
+            if entropy_weight != 0.0:
+                g = g + entropy_weight * self.mps_entropy_term(q64)[1]
+            return loss, entropy, q32, self.mps_backward(cores, g)
         mode = bm.born_mode
         if bm.conditioning_dim == 0:
             home = bm.params.device

@@ -27,6 +27,7 @@ import torch.optim as optim
 from . import backend
 from . import paramshift_shard as shard
 from .born_machine_classical_sim import ClassicalBornMachine
+from .born_machine_mps import MPSBornMachine
 from .stein_operator import DENSE_GRAM_MAX_N, SteinOperator      # noqa: F401  (DENSE_GRAM_MAX_N: exported from here too)
 from .stein_utils import base_hamming_kernel_torch, tvd_table
 from .utils import calculate_tvd
@@ -45,8 +46,15 @@ class KSDVariationalInference:
 
         # the reference forces this initialisation whatever the config says (ksd_vi.py:30)
         born_machine_config = {**born_machine_config, 'init_method': 'small_random'}
-        self.born_machine = ClassicalBornMachine(num_latent_vars=self.num_latent_vars,
-                                                 **born_machine_config).to(device)
+        # 'family': 'table' (default: the reference's probability table / MLP) or 'mps' (born_machine_mps.py, with 'bond_dim')
+        family = born_machine_config.pop('family', 'table')
+        if family == 'mps':
+            self.born_machine = MPSBornMachine(num_latent_vars=self.num_latent_vars, **born_machine_config).to(device)
+        elif family == 'table':
+            self.born_machine = ClassicalBornMachine(num_latent_vars=self.num_latent_vars,
+                                                     **born_machine_config).to(device)
+        else:
+            raise ValueError(f"born_machine_config['family'] must be 'table' or 'mps', got {family!r}")
 
         self.num_possible_latent_states = 2 ** self.num_latent_vars
         self.base_kernel_func = partial(base_hamming_kernel_torch,
@@ -90,9 +98,21 @@ class KSDVariationalInference:
         return optimizer_born, scheduler
 
     def loss_and_grads(self, x_condition, entropy_weight):
-        """Device part of one epoch: -> (loss_ksd [1] float64, entropy [1] float32, q [2^n] float32 of the loss forward,
-        grads): grads = [(tensor, its gradient), ...] for apply_grads.  Nothing is read back to the host."""
+        """Device part of one epoch: -> (loss_ksd [1] float64, entropy [1], q [2^n] float32 of the loss forward, grads):
+        grads = [(tensor, its gradient), ...] for apply_grads.  The entropy is float32 from the table family's kernel and
+        float64 from the MPS family (mps_entropy_term); train() only reads it with .item().  Nothing is read back to the
+        host."""
         bm = self.born_machine
+        if isinstance(bm, MPSBornMachine):
+            cores, q32, q64 = self.mps_forward()
+            ksd2, y = self._stein._stein_contract(q64)
+            # loss = sqrt(max(ksd2, 1e-12)); the clamp passes no gradient below 1e-12 (bornvi_born_table_vjp's convention)
+            loss = torch.sqrt(ksd2.clamp(min=1e-12))
+            g = torch.where(ksd2 >= 1e-12, y / loss, torch.zeros_like(y))
+            H, dH = self.mps_entropy_term(q64)
+            if entropy_weight != 0.0:
+                g = g + entropy_weight * dH
+            return loss, H, q32, self.mps_backward(cores, g)
         mode = bm.born_mode
         st = self._stein
         if bm.conditioning_dim == 0:
@@ -117,6 +137,25 @@ class KSDVariationalInference:
         _, q64e, H = backend.born_table_probs(w2.detach(), mode, want_entropy=True)
         g2 = backend.born_table_vjp(w2.detach(), q64e, mode, entropy_weight=entropy_weight)
         return loss, H, q32[0], [(w1, g1), (w2, g2)]
+
+    # ---- the MPS family's ends of an epoch (shared with the ELBO trainer): cores -> q, and dL/dq -> the cores' gradient
+    def mps_forward(self):
+        """(cores float64 on the compute device, q32 [2^n], q64 [2^n]); leaves the sweep in the workspace for mps_backward."""
+        bm = self.born_machine
+        cores = bm.cores.detach().to(device=backend.compute_device(bm.cores.device), dtype=torch.float64).contiguous()
+        q32, q64, _, _ = backend.mps_probs(cores)
+        return cores, q32, q64
+
+    @staticmethod
+    def mps_entropy_term(q64):
+        """(H [1] = -sum q log max(q, 1e-10), the derivative of -H: log max(q, 1e-10) + [q >= 1e-10]) in float64."""
+        logq = torch.log(q64.clamp(min=1e-10))
+        return -(q64 * logq).sum().reshape(1), logq + (q64 >= 1e-10).to(torch.float64)
+
+    def mps_backward(self, cores, g):
+        bm = self.born_machine
+        grad = backend.mps_vjp(cores, g.contiguous())
+        return [(bm.cores, grad.to(device=bm.cores.device, dtype=bm.cores.dtype))]
 
     @staticmethod
     def apply_grads(grads):
