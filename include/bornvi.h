@@ -192,6 +192,14 @@ typedef struct {
 /* S dev [2^n, n] (row z, column b = tuple position b), pxz dev [2^n] or NULL. */
 int bornvi_score_from_cpts(bornvi_handle h, const bornvi_bn_desc* bn, int n, double* S,
                            double* pxz, bornvi_stream stream);
+/* Log joint of sampled latent states: logp dev [B] float64, logp_b = sum over the nodes, in descriptor order, of
+ * log max(CPT_v[parents(z_b, x)][value], p_floor); idx dev [B] int64 outcome indices, 1 <= n <= 63, 1 <= B <= 2^24.  Every
+ * FACTOR is floored (the exact-ELBO objective floors the product: at n = 60 legitimate joints lie far below any floor of a
+ * product); the two agree whenever no factor is below p_floor and the product is >= p_floor.  A descriptor with a
+ * summed-out node (role -3) is refused with BORNVI_ERR_UNSUPPORTED: the roles are read back from the device for that,
+ * except while `stream` is being captured, where the kernel writes NaN instead. */
+int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx,
+                               double p_floor, double* logp, bornvi_stream stream);
 
 /* ---- Stein-kernel Gram matrix (replaces the N^2 calls of get_stein_kernel_kp_value, --------
  * stein_utils.py:138-197 with base_hamming_kernel_torch :30-55, made in
@@ -392,6 +400,34 @@ int bornvi_mps_probs(bornvi_handle h, int n, int D, const double* cores, double*
                      double* Z_out, void* workspace, size_t workspace_bytes, bornvi_stream stream);
 int bornvi_mps_vjp(bornvi_handle h, int n, int D, const double* cores, const double* g, double* grad_cores,
                    void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
+/* ---- sampled MPS Born machine (kernels_mps_sample.hip): no 2^n object anywhere -----------------
+ * Same cores layout and conventions as above; 1 <= n <= 63, 1 <= D <= 32, 1 <= B <= 2^24 samples per call, anything else is
+ * BORNVI_ERR_UNSUPPORTED before any launch.  A sample is one int64 outcome index, idx = sum_k z_k 2^(n-k) (tuple position 0 =
+ * the most significant bit).
+ * bornvi_mps_environments: the right environments E_n = e0 e0^T, E_{k-1} = sum_s A_k[s] E_k A_k[s]^T, the left ones
+ * L_0 = e0 e0^T, L_k = sum_s A_k[s]^T L_{k-1} A_k[s], each rescaled by an exact power of two after every step with its
+ * integer exponent kept beside it, and log Z (Z = E_0[0,0]) -> log_Z_out dev [1] or NULL.  They stay in the workspace: the
+ * two calls below need them for the same cores and the same (n, D, B) workspace (the begin/finish convention of
+ * bornvi_paramshift_dot_begin/_finish).
+ * bornvi_mps_sample: B exact ancestral draws z ~ q -> idx dev [B] int64, logq dev [B] float64 = log psi(z)^2 - log Z.  Draw
+ * k of sample b is a pure function of (seed, *epoch_dev, b, k) through Philox4x32-10 (the kernel file states it): it does
+ * not depend on B.  status dev [1] int32: 0, or 1 when some sample met conditional masses whose sum is 0 or not finite
+ * (its remaining bits are 0 and its logq NaN).
+ * bornvi_mps_score_vjp: idx dev [B], w dev [B] float64 -> logq dev [B] and grad_cores dev [n, 2, D, D] = sum_b w_b grad
+ * log q(z_b); the entries of the first and last core that do not enter psi get exactly 0.0.  status: 0, or 2 when some
+ * psi(z_b) is 0 or not finite (logq -inf / NaN, no contribution to the sample term) or Z is not positive and finite.
+ * No atomics (two calls are bitwise equal), no allocation or synchronisation (capturable).  The workspace is bounded in B:
+ * at most 256 tiles of 64 samples are in flight (bornvi_mps_sample_workspace_bytes). */
+size_t bornvi_mps_sample_workspace_bytes(bornvi_handle h, int n, int D, long long B);
+int bornvi_mps_environments(bornvi_handle h, int n, int D, long long B, const double* cores, double* log_Z_out,
+                            void* workspace, size_t workspace_bytes, bornvi_stream stream);
+int bornvi_mps_sample(bornvi_handle h, int n, int D, long long B, const double* cores, unsigned long long seed,
+                      const long long* epoch_dev, long long* idx, double* logq, int* status, void* workspace,
+                      size_t workspace_bytes, bornvi_stream stream);
+int bornvi_mps_score_vjp(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx,
+                         const double* w, double* logq, double* grad_cores, int* status, void* workspace,
+                         size_t workspace_bytes, bornvi_stream stream);
 
 /* ---- natural gradient (no reference counterpart: the reference steps theta with Adam on the raw gradient).
  * bornvi_fisher_gram: the classical Fisher information matrix of the Born distribution from the stored parameter-shift

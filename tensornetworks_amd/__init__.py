@@ -7,6 +7,7 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
+           "SampledMPSBornMachine", "SampledELBOVariationalInference",
            "generate_all_binary_outcomes", "calculate_tvd"]
 
 
@@ -35,4 +36,10 @@ def __getattr__(name):
     if name == "ClassicalELBOVariationalInference":
         from .elbo_vi import ELBOVariationalInference
         return ELBOVariationalInference
+    if name == "SampledMPSBornMachine":
+        from .born_machine_mps_sampled import SampledMPSBornMachine
+        return SampledMPSBornMachine
+    if name == "SampledELBOVariationalInference":
+        from .elbo_vi_sampled import SampledELBOVariationalInference
+        return SampledELBOVariationalInference
     raise AttributeError(name)

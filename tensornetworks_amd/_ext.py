@@ -113,6 +113,15 @@ _PROTOS = {
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "bornvi_mps_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
+    "bornvi_mps_sample_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_longlong]),
+    "bornvi_mps_environments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]),
+    "bornvi_mps_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_ulonglong, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bornvi_mps_score_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bornvi_bn_logjoint_samples": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_longlong, C.c_void_p, C.c_double,
+                                             C.c_void_p, C.c_void_p]),
     "bornvi_fisher_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "bornvi_fisher_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),

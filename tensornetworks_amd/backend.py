@@ -625,6 +625,132 @@ def mps_vjp(cores, g, out=None):
     return out
 
 
+# ---- sampled MPS Born machine (no 2^n object) -------------------------------------------------------------
+MPS_SAMPLED_MAX_N = 63
+MPS_SAMPLED_MAX_BATCH = 1 << 24
+
+
+def _mps_sampled_args(cores, B):
+    """(n, D, B) of cores [n, 2, D, D] and a sample count; every argument error is raised here, before any GPU call."""
+    if not torch.is_tensor(cores) or cores.dim() != 4 or cores.shape[1] != 2 or cores.shape[2] != cores.shape[3]:
+        raise BornviError(f"cores: expected an [n, 2, D, D] tensor, got {tuple(cores.shape) if torch.is_tensor(cores) else type(cores)}")
+    n, D = int(cores.shape[0]), int(cores.shape[2])
+    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
+    if not 1 <= D <= MPS_MAX_BOND:
+        raise BornviError(f"cores: bond dimension 1 ... {MPS_MAX_BOND}, got {D}")
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MPS_SAMPLED_MAX_BATCH:
+        raise BornviError(f"number of samples: 1 ... 2^24 per call, got {B!r}")
+    return n, D, int(B)
+
+
+def _mps_sampled_ws(h, dev, n, D, B):
+    """One workspace per (n, D, B) and stream: mps_environments leaves the environments in it for the two calls after it."""
+    return _ws(dev, _cached_size(h, "bornvi_mps_sample_workspace_bytes", n, D, B), f"mps_sampled_{n}_{D}_{B}")
+
+
+def mps_environments(cores, num_samples):
+    """Left and right environments of an MPS and log Z (bornvi_mps_environments): cores float64 [n, 2, D, D] on the GPU,
+    1 <= n <= 63 -> log Z float64 [1].  The environments stay in the cached workspace of (n, D, num_samples) for
+    mps_sample and mps_score_vjp: call those next, with the same cores and sample count, on this stream."""
+    n, D, B = _mps_sampled_args(cores, num_samples)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    log_Z = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _mps_sampled_ws(h, dev, n, D, B)
+    h.call("bornvi_mps_environments", n, D, B, _ptr(cores), _ptr(log_Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return log_Z
+
+
+def mps_sample(cores, num_samples, seed, epoch, out_idx=None, out_logq=None, status=None):
+    """Exact ancestral draws from an MPS Born machine (bornvi_mps_sample), after mps_environments(cores, num_samples):
+    -> (idx int64 [B] outcome indices, logq float64 [B] = log q(idx), status int32 [1]: 0, or 1 when a sample met
+    conditional masses summing to 0 or a non-finite number).  Draw k of sample b is a pure function of (seed, epoch, b, k).
+    epoch: an int64 device tensor [1] (read by the kernel: a captured graph sees its value at replay time)."""
+    n, D, B = _mps_sampled_args(cores, num_samples)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise BornviError(f"seed must be an integer, got {seed!r}")
+    _chk(epoch, torch.int64, dev, "epoch", 1)
+    if out_idx is None:
+        out_idx = torch.empty(B, dtype=torch.int64, device=dev)
+    else:
+        _chk(out_idx, torch.int64, dev, "out_idx", B)
+    if out_logq is None:
+        out_logq = torch.empty(B, dtype=torch.float64, device=dev)
+    else:
+        _chk(out_logq, torch.float64, dev, "out_logq", B)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(status, torch.int32, dev, "status", 1)
+    ws = _mps_sampled_ws(h, dev, n, D, B)
+    h.call("bornvi_mps_sample", n, D, B, _ptr(cores), int(seed) & ((1 << 64) - 1), _ptr(epoch), _ptr(out_idx), _ptr(out_logq),
+           _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out_idx, out_logq, status
+
+
+def mps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
+    """Score-function gradient of an MPS Born machine (bornvi_mps_score_vjp), after mps_environments(cores, len(idx)):
+    idx int64 [B] outcome indices in [0, 2^n), w float64 [B] -> (grad float64 [n, 2, D, D] = sum_b w_b grad log q(idx_b),
+    logq float64 [B], status int32 [1]: 0, or 2 when some psi(idx_b) is 0 or not finite).  out: destination of grad."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    n, D, B = _mps_sampled_args(cores, int(idx.numel()))
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    _chk(w, torch.float64, dev, "w", B)
+    if out is None:
+        out = torch.empty(cores.shape, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", cores.numel())
+    if out_logq is None:
+        out_logq = torch.empty(B, dtype=torch.float64, device=dev)
+    else:
+        _chk(out_logq, torch.float64, dev, "out_logq", B)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(status, torch.int32, dev, "status", 1)
+    ws = _mps_sampled_ws(h, dev, n, D, B)
+    h.call("bornvi_mps_score_vjp", n, D, B, _ptr(cores), _ptr(idx), _ptr(w), _ptr(out_logq), _ptr(out), _ptr(status), _ptr(ws),
+           ws.numel(), _ext.stream_ptr(dev))
+    return out, out_logq, status
+
+
+def bn_descriptor(packed, dev):
+    """(device arrays, BnDesc) of bayesian_network.pack_network's dict; the arrays must outlive every call that uses the
+    descriptor.  A network with a summed-out node is refused by bn_logjoint_samples, not here."""
+    t = {k: torch.as_tensor(np.ascontiguousarray(v)).to(dev) for k, v in packed.items()}
+    desc = _ext.BnDesc(int(t["role"].numel()), int(t["parents"].shape[1]), t["role"].data_ptr(),
+                       t["n_parents"].data_ptr(), t["parents"].data_ptr(), t["cpt_off"].data_ptr(), t["cpt"].data_ptr())
+    return t, desc
+
+
+def bn_logjoint_samples(desc, n, idx, p_floor=1e-30, out=None):
+    """Log joint of sampled latent states (bornvi_bn_logjoint_samples): desc from bn_descriptor, idx int64 [B] on the GPU
+    -> logp float64 [B], logp_b = sum over the nodes of log max(CPT factor, p_floor).  Every factor is floored, where
+    ElboObjective floors the product; the two agree whenever no factor is below p_floor and the product is >= p_floor."""
+    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
+    _chk_positive(p_floor, "p_floor")
+    if not torch.is_tensor(idx) or idx.dim() != 1 or not 1 <= int(idx.numel()) <= MPS_SAMPLED_MAX_BATCH:
+        raise BornviError("idx: expected a [B] int64 tensor, 1 <= B <= 2^24")
+    dev = idx.device
+    h = _ext.handle_for(dev)
+    B = int(idx.numel())
+    _chk(idx, torch.int64, dev, "idx")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", B)
+    h.call("bornvi_bn_logjoint_samples", C.byref(desc), int(n), B, _ptr(idx), float(p_floor), _ptr(out), _ext.stream_ptr(dev))
+    return out
+
+
 # ---- natural gradient ---------------------------------------------------------------------------------
 FISHER_MAX_PARAMS = 1024
 

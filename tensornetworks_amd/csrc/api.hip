@@ -847,6 +847,31 @@ int bornvi_score_from_cpts(bornvi_handle h, const bornvi_bn_desc* bn, int n, dou
   return BORNVI_OK;
 }
 
+int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx, double p_floor,
+                               double* logp, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
+  if (!bn || !idx || !logp || !(p_floor > 0.0) || !std::isfinite(p_floor)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  if (bn->num_nodes < 1 || bn->num_nodes > 64 || bn->max_parents < 1 || !bn->role || !bn->n_parents || !bn->parents ||
+      !bn->cpt_off || !bn->cpt)
+    return fail(h, BORNVI_ERR_INVALID, "bad network descriptor");
+  DEVICE_SCOPE(h);
+  // The roles live on the device.  Outside a stream capture they are read back and a summed-out node is refused here; inside
+  // one no copy is allowed, and the kernel writes NaN for such a descriptor.
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+  if (cap == hipStreamCaptureStatusNone) {
+    int32_t role[64];
+    HIPCHK(h, hipMemcpy(role, bn->role, sizeof(int32_t) * bn->num_nodes, hipMemcpyDeviceToHost));
+    for (int v = 0; v < bn->num_nodes; ++v) {
+      if (role[v] == -3) return fail(h, BORNVI_ERR_UNSUPPORTED, "a summed-out node (role -3) has no log joint per sample: use the enumerated paths");
+      if (role[v] < -3 || role[v] >= n) return fail(h, BORNVI_ERR_INVALID, "bad network descriptor: role out of range");
+    }
+  }
+  HIPCHK(h, launch_bn_logjoint_samples(*bn, n, B, idx, p_floor, logp, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 long long bornvi_stein_gram_ld(int n) {
   if (n < 1 || n > 17) return 0;
   // 256 bytes of padding per row.  Same-box A/B of the band kernel at n = 16 (tools/probes/sym_probe.py, three
@@ -1171,6 +1196,50 @@ int bornvi_mps_vjp(bornvi_handle h, int n, int D, const double* cores, const dou
   if (!workspace || workspace_bytes < mps_workspace_bytes(n, D)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_mps_vjp(n, D, cores, g, grad_cores, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+static bool valid_mps_sample(int n, int D, long long B) { return n >= 1 && n <= 63 && D >= 1 && D <= 32 && B >= 1 && B <= (1ll << 24); }
+static const char* const MPS_SAMPLE_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 32, 1 <= B <= 2^24)";
+
+size_t bornvi_mps_sample_workspace_bytes(bornvi_handle h, int n, int D, long long B) {
+  if (!h) return 0;
+  if (!valid_mps_sample(n, D, B)) { fail(h, BORNVI_ERR_UNSUPPORTED, MPS_SAMPLE_RANGE); return 0; }
+  return mps_sample_workspace_bytes(n, D, B);
+}
+
+int bornvi_mps_environments(bornvi_handle h, int n, int D, long long B, const double* cores, double* log_Z_out, void* workspace,
+                            size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_sample(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_SAMPLE_RANGE);
+  if (!cores) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < mps_sample_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_environments(n, D, B, cores, log_Z_out, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_mps_sample(bornvi_handle h, int n, int D, long long B, const double* cores, unsigned long long seed,
+                      const long long* epoch_dev, long long* idx, double* logq, int* status, void* workspace, size_t workspace_bytes,
+                      bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_sample(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_SAMPLE_RANGE);
+  if (!cores || !epoch_dev || !idx || !logq || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < mps_sample_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_sample(n, D, B, cores, seed, epoch_dev, idx, logq, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_mps_score_vjp(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, const double* w,
+                         double* logq, double* grad_cores, int* status, void* workspace, size_t workspace_bytes,
+                         bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_sample(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_SAMPLE_RANGE);
+  if (!cores || !idx || !w || !logq || !grad_cores || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < mps_sample_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_score_vjp(n, D, B, cores, idx, w, logq, grad_cores, status, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

@@ -9,8 +9,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "plan.cpp"]
-HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "plan.cpp"]
+HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-I" + os.path.join(REPO, "include"), "-I" + HERE,
@@ -54,6 +54,11 @@ RESOURCE_BUDGET = {
     "mps_bwd_fused_kernel": (0, 0),
     "mps_bwd_level_kernel": (0, 0),
     "mps_finish_kernel": (0, 0),
+    "mps_env_kernel": (0, 0),                     # sampled MPS (kernels_mps_sample.hip): l, u_0, u_1 (3 x 32 doubles) in registers
+    "mps_sample_kernel": (0, 0),
+    "mps_score_kernel": (0, 0),
+    "mps_score_finish_kernel": (0, 0),
+    "bn_logjoint_kernel": (0, 0),
     "circuit_pass_r3_kernelILb1": (0, 0),         # its fused-dot instantiation (last pass only): 8 weights more per thread, exactly
                                                   # 128 VGPRs; a scratch reload is a vector-memory load, and its wait is a wait for the
                                                   # whole prefetched tile (vmcnt retires in issue order)

@@ -82,6 +82,16 @@ hipError_t launch_mps_probs(int n, int D, const double* cores, double* q64, floa
                             hipStream_t st);
 hipError_t launch_mps_vjp(int n, int D, const double* cores, const double* g, double* grad_cores, void* ws, hipStream_t st);
 
+// ---- sampled MPS Born machine (kernels_mps_sample.hip): environments, exact sampler, score gradient, log joint of samples
+size_t mps_sample_workspace_bytes(int n, int D, long long B);
+hipError_t launch_mps_environments(int n, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st);
+hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, unsigned long long seed, const long long* epoch_dev,
+                             long long* idx, double* logq, int* status, void* ws, hipStream_t st);
+hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
+                                double* grad_cores, int* status, void* ws, hipStream_t st);
+hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
+                                      hipStream_t st);
+
 // ---- natural gradient: Fisher matrix of the stored parameter-shift rows, damped Cholesky solve (kernels_fisher.hip)
 size_t fisher_workspace_bytes(int n, int n_shift);
 hipError_t launch_fisher_gram(int n, const double* shifted, int n_shift, const double* q, double q_floor, double* F, void* ws,

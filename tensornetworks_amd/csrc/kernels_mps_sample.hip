@@ -1,0 +1,553 @@
+// Sampled matrix-product-state Born machine: nothing here touches 2^n of anything.
+//   q(z) = psi(z)^2 / Z,  psi(z) = e0^T A_1[z_1] ... A_n[z_n] e0,  cores [n, 2, D, D] float64, 1 <= n <= 63, 1 <= D <= 32.
+//
+// bornvi_mps_environments:  E_n = e0 e0^T,  E_{k-1} = sum_s A_k[s] E_k A_k[s]^T,  Z = E_0[0, 0];
+//                           L_0 = e0 e0^T,  L_k = sum_s A_k[s]^T L_{k-1} A_k[s].
+//   One launch of two workgroups (0: the right environments, 1: the left ones), n dependent steps each.  A step is two
+//   D x D x D products through LDS, T_s = A_s X (A_s^T X on the left) and X' = sum_s T_s A_s^T (T_s A_s), every entry one
+//   fma chain in index order (c, then s outer / d inner).  After every step the matrix is multiplied by 2^-e, e = ilogb of
+//   its largest magnitude (exact), and the running sum of the e's is stored beside it:  true E_k = E^_k 2^eE[k].
+//   log Z = log E^_0[0, 0] + eE[0] ln 2.
+//
+// bornvi_mps_sample: one sample per lane, one wave per workgroup; l (DP doubles, DP = 2, 4, 8, 16, 32 >= D) in registers,
+//   A_k[0], A_k[1], E^_k zero-padded in LDS and read as broadcasts.  For k = 1 .. n:
+//     u_s = l A_k[s],  m_s = u_s E^_k u_s^T = sum_d u_s[d] (sum_c u_s[c] E^_k[c][d]),  z_k = [U_k (m_0 + m_1) >= m_0],  l = u_{z_k}
+//   then l *= 2^-e (e = ilogb of its largest magnitude), the e's summed in el.  The common factor 2^eE[k] of both m_s drops out.
+//   U_k: Philox4x32-10 (philox_dev.hpp), key = (seed & 0xffffffff, seed >> 32),
+//     counter = (b, ceil(k / 2) - 1, 0xffffffff, epoch & 0xffffffff) -> w0 .. w3;
+//     odd k: U_k = ((w1:w0) >> 11) 2^-53,  even k: U_k = ((w3:w2) >> 11) 2^-53   (the call of k - 1).
+//   (0xffffffff is no circuit id of the shots path: those are 0 .. 2 P + 2 for P circuit parameters.)  A draw depends on
+//   (seed, epoch, b, k) and on the sample's own earlier bits only: not on B, the grid or the tiling.
+//   If m_0 + m_1 is 0 or not finite the status word becomes 1, the sample's remaining bits are 0 and its logq is NaN.
+//   logq = 2 log|l_n[0]| - log E^_0[0, 0] + (2 el - eE[0]) ln 2.
+//
+// bornvi_mps_score_vjp: grad = sum_b w_b grad log q(z_b) = sum_b (2 w_b / psi_b) l_{b,k-1}^T (x) r_{b,k}^T at [k, z_{b,k}]
+//                              - (sum_b w_b) 2 L_{k-1} A_k[s] E_k / Z.
+//   One wave per workgroup and a tile of 64 samples at a time, one sample per lane; at most MS_MAX_WG workgroups, each
+//   walking the tiles wg, wg + G, ...  Right-to-left sweep: r_k = A_{k+1}[z_{k+1}] r_{k+1} in registers (rescaled like l,
+//   exponent er_k), r^_1 .. r^_{n-1} and their exponents stored in the workgroup's slice of the workspace; psi = r^_0[0] 2^er_0.
+//   Left-to-right sweep: X[b][a] = 2 w_b / r^_0[0] * 2^(el_{k-1} + er_k - er_0) * l^_{k-1}[a] goes to LDS and
+//   dA_k[s] += X_s^T R_k (X_s: the rows with z_{b,k} = s, others 0) runs on v_mfma_f64_16x16x4_f64, 16 steps of 4 samples,
+//   the B operand read straight from the slice ([sample][DS], 16 consecutive doubles of 4 rows per step, the layout of
+//   kernels_mps.hip's dA_k); the workgroup adds the tile into its own partial [n, 2, D, D] (first tile: stores).
+//   mps_score_finish_kernel, one workgroup per site: the partials in workgroup order, sum_b w_b (per tile a butterfly over the
+//   64 lanes, tiles in order, then the workgroups' totals: 64-lane butterflies of lane-strided sums, waves in order) and the
+//   environment term, T_s = A_s E^_k and M_s = L^_{k-1} T_s as fma chains in index order, scaled by 2^(eL[k-1] + eE[k] - eE[0]) / E^_0[0, 0].
+//   A sample with psi = 0 (or not finite) gets logq = -inf (NaN), weight 0 in the first term, and sets the status word to 2.
+//
+// bornvi_bn_logjoint_samples: logp_b = sum_v log max(CPT_v[parents][value], p_floor), one lane per sample, nodes in order.
+//
+// No atomics, no allocation, no synchronisation: capturable, and two calls are bitwise equal.  The status word is cleared
+// by a one-lane kernel in front of the launch (a kernel node like the others when the calls are captured into a graph, so
+// every replay clears it in stream order) and set by plain stores (every writer of a launch stores the same value).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "kernels.hpp"
+#include "philox_dev.hpp"
+
+namespace bornvi {
+
+namespace {
+constexpr int MS_LANES = 64;               // sampler and score kernels: one wave per workgroup
+constexpr int MS_MAX_WG = 256;             // score kernel: workgroups (= workspace slices and partials) at most
+constexpr int ENV_THREADS = 256;
+constexpr int MS_DMAX = 32;
+constexpr uint32_t MS_PHILOX_DOMAIN = 0xffffffffu;
+constexpr double MS_LN2 = 0.693147180559945309417232121458;
+
+typedef double ms_d4 __attribute__((ext_vector_type(4)));
+
+struct MsLayout {
+  int DP, DS, G;
+  size_t hdr, E, L, eE, eL, r, er, parts, wpart, total;   // byte offsets from the aligned base
+};
+
+MsLayout ms_layout(int n, int D, long long B) {
+  MsLayout S;
+  S.DP = D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32;
+  S.DS = (D + 1) & ~1;
+  const long long tiles = (B + MS_LANES - 1) / MS_LANES;
+  S.G = (int)(tiles < MS_MAX_WG ? tiles : MS_MAX_WG);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  size_t o = 0;
+  S.hdr = o;   o += 256;                                                     // log Z, E^_0[0, 0], eE[0]
+  S.E = o;     o += up((size_t)(n + 1) * D * D * sizeof(double));
+  S.L = o;     o += up((size_t)(n + 1) * D * D * sizeof(double));
+  S.eE = o;    o += up((size_t)(n + 1) * sizeof(int));
+  S.eL = o;    o += up((size_t)(n + 1) * sizeof(int));
+  S.r = o;     o += up((size_t)S.G * n * MS_LANES * S.DS * sizeof(double));   // slot k of a slice: r^_k, k = 1 .. n - 1
+  S.er = o;    o += up((size_t)S.G * n * MS_LANES * sizeof(int));
+  S.parts = o; o += up((size_t)S.G * n * 2 * D * D * sizeof(double));
+  S.wpart = o; o += up((size_t)MS_MAX_WG * sizeof(double));
+  S.total = o;
+  return S;
+}
+
+char* ms_align(char* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+
+__device__ __forceinline__ double ms_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ double ms_wave_max(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+
+// exponent of the exact power-of-two rescaling: ilogb of a positive finite largest magnitude, else 0 (nothing to rescale)
+__device__ __forceinline__ int ms_exponent(double mx) { return (mx > 0.0 && isfinite(mx)) ? ilogb(mx) : 0; }
+
+template <int DP>
+__device__ __forceinline__ int ms_rescale(double (&v)[DP]) {
+  double mx = 0.0;
+#pragma unroll
+  for (int a = 0; a < DP; ++a) mx = fmax(mx, fabs(v[a]));
+  const int e = ms_exponent(mx);
+#pragma unroll
+  for (int a = 0; a < DP; ++a) v[a] = ldexp(v[a], -e);
+  return e;
+}
+
+// A_k[s] zero-padded to DP x DP in LDS, As[s][a][b]; optionally a D x D matrix M the same way
+template <int DP>
+__device__ __forceinline__ void ms_load_site(const double* cores, int k, int D, double* As, const double* M, double* Ms) {
+  const double* A = cores + (long long)(k - 1) * 2 * D * D;
+  for (int i = threadIdx.x; i < 2 * DP * DP; i += MS_LANES) {
+    const int s = i / (DP * DP), a = (i / DP) % DP, b = i % DP;
+    As[i] = (a < D && b < D) ? A[(s * D + a) * D + b] : 0.0;
+  }
+  if (M)
+    for (int i = threadIdx.x; i < DP * DP; i += MS_LANES) {
+      const int a = i / DP, b = i % DP;
+      Ms[i] = (a < D && b < D) ? M[a * D + b] : 0.0;
+    }
+}
+
+// ---- environments ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(ENV_THREADS) void mps_env_kernel(const double* __restrict__ cores, int n, int D, double* __restrict__ E,
+                                                              double* __restrict__ L, int* __restrict__ eE, int* __restrict__ eL,
+                                                              double* __restrict__ hdr, double* __restrict__ logZ_out) {
+  __shared__ double As[2 * MS_DMAX * MS_DMAX];
+  __shared__ double X[MS_DMAX * MS_DMAX];
+  __shared__ double T[2 * MS_DMAX * MS_DMAX];
+  __shared__ double red[ENV_THREADS / 64];
+  const bool right = blockIdx.x == 0;
+  double* out = right ? E : L;
+  int* eo = right ? eE : eL;
+  const int DD = D * D, t = threadIdx.x;
+  for (int i = t; i < DD; i += ENV_THREADS) {
+    X[i] = i == 0 ? 1.0 : 0.0;
+    out[(long long)(right ? n : 0) * DD + i] = X[i];
+  }
+  if (t == 0) eo[right ? n : 0] = 0;
+  int ex = 0;
+  for (int step = 0; step < n; ++step) {
+    const int k = right ? n - step : step + 1;       // the site whose matrices this step uses
+    const int dst = right ? k - 1 : k;
+    __syncthreads();
+    for (int i = t; i < 2 * DD; i += ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+    __syncthreads();
+    for (int i = t; i < 2 * DD; i += ENV_THREADS) {
+      const int s = i / DD, a = (i % DD) / D, d = i % D;
+      double acc = 0.0;
+      for (int c = 0; c < D; ++c) acc = fma(right ? As[s * DD + a * D + c] : As[s * DD + c * D + a], X[c * D + d], acc);
+      T[i] = acc;
+    }
+    __syncthreads();
+    double v[4];
+    double mx = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = t + ENV_THREADS * j;
+      v[j] = 0.0;
+      if (i < DD) {
+        const int a = i / D, b = i % D;
+        double acc = 0.0;
+        for (int s = 0; s < 2; ++s)
+          for (int d = 0; d < D; ++d) acc = fma(T[s * DD + a * D + d], right ? As[s * DD + b * D + d] : As[s * DD + d * D + b], acc);
+        v[j] = acc;
+        mx = fmax(mx, fabs(acc));
+      }
+    }
+    mx = ms_wave_max(mx);
+    if ((t & 63) == 0) red[t >> 6] = mx;
+    __syncthreads();
+    mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    const int e = ms_exponent(mx);
+    ex += e;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = t + ENV_THREADS * j;
+      if (i < DD) {
+        const double x = ldexp(v[j], -e);
+        X[i] = x;
+        out[(long long)dst * DD + i] = x;
+      }
+    }
+    if (t == 0) eo[dst] = ex;
+  }
+  __syncthreads();
+  if (right && t == 0) {
+    const double Zh = X[0];
+    const double lz = log(Zh) + (double)ex * MS_LN2;
+    hdr[0] = lz;
+    hdr[1] = Zh;
+    hdr[2] = (double)ex;
+    if (logZ_out) logZ_out[0] = lz;
+  }
+}
+
+// ---- status word -----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void ms_clear_status_kernel(int* status) {
+  if (threadIdx.x == 0) *status = 0;
+}
+
+// ---- sampler ---------------------------------------------------------------------------------------------------
+template <int DP>
+__global__ __launch_bounds__(MS_LANES) void mps_sample_kernel(const double* __restrict__ cores, int n, int D, long long B,
+                                                              const double* __restrict__ E, const double* __restrict__ hdr,
+                                                              uint32_t seed_lo, uint32_t seed_hi,
+                                                              const long long* __restrict__ epoch_dev, long long* __restrict__ idx,
+                                                              double* __restrict__ logq, int* status) {
+  __shared__ double As[2 * DP * DP];
+  __shared__ double Es[DP * DP];
+  const long long b = (long long)blockIdx.x * MS_LANES + threadIdx.x;
+  const bool active = b < B;
+  const uint32_t ep = (uint32_t)(unsigned long long)(*epoch_dev);
+  double l[DP];
+#pragma unroll
+  for (int a = 0; a < DP; ++a) l[a] = a == 0 ? 1.0 : 0.0;
+  int el = 0;
+  unsigned long long z = 0;
+  bool dead = false;
+  uint4 w = make_uint4(0, 0, 0, 0);
+#pragma unroll 1
+  for (int k = 1; k <= n; ++k) {
+    __syncthreads();
+    ms_load_site<DP>(cores, k, D, As, E + (long long)k * D * D, Es);
+    __syncthreads();
+    if (k & 1) w = philox4x32_10(make_uint4((uint32_t)b, (uint32_t)((k + 1) / 2 - 1), MS_PHILOX_DOMAIN, ep), seed_lo, seed_hi);
+    const double U = (k & 1) ? unit53(w.x, w.y) : unit53(w.z, w.w);
+    double u0[DP], u1[DP];
+#pragma unroll
+    for (int c = 0; c < DP; ++c) {
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int a = 0; a < DP; ++a) {
+        a0 = fma(l[a], As[a * DP + c], a0);
+        a1 = fma(l[a], As[DP * DP + a * DP + c], a1);
+      }
+      u0[c] = a0;
+      u1[c] = a1;
+    }
+    double m0 = 0.0, m1 = 0.0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+        const double e = Es[c * DP + d];
+        t0 = fma(u0[c], e, t0);
+        t1 = fma(u1[c], e, t1);
+      }
+      m0 = fma(t0, u0[d], m0);
+      m1 = fma(t1, u1[d], m1);
+    }
+    const double tot = m0 + m1;
+    if (!dead && !(tot > 0.0 && isfinite(tot))) {
+      dead = true;
+      if (active) *status = 1;
+    }
+    const bool bit = !dead && (U * tot >= m0);
+    z = (z << 1) | (bit ? 1ull : 0ull);
+#pragma unroll
+    for (int a = 0; a < DP; ++a) l[a] = bit ? u1[a] : u0[a];
+    el += ms_rescale<DP>(l);
+  }
+  if (active) {
+    idx[b] = (long long)z;
+    logq[b] = dead ? __builtin_nan("") : (2.0 * log(fabs(l[0])) - log(hdr[1])) + (2.0 * (double)el - hdr[2]) * MS_LN2;
+  }
+}
+
+// ---- score gradient --------------------------------------------------------------------------------------------
+template <int DP>
+__global__ __launch_bounds__(MS_LANES) void mps_score_kernel(const double* __restrict__ cores, int n, int D, int DS, long long B,
+                                                             long long ntiles, const long long* __restrict__ idx,
+                                                             const double* __restrict__ wgt, const double* __restrict__ hdr,
+                                                             double* __restrict__ logq, int* status, double* rws, int* erws,
+                                                             double* parts, double* __restrict__ wpart) {
+  constexpr int NT = DP > 16 ? 2 : 1;
+  constexpr int XP = 16 * NT + 1;            // row pitch of X in LDS (odd: the lanes' rows start in different banks)
+  __shared__ double As[2 * DP * DP];
+  __shared__ double Xs[MS_LANES * XP];
+  __shared__ int Zs[MS_LANES];
+  const int lane = threadIdx.x, fr = lane & 15, fk = lane >> 4;
+  double* rsl = rws + (size_t)blockIdx.x * n * MS_LANES * DS;
+  int* esl = erws + (size_t)blockIdx.x * n * MS_LANES;
+  double* part = parts + (size_t)blockIdx.x * n * 2 * D * D;
+  const double Zh = hdr[1], eE0 = hdr[2];
+  const bool Zok = Zh > 0.0 && isfinite(Zh);
+  double wacc = 0.0;
+  bool first = true;
+#pragma unroll 1
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x, first = false) {
+    const long long b = tile * MS_LANES + lane;
+    const bool active = b < B;
+    const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
+    const double wv = active ? wgt[b] : 0.0;
+    wacc += ms_wave_sum(wv);
+    // right to left: r_k for k = n - 1 .. 0
+    double r[DP];
+#pragma unroll
+    for (int a = 0; a < DP; ++a) r[a] = a == 0 ? 1.0 : 0.0;
+    int er = 0;
+#pragma unroll 1
+    for (int k = n; k >= 1; --k) {
+      if (k < n) {
+        double* dst = rsl + ((size_t)k * MS_LANES + lane) * DS;
+#pragma unroll
+        for (int a = 0; a < DP; ++a)
+          if (a < DS) dst[a] = r[a];
+        esl[k * MS_LANES + lane] = er;
+      }
+      __syncthreads();
+      ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
+      __syncthreads();
+      const double* Az = As + (int)((z >> (n - k)) & 1ull) * DP * DP;
+      double rn[DP];
+#pragma unroll
+      for (int a = 0; a < DP; ++a) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < DP; ++c) acc = fma(Az[a * DP + c], r[c], acc);
+        rn[a] = acc;
+      }
+#pragma unroll
+      for (int a = 0; a < DP; ++a) r[a] = rn[a];
+      er += ms_rescale<DP>(r);
+    }
+    const double r0 = r[0];
+    const int er0 = er;
+    const bool good = r0 != 0.0 && isfinite(r0) && Zok;
+    if (active) {
+      logq[b] = (2.0 * log(fabs(r0)) - log(Zh)) + (2.0 * (double)er0 - eE0) * MS_LN2;
+      if (!good) *status = 2;
+    }
+    const double g = good ? (wv + wv) / r0 : 0.0;
+    // left to right
+    double l[DP];
+#pragma unroll
+    for (int a = 0; a < DP; ++a) l[a] = a == 0 ? 1.0 : 0.0;
+    int el = 0;
+#pragma unroll 1
+    for (int k = 1; k <= n; ++k) {
+      __syncthreads();
+      ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
+      const int s = (int)((z >> (n - k)) & 1ull);
+      const int erk = k < n ? esl[k * MS_LANES + lane] : 0;
+      const double cf = ldexp(g, el + erk - er0);
+#pragma unroll
+      for (int a = 0; a < DP; ++a) Xs[lane * XP + a] = cf * l[a];
+      Zs[lane] = s;
+      __syncthreads();
+      ms_d4 acc[2][NT][NT];
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+          for (int tb = 0; tb < NT; ++tb) acc[q][ta][tb] = (ms_d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+      for (int kk = 0; kk < MS_LANES / 4; ++kk) {
+        const int bb = 4 * kk + fk;
+        const int sb = Zs[bb];
+        double av[NT], bv[NT];
+#pragma unroll
+        for (int ta = 0; ta < NT; ++ta) {
+          const int col = ta * 16 + fr;
+          av[ta] = col < D ? Xs[bb * XP + col] : 0.0;
+        }
+#pragma unroll
+        for (int tb = 0; tb < NT; ++tb) {
+          const int col = tb * 16 + fr;
+          if (k < n) bv[tb] = col < D ? rsl[((size_t)k * MS_LANES + bb) * DS + col] : 0.0;
+          else bv[tb] = col == 0 ? 1.0 : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+          for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+            for (int tb = 0; tb < NT; ++tb)
+              acc[q][ta][tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(sb == q ? av[ta] : 0.0, bv[tb], acc[q][ta][tb], 0, 0, 0);
+      }
+      // D[row = fk + 4 i][col = fr] of tile (ta, tb): entry (a = 16 ta + fk + 4 i, b = 16 tb + fr)
+      double* pk = part + (size_t)(k - 1) * 2 * D * D;
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+          for (int tb = 0; tb < NT; ++tb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int ar = ta * 16 + fk + 4 * i, bc = tb * 16 + fr;
+              if (ar < D && bc < D) {
+                double* p = pk + (q * D + ar) * D + bc;
+                *p = first ? acc[q][ta][tb][i] : *p + acc[q][ta][tb][i];
+              }
+            }
+      // l_k = l_{k-1} A_k[z_k]
+      const double* Az = As + s * DP * DP;
+      double ln[DP];
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+        double a0 = 0.0;
+#pragma unroll
+        for (int a = 0; a < DP; ++a) a0 = fma(l[a], Az[a * DP + c], a0);
+        ln[c] = a0;
+      }
+#pragma unroll
+      for (int a = 0; a < DP; ++a) l[a] = ln[a];
+      el += ms_rescale<DP>(l);
+    }
+  }
+  if (lane == 0) wpart[blockIdx.x] = wacc;
+}
+
+// grid n: grad[k - 1] = the workgroups' partials in order - (sum_b w_b) 2 L_{k-1} A_k[s] E_k / Z
+__global__ __launch_bounds__(ENV_THREADS) void mps_score_finish_kernel(const double* __restrict__ cores, int n, int D, int G,
+                                                                       const double* __restrict__ parts,
+                                                                       const double* __restrict__ wpart, const double* __restrict__ E,
+                                                                       const double* __restrict__ L, const int* __restrict__ eE,
+                                                                       const int* __restrict__ eL, const double* __restrict__ hdr,
+                                                                       double* __restrict__ grad) {
+  __shared__ double As[2 * MS_DMAX * MS_DMAX];
+  __shared__ double Em[MS_DMAX * MS_DMAX];
+  __shared__ double Lm[MS_DMAX * MS_DMAX];
+  __shared__ double T[2 * MS_DMAX * MS_DMAX];
+  __shared__ double red[ENV_THREADS / 64];
+  const int k = blockIdx.x + 1, t = threadIdx.x, DD = D * D;
+  double wv = 0.0;
+  for (int i = t; i < G; i += ENV_THREADS) wv += wpart[i];
+  wv = ms_wave_sum(wv);
+  if ((t & 63) == 0) red[t >> 6] = wv;
+  for (int i = t; i < 2 * DD; i += ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+  for (int i = t; i < DD; i += ENV_THREADS) {
+    Em[i] = E[(long long)k * DD + i];
+    Lm[i] = L[(long long)(k - 1) * DD + i];
+  }
+  __syncthreads();
+  const double W = ((red[0] + red[1]) + red[2]) + red[3];
+  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
+    const int s = i / DD, c = (i % DD) / D, d = i % D;
+    double acc = 0.0;
+    for (int e = 0; e < D; ++e) acc = fma(As[s * DD + c * D + e], Em[e * D + d], acc);
+    T[i] = acc;
+  }
+  __syncthreads();
+  const int ex = eL[k - 1] + eE[k] - eE[0];
+  const double Zh = hdr[1];
+  const size_t stride = (size_t)n * 2 * DD;
+  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
+    const int s = i / DD, a = (i % DD) / D, d = i % D;
+    double m = 0.0;
+    for (int c = 0; c < D; ++c) m = fma(Lm[a * D + c], T[s * DD + c * D + d], m);
+    double sum = 0.0;
+    const double* p = parts + (size_t)(k - 1) * 2 * DD + i;
+    for (int g = 0; g < G; ++g) sum += p[g * stride];
+    const double env = ldexp(m / Zh, ex);
+    grad[(size_t)(k - 1) * 2 * DD + i] = sum - W * (env + env);
+  }
+}
+
+// ---- log joint of samples --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bn_logjoint_kernel(bornvi_bn_desc bn, int n, long long B, const long long* __restrict__ idx,
+                                                          double p_floor, double* __restrict__ logp) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long z = (unsigned long long)idx[b];
+  unsigned long long vals = 0;   // bit v = value of node v
+  bool bad = false;
+  for (int v = 0; v < bn.num_nodes; ++v) {
+    const int role = bn.role[v];
+    unsigned long long bit = 0ull;
+    if (role >= 0 && role < n) bit = (z >> (n - 1 - role)) & 1ull;
+    else if (role == -2) bit = 1ull;
+    else if (role != -1) bad = true;           // a summed-out node: the host refuses it where it can look
+    vals |= bit << v;
+  }
+  double sum = 0.0;
+  for (int v = 0; v < bn.num_nodes; ++v) {
+    int cfg = 0;
+    const int np = bn.n_parents[v];
+    for (int p = 0; p < np; ++p) cfg = cfg * 2 + (int)((vals >> bn.parents[v * bn.max_parents + p]) & 1ull);
+    sum += log(fmax(bn.cpt[bn.cpt_off[v] + 2 * cfg + (int)((vals >> v) & 1ull)], p_floor));
+  }
+  logp[b] = bad ? __builtin_nan("") : sum;
+}
+
+#define MS_DISPATCH(DPV, CALL)                        \
+  switch (DPV) {                                      \
+    case 2: { constexpr int DP = 2; CALL; } break;    \
+    case 4: { constexpr int DP = 4; CALL; } break;    \
+    case 8: { constexpr int DP = 8; CALL; } break;    \
+    case 16: { constexpr int DP = 16; CALL; } break;  \
+    default: { constexpr int DP = 32; CALL; } break;  \
+  }
+}  // namespace
+
+size_t mps_sample_workspace_bytes(int n, int D, long long B) { return ms_layout(n, D, B).total + 256; }
+
+hipError_t launch_mps_environments(int n, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st) {
+  const MsLayout S = ms_layout(n, D, B);
+  char* base = ms_align((char*)ws);
+  mps_env_kernel<<<2, ENV_THREADS, 0, st>>>(cores, n, D, (double*)(base + S.E), (double*)(base + S.L), (int*)(base + S.eE),
+                                           (int*)(base + S.eL), (double*)(base + S.hdr), logZ_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, unsigned long long seed, const long long* epoch_dev,
+                             long long* idx, double* logq, int* status, void* ws, hipStream_t st) {
+  const MsLayout S = ms_layout(n, D, B);
+  char* base = ms_align((char*)ws);
+  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const unsigned grid = (unsigned)((B + MS_LANES - 1) / MS_LANES);
+  MS_DISPATCH(S.DP, (mps_sample_kernel<DP><<<grid, MS_LANES, 0, st>>>(cores, n, D, B, (const double*)(base + S.E),
+                                                                      (const double*)(base + S.hdr), (uint32_t)seed,
+                                                                      (uint32_t)(seed >> 32), epoch_dev, idx, logq, status)));
+  return hipGetLastError();
+}
+
+hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
+                                double* grad_cores, int* status, void* ws, hipStream_t st) {
+  const MsLayout S = ms_layout(n, D, B);
+  char* base = ms_align((char*)ws);
+  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const long long ntiles = (B + MS_LANES - 1) / MS_LANES;
+  MS_DISPATCH(S.DP, (mps_score_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
+                        cores, n, D, S.DS, B, ntiles, idx, w, (const double*)(base + S.hdr), logq, status, (double*)(base + S.r),
+                        (int*)(base + S.er), (double*)(base + S.parts), (double*)(base + S.wpart))));
+  mps_score_finish_kernel<<<(unsigned)n, ENV_THREADS, 0, st>>>(cores, n, D, S.G, (const double*)(base + S.parts),
+                                                              (const double*)(base + S.wpart), (const double*)(base + S.E),
+                                                              (const double*)(base + S.L), (const int*)(base + S.eE),
+                                                              (const int*)(base + S.eL), (const double*)(base + S.hdr), grad_cores);
+  return hipGetLastError();
+}
+
+hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
+                                      hipStream_t st) {
+  bn_logjoint_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(bn, n, B, idx, p_floor, logp);
+  return hipGetLastError();
+}
+
+}  // namespace bornvi

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "philox_dev.hpp"
 
 namespace bornvi {
 
@@ -27,22 +28,6 @@ namespace {
 constexpr int SH_BLOCK_BITS = 12, SH_BLOCK = 1 << SH_BLOCK_BITS;
 constexpr int SH_THREADS = 512, SH_EPT = SH_BLOCK / SH_THREADS;     // draw kernel: 8 consecutive entries per thread in the scan
 constexpr int SM_THREADS = 256, SM_EPT = SH_BLOCK / SM_THREADS;     // mass kernel
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-    const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
-__device__ __forceinline__ double unit53(uint32_t lo, uint32_t hi) {
-  return (double)((((uint64_t)hi << 32) | lo) >> 11) * 0x1p-53;
-}
 
 // global circuit id of batch row r in the layout of bornvi_paramshift_probs_strided: base = 0, +p = 2p + 1, -p = 2p + 2
 __device__ __forceinline__ uint32_t circuit_id(long long r, int include_base, int p_begin, int p_stride) {
