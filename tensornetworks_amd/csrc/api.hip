@@ -1316,7 +1316,7 @@ int bornvi_paramshift_states(bornvi_handle h, int ansatz, int n, int layers, con
   if (bc_max > rows) bc_max = rows;
   if (bc_max > 65535) bc_max = 65535;  // gridDim.y
   if (bc_max < 1) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small for one circuit");
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* base = ws_align(workspace);
   const size_t th_bytes = align_up((size_t)bc_max * p.n_params * 8, 256);
   const size_t gates_bytes = align_up((size_t)bc_max * gate_slots(p) * 64, 256);
   const size_t state_bytes = align_up((size_t)bc_max * ((size_t)16 << n), 256);

@@ -1,11 +1,35 @@
-// Launchers implemented in kernels_circuit.hip / kernels_stein.hip, called from api.hip.
+// Launchers implemented in the kernels_*.hip files and called from api.hip, and the host helpers those files share
+// (workspace alignment, raising a kernel's dynamic-LDS limit once per device).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 
 #include "bornvi.h"
 
 namespace bornvi {
+
+// ---- workspaces and launch helpers ---------------------------------------------------------------
+// Every launcher carves its caller's workspace from the first 256-byte boundary on, in 256-byte pieces.
+inline size_t ws_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+inline char* ws_align(void* p) { return (char*)ws_round((size_t)(uintptr_t)p); }
+// More than 64 KiB of dynamic LDS needs the kernel's attribute raised, once per device (idempotent, so a race between two
+// threads' first calls is harmless).  Later calls -- the ones a stream capture may record -- touch no function attribute.
+// One LdsRaised object per kernel, at namespace scope.
+constexpr int MAX_DEVICES = 64;
+struct LdsRaised {
+  std::atomic<unsigned char> done[MAX_DEVICES];
+};
+inline hipError_t raise_lds_once(const void* fn, size_t bytes, LdsRaised& r) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const bool known = dev >= 0 && dev < MAX_DEVICES;
+  if (known && r.done[dev].load(std::memory_order_acquire)) return hipSuccess;
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess && known) r.done[dev].store(1, std::memory_order_release);
+  return e;
+}
 
 // ---- circuit ------------------------------------------------------------------------------------
 // Prefix sharing inside a parameter-shift batch (api.hip: circuit_batch): the circuits of the batch are ordered by

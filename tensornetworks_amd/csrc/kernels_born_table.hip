@@ -333,7 +333,6 @@ __global__ __launch_bounds__(BT_THREADS) void born_table_vjp_kernel(const float*
   }
 }
 
-char* bt_align(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 }  // namespace
 
 size_t born_table_workspace_bytes(int n, long long rows) {
@@ -346,7 +345,7 @@ hipError_t launch_born_table_probs(int n, long long rows, int mode, const float*
   const long long N = 1ll << n;
   const BtGeom gm = bt_geom(N);
   const int vec = (N % 4 == 0) && ((((uintptr_t)w) | ((uintptr_t)q32) | ((uintptr_t)q64)) & 15) == 0;
-  double* part = (double*)bt_align(ws);
+  double* part = (double*)ws_align(ws);
   double* hpart = H ? part + 2 * rows * gm.G : nullptr;
   const dim3 grid((unsigned)gm.G, (unsigned)rows);
   born_table_stats_kernel<<<grid, BT_THREADS, 0, st>>>(w, N, gm.chunk, mode, vec, part);
@@ -361,7 +360,7 @@ hipError_t launch_born_table_vjp(int n, long long rows, int mode, const float* w
   const BtGeom gm = bt_geom(N);
   const int vec = (N % 4 == 0) &&
                   ((((uintptr_t)w) | ((uintptr_t)q64) | ((uintptr_t)y) | ((uintptr_t)grad)) & 15) == 0;
-  double* part = (double*)bt_align(ws);
+  double* part = (double*)ws_align(ws);
   const dim3 grid((unsigned)gm.G, (unsigned)rows);
   born_table_vjp_stats_kernel<<<grid, BT_THREADS, 0, st>>>(w, q64, y, ksd2, lam, N, gm.chunk, mode, vec, part);
   born_table_vjp_kernel<<<grid, BT_THREADS, 0, st>>>(w, q64, y, ksd2, lam, N, gm.chunk, mode, vec, part, grad, loss_out);

@@ -123,7 +123,6 @@ __global__ __launch_bounds__(EL_THREADS) void elbo_finish_kernel(const double* _
   }
 }
 
-char* el_align(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 }  // namespace
 
 size_t elbo_workspace_bytes(int n, long long rows) {
@@ -136,7 +135,7 @@ hipError_t launch_elbo_weights(int n, long long rows, const double* q, const dou
   const long long N = 1ll << n;
   const ElGeom gm = el_geom(N);
   const int vec = (N % 2 == 0) && ((((uintptr_t)q) | ((uintptr_t)log_p) | ((uintptr_t)w)) & 15) == 0;
-  double* part = (double*)el_align(ws);
+  double* part = (double*)ws_align(ws);
   elbo_weights_kernel<<<dim3((unsigned)gm.G, (unsigned)rows), EL_THREADS, 0, st>>>(q, log_p, N, gm.chunk, vec, q_floor, w, part);
   elbo_finish_kernel<<<dim3((unsigned)rows), EL_THREADS, 0, st>>>(part, gm.G, neg_elbo, entropy);
   return hipGetLastError();

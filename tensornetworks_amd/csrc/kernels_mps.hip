@@ -27,7 +27,7 @@
 //   Last level: psi(2p + s) = V_{n-1}[p, :] . A_n[s][:, 0] and the workgroup's partial of Z; a second launch adds the Z
 //   partials (every workgroup adds all of them in the same fixed order) and writes q = psi^2 / Z.
 // Every long sum is fixed-order partials plus a finishing step: no atomics, two calls are bitwise equal.  No allocation, no
-// synchronisation (capturable).  Fragment layout of the f64 MFMA as in kernels_fisher.hip.
+// synchronisation (capturable).  Fragment layout of the f64 MFMA as in syrk_f64.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -479,8 +479,6 @@ __global__ __launch_bounds__(MPS_THREADS) void mps_finish_kernel(const double* _
   }
 }
 
-char* mps_align(char* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
-
 struct MpsLayout {
   int DP, DS;
   size_t hdr, zpart, cpart, psi, V, Ga, Gb, parts, total;   // byte offsets from the aligned base
@@ -490,17 +488,16 @@ MpsLayout mps_layout(int n, int D) {
   MpsLayout L;
   L.DP = D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32;
   L.DS = (D + 1) & ~1;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t N = (size_t)1 << n;
   size_t o = 0;
   L.hdr = o;   o += 256;
-  L.zpart = o; o += up(MPS_MAX_PART * sizeof(double));
-  L.cpart = o; o += up(MPS_MAX_PART * sizeof(double));
-  L.psi = o;   o += up(N * sizeof(double));
-  L.V = o;     o += up((size_t)L.DS * (N - 1) * sizeof(double) + 16);           // V_0 .. V_{n-1}
-  L.Ga = o;    o += up((size_t)L.DS * (N / 2) * sizeof(double) + 16);           // G_{n-1}, G_{n-3}, ...
-  L.Gb = o;    o += up((size_t)L.DS * (N / 4) * sizeof(double) + 16);           // G_{n-2}, G_{n-4}, ...
-  L.parts = o; o += up((size_t)mps_part_off(n + 1, n, D) * sizeof(double));
+  L.zpart = o; o += ws_round(MPS_MAX_PART * sizeof(double));
+  L.cpart = o; o += ws_round(MPS_MAX_PART * sizeof(double));
+  L.psi = o;   o += ws_round(N * sizeof(double));
+  L.V = o;     o += ws_round((size_t)L.DS * (N - 1) * sizeof(double) + 16);           // V_0 .. V_{n-1}
+  L.Ga = o;    o += ws_round((size_t)L.DS * (N / 2) * sizeof(double) + 16);           // G_{n-1}, G_{n-3}, ...
+  L.Gb = o;    o += ws_round((size_t)L.DS * (N / 4) * sizeof(double) + 16);           // G_{n-2}, G_{n-4}, ...
+  L.parts = o; o += ws_round((size_t)mps_part_off(n + 1, n, D) * sizeof(double));
   L.total = o;
   return L;
 }
@@ -520,7 +517,7 @@ size_t mps_workspace_bytes(int n, int D) { return mps_layout(n, D).total + 256; 
 hipError_t launch_mps_probs(int n, int D, const double* cores, double* q64, float* q32, double* psi_out, double* Z_out, void* ws,
                             hipStream_t st) {
   const MpsLayout L = mps_layout(n, D);
-  char* base = mps_align((char*)ws);
+  char* base = ws_align(ws);
   double* hdr = (double*)(base + L.hdr);
   double* zpart = (double*)(base + L.zpart);
   double* psi = (double*)(base + L.psi);
@@ -548,7 +545,7 @@ hipError_t launch_mps_probs(int n, int D, const double* cores, double* q64, floa
 
 hipError_t launch_mps_vjp(int n, int D, const double* cores, const double* g, double* grad_cores, void* ws, hipStream_t st) {
   const MpsLayout L = mps_layout(n, D);
-  char* base = mps_align((char*)ws);
+  char* base = ws_align(ws);
   const double* hdr = (const double*)(base + L.hdr);
   double* cpart = (double*)(base + L.cpart);
   const double* psi = (const double*)(base + L.psi);

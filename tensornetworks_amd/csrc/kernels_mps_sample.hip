@@ -70,22 +70,19 @@ MsLayout ms_layout(int n, int D, long long B) {
   S.DS = (D + 1) & ~1;
   const long long tiles = (B + MS_LANES - 1) / MS_LANES;
   S.G = (int)(tiles < MS_MAX_WG ? tiles : MS_MAX_WG);
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   size_t o = 0;
   S.hdr = o;   o += 256;                                                     // log Z, E^_0[0, 0], eE[0]
-  S.E = o;     o += up((size_t)(n + 1) * D * D * sizeof(double));
-  S.L = o;     o += up((size_t)(n + 1) * D * D * sizeof(double));
-  S.eE = o;    o += up((size_t)(n + 1) * sizeof(int));
-  S.eL = o;    o += up((size_t)(n + 1) * sizeof(int));
-  S.r = o;     o += up((size_t)S.G * n * MS_LANES * S.DS * sizeof(double));   // slot k of a slice: r^_k, k = 1 .. n - 1
-  S.er = o;    o += up((size_t)S.G * n * MS_LANES * sizeof(int));
-  S.parts = o; o += up((size_t)S.G * n * 2 * D * D * sizeof(double));
-  S.wpart = o; o += up((size_t)MS_MAX_WG * sizeof(double));
+  S.E = o;     o += ws_round((size_t)(n + 1) * D * D * sizeof(double));
+  S.L = o;     o += ws_round((size_t)(n + 1) * D * D * sizeof(double));
+  S.eE = o;    o += ws_round((size_t)(n + 1) * sizeof(int));
+  S.eL = o;    o += ws_round((size_t)(n + 1) * sizeof(int));
+  S.r = o;     o += ws_round((size_t)S.G * n * MS_LANES * S.DS * sizeof(double));   // slot k of a slice: r^_k, k = 1 .. n - 1
+  S.er = o;    o += ws_round((size_t)S.G * n * MS_LANES * sizeof(int));
+  S.parts = o; o += ws_round((size_t)S.G * n * 2 * D * D * sizeof(double));
+  S.wpart = o; o += ws_round((size_t)MS_MAX_WG * sizeof(double));
   S.total = o;
   return S;
 }
-
-char* ms_align(char* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
 __device__ __forceinline__ double ms_wave_sum(double v) {
 #pragma unroll
@@ -506,7 +503,7 @@ size_t mps_sample_workspace_bytes(int n, int D, long long B) { return ms_layout(
 
 hipError_t launch_mps_environments(int n, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
-  char* base = ms_align((char*)ws);
+  char* base = ws_align(ws);
   mps_env_kernel<<<2, ENV_THREADS, 0, st>>>(cores, n, D, (double*)(base + S.E), (double*)(base + S.L), (int*)(base + S.eE),
                                            (int*)(base + S.eL), (double*)(base + S.hdr), logZ_out);
   return hipGetLastError();
@@ -515,7 +512,7 @@ hipError_t launch_mps_environments(int n, int D, long long B, const double* core
 hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, unsigned long long seed, const long long* epoch_dev,
                              long long* idx, double* logq, int* status, void* ws, hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
-  char* base = ms_align((char*)ws);
+  char* base = ws_align(ws);
   ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -529,7 +526,7 @@ hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, uns
 hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
                                 double* grad_cores, int* status, void* ws, hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
-  char* base = ms_align((char*)ws);
+  char* base = ws_align(ws);
   ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

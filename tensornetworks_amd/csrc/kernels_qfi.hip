@@ -13,27 +13,23 @@
 //
 // ---- bornvi_qfi_gram: Q_ab = Re<phi_a|phi_b> - Re(conj(c_a) c_b), c_a = <psi|phi_a>.  A complex128 row of 2^n amplitudes
 // is a real row of K = 2^(n+1) doubles, Re<phi_a|phi_b> the real dot product of two such rows, Re c_a the dot product
-// with psi and Im c_a the one with i psi = (-Im psi, Re psi): ONE real split-K SYRK on v_mfma_f64_16x16x4_f64 over
-// R = P + 2 rows (phi_0 .. phi_{P-1}, psi, i psi), grid (upper-triangle tile pairs) x (G groups of k-slabs):
-//   output tile 128 x 128 per workgroup of 4 waves (2 x 2; a wave owns 64 x 64 = 4 x 4 MFMA tiles: one ds_read_b64 feeds
-//   two MFMAs, 128 accumulator registers; with the operands of a whole k-step in flight the kernel takes 256 VGPRs +
-//   228 AGPRs, ONE wave per SIMD -- held to two waves it spills 84 registers or more, so it is not);
-//   a slab is at most 4096 columns (geometry: qg_geom); k-step 16, LDS double-buffered, one barrier per k-step, the next
-//   k-step's rows in flight in registers during the MFMAs (16-byte loads: 8 per thread and k-step);
-//   NOTHING is computed on the way into LDS: the rows go in as they are (row i psi: the pair exchanged and one sign
-//   flipped, exact), so a product carries the rounding of the product alone;
-//   LDS rows padded to 18 doubles as in kernels_fisher.hip (conflict-free ds_read_b64): 2 x 2 x 128 x 18 x 8 = 72 KiB.
-// Each slab starts from a zero accumulator; after a slab the workgroup adds its accumulators to ITS partial tile in the
-// workspace (first slab: stores them) -- the running total lives in the workspace (L2), not in 128 more registers --
-// and qfi_finish_kernel adds the G partial tiles of an entry in index order, forms the projection term from the sums
-// of the entries (a, psi), (a, i psi), (b, psi), (b, i psi) (recomputed per workgroup, from the same partials in the same
-// order: the same bits everywhere) and writes Q_ab and Q_ba from the same value.  No atomics; bitwise reproducible;
-// Q == Q^T bitwise.  Fragment layout of the f64 MFMA as in kernels_fisher.hip.
+// with psi and Im c_a the one with i psi = (-Im psi, Re psi): ONE real SYRK over R = P + 2 rows (phi_0 .. phi_{P-1}, psi,
+// i psi) -- the split-K SYRK of syrk_f64.hpp (layout, barriers, order of the sums: there; this kernel writes split_k's
+// slab loop out and shares the rest), with
+//   output tile 128 x 128 (a wave owns 64 x 64 = 4 x 4 MFMA tiles: one ds_read_b64 feeds two MFMAs, 128 accumulator
+//   registers; with the operands of a whole k-step in flight the kernel takes 256 VGPRs + 228 AGPRs, ONE wave per SIMD
+//   -- held to two waves it spills 84 registers or more, so it is not);
+//   what goes into LDS: the rows as they are (row i psi: the pair exchanged and one sign flipped, exact), so a product
+//   carries the rounding of the product alone; 8 16-byte loads per thread and k-step; 2 x 2 x 128 x 18 x 8 = 72 KiB;
+//   the running total over a workgroup's slabs in ITS partial tile in the workspace (first slab: stores, later slabs:
+//   adds) -- in L2, not in 128 more registers;
+//   a finisher, qfi_finish_kernel, that forms the projection term from the sums of the entries (a, psi), (a, i psi),
+//   (b, psi), (b, i psi) (recomputed per workgroup, from the same partials in the same order: the same bits everywhere)
+//   and writes Q_ab and Q_ba from the same value.  No atomics; bitwise reproducible; Q == Q^T bitwise.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "kernels.hpp"
+#include "syrk_f64.hpp"
 
 namespace bornvi {
 
@@ -68,46 +64,23 @@ __global__ __launch_bounds__(256) void state_tail_kernel(const qs_d2* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ QFI Gram
-constexpr int QG_T = 128, QG_BK = 16, QG_PITCH = 18, QG_THREADS = 256;
-constexpr int QG_SLAB_MAX = 4096, QG_GROUPS = 64;
-typedef double qg_d4 __attribute__((ext_vector_type(4)));
-typedef double qg_d2 __attribute__((ext_vector_type(2)));
-
-struct QgGeom {
-  long long K;         // real columns: 2^(n+1)
-  long long slab;      // columns per slab (<= 4096)
-  long long per_wg;    // slabs a workgroup adds up one after the other
-  int G;               // workgroups along k = partial tiles per entry
-  int T;               // 128-row tiles per side over R = P + 2 rows
-  int tiles;           // T (T + 1) / 2
-};
-
-QgGeom qg_geom(int n, int P) {
-  QgGeom g;
-  g.K = 2ll << n;
-  g.slab = g.K <= 256 ? g.K : (g.K / 64 < 256 ? 256 : (g.K / 64 > QG_SLAB_MAX ? QG_SLAB_MAX : g.K / 64));
-  const long long nslab = g.K / g.slab;
-  const long long gmax = nslab / 1024 > QG_GROUPS ? nslab / 1024 : QG_GROUPS;     // (per_wg <= 1024)
-  g.G = (int)(nslab < gmax ? nslab : gmax);
-  g.per_wg = nslab / g.G;
-  g.T = (P + 2 + QG_T - 1) / QG_T;
-  g.tiles = g.T * (g.T + 1) / 2;
-  return g;
-}
+constexpr int QG_MT = 4, QG_T = 32 * QG_MT;                           // wave tile 4 x 4 MFMA tiles, workgroup tile 128 x 128
+using syrk::d2;
 
 // grid (tiles, G).  part[(g * tiles + tile) * 16384 + row * 128 + col].  Row r of the SYRK: r < P: phi row r; r == P:
-// psi; r == P + 1: i psi; beyond: zero.
-__global__ __launch_bounds__(QG_THREADS) void qfi_gram_kernel(const double* __restrict__ phi, const double* __restrict__ psi,
+// psi; r == P + 1: i psi; beyond: zero.  The slab loop is syrk::split_k's, written out: through the template and a row
+// source the compiler took four more AGPRs (232) and bornvi_qfi_gram measured 0.6 % slower at n = 20, outside the span
+// of two runs of the hand-written loop.
+__global__ __launch_bounds__(syrk::THREADS) void qfi_gram_kernel(const double* __restrict__ phi, const double* __restrict__ psi,
                                                               long long K, int P, int T, long long slab, long long per_wg,
                                                               double* __restrict__ part) {
   extern __shared__ double qg_lds[];
-  double* __restrict__ As = qg_lds;                                    // [2][QG_T][QG_PITCH]
-  double* __restrict__ Bs = As + 2 * QG_T * QG_PITCH;                  // [2][QG_T][QG_PITCH]
+  double* __restrict__ As = qg_lds;                                    // [2][QG_T][syrk::PITCH]
+  double* __restrict__ Bs = As + 2 * QG_T * syrk::PITCH;               // [2][QG_T][syrk::PITCH]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wi = wave & 1, wj = wave >> 1;
-  int ti = 0, rem = blockIdx.x;                                       // tile pair (ti <= tj) number blockIdx.x, row by row
-  while (rem >= T - ti) { rem -= T - ti; ++ti; }
-  const int tj = ti + rem;
+  int ti, tj;
+  syrk::tile_pair(blockIdx.x, T, ti, tj);
   const int lrow = t >> 3, lk = (t & 7) * 2;
   // the thread's 4 rows of each side: pointer (null: a zero row) and whether the row is i psi
   const double* ag[4];
@@ -121,27 +94,27 @@ __global__ __launch_bounds__(QG_THREADS) void qfi_gram_kernel(const double* __re
     arot[u] = ra == P + 1;
     brot[u] = rb == P + 1;
   }
-  const long long len16 = (slab + QG_BK - 1) / QG_BK * QG_BK;         // (a slab shorter than a k-step: n <= 2)
-  const long long nk = len16 / QG_BK;
-  const qg_d2 zero2 = (qg_d2){0.0, 0.0};
-  qg_d2 av[4], bv[4];
+  const long long len16 = (slab + syrk::BK - 1) / syrk::BK * syrk::BK;         // (a slab shorter than a k-step: n <= 2)
+  const long long nk = len16 / syrk::BK;
+  const d2 zero2 = (d2){0.0, 0.0};
+  d2 av[4], bv[4];
 #define QG_LOAD_TILES(z0, k0)                                                                \
   {                                                                                          \
     const bool zok = (k0) + lk < slab;                                                       \
     const long long zoff = (z0) + (k0);                                                      \
     _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                          \
-      av[u] = (zok && ag[u]) ? *reinterpret_cast<const qg_d2*>(ag[u] + zoff) : zero2;        \
-      bv[u] = (zok && bg[u]) ? *reinterpret_cast<const qg_d2*>(bg[u] + zoff) : zero2;        \
+      av[u] = (zok && ag[u]) ? *reinterpret_cast<const d2*>(ag[u] + zoff) : zero2;           \
+      bv[u] = (zok && bg[u]) ? *reinterpret_cast<const d2*>(bg[u] + zoff) : zero2;           \
     }                                                                                        \
   }
   // (i psi)[2 z] = -Im psi_z, (i psi)[2 z + 1] = Re psi_z: lk is even, so a thread's pair is one amplitude
 #define QG_STORE_TILES(buf)                                                                  \
   {                                                                                          \
     _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                          \
-      const qg_d2 a = arot[u] ? (qg_d2){-av[u].y, av[u].x} : av[u];                          \
-      const qg_d2 b = brot[u] ? (qg_d2){-bv[u].y, bv[u].x} : bv[u];                          \
-      *reinterpret_cast<qg_d2*>(As + (((buf) * QG_T + lrow + 32 * u) * QG_PITCH + lk)) = a;  \
-      *reinterpret_cast<qg_d2*>(Bs + (((buf) * QG_T + lrow + 32 * u) * QG_PITCH + lk)) = b;  \
+      const d2 a = arot[u] ? (d2){-av[u].y, av[u].x} : av[u];                                \
+      const d2 b = brot[u] ? (d2){-bv[u].y, bv[u].x} : bv[u];                                \
+      *reinterpret_cast<d2*>(As + (((buf) * QG_T + lrow + 32 * u) * syrk::PITCH + lk)) = a;  \
+      *reinterpret_cast<d2*>(Bs + (((buf) * QG_T + lrow + 32 * u) * syrk::PITCH + lk)) = b;  \
     }                                                                                        \
   }
   const int fr = lane & 15, fk = lane >> 4;
@@ -155,29 +128,18 @@ __global__ __launch_bounds__(QG_THREADS) void qfi_gram_kernel(const double* __re
     // (the previous slab's last k-step ended with a barrier: nobody reads the tiles any more)
     QG_STORE_TILES(0)
     __syncthreads();
-    qg_d4 acc[4][4];
+    syrk::d4 acc[4][4];
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (qg_d4){0.0, 0.0, 0.0, 0.0};
+      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (syrk::d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
     for (long long kt = 0; kt < nk; ++kt) {
       const int cur = (int)(kt & 1);
-      if (kt + 1 < nk) QG_LOAD_TILES(z0, (kt + 1) * QG_BK)            // in flight during this k-step's MFMAs
-      const double* __restrict__ Ac = As + (cur * QG_T + wi * 64 + fr) * QG_PITCH + fk;
-      const double* __restrict__ Bc = Bs + (cur * QG_T + wj * 64 + fr) * QG_PITCH + fk;
-#pragma unroll
-      for (int ks = 0; ks < QG_BK / 4; ++ks) {
-        double a[4], b[4];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) a[mi] = Ac[mi * 16 * QG_PITCH + ks * 4];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) b[ni] = Bc[ni * 16 * QG_PITCH + ks * 4];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-      }
+      if (kt + 1 < nk) QG_LOAD_TILES(z0, (kt + 1) * syrk::BK)            // in flight during this k-step's MFMAs
+      const double* __restrict__ Ac = As + (cur * QG_T + wi * 64 + fr) * syrk::PITCH + fk;
+      const double* __restrict__ Bc = Bs + (cur * QG_T + wj * 64 + fr) * syrk::PITCH + fk;
+      syrk::mfma_k_step<QG_MT>(Ac, Bc, acc);
       if (kt + 1 < nk) QG_STORE_TILES(cur ^ 1)
       __syncthreads();
     }
@@ -200,52 +162,32 @@ __global__ __launch_bounds__(QG_THREADS) void qfi_gram_kernel(const double* __re
 
 // grid (tiles): Q_ab = Q_ba = (the G partials of entry (a <= b) in index order) - (re_a re_b + im_a im_b), re_a / im_a
 // the sums of the entries (a, P) / (a, P + 1), which lie in the upper triangle too (a < P).
-__global__ __launch_bounds__(QG_THREADS) void qfi_finish_kernel(const double* __restrict__ part, int P, int T, int G,
-                                                                double* __restrict__ Q) {
+__global__ __launch_bounds__(syrk::THREADS) void qfi_finish_kernel(const double* __restrict__ part, int P, int T, int G,
+                                                                   double* __restrict__ Q) {
   __shared__ double proj[2][2][QG_T];                                  // [side: rows of ti / of tj][re / im][row]
-  int ti = 0, rem = blockIdx.x;
-  while (rem >= T - ti) { rem -= T - ti; ++ti; }
-  const int tj = ti + rem;
+  int ti, tj;
+  syrk::tile_pair(blockIdx.x, T, ti, tj);
   const long long stride = (long long)gridDim.x * (QG_T * QG_T);
-  for (int e = threadIdx.x; e < 2 * 2 * QG_T; e += QG_THREADS) {
+  for (int e = threadIdx.x; e < 2 * 2 * QG_T; e += syrk::THREADS) {
     const int side = e / (2 * QG_T), c = (e / QG_T) & 1, row = e % QG_T;
     const int tr = side ? tj : ti, a = tr * QG_T + row, col = P + c;
-    double sum = 0.0;
-    if (a < P) {
-      const int tc = col / QG_T;                                       // (tc >= tr: col >= P > a)
-      const long long tile = (long long)tr * T - (long long)tr * (tr - 1) / 2 + (tc - tr);
-      const double* __restrict__ ps = part + tile * (QG_T * QG_T) + row * QG_T + col % QG_T;
-      for (int g = 0; g < G; ++g) sum += ps[g * stride];
-    }
+    double sum = 0.0;                                                  // (the tile of (a, col) is in the triangle: col >= P > a)
+    if (a < P) sum = syrk::sum_partials(part + syrk::tile_pair_index(tr, col / QG_T, T) * (QG_T * QG_T) + row * QG_T + col % QG_T, G, stride);
     proj[side][c][row] = sum;
   }
   __syncthreads();
   const double* __restrict__ pt = part + (long long)blockIdx.x * (QG_T * QG_T);
-  for (int e = threadIdx.x; e < QG_T * QG_T; e += QG_THREADS) {
+  for (int e = threadIdx.x; e < QG_T * QG_T; e += syrk::THREADS) {
     const int ra = e / QG_T, rb = e % QG_T;
     const int a = ti * QG_T + ra, b = tj * QG_T + rb;
     if (a >= P || b >= P || a > b) continue;
-    double sum = 0.0;
-    for (int g = 0; g < G; ++g) sum += pt[g * stride + e];
-    const double q = sum - (proj[0][0][ra] * proj[1][0][rb] + proj[0][1][ra] * proj[1][1][rb]);
+    const double q = syrk::sum_partials(pt + e, G, stride) - (proj[0][0][ra] * proj[1][0][rb] + proj[0][1][ra] * proj[1][1][rb]);
     Q[(long long)a * P + b] = q;
     Q[(long long)b * P + a] = q;
   }
 }
 
-// More than 64 KiB of dynamic LDS needs the kernel's attribute raised, once per device (as in kernels_fisher.hip).
-constexpr int QG_MAX_DEVICES = 64;
-std::atomic<unsigned char> qg_lds_done[QG_MAX_DEVICES];
-hipError_t qg_allow_lds(size_t bytes) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const bool known = dev >= 0 && dev < QG_MAX_DEVICES;
-  if (known && qg_lds_done[dev].load(std::memory_order_acquire)) return hipSuccess;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(qfi_gram_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess && known) qg_lds_done[dev].store(1, std::memory_order_release);
-  return e;
-}
+LdsRaised qg_lds_raised;
 }  // namespace
 
 hipError_t launch_pi_shift_thetas(const double* theta, int P, int row0, int include_base, int p_begin, int bc, double* thetas,
@@ -264,21 +206,18 @@ hipError_t launch_state_tail(const double* in, double* out, int n, int bc, const
   return hipGetLastError();
 }
 
-size_t qfi_workspace_bytes(int n, int P) {
-  const QgGeom g = qg_geom(n, P);
-  return (size_t)g.G * g.tiles * QG_T * QG_T * sizeof(double) + 512;
-}
+size_t qfi_workspace_bytes(int n, int P) { return syrk::workspace_bytes(syrk::geom(2ll << n, P + 2, QG_T), QG_T); }
 
 hipError_t launch_qfi_gram(int n, int P, const double* phi, const double* psi, double* Q, void* ws, hipStream_t st) {
-  const QgGeom g = qg_geom(n, P);
-  const size_t lds = (size_t)(4 * QG_T * QG_PITCH) * sizeof(double);
-  hipError_t e = qg_allow_lds(lds);
+  const syrk::Geom g = syrk::geom(2ll << n, P + 2, QG_T);             // a complex row: K = 2^(n+1) real columns
+  const size_t lds = syrk::tiles_lds_bytes(QG_T);
+  hipError_t e = raise_lds_once(reinterpret_cast<const void*>(qfi_gram_kernel), lds, qg_lds_raised);
   if (e != hipSuccess) return e;
-  double* part = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  qfi_gram_kernel<<<dim3((unsigned)g.tiles, (unsigned)g.G), QG_THREADS, lds, st>>>(phi, psi, g.K, P, g.T, g.slab, g.per_wg, part);
+  double* part = (double*)ws_align(ws);
+  qfi_gram_kernel<<<dim3((unsigned)g.tiles, (unsigned)g.G), syrk::THREADS, lds, st>>>(phi, psi, 2ll << n, P, g.T, g.slab, g.per_wg, part);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  qfi_finish_kernel<<<dim3((unsigned)g.tiles), QG_THREADS, 0, st>>>(part, P, g.T, g.G, Q);
+  qfi_finish_kernel<<<dim3((unsigned)g.tiles), syrk::THREADS, 0, st>>>(part, P, g.T, g.G, Q);
   return hipGetLastError();
 }
 

@@ -239,7 +239,6 @@ __global__ __launch_bounds__(RF_THREADS) void reinforce_loss_kernel(const double
   }
 }
 
-char* rf_align(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 }  // namespace
 
 size_t reinforce_workspace_bytes(int n, long long B) {
@@ -252,7 +251,7 @@ hipError_t launch_reinforce_step(int n, long long B, const long long* idx, const
                                  double* dLdq, float* loss, float* found_inf, void* ws, hipStream_t st) {
   const long long N = 1ll << n;
   const RfGeom gs = rf_geom(B, RF_SAMPLES_PER_WG), gz = rf_geom(N, RF_OUTCOMES_PER_WG);
-  char* w = rf_align(ws);
+  char* w = ws_align(ws);
   RfScalars* sc = (RfScalars*)w;
   double* part = (double*)(w + 256);
   double* lpart = part + 2 * gs.G;

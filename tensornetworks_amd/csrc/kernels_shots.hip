@@ -173,11 +173,11 @@ hipError_t launch_shots_histogram(int n, long long B, const double* probs, doubl
   const int L = shot_levels(n, lens);
   double* masses[8] = {nullptr};
   int* counts[8] = {nullptr};
-  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  char* w = ws_align(ws);
   for (int l = 1; l < L; ++l) {
     masses[l] = (double*)w;
     counts[l] = (int*)(w + (size_t)B * lens[l] * sizeof(double));
-    w += ((size_t)B * lens[l] * (sizeof(double) + sizeof(int)) + 255) & ~(size_t)255;
+    w += ws_round((size_t)B * lens[l] * (sizeof(double) + sizeof(int)));
   }
   const uint32_t slo = (uint32_t)seed, shi = (uint32_t)(seed >> 32);
   for (int l = 0; l + 1 < L; ++l) {

@@ -81,10 +81,13 @@ def arithmetic(kind=None):
     return _MpMath()
 
 
-def unavailable(n, X=None):
-    """None, or the reason a case of size n is left out (printed by the test that skips it)."""
+def unavailable(n, X=None, longdouble_max_n=None):
+    """None, or the reason a case of size n is left out (printed by the test that skips it).  max_n of the long-double
+    arithmetic is sized for the Stein references, which hold 4^n entries; a caller whose reference costs less (a Gram of
+    P rows of 2^n columns) names its own limit under long double with longdouble_max_n."""
     X = X or arithmetic()
-    if n > X.max_n:
+    limit = longdouble_max_n if longdouble_max_n is not None and X.name == "longdouble" else X.max_n
+    if n > limit:
         return f"long double unavailable (np.longdouble eps {np.finfo(LD).eps:.3g}); {X.name} covers n <= {X.max_n} only"
     return None
 
@@ -130,6 +133,23 @@ def measured_constant(oracle_ratio, derived):
     an N-term sum grow like sqrt(N), so a small integer factor separates correct orders from each other, while a
     dropped or misplaced term shows up as 1e3 ... 1e15."""
     return float(min(max(16.0, 8.0 * float(oracle_ratio)), float(derived)))
+
+
+# ------------------------------------------------------------------------------------------------ split-K SYRK
+def syrk_geometry(K):
+    """(slab, per_wg, G) of the Fisher / QFI Gram kernels over K columns (csrc/syrk_f64.hpp: geom): a slab is K columns up
+    to 256, else K / 64 clamped to [256, 4096]; G = min(K / slab, max(64, K / slab / 1024)) workgroups along the columns,
+    each adding per_wg = K / slab / G slabs one after the other."""
+    slab = K if K <= 256 else min(4096, max(256, K // 64))
+    nslab = K // slab
+    G = min(nslab, max(64, nslab // 1024))
+    return slab, nslab // G, G
+
+
+def syrk_chain(K):
+    """C_CHAIN of one entry, units of EPS64: at most `slab` additions on a path inside a slab's MFMAs, then the per_wg slab
+    results and the G partial tiles in order, half a unit each."""
+    return sum(syrk_geometry(K)) / 2.0
 
 
 # ------------------------------------------------------------------------------------------------ Gram

@@ -13,9 +13,10 @@ errs by at most 1/2):  |F_ab - ref| <= eps (C_TERM + C_CHAIN) sum_z |d_a d_b| r_
   C_CHAIN = (slab + per_wg + G) / 2: every slab starts from a zero accumulator and its MFMAs add at most `slab` products
       one after the other (whatever order the matrix core uses inside one instruction, a path holds no more additions than
       products); the workgroup then adds its per_wg slab results in order, and the finishing launch the G partial tiles in
-      index order.  slab, per_wg and G are fg_geom's: slab = N up to 256 entries, else N / 64 clamped to [256, 4096];
-      G = min(N / slab, max(64, N / slab / 1024)); per_wg = N / slab / G.  Largest case here (n = 13):
-      (256 + 1 + 32) / 2 = 144.5; the largest the library accepts (n = 30): (4096 + 1024 + 256) / 2 = 2688; C_TERM + C_CHAIN
+      index order.  slab, per_wg and G are syrk::geom's: slab = N up to 256 entries, else N / 64 clamped to [256, 4096];
+      G = min(N / slab, max(64, N / slab / 1024)); per_wg = N / slab / G (hp_reference.syrk_geometry).  n = 13:
+      (256 + 1 + 32) / 2 = 144.5; the largest case here (n = 19, the first with per_wg = 2): (4096 + 2 + 64) / 2 = 2081;
+      the largest the library accepts (n = 30): (4096 + 1024 + 256) / 2 = 2688; C_TERM + C_CHAIN
       stays under the cap 8 + 4096 for every n.
 The float64 mirror (natgrad_mirror.py) is held to the same bound on the same inputs, on the CPU."""
 import numpy as np
@@ -27,25 +28,22 @@ import natgrad_mirror as nm
 
 Q_FLOOR = 1e-10
 C_TERM = 3.0
-SHAPES = [(1, 1), (3, 2), (2, 5), (17, 5), (17, 13), (65, 9), (130, 9), (288, 9)]      # (n_shift, n)
+SHAPES = [(1, 1), (3, 2), (2, 5), (17, 5), (17, 13), (65, 9), (130, 9), (288, 9), (2, 19)]      # (n_shift, n)
+LONGDOUBLE_MAX_N = 20       # the long-double reference costs P^2 2^n products: seconds at the largest shape here
 
 
 def geometry(n):
-    N = 1 << n
-    slab = N if N <= 256 else min(4096, max(256, N // 64))
-    nslab = N // slab
-    G = min(nslab, max(64, nslab // 1024))
-    return slab, nslab // G, G
+    return hp.syrk_geometry(1 << n)
 
 
 def c_chain(n):
-    slab, per_wg, G = geometry(n)
-    return (slab + per_wg + G) / 2.0
+    return hp.syrk_chain(1 << n)
 
 
 def test_constants_stay_under_the_cap():
     assert all(C_TERM + c_chain(n) <= 8 + 4096 for n in range(1, 31))
     assert c_chain(13) == 144.5 and c_chain(30) == 2688.0 and geometry(9) == (256, 1, 2) and geometry(5) == (32, 1, 1)
+    assert geometry(18) == (4096, 1, 64) and geometry(19) == (4096, 2, 64) and c_chain(19) == 2081.0
 
 
 _cache = {}
@@ -74,8 +72,9 @@ def inputs(P, n):
 
 def check(F, P, n, what):
     shifted, q, ref, bound, X = inputs(P, n)
-    if hp.unavailable(n, X):
-        pytest.skip(hp.unavailable(n, X))
+    why = hp.unavailable(n, X, longdouble_max_n=LONGDOUBLE_MAX_N)
+    if why:
+        pytest.skip(why)
     c = C_TERM + c_chain(n)
     r = hp.worst(hp.ratio(F, ref, bound, X=X))
     print(f"{what} P={P} n={n}: worst ratio {r[0]:.3f} / {c} at {r[1]}")

@@ -14,9 +14,10 @@ S_a^im the same against i psi, and S^p_ab = S_a^re S_b^re + S_a^im S_b^im:
       subtraction's rounding, at most 1/2 eps |Q_ab| <= 1/2 eps (S_ab + S^p_ab).
   C_CHAIN = (slab + per_wg + G) / 2: every slab starts from a zero accumulator and its MFMAs add at most `slab` products on
       a path; the workgroup adds its per_wg slab results to its partial tile in order, the finishing launch the G partial
-      tiles in index order.  qg_geom: slab = K up to 256 columns, else K / 64 clamped to [256, 4096];
-      G = min(K / slab, max(64, K / slab / 1024)); per_wg = K / slab / G.  Largest case here (n = 13):
-      (256 + 1 + 64) / 2 = 160.5; the largest the library accepts (n = 30): (4096 + 1024 + 512) / 2 = 2816.
+      tiles in index order.  syrk::geom: slab = K up to 256 columns, else K / 64 clamped to [256, 4096];
+      G = min(K / slab, max(64, K / slab / 1024)); per_wg = K / slab / G (hp_reference.syrk_geometry).  n = 13:
+      (256 + 1 + 64) / 2 = 160.5; the largest case here (n = 18, the first with per_wg = 2): (4096 + 2 + 64) / 2 = 2081;
+      the largest the library accepts (n = 30): (4096 + 1024 + 512) / 2 = 2816.
   Projection: each of re_a, im_a is such a sum (relative error (C_TERM + C_CHAIN) eps of its S), a product of two carries
       both factors' errors -- the factor 2 --, and C_PROJ = 2 covers the product's rounding (1/2), the sum of the two
       products (1/2), the final subtraction's share (1/2) and the second-order terms.
@@ -31,25 +32,24 @@ import qng_mirror as qm
 
 C_TERM, C_PROJ = 1.0, 2.0
 PS, NS = (1, 2, 17, 64, 65, 288), (1, 3, 9, 13)
-SHAPES = [(P, n) for n in NS for P in PS]
+# (127, 3): R = 129 rows, psi is the last row of tile 0 and i psi the first of tile 1 -- the projection columns come from two
+# tiles; (2, 18): the first n with per_wg = 2
+SHAPES = [(P, n) for n in NS for P in PS] + [(127, 3), (2, 18)]
+LONGDOUBLE_MAX_N = 20       # the long-double reference costs P^2 2^n products: seconds at the largest shape here
 
 
 def geometry(n):
-    K = 2 << n
-    slab = K if K <= 256 else min(4096, max(256, K // 64))
-    nslab = K // slab
-    G = min(nslab, max(64, nslab // 1024))
-    return slab, nslab // G, G
+    return hp.syrk_geometry(2 << n)
 
 
 def c_chain(n):
-    slab, per_wg, G = geometry(n)
-    return (slab + per_wg + G) / 2.0
+    return hp.syrk_chain(2 << n)
 
 
 def test_constants():
     assert geometry(1) == (4, 1, 1) and geometry(9) == (256, 1, 4) and geometry(13) == (256, 1, 64)
-    assert c_chain(13) == 160.5 and c_chain(30) == 2816.0
+    assert geometry(3) == (16, 1, 1) and geometry(17) == (4096, 1, 64) and geometry(18) == (4096, 2, 64)
+    assert c_chain(13) == 160.5 and c_chain(18) == 2081.0 and c_chain(30) == 2816.0
     assert all(C_TERM + c_chain(n) <= 8 + 4096 for n in range(1, 31))
 
 
@@ -91,8 +91,9 @@ def reference_rows(P, n):
 
 def check(Q, P, n, what):
     phi, psi, ref, S, Sp, X, rows = inputs(P, n)
-    if hp.unavailable(n, X):
-        pytest.skip(hp.unavailable(n, X))
+    why = hp.unavailable(n, X, longdouble_max_n=LONGDOUBLE_MAX_N)
+    if why:
+        pytest.skip(why)
     c = C_TERM + c_chain(n)
     bound = S * X.num(c) + Sp * X.num(2 * c + C_PROJ)
     r = hp.worst(hp.ratio(np.asarray(Q)[rows], ref, bound, X=X))
