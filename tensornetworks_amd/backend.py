@@ -578,15 +578,23 @@ MPS_MAX_N = 26
 MPS_MAX_BOND = 32
 
 
-def _mps_args(cores):
-    """(n, D) of cores [n, 2, D, D]; every argument error is raised here, before any GPU call."""
+_ENUMERATED = object()
+
+
+def _mps_args(cores, num_samples=_ENUMERATED):
+    """(n, D) of cores [n, 2, D, D] for the enumerated calls (n <= MPS_MAX_N), or (n, D, B) with a sample count for the
+    sampled ones (n <= MPS_SAMPLED_MAX_N); every argument error is raised here, before any GPU call."""
     if not torch.is_tensor(cores) or cores.dim() != 4 or cores.shape[1] != 2 or cores.shape[2] != cores.shape[3]:
         raise BornviError(f"cores: expected an [n, 2, D, D] tensor, got {tuple(cores.shape) if torch.is_tensor(cores) else type(cores)}")
-    n, D = int(cores.shape[0]), int(cores.shape[2])
-    _chk_n(n, 1, MPS_MAX_N)
+    n, D, B = int(cores.shape[0]), int(cores.shape[2]), num_samples
+    _chk_n(n, 1, MPS_MAX_N if B is _ENUMERATED else MPS_SAMPLED_MAX_N)
     if not 1 <= D <= MPS_MAX_BOND:
         raise BornviError(f"cores: bond dimension 1 ... {MPS_MAX_BOND}, got {D}")
-    return n, D
+    if B is _ENUMERATED:
+        return n, D
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MPS_SAMPLED_MAX_BATCH:
+        raise BornviError(f"number of samples: 1 ... 2^24 per call, got {B!r}")
+    return n, D, int(B)
 
 
 def mps_probs(cores, want_q32=True, want_psi=False):
@@ -630,19 +638,6 @@ MPS_SAMPLED_MAX_N = 63
 MPS_SAMPLED_MAX_BATCH = 1 << 24
 
 
-def _mps_sampled_args(cores, B):
-    """(n, D, B) of cores [n, 2, D, D] and a sample count; every argument error is raised here, before any GPU call."""
-    if not torch.is_tensor(cores) or cores.dim() != 4 or cores.shape[1] != 2 or cores.shape[2] != cores.shape[3]:
-        raise BornviError(f"cores: expected an [n, 2, D, D] tensor, got {tuple(cores.shape) if torch.is_tensor(cores) else type(cores)}")
-    n, D = int(cores.shape[0]), int(cores.shape[2])
-    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
-    if not 1 <= D <= MPS_MAX_BOND:
-        raise BornviError(f"cores: bond dimension 1 ... {MPS_MAX_BOND}, got {D}")
-    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MPS_SAMPLED_MAX_BATCH:
-        raise BornviError(f"number of samples: 1 ... 2^24 per call, got {B!r}")
-    return n, D, int(B)
-
-
 def _mps_sampled_ws(h, dev, n, D, B):
     """One workspace per (n, D, B) and stream: mps_environments leaves the environments in it for the two calls after it."""
     return _ws(dev, _cached_size(h, "bornvi_mps_sample_workspace_bytes", n, D, B), f"mps_sampled_{n}_{D}_{B}")
@@ -652,7 +647,7 @@ def mps_environments(cores, num_samples):
     """Left and right environments of an MPS and log Z (bornvi_mps_environments): cores float64 [n, 2, D, D] on the GPU,
     1 <= n <= 63 -> log Z float64 [1].  The environments stay in the cached workspace of (n, D, num_samples) for
     mps_sample and mps_score_vjp: call those next, with the same cores and sample count, on this stream."""
-    n, D, B = _mps_sampled_args(cores, num_samples)
+    n, D, B = _mps_args(cores, num_samples)
     dev = cores.device
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")
@@ -667,7 +662,7 @@ def mps_sample(cores, num_samples, seed, epoch, out_idx=None, out_logq=None, sta
     -> (idx int64 [B] outcome indices, logq float64 [B] = log q(idx), status int32 [1]: 0, or 1 when a sample met
     conditional masses summing to 0 or a non-finite number).  Draw k of sample b is a pure function of (seed, epoch, b, k).
     epoch: an int64 device tensor [1] (read by the kernel: a captured graph sees its value at replay time)."""
-    n, D, B = _mps_sampled_args(cores, num_samples)
+    n, D, B = _mps_args(cores, num_samples)
     dev = cores.device
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")
@@ -698,7 +693,7 @@ def mps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
     logq float64 [B], status int32 [1]: 0, or 2 when some psi(idx_b) is 0 or not finite).  out: destination of grad."""
     if not torch.is_tensor(idx) or idx.dim() != 1:
         raise BornviError("idx: expected a [B] int64 tensor")
-    n, D, B = _mps_sampled_args(cores, int(idx.numel()))
+    n, D, B = _mps_args(cores, int(idx.numel()))
     dev = cores.device
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")

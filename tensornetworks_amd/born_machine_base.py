@@ -1,0 +1,185 @@
+"""What the classical Born-machine families have in common: the table / MLP machine (born_machine_classical_sim.py), the MPS
+machine (born_machine_mps.py) and the sampled MPS machine (born_machine_mps_sampled.py).
+
+  indices_to_bits / bits_to_indices   outcome index <-> bit row (tuple position 0 = the most significant bit), with the
+                                      validation of bit rows and its message; exact up to n = 63 (shifts reach 1 << 62)
+  EnumeratedBornMachine               the surface over the 2^n table of q that the classical trainers use: fixed
+                                      probabilities, all_outcome_tuples, sample, get_prob_dict, get_log_q_z_x, entropy.
+                                      A family supplies how q is computed (_probabilities, _entropy) and its two ends of a
+                                      training epoch: epoch_forward -> EpochForward, epoch_backward -> (loss, grads)
+  new_mps_cores / MPSCores            the MPS families' constructor checks, initialisations and move to the compute device
+"""
+import math
+from typing import Any, NamedTuple, Optional
+
+import torch
+import torch.nn as nn
+
+from . import backend
+from .utils import generate_all_binary_outcomes
+
+
+def indices_to_bits(idx, n):
+    """float32 bit rows [..., n] of int64 outcome indices [...]."""
+    shifts = torch.arange(n - 1, -1, -1, device=idx.device)
+    return ((idx.unsqueeze(-1) >> shifts) & 1).to(torch.float32)
+
+
+def bits_to_indices(z_samples, n, device=None):
+    """int64 outcome indices [B] (on `device`; default: where the rows are) of bit rows [B, n].  `.long()` truncates like
+    the reference's; a row with an entry other than 0 or 1, or an input that is not [B, n], raises."""
+    z = z_samples.detach().to(device=device).long()
+    row = None
+    if z.dim() != 2 or z.shape[1] != n:
+        row = z[0] if z.dim() >= 2 else z.reshape(-1)
+    else:
+        bad = ((z != 0) & (z != 1)).any(dim=1)
+        if bool(bad.any()):
+            row = z[int(torch.nonzero(bad)[0])]
+    if row is not None:
+        raise ValueError(f"Sample {tuple(row.tolist())} is not a valid outcome.")
+    return (z << torch.arange(n - 1, -1, -1, device=z.device)).sum(dim=1)
+
+
+class EpochForward(NamedTuple):
+    """What a family's epoch_forward hands the trainer, and the trainer hands back to epoch_backward."""
+    q32: torch.Tensor                   # [2^n] float32
+    q64: torch.Tensor                   # [2^n] float64, on the compute device: what the objective contracts
+    entropy: Optional[torch.Tensor]     # [1] = -sum q log max(q, 1e-10), or None when not asked for
+    state: Any                          # the family's own: what its backward needs
+
+
+class EnumeratedBornMachine(nn.Module):
+    """Born machine whose q is a table over the 2^n latent states."""
+    draws_in_forward = False            # True: a forward draws random numbers (Dropout), so two forwards differ
+
+    def __init__(self, num_latent_vars, conditioning_dim=0):
+        super().__init__()
+        self.num_latent_vars = num_latent_vars
+        self.num_outcomes = 2 ** num_latent_vars
+        self.conditioning_dim = conditioning_dim
+        self._fixed_probs = None
+        self._use_fixed_probs = False
+        self._outcomes = None
+
+    # ---- what a family supplies ------------------------------------------------------------------------------
+    def _probabilities(self, x_condition):
+        """float32 [B, 2^n] on the parameters' device, differentiable."""
+        raise NotImplementedError
+
+    def _entropy(self, x_condition):
+        raise NotImplementedError
+
+    def epoch_forward(self, x_condition, want_entropy):
+        """-> EpochForward of the current parameters; nothing is read back to the host."""
+        raise NotImplementedError
+
+    def epoch_backward(self, fwd, y, ksd2=None, entropy_weight=0.0):
+        """(loss, grads) of L = sqrt(max(ksd2, 1e-12)) - entropy_weight * H with y = K_p q (no gradient below the clamp),
+        or, with ksd2 = None, of a loss whose dL/dq is y (loss = None): backend.born_table_vjp's arguments.  grads =
+        [(tensor, its gradient), ...] for the trainers' apply_grads."""
+        raise NotImplementedError
+
+    # ---- the shared surface --------------------------------------------------------------------------------------
+    @property
+    def all_outcome_tuples(self):
+        """generate_all_binary_outcomes(n), built on first use (2^n Python tuples that no hot path needs)."""
+        if self._outcomes is None:
+            self._outcomes = generate_all_binary_outcomes(self.num_latent_vars)
+        return self._outcomes
+
+    def set_fixed_probs(self, prob_tensor):
+        """From now on get_probabilities returns (a copy of) this tensor."""
+        self._fixed_probs = prob_tensor.detach().clone()
+        self._use_fixed_probs = True
+
+    def clear_fixed_probs(self):
+        self._fixed_probs = None
+        self._use_fixed_probs = False
+
+    def get_probabilities(self, x_condition=None):
+        """float32 [B, 2^n] ([1, 2^n] unconditioned), differentiable; the fixed probabilities when set."""
+        if self._use_fixed_probs and self._fixed_probs is not None:
+            return self._fixed_probs.unsqueeze(0) if self._fixed_probs.ndim == 1 else self._fixed_probs
+        return self._probabilities(x_condition)
+
+    def sample(self, num_samples=1, x_condition=None):
+        """float32 bit rows [num, n], or [B, num, n] for a batch of conditions."""
+        probs = self.get_probabilities(x_condition).detach()
+        probs = probs + 1e-10
+        probs = probs / probs.sum(dim=-1, keepdim=True)
+        batched = probs.shape[0] > 1 or (x_condition is not None and x_condition.ndim > 1)
+        bits = indices_to_bits(torch.multinomial(probs, num_samples, replacement=True), self.num_latent_vars)
+        return bits if batched else bits[0]
+
+    def get_prob_dict(self, x_condition=None):
+        """{outcome tuple: probability} of a single distribution."""
+        probs_tensor = self.get_probabilities(x_condition)
+        if probs_tensor.shape[0] > 1 and not (probs_tensor.ndim == 1 and self.conditioning_dim == 0):
+            raise ValueError("get_prob_dict is for a single distribution.")
+        probs_1d = probs_tensor.squeeze().detach().cpu().numpy().reshape(-1)
+        return dict(zip(self.all_outcome_tuples, probs_1d))
+
+    def get_log_q_z_x(self, z_samples, x_condition=None):
+        """log max(q(z|x), 1e-10) for a batch of bit rows: one x for all rows, or one per row."""
+        if self.conditioning_dim > 0 and x_condition is None:
+            raise ValueError("x_condition must be provided for conditional Born machine.")
+        if self.conditioning_dim == 0 and x_condition is not None:
+            raise ValueError("x_condition provided but Born machine is not conditional.")
+        probs = self.get_probabilities(x_condition)
+        log_probs = torch.log(probs.clamp(min=1e-10))
+        bz, bx = z_samples.shape[0], probs.shape[0]
+        if bx != 1 and bx != bz:
+            raise ValueError(f"Batch size mismatch: x_condition ({bx}) vs z_samples ({bz}).")
+        idx = bits_to_indices(z_samples, self.num_latent_vars, log_probs.device)
+        if bx == 1:
+            return log_probs[0, idx]
+        return log_probs[torch.arange(bz, device=idx.device), idx]
+
+    def entropy(self, x_condition=None):
+        """-sum q log max(q, 1e-10) (a forward of its own, as in the reference), differentiable."""
+        if self._use_fixed_probs and self._fixed_probs is not None:
+            probs = self.get_probabilities(x_condition).squeeze()
+            return -(probs * torch.log(probs.clamp(min=1e-10))).sum()
+        return self._entropy(x_condition)
+
+
+def new_mps_cores(owner, num_latent_vars, bond_dim, init_method, conditioning_dim, max_n):
+    """The float64 parameter [n, 2, D, D] of an MPS machine after its constructor checks (`owner`: the class name in the
+    messages).  'small_random' and 'random' make one torch.randn(n, 2, D, D, dtype=float64) draw, 'zero' none."""
+    if conditioning_dim != 0:
+        raise ValueError(f"{owner} is not conditional: conditioning_dim must be 0.")
+    if isinstance(num_latent_vars, bool) or not isinstance(num_latent_vars, int) or not 1 <= num_latent_vars <= max_n:
+        raise ValueError(f"num_latent_vars must be an integer in 1 ... {max_n}, got {num_latent_vars!r}")
+    if isinstance(bond_dim, bool) or not isinstance(bond_dim, int) or not 1 <= bond_dim <= backend.MPS_MAX_BOND:
+        raise ValueError(f"bond_dim must be an integer in 1 ... {backend.MPS_MAX_BOND}, got {bond_dim!r}")
+    if init_method not in ('small_random', 'zero', 'random'):
+        raise ValueError(f"init_method must be 'small_random', 'zero' or 'random', got {init_method!r}")
+    n, D = num_latent_vars, bond_dim
+    eye = torch.eye(D, dtype=torch.float64).expand(n, 2, D, D)
+    if init_method == 'zero':            # psi(z) = 2^(-n/2) for every z: the exactly uniform q
+        init = eye / math.sqrt(2.0)
+    elif init_method == 'small_random':
+        init = (eye + 0.1 * torch.randn(n, 2, D, D, dtype=torch.float64)) / math.sqrt(2.0)
+    else:
+        init = torch.randn(n, 2, D, D, dtype=torch.float64) / math.sqrt(2.0 * D)
+    return nn.Parameter(init.clone().contiguous())
+
+
+class MPSCores:
+    """Mixin of the two MPS machines: `cores` [n, 2, D, D] float64 (from new_mps_cores) and its way to the kernels."""
+
+    @property
+    def bond_dim(self):
+        return int(self.cores.shape[2])
+
+    @property
+    def num_parameters(self):
+        return self.cores.numel()
+
+    def kernel_input(self, detach=False):
+        """(cores as a contiguous float64 tensor on the compute device -- differentiable unless detach --, the parameter's
+        own device)."""
+        home = self.cores.device
+        cores = self.cores.detach() if detach else self.cores
+        return cores.to(device=backend.compute_device(home), dtype=torch.float64).contiguous(), home

@@ -6,13 +6,15 @@ is where logits -> q happens: one `bornvi_born_table_probs` launch (softmax with
 |w| / sum |w|, plus the entropy when asked for), wrapped in a torch.autograd.Function whose backward is
 `bornvi_born_table_vjp`.  In MLP mode (conditioning_dim > 0) the network itself stays stock torch.nn; only its logits
 go through the kernels.  The kernels run on backend.compute_device(...) and results come back on the parameters'
-device.  Sampling is torch.multinomial plus bit unpacking, log q a vectorised gather: no lookups in 2^n tuples.
+device.  The surface the trainers use (fixed probabilities, sampling by torch.multinomial plus bit unpacking, log q as a
+vectorised gather, the probability dict) is born_machine_base.EnumeratedBornMachine's, shared with the MPS family; this
+file supplies logits -> q and the table's two ends of a training epoch (epoch_forward, epoch_backward).
 """
 import torch
 import torch.nn as nn
 
 from . import backend
-from .utils import generate_all_binary_outcomes
+from .born_machine_base import EnumeratedBornMachine, EpochForward
 
 
 class _TableProbs(torch.autograd.Function):
@@ -50,21 +52,15 @@ class _TableEntropy(torch.autograd.Function):
         return g * grad_h.to(g.dtype), None
 
 
-class ClassicalBornMachine(nn.Module):
+class ClassicalBornMachine(EnumeratedBornMachine):
     """Softmax (use_logits) or abs-normalised probability table over the 2^n latent states, or, with
     conditioning_dim > 0, an MLP of x producing its logits (reference born_machine_classical_sim.py:7-181)."""
 
     def __init__(self, num_latent_vars, use_logits=True, conditioning_dim=0,
                  init_method='small_random', hidden_dims=None, use_layer_norm=False):
-        super().__init__()
-        self.num_latent_vars = num_latent_vars
-        self.num_outcomes = 2 ** num_latent_vars
+        super().__init__(num_latent_vars, conditioning_dim)
         self.use_logits = use_logits
-        self.conditioning_dim = conditioning_dim
         self.use_layer_norm = use_layer_norm
-        self._fixed_probs = None
-        self._use_fixed_probs = False
-        self._outcomes = None
 
         if self.conditioning_dim > 0:
             if hidden_dims is None:
@@ -101,20 +97,9 @@ class ClassicalBornMachine(nn.Module):
         return 0 if self.use_logits else 1
 
     @property
-    def all_outcome_tuples(self):
-        """generate_all_binary_outcomes(n), built on first use (2^n Python tuples that no hot path needs)."""
-        if self._outcomes is None:
-            self._outcomes = generate_all_binary_outcomes(self.num_latent_vars)
-        return self._outcomes
-
-    def set_fixed_probs(self, prob_tensor):
-        """From now on get_probabilities returns (a copy of) this tensor."""
-        self._fixed_probs = prob_tensor.detach().clone()
-        self._use_fixed_probs = True
-
-    def clear_fixed_probs(self):
-        self._fixed_probs = None
-        self._use_fixed_probs = False
+    def draws_in_forward(self):
+        """The MLP's Dropout layers draw in every forward: two forwards are two different samples."""
+        return self.conditioning_dim > 0
 
     def raw_params(self, x_condition=None):
         """The table [1, 2^n] or the network's logits [B, 2^n], with the reference's x_condition checks."""
@@ -133,62 +118,32 @@ class ClassicalBornMachine(nn.Module):
         home = raw.device
         return raw.to(device=backend.compute_device(home), dtype=torch.float32).contiguous(), home
 
-    def get_probabilities(self, x_condition=None):
-        """float32 [B, 2^n] ([1, 2^n] unconditioned), differentiable; the fixed probabilities when set."""
-        if self._use_fixed_probs and self._fixed_probs is not None:
-            return self._fixed_probs.unsqueeze(0) if self._fixed_probs.ndim == 1 else self._fixed_probs
+    def _probabilities(self, x_condition):
         w, home = self.kernel_input(self.raw_params(x_condition))
         return _TableProbs.apply(w, self.born_mode).to(home)
 
-    def sample(self, num_samples=1, x_condition=None):
-        """float32 bit rows [num, n], or [B, num, n] for a batch of conditions."""
-        probs = self.get_probabilities(x_condition).detach()
-        probs = probs + 1e-10
-        probs = probs / probs.sum(dim=-1, keepdim=True)
-        batched = probs.shape[0] > 1 or (x_condition is not None and x_condition.ndim > 1)
-        idx = torch.multinomial(probs, num_samples, replacement=True)            # [B, num]
-        n = self.num_latent_vars
-        shifts = torch.arange(n - 1, -1, -1, device=idx.device)
-        bits = ((idx.unsqueeze(-1) >> shifts) & 1).to(torch.float32)
-        return bits if batched else bits[0]
-
-    def get_prob_dict(self, x_condition=None):
-        """{outcome tuple: probability} of a single distribution."""
-        probs_tensor = self.get_probabilities(x_condition)
-        if probs_tensor.shape[0] > 1 and not (probs_tensor.ndim == 1 and self.conditioning_dim == 0):
-            raise ValueError("get_prob_dict is for a single distribution.")
-        probs_1d = probs_tensor.squeeze().detach().cpu().numpy().reshape(-1)
-        return dict(zip(self.all_outcome_tuples, probs_1d))
-
-    def get_log_q_z_x(self, z_samples, x_condition=None):
-        """log max(q(z|x), 1e-10) for a batch of bit rows: one x for all rows, or one per row."""
-        if self.conditioning_dim > 0 and x_condition is None:
-            raise ValueError("x_condition must be provided for conditional Born machine.")
-        if self.conditioning_dim == 0 and x_condition is not None:
-            raise ValueError("x_condition provided but Born machine is not conditional.")
-        probs = self.get_probabilities(x_condition)
-        log_probs = torch.log(probs.clamp(min=1e-10))
-        bz, bx = z_samples.shape[0], probs.shape[0]
-        if bx != 1 and bx != bz:
-            raise ValueError(f"Batch size mismatch: x_condition ({bx}) vs z_samples ({bz}).")
-        z = z_samples.detach().to(log_probs.device).long()      # `.long()` truncates like the reference's
-        n = self.num_latent_vars
-        if z.dim() == 2 and z.shape[1] == n:
-            bad = ((z != 0) & (z != 1)).any(dim=1)
-        else:
-            bad = torch.ones(bz, dtype=torch.bool, device=z.device)
-        if bool(bad.any()):
-            row = int(torch.nonzero(bad)[0])
-            raise ValueError(f"Sample {tuple(z[row].tolist())} is not a valid outcome.")
-        idx = (z * (1 << torch.arange(n - 1, -1, -1, device=z.device))).sum(dim=1)
-        if bx == 1:
-            return log_probs[0, idx]
-        return log_probs[torch.arange(bz, device=idx.device), idx]
-
-    def entropy(self, x_condition=None):
-        """-sum q log max(q, 1e-10) (a second forward, as in the reference), differentiable."""
-        if self._use_fixed_probs and self._fixed_probs is not None:
-            probs = self.get_probabilities(x_condition).squeeze()
-            return -(probs * torch.log(probs.clamp(min=1e-10))).sum()
+    def _entropy(self, x_condition):
         w, home = self.kernel_input(self.raw_params(x_condition))
         return _TableEntropy.apply(w, self.born_mode).to(home)
+
+    # ---- the two ends of a training epoch: parameters -> q, and dL/dq -> the gradient of the table or of the logits
+    def epoch_forward(self, x_condition, want_entropy):
+        """state = (leaf: the table parameter or the network's logits on the compute device, w: the detached kernel input
+        [1, 2^n], q64 [1, 2^n], home: the table parameter's device or None); the entropy is float32."""
+        if self.conditioning_dim == 0:
+            leaf, home = self.params, self.params.device
+            w = leaf.detach().to(backend.compute_device(home)).reshape(1, -1)
+        else:
+            leaf, home = self.kernel_input(self.raw_params(x_condition))[0], None
+            if leaf.shape[0] != 1:
+                raise ValueError(f"Probabilities shape mismatch: {tuple(leaf.shape)}")
+            w = leaf.detach()
+        q32, q64, H = backend.born_table_probs(w, self.born_mode, want_entropy=want_entropy)
+        return EpochForward(q32[0], q64[0], H, (leaf, w, q64, home))
+
+    def epoch_backward(self, fwd, y=None, ksd2=None, entropy_weight=0.0):
+        leaf, w, q64, home = fwd.state
+        loss = torch.empty(1, dtype=torch.float64, device=w.device) if ksd2 is not None else None
+        g = backend.born_table_vjp(w, q64, self.born_mode, y=y.reshape(1, -1) if y is not None else None, ksd2=ksd2,
+                                   entropy_weight=entropy_weight, loss_out=loss)
+        return loss, [(leaf, g if home is None else g.reshape(leaf.shape).to(home))]

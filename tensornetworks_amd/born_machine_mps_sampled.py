@@ -5,58 +5,36 @@
 An exact draw z ~ q costs O(n D^2) (ancestral sampling against the right environments), and so do log q(z) and
 grad log q(z) for a given z (bornvi_mps_environments / bornvi_mps_sample / bornvi_mps_score_vjp).
 A sample is an int64 outcome index, idx = sum_k z_k 2^(n-k) (tuple position 0 = the most significant bit), or a float32
-bit row.  Same `cores` parameter, initialisations and messages as MPSBornMachine.  For n <= 26 the enumerated q is still
-there (probabilities64 / get_probabilities, through backend.mps_probs); above that those raise.
+bit row; the conversion, like the `cores` parameter, its checks, initialisations and messages, is born_machine_base's, shared
+with MPSBornMachine.  For n <= 26 the enumerated q is still there (probabilities64 / get_probabilities, through
+backend.mps_probs); above that those raise.
 """
-import math
-
 import torch
 import torch.nn as nn
 
 from . import backend
+from .born_machine_base import MPSCores, bits_to_indices, indices_to_bits, new_mps_cores
 from .born_machine_mps import _MPSProbs
 
 
-class SampledMPSBornMachine(nn.Module):
+class SampledMPSBornMachine(MPSCores, nn.Module):
     """MPS Born machine whose surface is samples, log q of samples and the score-function gradient."""
 
     def __init__(self, num_latent_vars, bond_dim=4, init_method='small_random', conditioning_dim=0, seed=0):
-        super().__init__()
-        if conditioning_dim != 0:
-            raise ValueError("SampledMPSBornMachine is not conditional: conditioning_dim must be 0.")
-        if isinstance(num_latent_vars, bool) or not isinstance(num_latent_vars, int) \
-                or not 1 <= num_latent_vars <= backend.MPS_SAMPLED_MAX_N:
-            raise ValueError(f"num_latent_vars must be an integer in 1 ... {backend.MPS_SAMPLED_MAX_N}, got {num_latent_vars!r}")
-        if isinstance(bond_dim, bool) or not isinstance(bond_dim, int) or not 1 <= bond_dim <= backend.MPS_MAX_BOND:
-            raise ValueError(f"bond_dim must be an integer in 1 ... {backend.MPS_MAX_BOND}, got {bond_dim!r}")
-        if init_method not in ('small_random', 'zero', 'random'):
-            raise ValueError(f"init_method must be 'small_random', 'zero' or 'random', got {init_method!r}")
+        cores = new_mps_cores("SampledMPSBornMachine", num_latent_vars, bond_dim, init_method, conditioning_dim,
+                              backend.MPS_SAMPLED_MAX_N)
         if isinstance(seed, bool) or not isinstance(seed, int):
             raise ValueError(f"seed must be an integer, got {seed!r}")
+        super().__init__()
         self.num_latent_vars = num_latent_vars
-        self.bond_dim = bond_dim
         self.conditioning_dim = 0
         self.seed = seed
         self._draws = 0            # epoch of the next sample() call: successive calls draw fresh samples
-
-        n, D = num_latent_vars, bond_dim
-        eye = torch.eye(D, dtype=torch.float64).expand(n, 2, D, D)
-        if init_method == 'zero':            # psi(z) = 2^(-n/2) for every z: the exactly uniform q
-            init = eye / math.sqrt(2.0)
-        elif init_method == 'small_random':
-            init = (eye + 0.1 * torch.randn(n, 2, D, D, dtype=torch.float64)) / math.sqrt(2.0)
-        else:
-            init = torch.randn(n, 2, D, D, dtype=torch.float64) / math.sqrt(2.0 * D)
-        self.cores = nn.Parameter(init.clone().contiguous())
-
-    @property
-    def num_parameters(self):
-        return self.cores.numel()
+        self.cores = cores
 
     def kernel_input(self):
         """(cores detached as a contiguous float64 tensor on the compute device, the parameter's own device)."""
-        home = self.cores.device
-        return self.cores.detach().to(device=backend.compute_device(home), dtype=torch.float64).contiguous(), home
+        return super().kernel_input(detach=True)
 
     # ---- samples ----------------------------------------------------------------------------------------------
     def sample_indices(self, num_samples, seed=None, epoch=0):
@@ -72,22 +50,11 @@ class SampledMPSBornMachine(nn.Module):
 
     def bits_of(self, idx):
         """float32 bit rows [B, n] of outcome indices."""
-        n = self.num_latent_vars
-        shifts = torch.arange(n - 1, -1, -1, device=idx.device)
-        return ((idx.unsqueeze(-1) >> shifts) & 1).to(torch.float32)
+        return indices_to_bits(idx, self.num_latent_vars)
 
     def indices_of(self, z_samples):
         """int64 outcome indices of bit rows [B, n] (validated like MPSBornMachine.get_log_q_z_x)."""
-        n = self.num_latent_vars
-        z = z_samples.detach().long()
-        if z.dim() == 2 and z.shape[1] == n:
-            bad = ((z != 0) & (z != 1)).any(dim=1)
-        else:
-            bad = torch.ones(z.shape[0], dtype=torch.bool, device=z.device)
-        if bool(bad.any()):
-            row = int(torch.nonzero(bad)[0])
-            raise ValueError(f"Sample {tuple(z[row].tolist())} is not a valid outcome.")
-        return (z << torch.arange(n - 1, -1, -1, device=z.device)).sum(dim=1)
+        return bits_to_indices(z_samples, self.num_latent_vars)
 
     def sample(self, num_samples=1, x_condition=None):
         """float32 bit rows [num, n] on the parameter's device, from the draws of sample_indices (fresh ones every call)."""
@@ -118,18 +85,14 @@ class SampledMPSBornMachine(nn.Module):
         return self.log_prob(self.indices_of(z_samples)).to(z_samples.device)
 
     # ---- the enumerated distribution, where it exists ------------------------------------------------------------
-    def _check_enumerable(self):
-        if self.num_latent_vars > backend.MPS_MAX_N:
-            raise ValueError(f"the 2^n probabilities exist for num_latent_vars <= {backend.MPS_MAX_N} only "
-                             f"(got {self.num_latent_vars}): use sample_indices and log_prob")
-
     def probabilities64(self, x_condition=None):
         """float64 [2^n], differentiable (n <= 26): backend.mps_probs, as MPSBornMachine."""
         if x_condition is not None:
             raise ValueError("x_condition provided but conditioning_dim is 0.")
-        self._check_enumerable()
-        home = self.cores.device
-        cores = self.cores.to(device=backend.compute_device(home), dtype=torch.float64).contiguous()
+        if self.num_latent_vars > backend.MPS_MAX_N:
+            raise ValueError(f"the 2^n probabilities exist for num_latent_vars <= {backend.MPS_MAX_N} only "
+                             f"(got {self.num_latent_vars}): use sample_indices and log_prob")
+        cores, home = MPSCores.kernel_input(self)
         return _MPSProbs.apply(cores).to(home)
 
     def get_probabilities(self, x_condition=None):

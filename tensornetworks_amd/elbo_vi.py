@@ -5,19 +5,13 @@
 for both table modes and the MLP-conditioned machine, exact in O(2^n) per epoch (elbo_objective.ElboObjective holds the
 log-joint table).  No reference counterpart: the reference's classical route to KL is the adversarial trainer.  An epoch:
 
-  born_table_probs: q32 and its float64 upcast q64        (as the KSD trainer)
+  the machine's epoch_forward: q32 and float64 q64         (as the KSD trainer; born_table_probs or mps_probs)
   objective.weights(q64): L, entropy, w = dL/dq           one pass over 2^n doubles, in place of the K_p contraction
-  born_table_vjp(y = w, ksd2 = None) -> params.grad       y is then dL/dq itself
-
-With born_machine_config['family'] = 'mps' the two ends are mps_probs and mps_vjp (born_machine_mps.py) and q stays float64.
+  the machine's epoch_backward(y = w, ksd2 = None)        y is then dL/dq itself (born_table_vjp or mps_vjp)
 
 train() -- optimiser, clip, guard, early stopping, restore of the best probabilities -- is the classical KSD trainer's
 own code (this class derives from it and overrides the objective hooks); its Stein side is never prepared.
 """
-import torch
-
-from . import backend
-from .born_machine_mps import MPSBornMachine
 from .elbo_objective import ElboObjective
 from .ksd_vi import KSDVariationalInference
 
@@ -43,30 +37,9 @@ class ELBOVariationalInference(KSDVariationalInference):
         float32, grads): grads = [(tensor, its gradient), ...] for apply_grads.  The gradient is that of
         L - entropy_weight * H (the KSD trainer's entropy bonus; L carries the entropy itself, so 0 is the ELBO).
         Nothing is read back to the host.  One forward per epoch, in MLP mode too."""
-        bm = self.born_machine
-        if isinstance(bm, MPSBornMachine):
-            cores, q32, q64 = self.mps_forward()
-            loss, entropy, dldq = self.objective.weights(q64)
-            g = dldq.reshape(-1)
-            if entropy_weight != 0.0:
-                g = g + entropy_weight * self.mps_entropy_term(q64)[1]
-            return loss, entropy, q32, self.mps_backward(cores, g)
-        mode = bm.born_mode
-        if bm.conditioning_dim == 0:
-            home = bm.params.device
-            w = bm.params.detach().to(backend.compute_device(home)).reshape(1, -1)
-            leaf = None
-        else:
-            leaf, _ = bm.kernel_input(bm.raw_params(x_condition))
-            if leaf.shape[0] != 1:
-                raise ValueError(f"Probabilities shape mismatch: {tuple(leaf.shape)}")
-            w = leaf.detach()
-        q32, q64, _ = backend.born_table_probs(w, mode, want_entropy=False)
-        loss, entropy, dldq = self.objective.weights(q64)
-        g = backend.born_table_vjp(w, q64, mode, y=dldq, entropy_weight=entropy_weight)
-        if leaf is None:
-            return loss, entropy, q32[0], [(bm.params, g.reshape(bm.params.shape).to(home))]
-        return loss, entropy, q32[0], [(leaf, g)]
+        fwd = self.born_machine.epoch_forward(x_condition, want_entropy=False)
+        loss, entropy, dldq = self.objective.weights(fwd.q64)
+        return loss, entropy, fwd.q32, self.born_machine.epoch_backward(fwd, dldq, None, entropy_weight)[1]
 
     def train(self, x_observation_dict, num_epochs, lr_born_machine,
               verbose=True, true_posterior_for_tvd=None,

@@ -5,8 +5,8 @@
 estimated from B exact samples per epoch, with the score-function gradient
   grad L = E[(f - b) grad log q],  f = log q - log p,  b the leave-one-out mean (unbiased):  w_b = (f_b - mean f) / (B - 1).
 An epoch: mps_environments, mps_sample (idx, log q), bn_logjoint_samples (log p), the mean and w as torch elementwise ops
-on B doubles, mps_score_vjp -> cores.grad; then clip, the NaN/Inf guard and Adam or SGD with cosine annealing through
-torch.optim on the float64 cores, as the classical trainers do.  Epoch e draws with (seed, e): fresh samples every epoch,
+on B doubles, mps_score_vjp -> cores.grad; then the NaN/Inf guard, clip and Adam or SGD with cosine annealing through
+torch.optim on the float64 cores: the enumerated trainers' own make_optimizer and guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every epoch,
 the same ones on a rerun.
 
 log p floors every CPT FACTOR at p_floor, where elbo_objective.ElboObjective floors the product p(x, z): at n = 60 a
@@ -15,12 +15,11 @@ Networks with summed-out nodes are refused (the enumerated trainers handle them)
 """
 import numpy as np
 import torch
-import torch.nn.utils as nn_utils
-import torch.optim as optim
 
 from . import backend
 from .bayesian_network import pack_network
 from .born_machine_mps_sampled import SampledMPSBornMachine
+from .ksd_vi import guarded_update, make_optimizer
 
 
 class SampledELBOVariationalInference:
@@ -90,11 +89,7 @@ class SampledELBOVariationalInference:
             raise ValueError("Keys in x_observation_dict must match self.observed_vars_names.")
         bm = self.born_machine
         self._prepare_observation(x_observation_dict)
-        if optimizer_type == "adam":
-            opt = optim.Adam(bm.parameters(), lr=lr_born_machine, betas=adam_betas)
-        else:
-            opt = optim.SGD(bm.parameters(), lr=lr_born_machine, momentum=0.9)
-        sched = optim.lr_scheduler.CosineAnnealingLR(opt, T_max=num_epochs, eta_min=lr_born_machine / 10) if use_lr_scheduler else None
+        opt, sched = make_optimizer(bm.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas)
         exact = true_posterior_for_tvd is not None and self.num_latent_vars <= backend.MPS_MAX_N
         history = {'loss_elbo': [], 'grad_norm': [], 'logq_mean': [], 'status': []}
         if exact:
@@ -104,14 +99,8 @@ class SampledELBOVariationalInference:
             opt.zero_grad()
             loss_t, grad, lq_t, st_t = self.loss_and_grad(epoch)
             loss = float(loss_t.item())                       # the epoch's host synchronisation
-            if np.isnan(loss) or np.isinf(loss):
-                print(f"Warning: NaN or Inf loss: {loss}. Skipping update.")
-            else:
-                bm.cores.grad = grad.to(device=bm.cores.device, dtype=bm.cores.dtype)
-                grad_norm = nn_utils.clip_grad_norm_(bm.parameters(), gradient_clip_norm)
-                opt.step()
-                if sched is not None:
-                    sched.step()
+            grads = [(bm.cores, grad.to(device=bm.cores.device, dtype=bm.cores.dtype))]
+            grad_norm = guarded_update(bm, opt, sched, loss, grads, gradient_clip_norm, grad_norm)
             history['loss_elbo'].append(loss)
             history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
             history['logq_mean'].append(float(lq_t.item()))

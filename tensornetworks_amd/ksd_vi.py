@@ -6,16 +6,20 @@ set_fixed_probs.  What changed is where the arithmetic happens:
 
   reference epoch (ksd_vi.py:102-157)                       here
   ---------------------------------------------------       ---------------------------------------------------------
-  q = get_probabilities(); 4^n get_stein_kernel_kp_value    born_table_probs: q32, q64 and the entropy in one launch
+  q = get_probabilities(); 4^n get_stein_kernel_kp_value    the machine's epoch_forward: q32, q64 and the entropy
      calls in a Python double loop; entropy() forward       y = K_p q, ksd2 = q.y: the quantum trainer's contraction
-  loss.backward() through 4^n autograd nodes                born_table_vjp -> params.grad (float32)
-  clip_grad_norm_, optimizer.step(), scheduler.step()       the same torch objects
+  loss.backward() through 4^n autograd nodes                the machine's epoch_backward -> the parameters' gradients
+  clip_grad_norm_, optimizer.step(), scheduler.step()       the same torch objects (make_optimizer, guarded_update)
+
+The two ends of an epoch belong to the family (born_table_probs / born_table_vjp for the table and the MLP, mps_probs /
+mps_vjp for the MPS machine: born_machine_base.EnumeratedBornMachine); the trainer knows the objective only.
 
 S and K_p are built once per train() call by a `stein_operator.SteinOperator` of this trainer's own, the one the quantum
 trainer derives from (scores on the GPU; dense Gram up to DENSE_GRAM_MAX_N, matrix-free Kronecker mat-vec beyond).  MLP mode
 (conditioning_dim > 0): the network stays stock torch.nn and makes the reference's forwards in its order and number
 (loss, entropy, TVD, best-probabilities snapshot: the same Dropout draws); logits -> q and the VJP back onto the logits
-are the kernels, once per term, and torch.autograd carries the two logit gradients into the network.
+are the kernels, once per term, and torch.autograd carries the two logit gradients into the network.  make_optimizer,
+apply_grads and guarded_update are plain functions: the sampled trainer (elbo_vi_sampled.py) uses the same ones.
 """
 from functools import partial
 
@@ -24,13 +28,48 @@ import torch
 import torch.nn.utils as nn_utils
 import torch.optim as optim
 
-from . import backend
 from . import paramshift_shard as shard
 from .born_machine_classical_sim import ClassicalBornMachine
 from .born_machine_mps import MPSBornMachine
 from .stein_operator import DENSE_GRAM_MAX_N, SteinOperator      # noqa: F401  (DENSE_GRAM_MAX_N: exported from here too)
 from .stein_utils import base_hamming_kernel_torch, tvd_table
 from .utils import calculate_tvd
+
+
+def make_optimizer(parameters, lr_born_machine, num_epochs, use_lr_scheduler=True, optimizer_type="adam",
+                   adam_betas=(0.9, 0.999)):
+    """The optimiser and scheduler the reference builds (ksd_vi.py:84-93)."""
+    if optimizer_type == "adam":
+        optimizer_born = optim.Adam(parameters, lr=lr_born_machine, betas=adam_betas)
+    else:
+        optimizer_born = optim.SGD(parameters, lr=lr_born_machine, momentum=0.9)
+    scheduler = None
+    if use_lr_scheduler:
+        scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer_born, T_max=num_epochs, eta_min=lr_born_machine / 10)
+    return optimizer_born, scheduler
+
+
+def apply_grads(grads):
+    """Puts the epoch's gradients into the parameters' .grad (what loss.backward() does in the reference)."""
+    if len(grads) == 1 and grads[0][0].is_leaf:
+        p, g = grads[0]
+        p.grad = g
+    else:
+        torch.autograd.backward([t for t, _ in grads], [g for _, g in grads])
+
+
+def guarded_update(born_machine, optimizer, scheduler, guard_value, grads, gradient_clip_norm, last_grad_norm):
+    """An epoch's update (ksd_vi.py:140-157): skipped with the reference's warning when the guarded loss is NaN or Inf,
+    else gradients, clip, optimiser and scheduler step.  -> the clipped-from gradient norm, or the last one when skipped."""
+    if np.isnan(guard_value) or np.isinf(guard_value):
+        print(f"Warning: NaN or Inf loss: {guard_value}. Skipping update.")
+        return last_grad_norm
+    apply_grads(grads)
+    grad_norm = nn_utils.clip_grad_norm_(born_machine.parameters(), gradient_clip_norm)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return grad_norm
 
 
 class KSDVariationalInference:
@@ -87,84 +126,26 @@ class KSDVariationalInference:
 
     def make_optimizer(self, lr_born_machine, num_epochs, use_lr_scheduler=True, optimizer_type="adam",
                        adam_betas=(0.9, 0.999)):
-        """The optimiser and scheduler the reference builds (ksd_vi.py:84-93)."""
-        if optimizer_type == "adam":
-            optimizer_born = optim.Adam(self.born_machine.parameters(), lr=lr_born_machine, betas=adam_betas)
-        else:
-            optimizer_born = optim.SGD(self.born_machine.parameters(), lr=lr_born_machine, momentum=0.9)
-        scheduler = None
-        if use_lr_scheduler:
-            scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer_born, T_max=num_epochs, eta_min=lr_born_machine / 10)
-        return optimizer_born, scheduler
+        return make_optimizer(self.born_machine.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type,
+                              adam_betas)
+
+    apply_grads = staticmethod(apply_grads)
 
     def loss_and_grads(self, x_condition, entropy_weight):
         """Device part of one epoch: -> (loss_ksd [1] float64, entropy [1], q [2^n] float32 of the loss forward, grads):
         grads = [(tensor, its gradient), ...] for apply_grads.  The entropy is float32 from the table family's kernel and
-        float64 from the MPS family (mps_entropy_term); train() only reads it with .item().  Nothing is read back to the
-        host."""
+        float64 from the MPS family; train() only reads it with .item().  Nothing is read back to the host."""
         bm = self.born_machine
-        if isinstance(bm, MPSBornMachine):
-            cores, q32, q64 = self.mps_forward()
-            ksd2, y = self._stein._stein_contract(q64)
-            # loss = sqrt(max(ksd2, 1e-12)); the clamp passes no gradient below 1e-12 (bornvi_born_table_vjp's convention)
-            loss = torch.sqrt(ksd2.clamp(min=1e-12))
-            g = torch.where(ksd2 >= 1e-12, y / loss, torch.zeros_like(y))
-            H, dH = self.mps_entropy_term(q64)
-            if entropy_weight != 0.0:
-                g = g + entropy_weight * dH
-            return loss, H, q32, self.mps_backward(cores, g)
-        mode = bm.born_mode
-        st = self._stein
-        if bm.conditioning_dim == 0:
-            # table: the forwards draw nothing, so one launch serves the loss and the entropy
-            home = bm.params.device
-            w = bm.params.detach().to(backend.compute_device(home)).reshape(1, -1)
-            q32, q64, H = backend.born_table_probs(w, mode, want_entropy=True)
-            ksd2, y = st._stein_contract(q64[0])
-            loss = torch.empty(1, dtype=torch.float64, device=w.device)
-            g = backend.born_table_vjp(w, q64, mode, y=y.reshape(1, -1), ksd2=ksd2, entropy_weight=entropy_weight,
-                                       loss_out=loss)
-            return loss, H, q32[0], [(bm.params, g.reshape(bm.params.shape).to(home))]
-        # MLP: the reference's two forwards (loss, then entropy()) -- with Dropout active two different samples
-        w1, _ = bm.kernel_input(bm.raw_params(x_condition))
-        if w1.shape[0] != 1:
-            raise ValueError(f"Probabilities shape mismatch: {tuple(w1.shape)}")
-        q32, q64, _ = backend.born_table_probs(w1.detach(), mode, want_entropy=False)
-        ksd2, y = st._stein_contract(q64[0])
-        loss = torch.empty(1, dtype=torch.float64, device=w1.device)
-        g1 = backend.born_table_vjp(w1.detach(), q64, mode, y=y.reshape(1, -1), ksd2=ksd2, loss_out=loss)
-        w2, _ = bm.kernel_input(bm.raw_params(x_condition))
-        _, q64e, H = backend.born_table_probs(w2.detach(), mode, want_entropy=True)
-        g2 = backend.born_table_vjp(w2.detach(), q64e, mode, entropy_weight=entropy_weight)
-        return loss, H, q32[0], [(w1, g1), (w2, g2)]
-
-    # ---- the MPS family's ends of an epoch (shared with the ELBO trainer): cores -> q, and dL/dq -> the cores' gradient
-    def mps_forward(self):
-        """(cores float64 on the compute device, q32 [2^n], q64 [2^n]); leaves the sweep in the workspace for mps_backward."""
-        bm = self.born_machine
-        cores = bm.cores.detach().to(device=backend.compute_device(bm.cores.device), dtype=torch.float64).contiguous()
-        q32, q64, _, _ = backend.mps_probs(cores)
-        return cores, q32, q64
-
-    @staticmethod
-    def mps_entropy_term(q64):
-        """(H [1] = -sum q log max(q, 1e-10), the derivative of -H: log max(q, 1e-10) + [q >= 1e-10]) in float64."""
-        logq = torch.log(q64.clamp(min=1e-10))
-        return -(q64 * logq).sum().reshape(1), logq + (q64 >= 1e-10).to(torch.float64)
-
-    def mps_backward(self, cores, g):
-        bm = self.born_machine
-        grad = backend.mps_vjp(cores, g.contiguous())
-        return [(bm.cores, grad.to(device=bm.cores.device, dtype=bm.cores.dtype))]
-
-    @staticmethod
-    def apply_grads(grads):
-        """Puts the epoch's gradients into the parameters' .grad (what loss.backward() does in the reference)."""
-        if len(grads) == 1 and grads[0][0].is_leaf:
-            p, g = grads[0]
-            p.grad = g
-        else:
-            torch.autograd.backward([t for t, _ in grads], [g for _, g in grads])
+        # a machine whose forward draws (the MLP's Dropout) makes the reference's two forwards, loss then entropy(): two
+        # different samples; otherwise one forward serves both terms
+        two = bm.draws_in_forward
+        fwd = bm.epoch_forward(x_condition, want_entropy=not two)
+        ksd2, y = self._stein._stein_contract(fwd.q64)
+        loss, grads = bm.epoch_backward(fwd, y, ksd2, 0.0 if two else entropy_weight)
+        if not two:
+            return loss, fwd.entropy, fwd.q32, grads
+        fwd_h = bm.epoch_forward(x_condition, want_entropy=True)
+        return loss, fwd_h.entropy, fwd.q32, grads + bm.epoch_backward(fwd_h, None, None, entropy_weight)[1]
 
     def train(self, x_observation_dict, num_epochs, lr_born_machine,
               verbose=True, true_posterior_for_tvd=None,
@@ -218,14 +199,7 @@ class KSDVariationalInference:
             entropy_value = float(entropy_t.item())
             # the guard is on the total loss (ksd_vi.py:140-142)
             total = ksd_value - float(np.float32(entropy_weight) * np.float32(entropy_value))
-            if np.isnan(total) or np.isinf(total):
-                print(f"Warning: NaN or Inf loss: {total}. Skipping update.")
-            else:
-                self.apply_grads(grads)
-                grad_norm = nn_utils.clip_grad_norm_(bm.parameters(), gradient_clip_norm)
-                optimizer_born.step()
-                if scheduler is not None:
-                    scheduler.step()
+            grad_norm = guarded_update(bm, optimizer_born, scheduler, total, grads, gradient_clip_norm, grad_norm)
 
             history[self._loss_key].append(ksd_value)
             history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)

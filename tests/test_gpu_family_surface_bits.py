@@ -1,0 +1,39 @@
+"""The classical trainers through their public surface, bit for bit, against the results recorded before the families moved
+onto born_machine_base.py: tests/golden/family_surface_parent_bits.npz, written on an MI355X by
+tests/golden/make_golden_family_surface_bits.py.  Every case is a pure function of its seed (the kernels' summation orders
+are specified, the MLP's Dropout draws follow torch.manual_seed), so host plumbing that launches the same kernels on the
+same values in the same order reproduces every bit: loss, entropy, q and gradients of one loss_and_grads, the history and
+final parameters of a short train(), with the parameters at home on the CPU and on the GPU.  A change of the arithmetic on
+purpose re-records the file and says so."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "family_surface_parent_bits.npz")
+# cases, pieces() and piece_bytes() are the recording script's own: what is compared is what was recorded
+_spec = importlib.util.spec_from_file_location("make_golden_family_surface_bits",
+                                               os.path.join(HERE, "golden", "make_golden_family_surface_bits.py"))
+rec = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(rec)
+
+
+@pytest.fixture(scope="module")
+def golden():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", rec.ENUMERATED + rec.SAMPLED, ids=rec.case_id)
+def test_bits_are_the_recorded_ones(golden, case):
+    want, at = golden[rec.case_id(case)].tobytes(), 0
+    for name, a in rec.pieces(case):
+        got = rec.piece_bytes(a)
+        assert got == want[at:at + len(got)], (rec.case_id(case), name, a.dtype, a.shape)
+        at += len(got)
+    assert at == len(want), (rec.case_id(case), at, len(want))
