@@ -73,7 +73,9 @@ def run_step(idx, logit, log_p, q32, baseline, first, decay=DECAY):
 def assert_step_close(d, loss, base, d_ref, loss_ref, base_ref, what):
     """dLdq to 1e-6 of its largest entry, loss and baseline to 1e-6 relative.  The kernel's own error is far below: the
     per-outcome sums are exact sums of weights rounded to 2^-44 of their bound (B = 65,536; kernels_reinforce.hip), the
-    means float64, the loss rounded to float32 once (6e-8)."""
+    means float64, the loss rounded to float32 once (6e-8).  This is the coarse check against NumPy and the reference's
+    trace: outcomes with a large q are small entries of dLdq and weigh nothing here.  Each outcome's own bound, the baseline's
+    and the loss's, against extended precision: test_gpu_classical_precision.py."""
     d = d.cpu().numpy()
     err = np.abs(d - d_ref).max()
     print(f"{what}: dLdq err {err:.3e} (max {np.abs(d_ref).max():.3e}), loss {float(loss):.9g} vs {loss_ref:.9g}, "
@@ -134,7 +136,8 @@ def test_reinforce_step_is_bitwise_repeatable_and_order_independent():
     sample order, so its last bits may move, and every weight with them.  Given the baseline's bits the design is
     order-free.  (Differences of float32 values of bounded range are short float64 numbers, so at this size the partial
     sums are usually exact and the bits usually agree; that is printed, not required.)  The permuted call must agree with
-    the unpermuted one within the tolerances of the NumPy comparison."""
+    the unpermuted one within the tolerances of the NumPy comparison.  (With the baseline's bits held fixed -- first = False,
+    baseline_decay = 1 -- bitwise equality under permutation is required: test_gpu_classical_precision.py.)"""
     idx, logit, log_p, q32 = step_inputs(16, 65536, "mixed", seed=5)
     outs = [run_step(idx, logit, log_p, q32, 0.3, False) for _ in range(2)]
     for a, b in zip(outs[0], outs[1]):

@@ -67,6 +67,9 @@ def make_rows(n, rows, kind, gen):
 @pytest.mark.parametrize("mode,kind", [(0, "random"), (0, "spread"), (0, "equal"),
                                        (1, "random"), (1, "spread"), (1, "equal"), (1, "zeros")])
 def test_kernels_against_autograd(n, mode, kind):
+    """The coarse check against torch: q to 3 float32 ulps, H to 2e-6, the gradient relative to its row's largest entry (so
+    entries proportional to a small q, and the entropy clamp's indicator, weigh nothing here).  The per-entry bounds
+    against extended precision, the clamp's edge and the unaligned (scalar) path are test_gpu_classical_precision.py's."""
     gen = torch.Generator().manual_seed(1000 * n + 10 * mode + len(kind))
     rows = 3 if n < 20 else 2
     w = make_rows(n, rows, kind, gen)
