@@ -1,6 +1,6 @@
 """The Stein side of KSD training, independent of the variational family: scores S of one observation, the Gram matrix
 K_p (dense, sharded over ranks and placed in HBM by measurement, or matrix-free) and the contraction (ksd2 = q^T K_p q,
-y = K_p q).  The quantum trainer derives from `SteinOperator`, the classical one holds one."""
+y = K_p q).  The quantum KSD trainer derives from `SteinOperator`, the classical one holds one."""
 import torch
 
 from . import backend
