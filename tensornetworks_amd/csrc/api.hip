@@ -178,12 +178,12 @@ int get_plan(bornvi_handle h, int ansatz, int n, int layers, DevPlan** out, bool
     if (!build_state_tail(tail, n, dp->tail)) return fail(h, BORNVI_ERR_UNSUPPORTED, "a CNOT follows a CZ at the end of the circuit");
     ok = true;
   } else if (h->opt.r == 3) {
-    // 8 amplitudes per thread where the plan is eligible for circuit_pass_r3_kernel (compact tables, tile and tables
-    // within the CU's LDS); otherwise the 16-amplitude plan below
+    // 8 amplitudes per thread where the plan is eligible for circuit_pass_r3_kernel (plan.hpp: r3_plan_eligible -- depth
+    // limit of the pivot-normalised gates, compact tables, tile and tables within the CU's LDS); otherwise the 16-amplitude
+    // plan below
     std::string m3;
     ok = (ansatz == -1) ? make_kron_plan(n, h->opt, dp->plan, m3) : make_plan(ansatz, n, layers, h->opt, dp->plan, m3);
-    use_r3 = ok && dp->plan.r == 3 && build_compact_tables(dp->plan, dp->compact, m3) &&
-             dp->compact.lds_bytes(dp->plan.k) <= MAX_LDS_BYTES;
+    use_r3 = ok && r3_plan_eligible(dp->plan, dp->compact, m3);
     if (!use_r3) { dp = std::make_unique<DevPlan>(); ok = false; }
   }
   if (!ok) {
@@ -1559,7 +1559,7 @@ long long bornvi_plan_compact_describe(int ansatz, int n, int layers, int tile_b
   const bool ok = (ansatz == -1) ? make_kron_plan(n, opt, p, msg) : make_plan(ansatz, n, layers, opt, p, msg);
   if (!ok) return -1;
   CompactTables ct;
-  if (!build_compact_tables(p, ct, msg) || ct.lds_bytes(p.k) > MAX_LDS_BYTES) return 0;
+  if (!r3_plan_eligible(p, ct, msg)) return 0;
   if (out) {
     const size_t c = ct.words.size() < cap_words ? ct.words.size() : cap_words;
     std::memcpy(out, ct.words.data(), c * sizeof(uint32_t));

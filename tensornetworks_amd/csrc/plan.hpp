@@ -265,6 +265,25 @@ struct CompactTables {
 // 2^22 of them per row, a fixed sample beyond)
 bool build_compact_tables(const Plan& plan, CompactTables& out, std::string& msg);
 
+// Depth limit of circuit_pass_r3_kernel.  Its gates are pivot-normalised (build_gates_kernel): every fused gate divides the
+// amplitudes by |p|, |p|^2 >= 1/2, and the probabilities are multiplied back by scale = prod |p|^2.  After f fused gates
+// |x|^2 can reach 2^f and scale can fall to 2^-f (1 - 16 eps)^f: the computed |p|^2 is the larger squared modulus of a column
+// whose squared norm is within 13 eps of 1 (up to three 2x2 complex products of at most four roundings each, sincos, the three
+// roundings of the sum of squares: 16 eps covers them).  (1 - 16 eps)^f is above 1 - 4e-12 for f <= 1022: less than one
+// binade.  So f <= 1021 keeps scale, every partial product of it and every |x|^2 inside fp64's normal range
+// [2^-1022, 2^1024).  The limit is 1000: a margin of 21 binades over the one the rounding needs.  (Past 1074 gates of
+// |p|^2 = 1/2 -- every angle pi/2 -- scale is 0 and |x|^2 is inf: q = nan.)  A deeper plan runs on the 16-amplitude kernel,
+// which reads raw matrices and has no such limit.
+constexpr int R3_MAX_FUSED = 1000;
+// The one answer to "does circuit_pass_r3_kernel run this plan": 3 register wires, within the depth limit, compact tables
+// that build, tile and tables within the CU's LDS.  (api.hip: get_plan and bornvi_plan_compact_describe; the fused dot
+// follows get_plan's choice.)
+inline bool r3_plan_eligible(const Plan& plan, CompactTables& out, std::string& msg) {
+  if (plan.r != 3) { msg = "not a 3-register-wire plan"; return false; }
+  if (plan.n_fused > R3_MAX_FUSED) { msg = "more fused gates than the pivot-normalised kernel's depth limit"; return false; }
+  return build_compact_tables(plan, out, msg) && out.lds_bytes(plan.k) <= MAX_LDS_BYTES;
+}
+
 // Largest state a plan can address: tile and workgroup indices are 16 bits each and tiles hold at most 2^13 amplitudes,
 // so n - 13 <= 16.
 constexpr int MAX_PLAN_QUBITS = 29;

@@ -44,7 +44,7 @@ int main(int argc, char** argv) {
     // the compact tables of the 8-amplitude kernel (every word checked against its point evaluation by the builder)
     bornvi::CompactTables ct;
     std::string cmsg;
-    const bool compact = p.r == 3 && bornvi::build_compact_tables(p, ct, cmsg) && ct.lds_bytes(p.k) <= bornvi::MAX_LDS_BYTES;
+    const bool compact = bornvi::r3_plan_eligible(p, ct, cmsg);
     printf("%d %d %d %d plan %zu %016llx fast %zu %016llx kinds %d compact %zu %016llx\n", ansatz, n, L, kb, p.words.size(),
            (unsigned long long)fnv(p.words), fast ? ft.words.size() : (size_t)0,
            (unsigned long long)(fast ? fnv(ft.words) : 0ull), kinds_ok ? 1 : 0, compact ? ct.words.size() : (size_t)0,

@@ -1,5 +1,7 @@
 """OPT-IN adjoint differentiation engine against the reference's rule -- 2P
-parameter-shift evaluations (diff_method="parameter-shift", quantum_born_machine.py:58, :90, :114) -- and the oracle."""
+parameter-shift evaluations (diff_method="parameter-shift", quantum_born_machine.py:58, :90, :114) -- and the oracle.
+(Tolerances relative to the largest gradient entry; per-parameter bounds against extended precision, small gradients
+included, are test_gpu_circuit_precision.py's.)"""
 import math
 
 import numpy as np

@@ -1,7 +1,9 @@
 """GPU parity of the circuit engine (through the C ABI) against the CPU oracle.
 
 Tolerance: q_theta within 1e-10 relative / 1e-14 absolute of the oracle (north_star asks 1e-6
-relative, fp64); fp64 throughout."""
+relative, fp64); fp64 throughout.  That tolerance does not see entries of q below 1e-14 and allows some 4.5e5 eps; the
+per-entry bounds against extended precision, small entries and the angle edges (tiny, mixed-scale, pivot ties, large
+arguments) are test_gpu_circuit_precision.py's."""
 import math
 
 import numpy as np

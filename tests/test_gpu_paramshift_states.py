@@ -4,7 +4,8 @@ reg_wires, at n = 1, 2, 3, at the sizes where the planner's describe calls repor
 pass kernel, and with small tiles that force several passes at a size the oracle covers.
 
 Tolerance: 64 eps (number of gates) per amplitude, absolute, eps = 2^-52 (|amplitude| <= 1: a gate's 2 x 2 complex product
-errs by a few eps of the pair's magnitude, and the errors of successive gates add)."""
+errs by a few eps of the pair's magnitude, and the errors of successive gates add).  A flat absolute tolerance: amplitudes
+far below it are not checked here; the per-entry bound (envelope and 2-norm arms) is test_gpu_circuit_precision.py's."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,7 @@
 """Size-independent properties of the hot path on the GPU, on randomly drawn cases (hypothesis, derandomised):
 SURVEY.md section 4 (iv) -- sum q = 1, K_p symmetric PSD, K_p p_true = 0 (so KSD(p_true) = 0), parameter shift ==
-finite difference, linearity of the contraction -- each through the C ABI, each also compared with the CPU oracle."""
+finite difference, linearity of the contraction -- each through the C ABI, each also compared with the CPU oracle
+(to rtol 1e-10 / atol 1e-14; per-entry bounds of the circuit engines: test_gpu_circuit_precision.py)."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,8 @@
 """GPU parity of circuit_pass_r3_kernel (8 amplitudes per thread, four waves per SIMD, compact tables, matrices by scalar
 loads, pivot-normalised 12-instruction gates) against the CPU oracle and against the 16-amplitude kernel, through the C ABI.
-Reference circuit: quantum_born_machine.py:58-128."""
+Reference circuit: quantum_born_machine.py:58-128.  (Parity to rtol 1e-10 / atol 1e-14 of the fp64 oracle; the per-entry
+bounds of the records, the exchange flag at pivot ties and the scale chain against extended precision, and the depth
+limit of the pivot normalisation, are test_gpu_circuit_precision.py's.)"""
 import numpy as np
 import pytest
 import torch
