@@ -83,24 +83,43 @@ void fuse_gates(const std::vector<Gate>& gates, int n, std::vector<Op>& ops, std
 
 inline int op_target(const Op& o) { return o.kind == K_U1 ? o.a : (o.kind == K_CX ? o.b : -1); }
 
-// Greedy selection in program order: an op runs if none of its wires is blocked and its
+// Commutation rule shared by the three scans below.  An op that cannot run stays behind and blocks its wires for the ops
+// after it in program order -- at one of two levels per wire, by how it acts there: DIAGONALLY (in the computational
+// basis: either wire of a CZ, the control of a CNOT) or not (a fused U, the target of a CNOT).  A later op passes a wire
+// blocked diagonally if it acts diagonally there itself: two ops that act diagonally on every wire they share commute
+// (CZ with CZ, CZ with a CNOT's control, two CNOTs with a common control), and ops on disjoint wires always do.  So an
+// accepted op commutes, wire by wire, with EVERY earlier op still waiting, and running it first is exact.  (Two CNOTs
+// that share only their target commute too; that case is not taken: it changes none of the benchmark plans.)  The scans
+// stay in program order, so a circuit without such pairs plans as it did under the one-level rule (`commute` = false:
+// every block holds every later op; build_plan keeps that plan wherever the rule gains nothing).
+enum : char { BLOCK_DIAG = 1, BLOCK_FULL = 2 };
+inline bool acts_diagonally(const Op& o, int w) { return o.kind == K_CZ || (o.kind == K_CX && w == o.a); }
+inline bool held_back(const Op& o, const std::vector<char>& blocked, bool commute) {
+  auto held = [&](int w) { return w >= 0 && (blocked[w] == BLOCK_FULL || (blocked[w] == BLOCK_DIAG && !(commute && acts_diagonally(o, w)))); };
+  return held(o.a) || held(o.b);
+}
+inline void block_wires(const Op& o, std::vector<char>& blocked) {
+  auto block = [&](int w) { if (w >= 0) blocked[w] = std::max<char>(blocked[w], acts_diagonally(o, w) ? BLOCK_DIAG : BLOCK_FULL); };
+  block(o.a); block(o.b);
+}
+
+// Greedy selection in program order: an op runs if none of its wires is blocked for it (above) and its
 // non-diagonal target is (or can become) one of at most `cap` "near" wires.  Anything that
-// cannot run blocks its wires for the rest of the scan (ops on disjoint wires commute).
-void greedy_select(const std::vector<Op>& ops, const std::vector<int>& pool, int n, int cap,
+// cannot run blocks its wires for the rest of the scan.
+void greedy_select(const std::vector<Op>& ops, const std::vector<int>& pool, int n, int cap, bool commute,
                    std::vector<int>& sel, std::vector<int>& rest, std::vector<int>& targets) {
   std::vector<char> blocked(n, 0), in_t(n, 0);
   sel.clear(); rest.clear(); targets.clear();
   for (int idx : pool) {
     const Op& o = ops[idx];
-    bool blk = blocked[o.a] || (o.b >= 0 && blocked[o.b]);
+    bool blk = held_back(o, blocked, commute);
     int t = op_target(o);
     if (!blk && t >= 0 && !in_t[t]) {
       if ((int)targets.size() < cap) { in_t[t] = 1; targets.push_back(t); }
       else blk = true;
     }
     if (blk) {
-      blocked[o.a] = 1;
-      if (o.b >= 0) blocked[o.b] = 1;
+      block_wires(o, blocked);
       rest.push_back(idx);
     } else {
       sel.push_back(idx);
@@ -110,19 +129,18 @@ void greedy_select(const std::vector<Op>& ops, const std::vector<int>& pool, int
 
 // Same scan with a FIXED set of allowed target wires (a candidate local set of a pass).
 // Returns the number of locality-bound ops (U1, CNOT) it executes.
-int fixed_select(const std::vector<Op>& ops, const std::vector<int>& pool, int n, const std::vector<char>& allowed,
+int fixed_select(const std::vector<Op>& ops, const std::vector<int>& pool, int n, const std::vector<char>& allowed, bool commute,
                  std::vector<int>& sel, std::vector<int>& rest, std::vector<int>& targets) {
   std::vector<char> blocked(n, 0), in_t(n, 0);
   sel.clear(); rest.clear(); targets.clear();
   int bound_ops = 0;
   for (int idx : pool) {
     const Op& o = ops[idx];
-    bool blk = blocked[o.a] || (o.b >= 0 && blocked[o.b]);
+    bool blk = held_back(o, blocked, commute);
     const int t = op_target(o);
     if (!blk && t >= 0 && !allowed[t]) blk = true;
     if (blk) {
-      blocked[o.a] = 1;
-      if (o.b >= 0) blocked[o.b] = 1;
+      block_wires(o, blocked);
       rest.push_back(idx);
     } else {
       if (t >= 0) { ++bound_ops; if (!in_t[t]) { in_t[t] = 1; targets.push_back(t); } }
@@ -135,12 +153,12 @@ int fixed_select(const std::vector<Op>& ops, const std::vector<int>& pool, int n
 // Pass selection: the program-order greedy set and every cyclic window of k consecutive wires are tried;
 // the candidate that lets this pass plus the best following pass execute the most locality-bound ops wins
 // (one step of look-ahead).  Fewer passes = fewer HBM round trips of the whole batch of states.
-void choose_pass(const std::vector<Op>& ops, const std::vector<int>& pool, int n, int k, std::vector<int>& sel,
+void choose_pass(const std::vector<Op>& ops, const std::vector<int>& pool, int n, int k, bool commute, std::vector<int>& sel,
                  std::vector<int>& rest, std::vector<int>& targets) {
   std::vector<std::vector<char>> cands;
   {
     std::vector<int> s, r, t;
-    greedy_select(ops, pool, n, k, s, r, t);
+    greedy_select(ops, pool, n, k, commute, s, r, t);
     std::vector<char> a(n, 0);
     for (int w : t) a[w] = 1;
     int cnt = (int)t.size();
@@ -156,24 +174,24 @@ void choose_pass(const std::vector<Op>& ops, const std::vector<int>& pool, int n
   long best_score = -1;
   std::vector<int> s1, r1, t1, s2, r2, t2;
   for (const auto& a : cands) {
-    const int here = fixed_select(ops, pool, n, a, s1, r1, t1);
+    const int here = fixed_select(ops, pool, n, a, commute, s1, r1, t1);
     if (s1.empty()) continue;
     int next_best = 0;
     if (!r1.empty() && k < n)
       for (const auto& a2 : cands) {   // (the greedy candidate of the NEXT pool is approximated by the windows)
-        const int nb = fixed_select(ops, r1, n, a2, s2, r2, t2);
+        const int nb = fixed_select(ops, r1, n, a2, commute, s2, r2, t2);
         if (nb > next_best) next_best = nb;
       }
     const long score = (long)(here + next_best) * 4096 + (long)s1.size();
     if (score > best_score) { best_score = score; sel = s1; rest = r1; targets = t1; }
   }
-  if (best_score < 0) greedy_select(ops, pool, n, k, sel, rest, targets);
+  if (best_score < 0) greedy_select(ops, pool, n, k, commute, sel, rest, targets);
 }
 
 // Stage selection.  A stage runs its ops in five global phases -- 0: CNOTs (folded into the LDS read
 // address), 1: CZs, 2: at most one fused U per register wire, 3: CNOTs (folded into the write address),
 // 4: CZs -- so an op is accepted in the earliest phase its kind allows that is not before the phase of
-// the last op accepted on any of its wires (ops on disjoint wires commute).
+// the last op accepted on any of its wires.  What stays behind blocks its wires by the commutation rule above.
 struct StageSel {
   std::vector<int> pre_cx, pre_cz, us, post_cx, post_cz, targets;
   size_t count() const { return pre_cx.size() + pre_cz.size() + us.size() + post_cx.size() + post_cz.size(); }
@@ -181,14 +199,14 @@ struct StageSel {
 
 // defer_cx3: a CNOT that could only run in phase 3 AND would claim a new register wire is left for the next stage,
 // where it is a phase-0 CNOT (folded into the read map: free) -- the register wires then go to fused U's.
-void stage_select(const std::vector<Op>& ops, const std::vector<int>& pool, int n, int cap, StageSel& S,
+void stage_select(const std::vector<Op>& ops, const std::vector<int>& pool, int n, int cap, bool commute, StageSel& S,
                   std::vector<int>& rest, bool defer_cx3 = false, bool read_map = false) {
   std::vector<char> blocked(n, 0), in_t(n, 0), has_u(n, 0);
   std::vector<int> wphase(n, 0);
   rest.clear();
   for (int idx : pool) {
     const Op& o = ops[idx];
-    bool blk = blocked[o.a] || (o.b >= 0 && blocked[o.b]);
+    bool blk = held_back(o, blocked, commute);
     int ph = -1;
     if (!blk) {
       const int mx = std::max(wphase[o.a], o.b >= 0 ? wphase[o.b] : 0);
@@ -207,8 +225,7 @@ void stage_select(const std::vector<Op>& ops, const std::vector<int>& pool, int 
       else blk = true;
     }
     if (blk) {
-      blocked[o.a] = 1;
-      if (o.b >= 0) blocked[o.b] = 1;
+      block_wires(o, blocked);
       rest.push_back(idx);
       continue;
     }
@@ -279,12 +296,12 @@ void split_pass_ops(const std::vector<Op>& ops, const std::vector<int>& pass_ops
 
 // target wires of the first and of the last stage of a pass (they depend on the ops only, not on the layout)
 // number of stages the core ops of a pass need under a stage-selection policy
-int count_stages(const std::vector<Op>& ops, const std::vector<int>& core, int n, int r, bool defer_cx3, bool read_map) {
+int count_stages(const std::vector<Op>& ops, const std::vector<int>& core, int n, int r, bool commute, bool defer_cx3, bool read_map) {
   std::vector<int> pool = core, rest;
   int cnt = 0;
   while (!pool.empty()) {
     StageSel sel;
-    stage_select(ops, pool, n, r, sel, rest, defer_cx3, read_map);
+    stage_select(ops, pool, n, r, commute, sel, rest, defer_cx3, read_map);
     if (sel.count() == 0) return 1 << 20;
     ++cnt;
     pool = rest;
@@ -292,21 +309,21 @@ int count_stages(const std::vector<Op>& ops, const std::vector<int>& core, int n
   return cnt;
 }
 // the policy with fewer stages (ties: the program-order greedy one)
-bool pick_defer_policy(const std::vector<Op>& ops, const std::vector<int>& core, int n, int r, bool read_map) {
-  return read_map && count_stages(ops, core, n, r, true, true) < count_stages(ops, core, n, r, false, true);
+bool pick_defer_policy(const std::vector<Op>& ops, const std::vector<int>& core, int n, int r, bool commute, bool read_map) {
+  return read_map && count_stages(ops, core, n, r, commute, true, true) < count_stages(ops, core, n, r, commute, false, true);
 }
 
-void first_last_stage_targets(const std::vector<Op>& ops, const std::vector<int>& pass_ops, int n, int r, bool is_init,
+void first_last_stage_targets(const std::vector<Op>& ops, const std::vector<int>& pass_ops, int n, int r, bool is_init, bool commute,
                               std::vector<int>& first_t, std::vector<int>& last_t, bool read_map) {
   std::vector<int> lead, core, trail, rest;
   split_pass_ops(ops, pass_ops, n, is_init, lead, core, trail);
   first_t.clear(); last_t.clear();
   std::vector<int> pool = core;
   bool first = true;
-  const bool defer = pick_defer_policy(ops, core, n, r, read_map);
+  const bool defer = pick_defer_policy(ops, core, n, r, commute, read_map);
   while (!pool.empty()) {
     StageSel sel;
-    stage_select(ops, pool, n, r, sel, rest, defer, read_map);
+    stage_select(ops, pool, n, r, commute, sel, rest, defer, read_map);
     if (sel.count() == 0) break;
     if (first) { first_t = sel.targets; first = false; }
     last_t = sel.targets;
@@ -338,7 +355,7 @@ struct BuildSpec {
   // of the probabilities instead (|CX psi|^2 is a permutation of |psi|^2)
   std::vector<std::pair<int, int>> out_perm;
 };
-bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::string& msg);
+bool build_plan(const BuildSpec& spec, const PlanOptions& opt, bool may_commute, Plan& plan, std::string& msg);
 }  // namespace
 
 namespace {
@@ -379,6 +396,10 @@ bool make_plan_impl(int ansatz, int n, int layers, const PlanOptions& opt, Plan&
   spec.out_state = tail != nullptr;
   spec.n_params = num_params(ansatz, n, layers);
   spec.n_gates = (int)gates.size();
+  // The commutation rule is taken with the tile size the library chooses itself.  A tile size forced by the caller (option
+  // tile_bits) is a test instrument: the GPU tests pick such sizes for the pass and stage shapes the program-order plan has
+  // there, to walk every path of the pass kernels, and the rule's gain was measured on the library's own tiles only.
+  const bool own_tile = opt.kmulti == 0;
   if (opt.kmulti == 0 && n > opt.kmax && opt.kmax >= 13) {
     // Tile size by measurement on the MI355X (tools/tile_sweep_n.py).  Round 1: 2^13 tiles (one
     // 512-thread workgroup per CU) ran a stage ~10 % slower than 2^11 tiles (four 128-thread workgroups per CU) and paid
@@ -392,10 +413,10 @@ bool make_plan_impl(int ansatz, int n, int layers, const PlanOptions& opt, Plan&
     o13.kmulti = 13;
     // (3 register wires: 2^13 tiles, one 1024-thread workgroup per CU; the caller checks the compact tables' eligibility
     // and falls back to the 4-wire plan otherwise)
-    if (opt.r == 3) return build_plan(spec, o13, plan, msg);
+    if (opt.r == 3) return build_plan(spec, o13, own_tile, plan, msg);
     Plan p13;
     std::string m13;
-    if (build_plan(spec, o13, p13, m13)) {
+    if (build_plan(spec, o13, own_tile, p13, m13)) {
       FastTables ft;
       // (2^11 tiles cannot address more than 2^27 amplitudes -- tile and workgroup indices are 16 bits: above that the
       // 2^13-tile plan runs on the generic kernel)
@@ -405,9 +426,9 @@ bool make_plan_impl(int ansatz, int n, int layers, const PlanOptions& opt, Plan&
         return true;
       }
     }
-    return build_plan(spec, o11, plan, msg);
+    return build_plan(spec, o11, own_tile, plan, msg);
   }
-  return build_plan(spec, opt, plan, msg);
+  return build_plan(spec, opt, own_tile, plan, msg);
 }
 }  // namespace
 
@@ -426,13 +447,46 @@ bool make_kron_plan(int n, const PlanOptions& opt, Plan& plan, std::string& msg)
   if (opt.kmulti == 0 && n - 12 > 16 && opt.kmax >= 13) {   // (the default 2^12 tiles leave a 17-bit workgroup index at n = 29)
     PlanOptions o13 = opt;
     o13.kmulti = 13;
-    return build_plan(spec, o13, plan, msg);
+    return build_plan(spec, o13, false, plan, msg);
   }
-  return build_plan(spec, opt, plan, msg);
+  return build_plan(spec, opt, false, plan, msg);
 }
 
 namespace {
-bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::string& msg) {
+bool build_plan_under(const BuildSpec& spec, const PlanOptions& opt, bool commute, Plan& plan, std::string& msg);
+
+// What a plan costs, in the order it is compared: passes (an HBM round trip of every state each), LDS stages, and LDS
+// stages outside the INIT pass.  (The INIT pass of a multi-tile plan reads nothing and writes only the tiles |0..0> reaches:
+// a stage there costs a fraction of a stage of a pass that moves every tile)
+std::array<long, 3> plan_cost(const Plan& p) {
+  long stages = 0, first = 0;
+  for (int i = 0; i < p.n_passes; ++i) {
+    const uint32_t* P = p.words.data() + p.pass_off[i];
+    stages += P[PW_NSTAGES];
+    if (i == 0 && (P[PW_FLAGS] & PASS_INIT) && p.n_passes > 1) first = P[PW_NSTAGES];
+  }
+  return {p.n_passes, stages, stages - first};
+}
+
+// The scans are greedy, so letting diagonal gates commute is not a gain in every circuit: both plans are built, the one
+// under the commutation rule is taken where it costs LESS without more passes or more stages (a pass saved for a stage
+// more would be a trade, and no trade is made here), and the program-order plan everywhere else -- so no circuit plans
+// worse than it did, and a circuit the rule gains nothing in keeps its plan word for word.  `may_commute` = false: the
+// program-order plan alone (make_plan_impl says where).
+bool build_plan(const BuildSpec& spec, const PlanOptions& opt, bool may_commute, Plan& plan, std::string& msg) {
+  const bool ok = build_plan_under(spec, opt, false, plan, msg);
+  bool two_qubit = false;
+  for (const Op& o : spec.ops) two_qubit |= o.kind != K_U1;
+  if (!may_commute || !two_qubit) return ok;
+  Plan pc;
+  std::string mc;
+  if (!build_plan_under(spec, opt, true, pc, mc)) return ok;
+  const std::array<long, 3> cc = plan_cost(pc), c0 = ok ? plan_cost(plan) : cc;
+  if (!ok || (cc < c0 && cc[1] <= c0[1])) { plan = std::move(pc); msg.clear(); }
+  return true;
+}
+
+bool build_plan_under(const BuildSpec& spec, const PlanOptions& opt, bool commute, Plan& plan, std::string& msg) {
   const int n = spec.n;
   const std::vector<Op>& ops = spec.ops;
   const std::vector<Fused>& fused = spec.fused;
@@ -452,7 +506,7 @@ bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::
     for (size_t i = 0; i < ops.size(); ++i) pool[i] = (int)i;
     std::vector<int> sel, rest, tg;
     while (!pool.empty()) {
-      choose_pass(ops, pool, n, k, sel, rest, tg);
+      choose_pass(ops, pool, n, k, commute, sel, rest, tg);
       if (sel.empty()) { msg = "planner made no progress"; return false; }
       PassInfo pi; pi.ops = sel; pi.targets = tg;
       passes.push_back(pi);
@@ -526,8 +580,8 @@ bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::
     // thread index, not from the register wires).  At least 2^4 contiguous elements are kept (256-byte runs).
     {
       std::vector<int> f_cur, l_cur, f_nxt, l_nxt;
-      first_last_stage_targets(ops, P.ops, n, r, i == 0 && !spec.in_state, f_cur, l_cur, opt.use_read_map());
-      first_last_stage_targets(ops, passes[i + 1].ops, n, r, false, f_nxt, l_nxt, opt.use_read_map());
+      first_last_stage_targets(ops, P.ops, n, r, i == 0 && !spec.in_state, commute, f_cur, l_cur, opt.use_read_map());
+      first_last_stage_targets(ops, passes[i + 1].ops, n, r, false, commute, f_nxt, l_nxt, opt.use_read_map());
       std::vector<char> busy(n, 0);
       for (int w : l_cur) busy[w] = 1;
       for (int w : f_nxt) busy[w] = 1;
@@ -679,10 +733,10 @@ bool build_plan(const BuildSpec& spec, const PlanOptions& opt, Plan& plan, std::
     //      the 2^r-element group a thread owns, so the in-place write-back needs no extra barrier.
     std::vector<int> pool = core, rest;
     uint32_t nstages = 0;
-    const bool defer_cx3 = pick_defer_policy(ops, core, n, r, opt.use_read_map());
+    const bool defer_cx3 = pick_defer_policy(ops, core, n, r, commute, opt.use_read_map());
     while (!pool.empty()) {
       StageSel sel;
-      stage_select(ops, pool, n, r, sel, rest, defer_cx3, opt.use_read_map());
+      stage_select(ops, pool, n, r, commute, sel, rest, defer_cx3, opt.use_read_map());
       if (sel.count() == 0) { msg = "stage planner made no progress"; return false; }
       // register wires: targets, padded with local wires (highest LDS bits first)
       std::vector<char> isr(n, 0);
