@@ -30,6 +30,8 @@
  *       ELBO weights, Fisher matrix ............................... 1 <= n <= 30;
  *       probability-table Born machine ............................ 0 <= n <= 30;
  *       matrix-product-state Born machine (bond 1 <= D <= 32) ..... 1 <= n <= 26;
+ *       sampled MPS calls, log joint and scores of samples,
+ *       pairwise Stein kernel row sums (n * length_scale >= 1) ..... 1 <= n <= 63;
  *       un-fused gate application ................................. 1 <= n <= 40.
  */
 #ifndef BORNVI_H
@@ -200,6 +202,35 @@ int bornvi_score_from_cpts(bornvi_handle h, const bornvi_bn_desc* bn, int n, dou
  * except while `stream` is being captured, where the kernel writes NaN instead. */
 int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx,
                                double p_floor, double* logp, bornvi_stream stream);
+
+/* ---- sampled KSD: no object of size 2^n -------------------------------------------------
+ * Stein score of p at sampled states: S dev [B, n] float64,
+ *   S[b, i] = 1 - prod_v max(f_v(flip_i z_b), p_floor) / max(f_v(z_b), p_floor),
+ * f_v node v's CPT factor, i the tuple position (position 0 = most significant bit of idx), the product over node i and
+ * its children only (every other factor cancels).  Every FACTOR is floored, as in bornvi_bn_logjoint_samples and for its
+ * reason.  There is NO "|p(x, z)| < 1e-12 -> zero row" rule here (bornvi_score_from_cpts and the reference have one): at
+ * n = 60 every legitimate joint lies below 1e-12.  The two agree wherever p(x, z) >= 1e-12 and no factor is below p_floor.
+ * logp dev [B] or NULL: when given, bit for bit what bornvi_bn_logjoint_samples writes.  1 <= n <= 63, 1 <= B <= 2^24,
+ * else BORNVI_ERR_UNSUPPORTED; a summed-out node is refused as by bornvi_bn_logjoint_samples (NaN while capturing).
+ * No allocation, no synchronisation. */
+int bornvi_bn_score_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx,
+                            double p_floor, double* S, double* logp, bornvi_stream stream);
+
+/* Row sums of the pairwise Stein kernel of B samples: r dev [B], r_b = sum_{b' != b} k_p(z_b, z_b' | x), total dev [1] =
+ * sum_b r_b; k_p as in bornvi_stein_kp_pairs, idx dev [B] int64, S dev [B, n] the score rows of the samples.  b' != b is
+ * by SAMPLE INDEX: a duplicate state z_b' = z_b with b' != b is included with k_p(z, z) (that is what makes
+ * total / (B (B - 1)) unbiased for q^T K_p q).  On v_mfma_f64_16x16x4_f64; fixed summation order, no atomics: two calls
+ * are bitwise equal; no allocation or synchronisation: capturable.
+ * 1 <= n <= 63, 2 <= B <= BORNVI_STEIN_PAIRS_MAX_B, n * length_scale >= 1 (in double), else BORNVI_ERR_UNSUPPORTED,
+ * returned before any launch. */
+#define BORNVI_STEIN_PAIRS_MAX_B (1 << 17)
+size_t bornvi_stein_pairs_workspace_bytes(bornvi_handle h, int n, long long B);
+int bornvi_stein_pairs_rowsum(bornvi_handle h, int n, long long B, double length_scale, const long long* idx,
+                              const double* S, double* r, double* total, void* workspace, size_t workspace_bytes,
+                              bornvi_stream stream);
+/* The geometry the row-sum kernel uses for B samples (a function of B only): 32-column tiles per column range, and the
+ * number G of column ranges = partials added per row by the finishing launch.  For error analyses and tests. */
+int bornvi_stein_pairs_geometry(long long B, int* tiles_per_range, int* num_ranges);
 
 /* ---- Stein-kernel Gram matrix (replaces the N^2 calls of get_stein_kernel_kp_value, --------
  * stein_utils.py:138-197 with base_hamming_kernel_torch :30-55, made in

@@ -7,7 +7,7 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
-           "SampledMPSBornMachine", "SampledELBOVariationalInference",
+           "SampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
            "generate_all_binary_outcomes", "calculate_tvd"]
 
 
@@ -42,4 +42,7 @@ def __getattr__(name):
     if name == "SampledELBOVariationalInference":
         from .elbo_vi_sampled import SampledELBOVariationalInference
         return SampledELBOVariationalInference
+    if name == "SampledKSDVariationalInference":
+        from .ksd_vi_sampled import SampledKSDVariationalInference
+        return SampledKSDVariationalInference
     raise AttributeError(name)

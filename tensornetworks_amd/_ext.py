@@ -122,6 +122,12 @@ _PROTOS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bornvi_bn_logjoint_samples": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_longlong, C.c_void_p, C.c_double,
                                              C.c_void_p, C.c_void_p]),
+    "bornvi_bn_score_samples": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_longlong, C.c_void_p, C.c_double,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bornvi_stein_pairs_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
+    "bornvi_stein_pairs_rowsum": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bornvi_stein_pairs_geometry": (C.c_int, [C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bornvi_fisher_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "bornvi_fisher_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),

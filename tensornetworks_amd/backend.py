@@ -746,6 +746,72 @@ def bn_logjoint_samples(desc, n, idx, p_floor=1e-30, out=None):
     return out
 
 
+# ---- sampled KSD: scores of p at sampled states, pairwise Stein kernel row sums -----------------------------
+STEIN_PAIRS_MAX_BATCH = 1 << 17
+
+
+def bn_score_samples(desc, n, idx, p_floor=1e-30, out=None, want_logp=False):
+    """Stein score of p at sampled latent states (bornvi_bn_score_samples): desc from bn_descriptor, idx int64 [B] on the
+    GPU -> S float64 [B, n], S[b, i] = 1 - prod_v max(f_v(flip_i z_b), p_floor) / max(f_v(z_b), p_floor) over node i's own
+    factor and its children's; with want_logp (S, logp [B]), logp bit-equal to bn_logjoint_samples.  Every factor is
+    floored; there is no zero row where p(x, z) < 1e-12 (score_from_packed has that rule; at n = 60 every joint is below it)."""
+    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
+    _chk_positive(p_floor, "p_floor")
+    if not torch.is_tensor(idx) or idx.dim() != 1 or not 1 <= int(idx.numel()) <= MPS_SAMPLED_MAX_BATCH:
+        raise BornviError("idx: expected a [B] int64 tensor, 1 <= B <= 2^24")
+    dev = idx.device
+    h = _ext.handle_for(dev)
+    B = int(idx.numel())
+    _chk(idx, torch.int64, dev, "idx")
+    if out is None:
+        out = torch.empty((B, int(n)), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", B * int(n))
+    logp = torch.empty(B, dtype=torch.float64, device=dev) if want_logp else None
+    h.call("bornvi_bn_score_samples", C.byref(desc), int(n), B, _ptr(idx), float(p_floor), _ptr(out),
+           _ptr(logp) if logp is not None else None, _ext.stream_ptr(dev))
+    return (out, logp) if want_logp else out
+
+
+def stein_pairs_geometry(B):
+    """(32-column tiles per column range, number of column ranges G) of stein_pairs_rowsum for B samples: a function of B
+    only; a row sum is G partials added in order, each a chain over its range's tiles (host only, no GPU needed)."""
+    per, G = C.c_int(0), C.c_int(0)
+    if _ext.lib().bornvi_stein_pairs_geometry(int(B), C.byref(per), C.byref(G)) != 0:
+        raise BornviError(f"stein_pairs_geometry: 2 <= B <= 2^17, got {B!r}")
+    return per.value, G.value
+
+
+def stein_pairs_rowsum(idx, S, n, length_scale=1.0, out=None, total=None):
+    """Row sums of the pairwise Stein kernel of B samples (bornvi_stein_pairs_rowsum): idx int64 [B], S float64 [B, n] the
+    samples' score rows -> (r float64 [B], r_b = sum over b' != b BY SAMPLE INDEX of k_p(z_b, z_b'), total float64 [1] =
+    sum_b r_b).  2 <= B <= 2^17, n * length_scale >= 1.  The workspace is cached per (n, B)."""
+    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
+    _chk_positive(length_scale, "length_scale")
+    if not float(int(n)) * float(length_scale) >= 1.0:
+        raise BornviError(f"stein_pairs_rowsum: n * length_scale >= 1 is required (the Gram form loses accuracy below it), "
+                          f"got {int(n)} * {length_scale!r}")
+    if not torch.is_tensor(idx) or idx.dim() != 1 or not 2 <= int(idx.numel()) <= STEIN_PAIRS_MAX_BATCH:
+        raise BornviError("idx: expected a [B] int64 tensor, 2 <= B <= 2^17")
+    dev = idx.device
+    h = _ext.handle_for(dev)
+    n, B = int(n), int(idx.numel())
+    _chk(idx, torch.int64, dev, "idx")
+    _chk(S, torch.float64, dev, "S", B * n)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", B)
+    if total is None:
+        total = torch.empty(1, dtype=torch.float64, device=dev)
+    else:
+        _chk(total, torch.float64, dev, "total", 1)
+    ws = _ws(dev, _cached_size(h, "bornvi_stein_pairs_workspace_bytes", n, B), f"stein_pairs_{n}_{B}")
+    h.call("bornvi_stein_pairs_rowsum", n, B, float(length_scale), _ptr(idx), _ptr(S), _ptr(out), _ptr(total), _ptr(ws),
+           ws.numel(), _ext.stream_ptr(dev))
+    return out, total
+
+
 # ---- natural gradient ---------------------------------------------------------------------------------
 FISHER_MAX_PARAMS = 1024
 

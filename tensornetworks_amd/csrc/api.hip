@@ -847,17 +847,12 @@ int bornvi_score_from_cpts(bornvi_handle h, const bornvi_bn_desc* bn, int n, dou
   return BORNVI_OK;
 }
 
-int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx, double p_floor,
-                               double* logp, bornvi_stream stream) {
-  if (!h) return BORNVI_ERR_INVALID;
-  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
-  if (!bn || !idx || !logp || !(p_floor > 0.0) || !std::isfinite(p_floor)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+// The descriptor checks of the per-sample network calls.  The roles live on the device.  Outside a stream capture they are
+// read back and a summed-out node is refused here; inside one no copy is allowed, and the kernels write NaN for such a descriptor.
+static int check_sample_descriptor(bornvi_handle h, const bornvi_bn_desc* bn, int n, bornvi_stream stream) {
   if (bn->num_nodes < 1 || bn->num_nodes > 64 || bn->max_parents < 1 || !bn->role || !bn->n_parents || !bn->parents ||
       !bn->cpt_off || !bn->cpt)
     return fail(h, BORNVI_ERR_INVALID, "bad network descriptor");
-  DEVICE_SCOPE(h);
-  // The roles live on the device.  Outside a stream capture they are read back and a summed-out node is refused here; inside
-  // one no copy is allowed, and the kernel writes NaN for such a descriptor.
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
   if (cap == hipStreamCaptureStatusNone) {
@@ -868,7 +863,56 @@ int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n,
       if (role[v] < -3 || role[v] >= n) return fail(h, BORNVI_ERR_INVALID, "bad network descriptor: role out of range");
     }
   }
+  return BORNVI_OK;
+}
+
+int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx, double p_floor,
+                               double* logp, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
+  if (!bn || !idx || !logp || !(p_floor > 0.0) || !std::isfinite(p_floor)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  DEVICE_SCOPE(h);
+  if (int rc = check_sample_descriptor(h, bn, n, stream)) return rc;
   HIPCHK(h, launch_bn_logjoint_samples(*bn, n, B, idx, p_floor, logp, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_bn_score_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx, double p_floor,
+                            double* S, double* logp, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
+  if (!bn || !idx || !S || !(p_floor > 0.0) || !std::isfinite(p_floor)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  DEVICE_SCOPE(h);
+  if (int rc = check_sample_descriptor(h, bn, n, stream)) return rc;
+  HIPCHK(h, launch_bn_score_samples(*bn, n, B, idx, p_floor, S, logp, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+static bool stein_pairs_supported(int n, long long B, double length_scale) {
+  return n >= 1 && n <= 63 && B >= 2 && B <= STEIN_PAIRS_MAX_B && std::isfinite(length_scale) && (double)n * length_scale >= 1.0;
+}
+
+size_t bornvi_stein_pairs_workspace_bytes(bornvi_handle h, int n, long long B) {
+  (void)h;
+  if (n < 1 || n > 63 || B < 2 || B > STEIN_PAIRS_MAX_B) return 0;
+  return stein_pairs_workspace_bytes(B);
+}
+
+int bornvi_stein_pairs_geometry(long long B, int* tiles_per_range, int* num_ranges) {
+  if (B < 2 || B > STEIN_PAIRS_MAX_B || !tiles_per_range || !num_ranges) return BORNVI_ERR_INVALID;
+  stein_pairs_geometry(B, tiles_per_range, num_ranges);
+  return BORNVI_OK;
+}
+
+int bornvi_stein_pairs_rowsum(bornvi_handle h, int n, long long B, double length_scale, const long long* idx, const double* S,
+                              double* r, double* total, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!stein_pairs_supported(n, B, length_scale))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 2 <= B <= 2^17, n * length_scale >= 1)");
+  if (!idx || !S || !r || !total) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < stein_pairs_workspace_bytes(B)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_stein_pairs_rowsum(n, B, length_scale, idx, S, r, total, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "plan.cpp"]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_ksd_sampled.hip", "plan.cpp"]
 HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "syrk_f64.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
@@ -59,6 +59,10 @@ RESOURCE_BUDGET = {
     "mps_score_kernel": (0, 0),
     "mps_score_finish_kernel": (0, 0),
     "bn_logjoint_kernel": (0, 0),
+    "bn_score_samples_kernel": (0, 0),            # sampled KSD (kernels_ksd_sampled.hip): the row side's A fragments (up to 48
+    "stein_pairs_prep_kernel": (0, 0),            # doubles per lane) and the tile in flight live in registers, no scratch
+    "stein_pairs_kernel": (0, 0),
+    "stein_pairs_finish_kernel": (0, 0),
     "circuit_pass_r3_kernelILb1": (0, 0),         # its fused-dot instantiation (last pass only): 8 weights more per thread, exactly
                                                   # 128 VGPRs; a scratch reload is a vector-memory load, and its wait is a wait for the
                                                   # whole prefetched tile (vmcnt retires in issue order)

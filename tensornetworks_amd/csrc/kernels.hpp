@@ -116,6 +116,15 @@ hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, 
 hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
                                       hipStream_t st);
 
+// ---- sampled KSD: scores of p at sampled states, pairwise Stein kernel row sums (kernels_ksd_sampled.hip) ----
+constexpr long long STEIN_PAIRS_MAX_B = 1ll << 17;   // B^2 is the cost: 1.7e10 pairs at the cap
+size_t stein_pairs_workspace_bytes(long long B);
+void stein_pairs_geometry(long long B, int* per_tiles, int* G);
+hipError_t launch_bn_score_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* S,
+                                   double* logp, hipStream_t st);
+hipError_t launch_stein_pairs_rowsum(int n, long long B, double length_scale, const long long* idx, const double* S, double* r,
+                                     double* total, void* ws, hipStream_t st);
+
 // ---- natural gradient: Fisher matrix of the stored parameter-shift rows, damped Cholesky solve (kernels_fisher.hip)
 size_t fisher_workspace_bytes(int n, int n_shift);
 hipError_t launch_fisher_gram(int n, const double* shifted, int n_shift, const double* q, double q_floor, double* F, void* ws,

@@ -4,126 +4,36 @@
 
 estimated from B exact samples per epoch, with the score-function gradient
   grad L = E[(f - b) grad log q],  f = log q - log p,  b the leave-one-out mean (unbiased):  w_b = (f_b - mean f) / (B - 1).
-An epoch: mps_environments, mps_sample (idx, log q), bn_logjoint_samples (log p), the mean and w as torch elementwise ops
-on B doubles, mps_score_vjp -> cores.grad; then the NaN/Inf guard, clip and Adam or SGD with cosine annealing through
-torch.optim on the float64 cores: the enumerated trainers' own make_optimizer and guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every epoch,
-the same ones on a rerun.
+An epoch (sampled_trainer.SampledTrainer owns it): mps_environments, mps_sample (idx, log q), bn_logjoint_samples (log p),
+the mean and w as torch elementwise ops on B doubles, mps_score_vjp -> cores.grad; then the guarded update.
 
 log p floors every CPT FACTOR at p_floor, where elbo_objective.ElboObjective floors the product p(x, z): at n = 60 a
 legitimate joint lies far below 1e-30.  The two agree whenever no factor is below the floor and the product is >= p_floor.
 Networks with summed-out nodes are refused (the enumerated trainers handle them).
 """
-import numpy as np
-import torch
-
 from . import backend
-from .bayesian_network import pack_network
-from .born_machine_mps_sampled import SampledMPSBornMachine
-from .ksd_vi import guarded_update, make_optimizer
+from .sampled_trainer import SampledTrainer
 
 
-class SampledELBOVariationalInference:
-    def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu',
-                 p_floor=1e-30):
-        cfg = dict(born_machine_config or {})
-        unknown = set(cfg) - {'bond_dim', 'num_samples', 'seed', 'init_method'}
-        if unknown:
-            raise ValueError(f"born_machine_config: unknown keys {sorted(unknown)}")
-        B = cfg.get('num_samples', 1024)
-        if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= backend.MPS_SAMPLED_MAX_BATCH:
-            raise ValueError(f"num_samples must be an integer in 1 ... 2^24, got {B!r}")
-        if isinstance(p_floor, bool) or not isinstance(p_floor, (int, float)) or not np.isfinite(p_floor) or not p_floor > 0:
-            raise ValueError(f"p_floor must be a positive finite number, got {p_floor!r}")
-        self.bn = bayesian_network
-        self.latent_vars_names = list(latent_vars_names)
-        self.observed_vars_names = list(observed_vars_names)
-        self.num_latent_vars = len(self.latent_vars_names)
-        self.num_observed_vars = len(self.observed_vars_names)
-        self.num_samples = B
-        self.seed = cfg.get('seed', 0)
-        self.p_floor = float(p_floor)
-        self.device = torch.device(device)
-        self.born_machine = SampledMPSBornMachine(self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4),
-                                                  init_method=cfg.get('init_method', 'small_random'),
-                                                  seed=self.seed).to(self.device)
-        self._desc = None
-        self.last_idx = None
-
-    def _prepare_observation(self, x_dict):
-        packed = pack_network(self.bn, self.latent_vars_names, x_dict)
-        if (packed["role"] == -3).any():
-            raise ValueError("a network node is neither latent nor observed: the sampled trainer has no log joint per "
-                             "sample for summed-out nodes (use the enumerated trainers)")
-        dev = backend.compute_device(self.device)
-        self._desc = backend.bn_descriptor(packed, dev)          # (device arrays kept alive, descriptor)
-        self._epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+class SampledELBOVariationalInference(SampledTrainer):
+    """History: loss_elbo (the estimate of L), grad_norm, logq_mean, status, and for n <= 26 with a posterior: tvd and kl."""
+    LOSS_KEYS = ('loss_elbo',)
 
     def log_joint(self, idx):
         """log p(x, z_b) of outcome indices, every factor floored at p_floor: float64 [B] on the compute device."""
         return backend.bn_logjoint_samples(self._desc[1], self.num_latent_vars, idx, self.p_floor)
 
-    def loss_and_grad(self, epoch):
-        """Device part of one epoch -> (loss [] float64 = mean f, grad float64 [n, 2, D, D], logq mean [], status [1] int32:
-        the sampler's and the gradient's status words or-ed).  Nothing is read back to the host."""
-        bm = self.born_machine
-        cores, _ = bm.kernel_input()
+    def sample_weights(self, idx, logq):
+        """(loss [] = mean f, w [B])."""
         B = self.num_samples
-        self._epoch_dev.fill_(int(epoch))
-        backend.mps_environments(cores, B)
-        idx, logq, st_s = backend.mps_sample(cores, B, self.seed, self._epoch_dev)
         logp = self.log_joint(idx)
         f = logq - logp
         loss = f.mean()
         w = (f - loss) / (B - 1) if B > 1 else f.clone()
-        grad, _, st_g = backend.mps_score_vjp(cores, idx, w.contiguous())
-        self.last_idx = idx
-        return loss, grad, logq.mean(), st_s | st_g
+        return loss, w
 
-    def train(self, x_observation_dict, num_epochs, lr_born_machine, verbose=True, true_posterior_for_tvd=None,
-              use_lr_scheduler=True, gradient_clip_norm=10.0, optimizer_type="adam", adam_betas=(0.9, 0.999)):
-        """The arguments of elbo_vi's train() that make sense here (no entropy_weight, no early stopping).
-        true_posterior_for_tvd: a float tensor [2^n] (stein_utils.true_posterior_table), honoured for n <= 26 only, where
-        q is enumerated by mps_probs for the report.  History: loss_elbo (the estimate of L), grad_norm, logq_mean, status,
-        and for n <= 26 with a posterior: tvd and kl (= exact KL(q || posterior))."""
-        if self.num_observed_vars > 0 and set(x_observation_dict.keys()) != set(self.observed_vars_names):
-            raise ValueError("Keys in x_observation_dict must match self.observed_vars_names.")
-        bm = self.born_machine
-        self._prepare_observation(x_observation_dict)
-        opt, sched = make_optimizer(bm.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas)
-        exact = true_posterior_for_tvd is not None and self.num_latent_vars <= backend.MPS_MAX_N
-        history = {'loss_elbo': [], 'grad_norm': [], 'logq_mean': [], 'status': []}
-        if exact:
-            history['tvd'], history['kl'] = [], []
-        grad_norm = None
-        for epoch in range(num_epochs):
-            opt.zero_grad()
-            loss_t, grad, lq_t, st_t = self.loss_and_grad(epoch)
-            loss = float(loss_t.item())                       # the epoch's host synchronisation
-            grads = [(bm.cores, grad.to(device=bm.cores.device, dtype=bm.cores.dtype))]
-            grad_norm = guarded_update(bm, opt, sched, loss, grads, gradient_clip_norm, grad_norm)
-            history['loss_elbo'].append(loss)
-            history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
-            history['logq_mean'].append(float(lq_t.item()))
-            history['status'].append(int(st_t.item()))
-            if exact:
-                tvd, kl = self.exact_report(true_posterior_for_tvd)
-                history['tvd'].append(tvd)
-                history['kl'].append(kl)
-            if verbose and (epoch % max(1, num_epochs // 20) == 0 or epoch == num_epochs - 1):
-                msg = f"Epoch {epoch+1}/{num_epochs} | ELBO (sampled): {loss:.6f} | mean log q: {history['logq_mean'][-1]:.4f}"
-                if sched is not None:
-                    msg += f" | LR: {sched.get_last_lr()[0]:.6f}"
-                if exact:
-                    msg += f" | TVD: {history['tvd'][-1]:.6f} | KL: {history['kl'][-1]:.6f}"
-                print(msg)
-        return history
+    def record_loss(self, history, loss):
+        history['loss_elbo'].append(loss)
 
-    def exact_report(self, posterior):
-        """(TVD, KL(q || posterior)) of the current cores against a posterior table [2^n], by enumeration (n <= 26)."""
-        with torch.no_grad():
-            q = self.born_machine.probabilities64().detach()
-            p = posterior.to(device=q.device, dtype=torch.float64).reshape(-1)
-            tvd = 0.5 * (q - p).abs().sum()
-            m = q > 0
-            kl = (q[m] * (torch.log(q[m]) - torch.log(p[m].clamp(min=1e-300)))).sum()
-        return float(tvd), float(kl)
+    def describe(self, loss):
+        return f"ELBO (sampled): {loss:.6f}"

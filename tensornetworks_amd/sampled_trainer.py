@@ -1,0 +1,140 @@
+"""The epoch of the sampled MPS trainers, owned once: no 2^n object at any n <= 63.
+
+An epoch: mps_environments, mps_sample with (seed, epoch) -> (idx, log q); the objective's weights w_b from the samples
+(the subclass: `sample_weights`); mps_score_vjp -> sum_b w_b grad log q(z_b); then the NaN/Inf guard, clip and Adam or SGD
+with cosine annealing through torch.optim on the float64 cores: the enumerated trainers' own make_optimizer and
+guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every epoch, the same ones on a rerun.
+
+A subclass supplies
+  LOSS_KEYS                     the history keys it fills per epoch, MIN_SAMPLES / MAX_SAMPLES and their wording,
+  sample_weights(idx, logq)     -> (loss [] float64, w [B] float64) on the device, nothing read back,
+  record_loss(history, loss)    the epoch's entries of LOSS_KEYS from the loss as a float,
+  describe(loss)                the loss part of the progress line.
+SampledELBOVariationalInference (elbo_vi_sampled.py) and SampledKSDVariationalInference (ksd_vi_sampled.py) are the two.
+Networks with summed-out nodes are refused (the enumerated trainers handle them).
+"""
+import numpy as np
+import torch
+
+from . import backend
+from .bayesian_network import pack_network
+from .born_machine_mps_sampled import SampledMPSBornMachine
+from .ksd_vi import guarded_update, make_optimizer
+
+
+class SampledTrainer:
+    LOSS_KEYS = ()
+    MIN_SAMPLES = 1
+    MAX_SAMPLES = backend.MPS_SAMPLED_MAX_BATCH
+    SAMPLES_RANGE = "1 ... 2^24"
+
+    def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu',
+                 p_floor=1e-30):
+        cfg = dict(born_machine_config or {})
+        unknown = set(cfg) - {'bond_dim', 'num_samples', 'seed', 'init_method'}
+        if unknown:
+            raise ValueError(f"born_machine_config: unknown keys {sorted(unknown)}")
+        B = cfg.get('num_samples', 1024)
+        if isinstance(B, bool) or not isinstance(B, int) or not self.MIN_SAMPLES <= B <= self.MAX_SAMPLES:
+            raise ValueError(f"num_samples must be an integer in {self.SAMPLES_RANGE}, got {B!r}")
+        if isinstance(p_floor, bool) or not isinstance(p_floor, (int, float)) or not np.isfinite(p_floor) or not p_floor > 0:
+            raise ValueError(f"p_floor must be a positive finite number, got {p_floor!r}")
+        self.bn = bayesian_network
+        self.latent_vars_names = list(latent_vars_names)
+        self.observed_vars_names = list(observed_vars_names)
+        self.num_latent_vars = len(self.latent_vars_names)
+        self.num_observed_vars = len(self.observed_vars_names)
+        self.num_samples = B
+        self.seed = cfg.get('seed', 0)
+        self.p_floor = float(p_floor)
+        self.device = torch.device(device)
+        self.born_machine = SampledMPSBornMachine(self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4),
+                                                  init_method=cfg.get('init_method', 'small_random'),
+                                                  seed=self.seed).to(self.device)
+        self._desc = None
+        self.last_idx = None
+
+    def _prepare_observation(self, x_dict):
+        packed = pack_network(self.bn, self.latent_vars_names, x_dict)
+        if (packed["role"] == -3).any():
+            raise ValueError("a network node is neither latent nor observed: the sampled trainer has no log joint per "
+                             "sample for summed-out nodes (use the enumerated trainers)")
+        dev = backend.compute_device(self.device)
+        self._desc = backend.bn_descriptor(packed, dev)          # (device arrays kept alive, descriptor)
+        self._epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def draw(self, epoch):
+        """The epoch's exact samples -> (cores, idx int64 [B], logq float64 [B], status int32 [1]), all on the device."""
+        cores, _ = self.born_machine.kernel_input()
+        B = self.num_samples
+        self._epoch_dev.fill_(int(epoch))
+        backend.mps_environments(cores, B)
+        idx, logq, st_s = backend.mps_sample(cores, B, self.seed, self._epoch_dev)
+        return cores, idx, logq, st_s
+
+    def sample_weights(self, idx, logq):
+        raise NotImplementedError
+
+    def loss_and_grad(self, epoch):
+        """Device part of one epoch -> (loss [] float64, grad float64 [n, 2, D, D], logq mean [], status [1] int32: the
+        sampler's and the gradient's status words or-ed).  Nothing is read back to the host."""
+        cores, idx, logq, st_s = self.draw(epoch)
+        loss, w = self.sample_weights(idx, logq)
+        grad, _, st_g = backend.mps_score_vjp(cores, idx, w.contiguous())
+        self.last_idx = idx
+        return loss, grad, logq.mean(), st_s | st_g
+
+    def record_loss(self, history, loss):
+        raise NotImplementedError
+
+    def describe(self, loss):
+        raise NotImplementedError
+
+    def train(self, x_observation_dict, num_epochs, lr_born_machine, verbose=True, true_posterior_for_tvd=None,
+              use_lr_scheduler=True, gradient_clip_norm=10.0, optimizer_type="adam", adam_betas=(0.9, 0.999)):
+        """The arguments of elbo_vi's train() that make sense here (no entropy_weight, no early stopping).
+        true_posterior_for_tvd: a float tensor [2^n] (stein_utils.true_posterior_table), honoured for n <= 26 only, where
+        q is enumerated by mps_probs for the report.  History: the trainer's LOSS_KEYS, grad_norm, logq_mean, status,
+        and for n <= 26 with a posterior: tvd and kl (= exact KL(q || posterior))."""
+        if self.num_observed_vars > 0 and set(x_observation_dict.keys()) != set(self.observed_vars_names):
+            raise ValueError("Keys in x_observation_dict must match self.observed_vars_names.")
+        bm = self.born_machine
+        self._prepare_observation(x_observation_dict)
+        opt, sched = make_optimizer(bm.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas)
+        exact = true_posterior_for_tvd is not None and self.num_latent_vars <= backend.MPS_MAX_N
+        history = {k: [] for k in self.LOSS_KEYS + ('grad_norm', 'logq_mean', 'status')}
+        if exact:
+            history['tvd'], history['kl'] = [], []
+        grad_norm = None
+        for epoch in range(num_epochs):
+            opt.zero_grad()
+            loss_t, grad, lq_t, st_t = self.loss_and_grad(epoch)
+            loss = float(loss_t.item())                       # the epoch's host synchronisation
+            grads = [(bm.cores, grad.to(device=bm.cores.device, dtype=bm.cores.dtype))]
+            grad_norm = guarded_update(bm, opt, sched, loss, grads, gradient_clip_norm, grad_norm)
+            self.record_loss(history, loss)
+            history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
+            history['logq_mean'].append(float(lq_t.item()))
+            history['status'].append(int(st_t.item()))
+            if exact:
+                tvd, kl = self.exact_report(true_posterior_for_tvd)
+                history['tvd'].append(tvd)
+                history['kl'].append(kl)
+            if verbose and (epoch % max(1, num_epochs // 20) == 0 or epoch == num_epochs - 1):
+                msg = f"Epoch {epoch+1}/{num_epochs} | {self.describe(loss)} | mean log q: {history['logq_mean'][-1]:.4f}"
+                if sched is not None:
+                    msg += f" | LR: {sched.get_last_lr()[0]:.6f}"
+                if exact:
+                    msg += f" | TVD: {history['tvd'][-1]:.6f} | KL: {history['kl'][-1]:.6f}"
+                print(msg)
+        return history
+
+    def exact_report(self, posterior):
+        """(TVD, KL(q || posterior)) of the current cores against a posterior table [2^n], by enumeration (n <= 26)."""
+        with torch.no_grad():
+            q = self.born_machine.probabilities64().detach()
+            p = posterior.to(device=q.device, dtype=torch.float64).reshape(-1)
+            tvd = 0.5 * (q - p).abs().sum()
+            m = q > 0
+            kl = (q[m] * (torch.log(q[m]) - torch.log(p[m].clamp(min=1e-300)))).sum()
+        return float(tvd), float(kl)
