@@ -485,6 +485,44 @@ size_t bornvi_spd_solve_workspace_bytes(bornvi_handle h, int P);
 int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, const double* b, double* x, int* info,
                      void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
+/* bornvi_spd_solve_batched: nb independent systems (A[j] + damping I) x[j] = b[j], one workgroup per system in one launch.
+ * A dev [nb, P, P], b, x dev [nb, P], info dev [nb] int32.  System j has the operation order, the info codes and the
+ * "x = b where info != 0" rule of bornvi_spd_solve: it equals that call on (A[j], b[j]) bit for bit.  1 <= P <= 1024,
+ * 1 <= nb <= 65535 (else BORNVI_ERR_UNSUPPORTED before any launch), damping >= 0.  No allocation or synchronisation
+ * (capturable).  Workspace: bornvi_spd_solve_batched_workspace_bytes(h, P, nb) (nb factors of P x P). */
+size_t bornvi_spd_solve_batched_workspace_bytes(bornvi_handle h, int P, int nb);
+int bornvi_spd_solve_batched(bornvi_handle h, int P, int nb, const double* A, double damping, const double* b, double* x,
+                             int* info, void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
+/* ---- natural gradient of the sampled MPS Born machine: the sampled Fisher estimate is a Gram of
+ * per-sample score rows (stochastic reconfiguration).
+ * bornvi_mps_score_rows, after bornvi_mps_environments on the same (n, D, B) workspace: for the sites k_begin ..
+ * k_begin + k_count - 1 (counted from 0: site j uses cores[j]) and the samples idx dev [B],
+ *   rows[j - k_begin][(s D + a) D + c][b] = 2 [z_b,j = s] l_b[a] r_b[c] / psi_b - mu[j][s][a][c],  mu = 2 (L A_j[s] E)[a][c] / Z
+ * (l_b the left vector of sample b in front of site j, r_b the right vector behind it, L and E the environments there): the
+ * centred score of sample b with respect to cores[j][s][a][c]; mu is the exact mean of the first term under q.
+ * rows dev [k_count, 2 D^2, ld] float64, 16-byte aligned; ld a power of two, >= 64 and >= B (what bornvi_score_fisher_gram
+ * takes); the columns B .. ld - 1 are written as 0.0.  A sample with psi = 0 or not finite gets an all-zero column and
+ * status (dev [1] int32) becomes 2, else 0.  Sites outside the range are swept and not written, so the caller bounds
+ * the buffer.  2 <= B <= 2^24, 1 <= n <= 63, 1 <= D <= 32, else BORNVI_ERR_UNSUPPORTED before any launch.  No atomics, no
+ * allocation or synchronisation (capturable); two calls are bitwise equal, and a sub-range equals the same slice of a
+ * whole call bit for bit.  mu lives in a region of its own at the end of the (n, D, B) workspace:
+ * bornvi_mps_sample_workspace_bytes counts it (16 n D^2 bytes more than before, for every caller).
+ * bornvi_score_fisher_gram: F[j] = (1 / B) X_j X_j^T for nblocks consecutive blocks X_j of R rows x ld columns of `rows`
+ * (site blocks: R = 2 D^2, nblocks = sites; the whole matrix: R = 2 n D^2, nblocks = 1, over the same buffer).
+ * F dev [nblocks, R, R] float64.  The split-K SYRK of bornvi_fisher_gram on the fp64 matrix cores with a plain row source;
+ * slab partials go to the workspace, a finishing launch adds them in index order, divides by B once and writes F_ab and
+ * F_ba from one value (F == F^T bitwise; no atomics: two calls are bitwise equal).  An entry's order of summation depends
+ * on ld only: a site block equals the diagonal block of the whole matrix bit for bit.  1 <= R <= 1024, 1 <= nblocks <=
+ * 65535, 2 <= B <= ld, else BORNVI_ERR_UNSUPPORTED before any launch.  Workspace:
+ * bornvi_score_fisher_workspace_bytes(h, R, nblocks, ld). */
+int bornvi_mps_score_rows(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx,
+                          int k_begin, int k_count, long long ld, double* rows, int* status, void* workspace,
+                          size_t workspace_bytes, bornvi_stream stream);
+size_t bornvi_score_fisher_workspace_bytes(bornvi_handle h, int R, int nblocks, long long ld);
+int bornvi_score_fisher_gram(bornvi_handle h, int R, int nblocks, long long B, long long ld, const double* rows, double* F,
+                             void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
 /* ---- quantum natural gradient: the Fubini-Study metric instead of the classical Fisher matrix (what PennyLane's
  * QNGOptimizer preconditions with; no reference counterpart).  Every parameter enters exactly one gate exp(-i theta s / 2),
  * so d_a psi = 1/2 psi(theta + pi e_a).

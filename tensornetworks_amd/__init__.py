@@ -8,7 +8,7 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
            "SampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
-           "generate_all_binary_outcomes", "calculate_tvd"]
+           "SampledFisherPreconditioner", "generate_all_binary_outcomes", "calculate_tvd"]
 
 
 def __getattr__(name):
@@ -45,4 +45,7 @@ def __getattr__(name):
     if name == "SampledKSDVariationalInference":
         from .ksd_vi_sampled import SampledKSDVariationalInference
         return SampledKSDVariationalInference
+    if name == "SampledFisherPreconditioner":
+        from .natural_gradient import SampledFisherPreconditioner
+        return SampledFisherPreconditioner
     raise AttributeError(name)

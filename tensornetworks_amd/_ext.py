@@ -134,6 +134,14 @@ _PROTOS = {
     "bornvi_spd_solve_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "bornvi_spd_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
+    "bornvi_spd_solve_batched_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "bornvi_spd_solve_batched": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bornvi_mps_score_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bornvi_score_fisher_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_longlong]),
+    "bornvi_score_fisher_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     "bornvi_paramshift_states_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bornvi_paramshift_states": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -883,6 +883,115 @@ def spd_solve(A, b, damping=0.0, out=None, info=None):
     return out, info
 
 
+def spd_solve_batched(A, b, damping=0.0, out=None, info=None):
+    """nb independent systems (A[j] + damping I) x[j] = b[j] in one launch (bornvi_spd_solve_batched): A float64 [nb, P, P],
+    b float64 [nb, P] -> (x float64 [nb, P], info int32 [nb]).  System j is bit for bit what spd_solve gives on (A[j], b[j]),
+    with its info codes and its rule x[j] = b[j] where info[j] != 0.  Capturable once the stream's workspace exists."""
+    if not torch.is_tensor(A) or not torch.is_tensor(b) or A.dim() != 3 or A.shape[1] != A.shape[2] or b.dim() != 2 \
+            or b.shape[0] != A.shape[0]:
+        raise BornviError("spd_solve_batched: A must be a [nb, P, P] tensor and b a [nb, P] tensor")
+    nb, P = int(A.shape[0]), int(A.shape[1])
+    if not 1 <= P <= FISHER_MAX_PARAMS:
+        raise BornviError(f"A: 1 ... {FISHER_MAX_PARAMS} rows per system, got {P}")
+    if not 1 <= nb <= 65535:
+        raise BornviError(f"A: 1 ... 65535 systems, got {nb}")
+    _chk_positive(damping, "damping", allow_zero=True)
+    dev = A.device
+    h = _ext.handle_for(dev)
+    _chk(A, torch.float64, dev, "A")
+    _chk(b, torch.float64, dev, "b", nb * P)
+    if out is None:
+        out = torch.empty((nb, P), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", nb * P)
+    if info is None:
+        info = torch.empty(nb, dtype=torch.int32, device=dev)
+    else:
+        _chk(info, torch.int32, dev, "info", nb)
+    ws = _ws(dev, _cached_size(h, "bornvi_spd_solve_batched_workspace_bytes", P, nb), "spd_solve_batched")
+    h.call("bornvi_spd_solve_batched", P, nb, _ptr(A), float(damping), _ptr(b), _ptr(out), _ptr(info), _ptr(ws), ws.numel(),
+           _ext.stream_ptr(dev))
+    return out, info
+
+
+# ---- natural gradient of the sampled MPS Born machine ---------------------------------------------------
+SCORE_ROWS_MIN_BATCH = 2
+
+
+def score_rows_ld(num_samples):
+    """Leading dimension of the score rows of B samples: the power of two >= max(B, 64) (what score_fisher_gram takes)."""
+    return max(64, 1 << (int(num_samples) - 1).bit_length())
+
+
+def mps_score_rows(cores, idx, k_begin=0, k_count=None, out=None, status=None):
+    """Per-sample score rows of an MPS Born machine (bornvi_mps_score_rows), after mps_environments(cores, len(idx)):
+    -> (rows float64 [k_count, 2 D^2, ld], status int32 [1]) for the sites k_begin .. k_begin + k_count - 1 (from 0),
+    rows[j, (s D + a) D + c, b] = d log q(idx_b) / d cores[k_begin + j, s, a, c] in centred form (2 [z = s] l r / psi - mu with
+    mu its exact mean under q), ld = score_rows_ld(B), the columns B .. ld - 1 exactly 0.0.  status: 0, or 2 when some
+    psi(idx_b) is 0 or not finite (that sample's column is all 0.0).  B >= 2."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    n, D, B = _mps_args(cores, int(idx.numel()))
+    if B < SCORE_ROWS_MIN_BATCH:
+        raise BornviError(f"mps_score_rows: at least {SCORE_ROWS_MIN_BATCH} samples, got {B}")
+    if k_count is None:
+        k_count = n - int(k_begin)
+    if isinstance(k_begin, bool) or isinstance(k_count, bool) or not isinstance(k_begin, (int, np.integer)) \
+            or not isinstance(k_count, (int, np.integer)) or k_begin < 0 or k_count < 1 or k_begin + k_count > n:
+        raise BornviError(f"mps_score_rows: sites {k_begin!r} .. + {k_count!r} are not a range of the {n} sites")
+    k_begin, k_count = int(k_begin), int(k_count)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    ld, R = score_rows_ld(B), 2 * D * D
+    if out is None:
+        out = torch.empty((k_count, R, ld), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", k_count * R * ld)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(status, torch.int32, dev, "status", 1)
+    ws = _mps_sampled_ws(h, dev, n, D, B)
+    h.call("bornvi_mps_score_rows", n, D, B, _ptr(cores), _ptr(idx), k_begin, k_count, ld, _ptr(out), _ptr(status), _ptr(ws),
+           ws.numel(), _ext.stream_ptr(dev))
+    return out, status
+
+
+def score_fisher_workspace_bytes(dev, R, nblocks, ld):
+    return _cached_size(_ext.handle_for(dev), "bornvi_score_fisher_workspace_bytes", int(R), int(nblocks), int(ld))
+
+
+def score_fisher_gram(rows, num_samples, out=None):
+    """Sampled Fisher estimate from score rows (bornvi_score_fisher_gram): rows float64 [nblocks, R, ld] (ld a power of two
+    >= 64, the columns num_samples .. ld - 1 zero) -> F float64 [nblocks, R, R], F[j] = rows[j] rows[j]^T / num_samples on the
+    fp64 matrix cores.  F[j] == F[j].T bitwise; two calls are bitwise equal; an entry's order of summation depends on ld
+    only.  1 <= R <= 1024.  Capturable once the stream's workspace exists."""
+    if not torch.is_tensor(rows) or rows.dim() != 3:
+        raise BornviError("score_fisher_gram: rows must be an [nblocks, R, ld] tensor")
+    nblocks, R, ld = (int(v) for v in rows.shape)
+    B = num_samples
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not SCORE_ROWS_MIN_BATCH <= int(B) <= ld:
+        raise BornviError(f"number of samples: {SCORE_ROWS_MIN_BATCH} ... ld = {ld}, got {B!r}")
+    if not 1 <= R <= FISHER_MAX_PARAMS:
+        raise BornviError(f"rows: 1 ... {FISHER_MAX_PARAMS} rows per block, got {R}")
+    if not 1 <= nblocks <= 65535:
+        raise BornviError(f"rows: 1 ... 65535 blocks, got {nblocks}")
+    if ld < 64 or ld & (ld - 1) or ld > MPS_SAMPLED_MAX_BATCH:
+        raise BornviError(f"rows: the leading dimension must be a power of two in 64 ... 2^24, got {ld}")
+    dev = rows.device
+    h = _ext.handle_for(dev)
+    _chk(rows, torch.float64, dev, "rows")
+    if out is None:
+        out = torch.empty((nblocks, R, R), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", nblocks * R * R)
+    ws = _ws(dev, _cached_size(h, "bornvi_score_fisher_workspace_bytes", R, nblocks, ld), "score_fisher")
+    h.call("bornvi_score_fisher_gram", R, nblocks, int(B), ld, _ptr(rows), _ptr(out), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out
+
+
 def paramshift_states_bytes(n, count, include_base=True):
     """Bytes of the rows paramshift_states writes: 16 (count + base) 2^n."""
     return 16 * (int(count) + (1 if include_base else 0)) << int(n)

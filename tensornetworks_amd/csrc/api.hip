@@ -1287,6 +1287,48 @@ int bornvi_mps_score_vjp(bornvi_handle h, int n, int D, long long B, const doubl
   return BORNVI_OK;
 }
 
+static bool valid_ld(long long ld, long long B) { return ld >= 64 && ld <= (1ll << 24) && (ld & (ld - 1)) == 0 && ld >= B; }
+static const char* const SCORE_LD_RANGE = "ld must be a power of two, 64 <= ld <= 2^24, ld >= B";
+
+int bornvi_mps_score_rows(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, int k_begin,
+                          int k_count, long long ld, double* rows, int* status, void* workspace, size_t workspace_bytes,
+                          bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_sample(n, D, B) || B < 2) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= D <= 32, 2 <= B <= 2^24)");
+  if (!valid_ld(ld, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_LD_RANGE);
+  if (k_begin < 0 || k_count < 1 || (long long)k_begin + k_count > n) return fail(h, BORNVI_ERR_INVALID, "site range out of bounds");
+  if (!cores || !idx || !rows || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (((uintptr_t)rows) & 15) return fail(h, BORNVI_ERR_INVALID, "rows must be 16-byte aligned");
+  if (!workspace || workspace_bytes < mps_sample_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_score_rows(n, D, B, cores, idx, k_begin, k_count, ld, rows, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+static bool valid_score_fisher(int R, int nblocks) { return R >= 1 && R <= 1024 && nblocks >= 1 && nblocks <= 65535; }
+static const char* const SCORE_FISHER_RANGE = "unsupported size (1 <= R <= 1024, 1 <= nblocks <= 65535)";
+
+size_t bornvi_score_fisher_workspace_bytes(bornvi_handle h, int R, int nblocks, long long ld) {
+  if (!h) return 0;
+  if (!valid_score_fisher(R, nblocks)) { fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_FISHER_RANGE); return 0; }
+  if (!valid_ld(ld, 0)) { fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_LD_RANGE); return 0; }
+  return score_fisher_workspace_bytes(R, nblocks, ld);
+}
+
+int bornvi_score_fisher_gram(bornvi_handle h, int R, int nblocks, long long B, long long ld, const double* rows, double* F,
+                             void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_score_fisher(R, nblocks)) return fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_FISHER_RANGE);
+  if (B < 2 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (2 <= B <= 2^24)");
+  if (!valid_ld(ld, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_LD_RANGE);
+  if (!rows || !F) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (((uintptr_t)rows) & 15) return fail(h, BORNVI_ERR_INVALID, "rows must be 16-byte aligned");
+  if (!workspace || workspace_bytes < score_fisher_workspace_bytes(R, nblocks, ld)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_score_fisher_gram(R, nblocks, B, ld, rows, F, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 static bool valid_fisher(int n, int n_shift) { return n >= 1 && n <= 30 && n_shift >= 1 && n_shift <= 1024; }
 
 size_t bornvi_fisher_workspace_bytes(bornvi_handle h, int n, int n_shift) {
@@ -1323,6 +1365,26 @@ int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, co
   if (!workspace || workspace_bytes < spd_solve_workspace_bytes(P)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_spd_solve(P, A, damping, b, x, info, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+static bool valid_spd_batched(int P, int nb) { return P >= 1 && P <= 1024 && nb >= 1 && nb <= 65535; }
+
+size_t bornvi_spd_solve_batched_workspace_bytes(bornvi_handle h, int P, int nb) {
+  if (!h) return 0;
+  if (!valid_spd_batched(P, nb)) { fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= P <= 1024, 1 <= nb <= 65535)"); return 0; }
+  return spd_solve_batched_workspace_bytes(P, nb);
+}
+
+int bornvi_spd_solve_batched(bornvi_handle h, int P, int nb, const double* A, double damping, const double* b, double* x, int* info,
+                             void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_spd_batched(P, nb)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= P <= 1024, 1 <= nb <= 65535)");
+  if (!(damping >= 0.0) || !std::isfinite(damping)) return fail(h, BORNVI_ERR_INVALID, "damping must be finite and >= 0");
+  if (!A || !b || !x || !info) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < spd_solve_batched_workspace_bytes(P, nb)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_spd_solve_batched(P, nb, A, damping, b, x, info, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

@@ -42,7 +42,9 @@ RESOURCE_BUDGET = {
     "elbo_finish_kernel": (0, 0),
     "fisher_gram_kernel": (0, 0),                 # natural gradient (kernels_fisher.hip): no scratch anywhere
     "fisher_finish_kernel": (0, 0),
-    "spd_solve_kernel": (0, 0),
+    "spd_solve_kernel": (0, 0),                   # both instantiations: the single solve and one workgroup per system
+    "score_gram_kernel": (0, 0),                  # Gram of the score rows: the Fisher kernel's tile with a plain row source
+    "score_gram_finish_kernel": (0, 0),
     "qfi_gram_kernel": (0, 0),                    # quantum natural gradient (kernels_qfi.hip): no scratch anywhere
     "qfi_finish_kernel": (0, 0),
     "state_tail_kernel": (0, 0),
@@ -58,6 +60,8 @@ RESOURCE_BUDGET = {
     "mps_sample_kernel": (0, 0),
     "mps_score_kernel": (0, 0),
     "mps_score_finish_kernel": (0, 0),
+    "mps_score_mu_kernel": (0, 0),                # score rows of the sampled Fisher estimate: l in registers, l and r of the
+    "mps_score_rows_kernel": (0, 0),              # site through LDS, no scratch
     "bn_logjoint_kernel": (0, 0),
     "bn_score_samples_kernel": (0, 0),            # sampled KSD (kernels_ksd_sampled.hip): the row side's A fragments (up to 48
     "stein_pairs_prep_kernel": (0, 0),            # doubles per lane) and the tile in flight live in registers, no scratch

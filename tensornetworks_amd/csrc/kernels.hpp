@@ -113,6 +113,8 @@ hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, uns
                              long long* idx, double* logq, int* status, void* ws, hipStream_t st);
 hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
                                 double* grad_cores, int* status, void* ws, hipStream_t st);
+hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores, const long long* idx, int k_begin, int k_count,
+                                 long long ld, double* rows, int* status, void* ws, hipStream_t st);
 hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
                                       hipStream_t st);
 
@@ -131,6 +133,12 @@ hipError_t launch_fisher_gram(int n, const double* shifted, int n_shift, const d
                               hipStream_t st);
 size_t spd_solve_workspace_bytes(int P);
 hipError_t launch_spd_solve(int P, const double* A, double damping, const double* b, double* x, int* info, void* ws, hipStream_t st);
+size_t spd_solve_batched_workspace_bytes(int P, int nb);
+hipError_t launch_spd_solve_batched(int P, int nb, const double* A, double damping, const double* b, double* x, int* info, void* ws,
+                                    hipStream_t st);
+size_t score_fisher_workspace_bytes(int R, int nblocks, long long ld);
+hipError_t launch_score_fisher_gram(int R, int nblocks, long long B, long long ld, const double* rows, double* F, void* ws,
+                                    hipStream_t st);
 
 // ---- quantum natural gradient (kernels_qfi.hip): coherent states of pi-shifted circuits, quantum Fisher information
 // thetas[c][p] = theta[p] + pi where p is the parameter of row row0 + c (row < include_base: the base circuit, no shift)

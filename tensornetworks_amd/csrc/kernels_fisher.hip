@@ -30,6 +30,18 @@
 // Every sum has a fixed order: bitwise reproducible.  LDS at P = 1024: 136 KiB panel + 8 KiB y + 5 KiB = 149 KiB.
 // Failure rule: pivot k (from 0) not positive or not finite -> info = k + 1; b not finite -> info = P + 1; a solution
 // that is not finite -> info = P + 2; in each case x = b, bit for bit, and nothing else is written to x.
+//
+// ---- bornvi_score_fisher_gram: F[j] = (1 / B) X_j X_j^T for nblocks consecutive blocks X_j of R
+// rows x ld columns of the score rows bornvi_mps_score_rows wrote (the columns B .. ld - 1 are 0.0).  The same split-K
+// SYRK with a plain row source (16-byte loads, stores to LDS, nothing computed on the way), the 64 x 64 tile of the Fisher
+// kernel (a site block at D = 4 has 32 rows: a 128-row tile would be 15/16 padding), grid (tile pairs, G, nblocks); the
+// geometry is syrk::geom(ld, R, 64) with ld a power of two >= 64, so an entry's sum has the same order whatever R is: a
+// site's block equals the diagonal block of the whole matrix bit for bit.  score_gram_finish_kernel adds the G partials in
+// index order, divides by B once and writes F_ab and F_ba from that value.
+//
+// ---- bornvi_spd_solve_batched: the body of bornvi_spd_solve (spd_solve_kernel<true>), one workgroup per system: system j
+// works on A[j], b[j], x[j], info[j] and its own P x P slice of the workspace, with the same operation order, info codes and
+// "x = b where info != 0" rule: bit for bit what bornvi_spd_solve gives on that system.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -140,6 +152,74 @@ __global__ __launch_bounds__(syrk::THREADS) void fisher_finish_kernel(const doub
   }
 }
 
+// ------------------------------------------------------------------------------------------------ score-rows Gram
+// The plain row source of syrk::split_k: row p of the block is X[p][0 .. ld), both sides get it as it is; rows past R
+// read as zero.
+struct PlainRows {
+  int lrow, lk;
+  const double* ag[FG_MT];
+  const double* bg[FG_MT];
+  bool aok[FG_MT], bok[FG_MT];
+  d2 av[FG_MT], bv[FG_MT];
+
+  __device__ __forceinline__ PlainRows(const double* __restrict__ X, long long ld, int R, int ti, int tj)
+      : lrow(threadIdx.x >> 3), lk((threadIdx.x & 7) * 2) {
+#pragma unroll
+    for (int u = 0; u < FG_MT; ++u) {
+      const int pa = ti * FG_T + lrow + 32 * u, pb = tj * FG_T + lrow + 32 * u;
+      aok[u] = pa < R;
+      bok[u] = pb < R;
+      ag[u] = X + (long long)(aok[u] ? pa : 0) * ld + lk;
+      bg[u] = X + (long long)(bok[u] ? pb : 0) * ld + lk;
+    }
+  }
+  __device__ __forceinline__ void load(long long z0, long long k0, long long slab) {
+    const bool zok = k0 + lk < slab;
+    const long long zoff = z0 + k0;
+#pragma unroll
+    for (int u = 0; u < FG_MT; ++u) {
+      av[u] = zok && aok[u] ? *reinterpret_cast<const d2*>(ag[u] + zoff) : (d2){0.0, 0.0};
+      bv[u] = zok && bok[u] ? *reinterpret_cast<const d2*>(bg[u] + zoff) : (d2){0.0, 0.0};
+    }
+  }
+  __device__ __forceinline__ void begin_slab(long long, long long, long long) {}
+  __device__ __forceinline__ void store(double* __restrict__ As, double* __restrict__ Bs, int buf, long long) const {
+#pragma unroll
+    for (int u = 0; u < FG_MT; ++u) {
+      *reinterpret_cast<d2*>(As + ((buf * FG_T + lrow + 32 * u) * syrk::PITCH + lk)) = av[u];
+      *reinterpret_cast<d2*>(Bs + ((buf * FG_T + lrow + 32 * u) * syrk::PITCH + lk)) = bv[u];
+    }
+  }
+};
+
+// grid (tiles, G, nblocks).  Block j: rows X + j R ld, partials part + j G tiles 4096.
+__global__ __launch_bounds__(syrk::THREADS) void score_gram_kernel(const double* __restrict__ X, long long ld, int R, int T,
+                                                                   long long slab, long long per_wg, double* __restrict__ part) {
+  __shared__ double sg_lds[4 * FG_T * syrk::PITCH];                    // As, Bs: [2][FG_T][PITCH] each (36 KiB)
+  int ti, tj;
+  syrk::tile_pair(blockIdx.x, T, ti, tj);
+  PlainRows rows(X + (long long)blockIdx.z * R * ld, ld, R, ti, tj);
+  syrk::split_k<FG_MT>(rows, sg_lds, sg_lds + 2 * FG_T * syrk::PITCH, slab, per_wg,
+                       part + (long long)blockIdx.z * gridDim.y * gridDim.x * (FG_T * FG_T));
+}
+
+// grid (tiles, nblocks): F[j]_ab = F[j]_ba = (the G partials of entry (a <= b) added in index order) / B.
+__global__ __launch_bounds__(syrk::THREADS) void score_gram_finish_kernel(const double* __restrict__ part, int R, int T, int G, double Bd,
+                                                                     double* __restrict__ F) {
+  int ti, tj;
+  syrk::tile_pair(blockIdx.x, T, ti, tj);
+  const long long stride = (long long)gridDim.x * (FG_T * FG_T);
+  const double* __restrict__ pt = part + ((long long)blockIdx.y * G * gridDim.x + blockIdx.x) * (FG_T * FG_T);
+  double* __restrict__ Fj = F + (long long)blockIdx.y * R * R;
+  for (int e = threadIdx.x; e < FG_T * FG_T; e += syrk::THREADS) {
+    const int a = ti * FG_T + e / FG_T, b = tj * FG_T + e % FG_T;
+    if (a >= R || b >= R || a > b) continue;
+    const double v = syrk::sum_partials(pt + e, G, stride) / Bd;
+    Fj[(long long)a * R + b] = v;
+    Fj[(long long)b * R + a] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ SPD solve
 constexpr int SS_NB = 16, SS_PITCH = 17, SS_MAX_P = 1024;
 
@@ -180,11 +260,22 @@ __device__ __forceinline__ void ss_diag_solve(const double* __restrict__ diag, d
   if (lane < nb) ys[k0 + r] = v;
 }
 
+// BATCHED = false: bornvi_spd_solve, grid 1.  BATCHED = true: bornvi_spd_solve_batched, grid nb: workgroup j moves to
+// system j's A, b, x, info and P x P slice of the workspace and then runs the same body.
+template <bool BATCHED>
 __global__ __launch_bounds__(1024) void spd_solve_kernel(const double* __restrict__ A, int P, double damping,
                                                          const double* __restrict__ b, double* __restrict__ x,
                                                          int* __restrict__ info, double* __restrict__ W) {
   extern __shared__ double ss_lds[];
   __shared__ int ss_flag;
+  if (BATCHED) {
+    const long long j = blockIdx.x;
+    A += j * P * P;
+    b += j * P;
+    x += j * P;
+    info += j;
+    W += j * P * P;
+  }
   SsLds L;
   L.pan = ss_lds;
   L.ys = L.pan + (size_t)P * SS_PITCH;
@@ -343,7 +434,7 @@ __global__ __launch_bounds__(1024) void spd_solve_kernel(const double* __restric
   if (t == 0) *info = fail;
 }
 
-LdsRaised fg_lds_raised, ss_lds_raised;
+LdsRaised fg_lds_raised, ss_lds_raised, ssb_lds_raised;
 }  // namespace
 
 size_t fisher_workspace_bytes(int n, int n_shift) { return syrk::workspace_bytes(syrk::geom(1ll << n, n_shift, FG_T), FG_T); }
@@ -363,16 +454,47 @@ hipError_t launch_fisher_gram(int n, const double* shifted, int n_shift, const d
   return hipGetLastError();
 }
 
+size_t score_fisher_workspace_bytes(int R, int nblocks, long long ld) {
+  const syrk::Geom g = syrk::geom(ld, R, FG_T);
+  return (size_t)nblocks * g.G * g.tiles * FG_T * FG_T * sizeof(double) + 512;
+}
+
+hipError_t launch_score_fisher_gram(int R, int nblocks, long long B, long long ld, const double* rows, double* F, void* ws,
+                                    hipStream_t st) {
+  const syrk::Geom g = syrk::geom(ld, R, FG_T);
+  double* part = (double*)ws_align(ws);
+  score_gram_kernel<<<dim3((unsigned)g.tiles, (unsigned)g.G, (unsigned)nblocks), syrk::THREADS, 0, st>>>(rows, ld, R, g.T, g.slab,
+                                                                                                         g.per_wg, part);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  score_gram_finish_kernel<<<dim3((unsigned)g.tiles, (unsigned)nblocks), syrk::THREADS, 0, st>>>(part, R, g.T, g.G, (double)B, F);
+  return hipGetLastError();
+}
+
 size_t spd_solve_workspace_bytes(int P) { return (size_t)P * P * sizeof(double) + 512; }
 
 hipError_t launch_spd_solve(int P, const double* A, double damping, const double* b, double* x, int* info, void* ws, hipStream_t st) {
   const size_t fixed = SS_NB * SS_PITCH + 16 * SS_NB + SS_NB;
   const size_t lds = ((size_t)P * SS_PITCH + P + fixed) * sizeof(double);
-  hipError_t e = raise_lds_once(reinterpret_cast<const void*>(spd_solve_kernel),
+  hipError_t e = raise_lds_once(reinterpret_cast<const void*>(spd_solve_kernel<false>),
                                 ((size_t)SS_MAX_P * SS_PITCH + SS_MAX_P + fixed) * sizeof(double), ss_lds_raised);
   if (e != hipSuccess) return e;
   const int threads = P <= 64 ? 64 : (P <= 256 ? 256 : 1024);
-  spd_solve_kernel<<<1, threads, lds, st>>>(A, P, damping, b, x, info, (double*)ws_align(ws));
+  spd_solve_kernel<false><<<1, threads, lds, st>>>(A, P, damping, b, x, info, (double*)ws_align(ws));
+  return hipGetLastError();
+}
+
+size_t spd_solve_batched_workspace_bytes(int P, int nb) { return (size_t)nb * P * P * sizeof(double) + 512; }
+
+hipError_t launch_spd_solve_batched(int P, int nb, const double* A, double damping, const double* b, double* x, int* info, void* ws,
+                                    hipStream_t st) {
+  const size_t fixed = SS_NB * SS_PITCH + 16 * SS_NB + SS_NB;
+  const size_t lds = ((size_t)P * SS_PITCH + P + fixed) * sizeof(double);
+  hipError_t e = raise_lds_once(reinterpret_cast<const void*>(spd_solve_kernel<true>),
+                                ((size_t)SS_MAX_P * SS_PITCH + SS_MAX_P + fixed) * sizeof(double), ssb_lds_raised);
+  if (e != hipSuccess) return e;
+  const int threads = P <= 64 ? 64 : (P <= 256 ? 256 : 1024);
+  spd_solve_kernel<true><<<(unsigned)nb, threads, lds, st>>>(A, P, damping, b, x, info, (double*)ws_align(ws));
   return hipGetLastError();
 }
 

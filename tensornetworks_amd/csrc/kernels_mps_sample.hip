@@ -35,6 +35,18 @@
 //   environment term, T_s = A_s E^_k and M_s = L^_{k-1} T_s as fma chains in index order, scaled by 2^(eL[k-1] + eE[k] - eE[0]) / E^_0[0, 0].
 //   A sample with psi = 0 (or not finite) gets logq = -inf (NaN), weight 0 in the first term, and sets the status word to 2.
 //
+// bornvi_mps_score_rows: the per-sample score rows of the sampled Fisher estimate,
+//   o_b[k, s, a, c] = 2 [z_{b,k} = s] l_{b,k-1}[a] r_{b,k}[c] / psi_b - mu[k, s, a, c],   mu = 2 L_{k-1} A_k[s] E_k / Z,
+//   rows[k - 1 - k_begin][(s D + a) D + c][b], leading dimension ld (a power of two >= max(B, 64): what the Gram takes).
+//   mps_score_mu_kernel, one workgroup per site, forms mu by mps_score_finish_kernel's expression, in its order and with
+//   its scaling exponents, into the workspace.  mps_score_rows_kernel has the shape of mps_score_kernel (one sample per
+//   lane, one wave per workgroup, workgroup g walks the 64-column tiles g, g + G, ... of the ld columns; the same
+//   right-to-left sweep into the workgroup's slice); on the way back l^_{k-1} and r^_k of the lane's sample go to LDS
+//   ([a][lane]: conflict free) and for the sites k_begin < k <= k_begin + k_count the lane writes its 2 D^2 entries
+//     (cf l^[a]) r^[c] - mu  (z = s),   0 - mu  (z != s),   cf = (2 / r^_0[0]) 2^(el_{k-1} + er_k - er_0),
+//   each store contiguous over the 64 lanes.  A sample with psi = 0 (or not finite) gets an all-zero column and status 2;
+//   the columns B .. ld - 1 are written as 0.0.  Sites outside the range are swept and not written.
+//
 // bornvi_bn_logjoint_samples: logp_b = sum_v log max(CPT_v[parents][value], p_floor), one lane per sample, nodes in order.
 //
 // No atomics, no allocation, no synchronisation: capturable, and two calls are bitwise equal.  The status word is cleared
@@ -61,7 +73,7 @@ typedef double ms_d4 __attribute__((ext_vector_type(4)));
 
 struct MsLayout {
   int DP, DS, G;
-  size_t hdr, E, L, eE, eL, r, er, parts, wpart, total;   // byte offsets from the aligned base
+  size_t hdr, E, L, eE, eL, r, er, parts, wpart, mu, total;   // byte offsets from the aligned base
 };
 
 MsLayout ms_layout(int n, int D, long long B) {
@@ -80,6 +92,7 @@ MsLayout ms_layout(int n, int D, long long B) {
   S.er = o;    o += ws_round((size_t)S.G * n * MS_LANES * sizeof(int));
   S.parts = o; o += ws_round((size_t)S.G * n * 2 * D * D * sizeof(double));
   S.wpart = o; o += ws_round((size_t)MS_MAX_WG * sizeof(double));
+  S.mu = o;    o += ws_round((size_t)n * 2 * D * D * sizeof(double));               // score rows: the exact mean mu[k, s, a, c]
   S.total = o;
   return S;
 }
@@ -463,6 +476,154 @@ __global__ __launch_bounds__(ENV_THREADS) void mps_score_finish_kernel(const dou
   }
 }
 
+// ---- score rows (sampled Fisher estimate) ----------------------------------------------------------------------
+// grid n: mu[k - 1][s][a][d] = 2 (L_{k-1} A_k[s] E_k)[a][d] / Z, the environment term of mps_score_finish_kernel
+__global__ __launch_bounds__(ENV_THREADS) void mps_score_mu_kernel(const double* __restrict__ cores, int D, const double* __restrict__ E,
+                                                                   const double* __restrict__ L, const int* __restrict__ eE,
+                                                                   const int* __restrict__ eL, const double* __restrict__ hdr,
+                                                                   double* __restrict__ mu) {
+  __shared__ double As[2 * MS_DMAX * MS_DMAX];
+  __shared__ double Em[MS_DMAX * MS_DMAX];
+  __shared__ double Lm[MS_DMAX * MS_DMAX];
+  __shared__ double T[2 * MS_DMAX * MS_DMAX];
+  const int k = blockIdx.x + 1, t = threadIdx.x, DD = D * D;
+  for (int i = t; i < 2 * DD; i += ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+  for (int i = t; i < DD; i += ENV_THREADS) {
+    Em[i] = E[(long long)k * DD + i];
+    Lm[i] = L[(long long)(k - 1) * DD + i];
+  }
+  __syncthreads();
+  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
+    const int s = i / DD, c = (i % DD) / D, d = i % D;
+    double acc = 0.0;
+    for (int e = 0; e < D; ++e) acc = fma(As[s * DD + c * D + e], Em[e * D + d], acc);
+    T[i] = acc;
+  }
+  __syncthreads();
+  const int ex = eL[k - 1] + eE[k] - eE[0];
+  const double Zh = hdr[1];
+  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
+    const int s = i / DD, a = (i % DD) / D, d = i % D;
+    double m = 0.0;
+    for (int c = 0; c < D; ++c) m = fma(Lm[a * D + c], T[s * DD + c * D + d], m);
+    const double env = ldexp(m / Zh, ex);
+    mu[(size_t)(k - 1) * 2 * DD + i] = env + env;
+  }
+}
+
+template <int DP>
+__global__ __launch_bounds__(MS_LANES) void mps_score_rows_kernel(const double* __restrict__ cores, int n, int D, int DS, long long B,
+                                                                  long long ntiles, const long long* __restrict__ idx,
+                                                                  const double* __restrict__ hdr, const double* __restrict__ mu,
+                                                                  int k_begin, int k_count, long long ld, double* __restrict__ rows,
+                                                                  int* status, double* rws, int* erws) {
+  __shared__ double As[2 * DP * DP];
+  __shared__ double Mu[2 * DP * DP];         // mu[k] as stored: [s][a][c] with pitch D
+  __shared__ double Ls[DP * MS_LANES];       // l^_{k-1}[a] of the lane's sample at [a][lane]
+  __shared__ double Rs[DP * MS_LANES];       // r^_k[c]
+  const int lane = threadIdx.x, DD = D * D, R = 2 * DD;
+  double* rsl = rws + (size_t)blockIdx.x * n * MS_LANES * DS;
+  int* esl = erws + (size_t)blockIdx.x * n * MS_LANES;
+  const double Zh = hdr[1];
+  const bool Zok = Zh > 0.0 && isfinite(Zh);
+#pragma unroll 1
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long long b = tile * MS_LANES + lane;            // b < ld: the tiles cover the ld columns exactly
+    if (tile * MS_LANES >= B) {                            // (uniform) a tile of padding columns
+      for (int kk = 0; kk < k_count; ++kk)
+        for (int j = 0; j < R; ++j) rows[((size_t)kk * R + j) * ld + b] = 0.0;
+      continue;
+    }
+    const bool active = b < B;
+    const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
+    // right to left: r_k for k = n - 1 .. 0 (as mps_score_kernel)
+    double r[DP];
+#pragma unroll
+    for (int a = 0; a < DP; ++a) r[a] = a == 0 ? 1.0 : 0.0;
+    int er = 0;
+#pragma unroll 1
+    for (int k = n; k >= 1; --k) {
+      if (k < n) {
+        double* dst = rsl + ((size_t)k * MS_LANES + lane) * DS;
+#pragma unroll
+        for (int a = 0; a < DP; ++a)
+          if (a < DS) dst[a] = r[a];
+        esl[k * MS_LANES + lane] = er;
+      }
+      __syncthreads();
+      ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
+      __syncthreads();
+      const double* Az = As + (int)((z >> (n - k)) & 1ull) * DP * DP;
+      double rn[DP];
+#pragma unroll
+      for (int a = 0; a < DP; ++a) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < DP; ++c) acc = fma(Az[a * DP + c], r[c], acc);
+        rn[a] = acc;
+      }
+#pragma unroll
+      for (int a = 0; a < DP; ++a) r[a] = rn[a];
+      er += ms_rescale<DP>(r);
+    }
+    const double r0 = r[0];
+    const int er0 = er;
+    const bool good = active && r0 != 0.0 && isfinite(r0) && Zok;
+    if (active && !good) *status = 2;
+    const double g = good ? 2.0 / r0 : 0.0;
+    // left to right
+    double l[DP];
+#pragma unroll
+    for (int a = 0; a < DP; ++a) l[a] = a == 0 ? 1.0 : 0.0;
+    int el = 0;
+#pragma unroll 1
+    for (int k = 1; k <= n; ++k) {
+      const bool wanted = k - 1 >= k_begin && k - 1 < k_begin + k_count;
+      __syncthreads();
+      ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
+      const int s = (int)((z >> (n - k)) & 1ull);
+      if (wanted) {
+        for (int i = lane; i < R; i += MS_LANES) Mu[i] = mu[(size_t)(k - 1) * R + i];
+        const int erk = k < n ? esl[k * MS_LANES + lane] : 0;
+        const double cf = ldexp(g, el + erk - er0);
+        const double* src = rsl + ((size_t)k * MS_LANES + lane) * DS;
+#pragma unroll
+        for (int a = 0; a < DP; ++a) {
+          Ls[a * MS_LANES + lane] = cf * l[a];
+          if (a < D) Rs[a * MS_LANES + lane] = k < n ? src[a] : (a == 0 ? 1.0 : 0.0);
+        }
+      }
+      __syncthreads();
+      if (wanted) {
+        double* out = rows + (size_t)(k - 1 - k_begin) * R * ld + b;
+        for (int q = 0; q < 2; ++q) {
+          const bool on = good && q == s;
+          for (int a = 0; a < D; ++a) {
+            const double cl = Ls[a * MS_LANES + lane];
+            for (int c = 0; c < D; ++c) {
+              const double t = on ? cl * Rs[c * MS_LANES + lane] : 0.0;
+              out[(size_t)((q * D + a) * D + c) * ld] = good ? t - Mu[(q * D + a) * D + c] : 0.0;
+            }
+          }
+        }
+      }
+      // l_k = l_{k-1} A_k[z_k]
+      const double* Az = As + s * DP * DP;
+      double ln[DP];
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+        double a0 = 0.0;
+#pragma unroll
+        for (int a = 0; a < DP; ++a) a0 = fma(l[a], Az[a * DP + c], a0);
+        ln[c] = a0;
+      }
+#pragma unroll
+      for (int a = 0; a < DP; ++a) l[a] = ln[a];
+      el += ms_rescale<DP>(l);
+    }
+  }
+}
+
 // ---- log joint of samples --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bn_logjoint_kernel(bornvi_bn_desc bn, int n, long long B, const long long* __restrict__ idx,
                                                           double p_floor, double* __restrict__ logp) {
@@ -538,6 +699,24 @@ hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, 
                                                               (const double*)(base + S.wpart), (const double*)(base + S.E),
                                                               (const double*)(base + S.L), (const int*)(base + S.eE),
                                                               (const int*)(base + S.eL), (const double*)(base + S.hdr), grad_cores);
+  return hipGetLastError();
+}
+
+hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores, const long long* idx, int k_begin, int k_count,
+                                 long long ld, double* rows, int* status, void* ws, hipStream_t st) {
+  const MsLayout S = ms_layout(n, D, B);
+  char* base = ws_align(ws);
+  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  mps_score_mu_kernel<<<(unsigned)n, ENV_THREADS, 0, st>>>(cores, D, (const double*)(base + S.E), (const double*)(base + S.L),
+                                                          (const int*)(base + S.eE), (const int*)(base + S.eL),
+                                                          (const double*)(base + S.hdr), (double*)(base + S.mu));
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  MS_DISPATCH(S.DP, (mps_score_rows_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
+                        cores, n, D, S.DS, B, ld / MS_LANES, idx, (const double*)(base + S.hdr), (const double*)(base + S.mu),
+                        k_begin, k_count, ld, rows, status, (double*)(base + S.r), (int*)(base + S.er))));
   return hipGetLastError();
 }
 

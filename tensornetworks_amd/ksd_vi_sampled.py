@@ -38,7 +38,7 @@ class SampledKSDVariationalInference(SampledTrainer):
     SAMPLES_RANGE = "3 ... 2^17"
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config,
-                 base_kernel_length_scale=1.0, device='cpu', p_floor=1e-30, objective='ksd2'):
+                 base_kernel_length_scale=1.0, device='cpu', p_floor=1e-30, objective='ksd2', natural_gradient=None):
         if objective not in ('ksd2', 'ksd'):
             raise ValueError(f"objective must be 'ksd2' or 'ksd', got {objective!r}")
         ls = base_kernel_length_scale
@@ -48,7 +48,7 @@ class SampledKSDVariationalInference(SampledTrainer):
         if not float(n) * float(ls) >= 1.0:
             raise ValueError(f"the sampled Stein kernel needs num_latent_vars * base_kernel_length_scale >= 1, got {n} * {ls!r}")
         super().__init__(bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device=device,
-                         p_floor=p_floor)
+                         p_floor=p_floor, natural_gradient=natural_gradient)
         self.base_kernel_length_scale = float(ls)
         self.objective = objective
 

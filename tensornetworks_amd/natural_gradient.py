@@ -21,12 +21,26 @@ It needs the P + 1 statevectors (backend.paramshift_states) and neither the para
 keep whichever gradient route they would take without it (fused dot, stored rows, adjoint), and no state is dropped at a
 floor.  Q >= F in the Loewner order, so a given damping weighs no more against Q than against F.  The matrix is
 backend.qfi_gram, the solve the same backend.spd_solve.
+
+`SampledFisherPreconditioner` is the natural gradient of the sampled MPS trainers (sampled_trainer.py), where no 2^n row
+exists: the Fisher matrix of the family is estimated from the epoch's own samples as the Gram of their centred score rows
+(stochastic reconfiguration),
+
+  F^ = (1/B) sum_b o_b o_b^T,   o_b[k, s, a, c] = 2 [z_bk = s] l_b,k-1[a] r_b,k[c] / psi_b - mu[k, s, a, c],
+
+mu the exact mean of the first term under q (backend.mps_score_rows: E_q[o] = 0, so no sample-mean correction), on the
+same SYRK core (backend.score_fisher_gram) and the same Cholesky body, one workgroup per block
+(backend.spd_solve_batched).  blocks='site' keeps the n diagonal blocks of 2 D^2 x 2 D^2, blocks='full' the whole matrix
+of P = 2 n D^2.  F is singular (scale and gauge of every core leave q unchanged): the damping is what makes the solve
+succeed, and a block whose factorisation fails keeps its plain gradient.  DESIGN.md section 6i.
 """
 import numpy as np
+import torch
 
 from . import backend
 
 MAX_PARAMS = backend.FISHER_MAX_PARAMS
+SAMPLED_ROWS_BUDGET = min(2 << 30, backend.WORKSPACE_CAP)      # bytes of score rows held at once (SampledFisherPreconditioner)
 
 
 class FisherPreconditioner:
@@ -118,3 +132,111 @@ class QuantumFisherPreconditioner:
     def precondition(self, theta64, grad64):
         """-> (delta [P] float64 = (Q + damping I)^-1 grad64, info int32 [1]); delta = grad64 where info != 0."""
         return backend.spd_solve(self.qfi(theta64), grad64.reshape(-1), self.damping)
+
+
+class SampledFisherPreconditioner:
+    """delta = (F^ + damping I)^-1 grad with F^ the sampled Fisher estimate of an MPS Born machine (module docstring), per
+    site (blocks='site', 2 D^2 <= 1024) or for all P = 2 n D^2 <= 1024 parameters at once (blocks='full').  It owns the rows
+    buffer, F, delta and the infos, reused across calls (a captured step writes into the same tensors).  In 'site' mode
+    the sites go through in chunks whose score rows fit rows_budget_bytes."""
+    BLOCKS = ("site", "full")
+
+    def __init__(self, damping=1e-3, blocks='site', rows_budget_bytes=SAMPLED_ROWS_BUDGET):
+        if isinstance(damping, bool) or not isinstance(damping, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(damping) or not damping >= 0:
+            raise ValueError(f"damping must be a finite number >= 0, got {damping!r}")
+        if blocks not in self.BLOCKS:
+            raise ValueError(f"blocks must be 'site' or 'full', got {blocks!r}")
+        rb = rows_budget_bytes
+        if isinstance(rb, bool) or not isinstance(rb, (int, np.integer)) or not 1 <= rb <= backend.WORKSPACE_CAP:
+            raise ValueError(f"rows_budget_bytes must be an integer in 1 ... {backend.WORKSPACE_CAP} (the workspace cap), got {rb!r}")
+        self.damping, self.blocks, self.rows_budget_bytes = float(damping), blocks, int(rb)
+        self.info = None          # int32 [nblocks] of the last call
+        self.status = None        # int32 [1]: the rows' status word of the last call (2: some psi(z_b) was 0 or not finite)
+        self._key = None
+        self._rows = self._F = self._delta = None
+
+    @classmethod
+    def coerce(cls, spec):
+        """What the sampled trainers' `natural_gradient` keyword accepts: None / False -> None, True -> the defaults, a
+        number -> that damping, 'site' / 'full' -> that block structure, a SampledFisherPreconditioner -> itself."""
+        if spec is None or spec is False:
+            return None
+        if spec is True:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str):
+            if spec in cls.BLOCKS:
+                return cls(blocks=spec)
+            raise ValueError(f"natural_gradient: the strings accepted are 'site' and 'full', got {spec!r}")
+        if isinstance(spec, (int, float, np.integer, np.floating)):
+            return cls(damping=spec)
+        raise ValueError("natural_gradient must be None, True, a damping, 'site', 'full' or a SampledFisherPreconditioner, "
+                         f"got {spec!r}")
+
+    def plan(self, n, D, B):
+        """(block size R, number of blocks, sites per chunk) for cores [n, 2, D, D] and B samples; every ValueError of the
+        shape is raised here, without touching the GPU."""
+        n, D, B = int(n), int(D), int(B)
+        if not 1 <= n <= backend.MPS_SAMPLED_MAX_N:
+            raise ValueError(f"natural_gradient: 1 ... {backend.MPS_SAMPLED_MAX_N} sites, got {n}")
+        if not backend.SCORE_ROWS_MIN_BATCH <= B <= backend.MPS_SAMPLED_MAX_BATCH:
+            raise ValueError(f"natural_gradient: {backend.SCORE_ROWS_MIN_BATCH} ... 2^24 samples, got {B}")
+        site = 2 * D * D
+        site_bytes = site * backend.score_rows_ld(B) * 8
+        if self.blocks == "full":
+            P = n * site
+            if D < 1 or P > MAX_PARAMS:
+                raise ValueError(f"natural_gradient blocks='full': {P} parameters (2 n D^2 at n = {n}, D = {D}); the device "
+                                 f"solve holds at most {MAX_PARAMS} (use blocks='site')")
+            if n * site_bytes > self.rows_budget_bytes:
+                raise ValueError(f"natural_gradient blocks='full': the score rows take {n * site_bytes} bytes, more than "
+                                 f"rows_budget_bytes = {self.rows_budget_bytes}")
+            return P, 1, n
+        if D < 1 or site > MAX_PARAMS:
+            raise ValueError(f"natural_gradient blocks='site': {site} parameters per site (2 D^2 at D = {D}); the device solve "
+                             f"holds at most {MAX_PARAMS} (D <= 22)")
+        if site_bytes > self.rows_budget_bytes:
+            raise ValueError(f"natural_gradient blocks='site': the score rows of one site take {site_bytes} bytes, more than "
+                             f"rows_budget_bytes = {self.rows_budget_bytes}")
+        return site, n, min(n, self.rows_budget_bytes // site_bytes)
+
+    def precondition(self, cores, idx, grad):
+        """After backend.mps_environments(cores, len(idx)): -> (delta float64 [n, 2, D, D], info int32 [nblocks]); block j of
+        delta is (F^_j + damping I)^-1 grad_j, or grad_j bit for bit where info[j] != 0 (backend.spd_solve's codes)."""
+        n, D, B = backend._mps_args(cores, int(idx.numel()))
+        R, nblocks, chunk = self.plan(n, D, B)
+        dev = cores.device
+        if tuple(grad.shape) != tuple(cores.shape) or grad.dtype != cores.dtype or grad.device != dev:
+            raise ValueError(f"grad: expected float64 {tuple(cores.shape)} on {dev}, got {grad.dtype} {tuple(grad.shape)} on {grad.device}")
+        ld = backend.score_rows_ld(B)
+        if self.blocks == "site":     # the Gram's partial tiles of a chunk stay within the same budget
+            per_site = backend.score_fisher_workspace_bytes(dev, R, 1, ld)
+            chunk = max(1, min(chunk, self.rows_budget_bytes // per_site))
+        key = (n, D, B, chunk, dev)
+        if self._key != key:
+            self._rows = torch.empty((chunk, 2 * D * D, ld), dtype=torch.float64, device=dev)
+            held = 1 if self.blocks == "full" else chunk
+            self._F = torch.empty((held, R, R), dtype=torch.float64, device=dev)
+            self._delta = torch.empty((nblocks, R), dtype=torch.float64, device=dev)
+            self.info = torch.empty(nblocks, dtype=torch.int32, device=dev)
+            self.status = torch.empty(1, dtype=torch.int32, device=dev)
+            self._status_chunk = torch.empty(1, dtype=torch.int32, device=dev)
+            self._key = key
+        g = grad.contiguous().reshape(nblocks, R)
+        if self.blocks == "full":
+            backend.mps_score_rows(cores, idx, 0, n, out=self._rows, status=self.status)
+            backend.score_fisher_gram(self._rows.reshape(1, R, ld), B, out=self._F)
+            backend.spd_solve_batched(self._F, g, self.damping, out=self._delta, info=self.info)
+        else:
+            for k0 in range(0, n, chunk):
+                cnt = min(chunk, n - k0)
+                st = self.status if k0 == 0 else self._status_chunk
+                backend.mps_score_rows(cores, idx, k0, cnt, out=self._rows[:cnt], status=st)
+                if k0:
+                    self.status |= st
+                backend.score_fisher_gram(self._rows[:cnt], B, out=self._F[:cnt])
+                backend.spd_solve_batched(self._F[:cnt], g[k0:k0 + cnt], self.damping, out=self._delta[k0:k0 + cnt],
+                                          info=self.info[k0:k0 + cnt])
+        return self._delta.reshape(cores.shape), self.info

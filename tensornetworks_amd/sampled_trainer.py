@@ -4,6 +4,9 @@ An epoch: mps_environments, mps_sample with (seed, epoch) -> (idx, log q); the o
 (the subclass: `sample_weights`); mps_score_vjp -> sum_b w_b grad log q(z_b); then the NaN/Inf guard, clip and Adam or SGD
 with cosine annealing through torch.optim on the float64 cores: the enumerated trainers' own make_optimizer and
 guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every epoch, the same ones on a rerun.
+With `natural_gradient` (natural_gradient.SampledFisherPreconditioner.coerce says what it accepts) the gradient is replaced,
+before the guard and the clip, by delta = (F^ + damping I)^-1 grad, F^ the Fisher estimate from the epoch's own samples;
+history['natgrad_info'] counts the blocks per epoch whose factorisation failed (they keep the plain gradient).
 
 A subclass supplies
   LOSS_KEYS                     the history keys it fills per epoch, MIN_SAMPLES / MAX_SAMPLES and their wording,
@@ -20,6 +23,7 @@ from . import backend
 from .bayesian_network import pack_network
 from .born_machine_mps_sampled import SampledMPSBornMachine
 from .ksd_vi import guarded_update, make_optimizer
+from .natural_gradient import SampledFisherPreconditioner
 
 
 class SampledTrainer:
@@ -29,7 +33,7 @@ class SampledTrainer:
     SAMPLES_RANGE = "1 ... 2^24"
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu',
-                 p_floor=1e-30):
+                 p_floor=1e-30, natural_gradient=None):
         cfg = dict(born_machine_config or {})
         unknown = set(cfg) - {'bond_dim', 'num_samples', 'seed', 'init_method'}
         if unknown:
@@ -51,6 +55,9 @@ class SampledTrainer:
         self.born_machine = SampledMPSBornMachine(self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4),
                                                   init_method=cfg.get('init_method', 'small_random'),
                                                   seed=self.seed).to(self.device)
+        self.natural_gradient = SampledFisherPreconditioner.coerce(natural_gradient)
+        if self.natural_gradient is not None:
+            self.natural_gradient.plan(self.num_latent_vars, int(self.born_machine.cores.shape[2]), B)
         self._desc = None
         self.last_idx = None
 
@@ -82,6 +89,9 @@ class SampledTrainer:
         loss, w = self.sample_weights(idx, logq)
         grad, _, st_g = backend.mps_score_vjp(cores, idx, w.contiguous())
         self.last_idx = idx
+        if self.natural_gradient is not None:
+            grad, _ = self.natural_gradient.precondition(cores, idx, grad)
+            return loss, grad, logq.mean(), st_s | st_g | self.natural_gradient.status
         return loss, grad, logq.mean(), st_s | st_g
 
     def record_loss(self, history, loss):
@@ -91,8 +101,10 @@ class SampledTrainer:
         raise NotImplementedError
 
     def train(self, x_observation_dict, num_epochs, lr_born_machine, verbose=True, true_posterior_for_tvd=None,
-              use_lr_scheduler=True, gradient_clip_norm=10.0, optimizer_type="adam", adam_betas=(0.9, 0.999)):
-        """The arguments of elbo_vi's train() that make sense here (no entropy_weight, no early stopping).
+              use_lr_scheduler=True, gradient_clip_norm=10.0, optimizer_type="adam", adam_betas=(0.9, 0.999), sgd_momentum=0.9):
+        """The arguments of elbo_vi's train() that make sense here (no entropy_weight, no early stopping), and sgd_momentum:
+        the momentum of optimizer_type="sgd" (0.9: make_optimizer's; 0 gives the plain step lr * delta); Adam has none and
+        ignores it.
         true_posterior_for_tvd: a float tensor [2^n] (stein_utils.true_posterior_table), honoured for n <= 26 only, where
         q is enumerated by mps_probs for the report.  History: the trainer's LOSS_KEYS, grad_norm, logq_mean, status,
         and for n <= 26 with a posterior: tvd and kl (= exact KL(q || posterior))."""
@@ -101,10 +113,17 @@ class SampledTrainer:
         bm = self.born_machine
         self._prepare_observation(x_observation_dict)
         opt, sched = make_optimizer(bm.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas)
+        if optimizer_type != "adam":
+            if isinstance(sgd_momentum, bool) or not isinstance(sgd_momentum, (int, float)) or not 0 <= sgd_momentum < 1:
+                raise ValueError(f"sgd_momentum must be a number in [0, 1), got {sgd_momentum!r}")
+            for group in opt.param_groups:
+                group['momentum'] = float(sgd_momentum)
         exact = true_posterior_for_tvd is not None and self.num_latent_vars <= backend.MPS_MAX_N
         history = {k: [] for k in self.LOSS_KEYS + ('grad_norm', 'logq_mean', 'status')}
         if exact:
             history['tvd'], history['kl'] = [], []
+        if self.natural_gradient is not None:
+            history['natgrad_info'] = []
         grad_norm = None
         for epoch in range(num_epochs):
             opt.zero_grad()
@@ -116,6 +135,8 @@ class SampledTrainer:
             history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
             history['logq_mean'].append(float(lq_t.item()))
             history['status'].append(int(st_t.item()))
+            if self.natural_gradient is not None:
+                history['natgrad_info'].append(int((self.natural_gradient.info != 0).sum().item()))
             if exact:
                 tvd, kl = self.exact_report(true_posterior_for_tvd)
                 history['tvd'].append(tvd)
