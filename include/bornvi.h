@@ -523,6 +523,24 @@ size_t bornvi_score_fisher_workspace_bytes(bornvi_handle h, int R, int nblocks, 
 int bornvi_score_fisher_gram(bornvi_handle h, int R, int nblocks, long long B, long long ld, const double* rows, double* F,
                              void* workspace, size_t workspace_bytes, bornvi_stream stream);
 
+/* ---- the same natural gradient solved in sample space.  With O the B x P matrix of the centred
+ * score rows, (O^T O / B + damping I)^-1 O^T w = O^T u with (T + damping I) u = w, T = O O^T / B: a B x B system whatever P is.
+ * bornvi_mps_score_sample_gram, after bornvi_mps_environments on env_workspace (the (n, D, B) workspace of
+ * bornvi_mps_sample_workspace_bytes), writes T dev [B, B] float64 for the samples idx dev [B] without forming a row:
+ *   B T_bb' = sum_k [z_bk = z_b'k] (x_bk . x_b'k)(r_bk . r_b'k) - m_b - m_b' + M,
+ *   x_bk = (2 / psi_b) l_b,k-1,  m_b = sum_k x_bk^T mu_k[z_bk] r_bk,  M = sum_k,s ||mu_k[s]||_F^2,
+ * the dot products on the fp64 matrix cores, the sites added in order.  T == T^T bitwise, two calls are bitwise equal, and
+ * an entry's bits depend on (n, D, cores, the two samples) and B's one division only: not on the tile or the grid.  A sample
+ * with psi = 0 or not finite gets a row and a column of exactly 0.0 and status (dev [1] int32) becomes 2, else 0.
+ * 2 <= B <= 1024 (what bornvi_spd_solve factors), 1 <= n <= 63, 1 <= D <= 32; anything else, a short workspace included,
+ * is BORNVI_ERR_UNSUPPORTED before any launch.  It rewrites the mu region of env_workspace (as bornvi_mps_score_rows does) and
+ * keeps its vectors in `workspace`: bornvi_mps_score_sample_gram_workspace_bytes(h, n, D, B).  No atomics, no allocation
+ * or synchronisation (capturable). */
+size_t bornvi_mps_score_sample_gram_workspace_bytes(bornvi_handle h, int n, int D, long long B);
+int bornvi_mps_score_sample_gram(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, double* T,
+                                 int* status, void* env_workspace, size_t env_workspace_bytes, void* workspace,
+                                 size_t workspace_bytes, bornvi_stream stream);
+
 /* ---- quantum natural gradient: the Fubini-Study metric instead of the classical Fisher matrix (what PennyLane's
  * QNGOptimizer preconditions with; no reference counterpart).  Every parameter enters exactly one gate exp(-i theta s / 2),
  * so d_a psi = 1/2 psi(theta + pi e_a).

@@ -8,7 +8,7 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
            "SampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
-           "SampledFisherPreconditioner", "generate_all_binary_outcomes", "calculate_tvd"]
+           "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "generate_all_binary_outcomes", "calculate_tvd"]
 
 
 def __getattr__(name):
@@ -48,4 +48,7 @@ def __getattr__(name):
     if name == "SampledFisherPreconditioner":
         from .natural_gradient import SampledFisherPreconditioner
         return SampledFisherPreconditioner
+    if name == "SampleSpaceFisherPreconditioner":
+        from .natural_gradient import SampleSpaceFisherPreconditioner
+        return SampleSpaceFisherPreconditioner
     raise AttributeError(name)

@@ -992,6 +992,43 @@ def score_fisher_gram(rows, num_samples, out=None):
     return out
 
 
+SAMPLE_GRAM_MAX_BATCH = FISHER_MAX_PARAMS           # T is [B, B] and spd_solve factors it
+
+
+def mps_score_sample_gram_workspace_bytes(dev, n, D, num_samples):
+    return _cached_size(_ext.handle_for(dev), "bornvi_mps_score_sample_gram_workspace_bytes", int(n), int(D), int(num_samples))
+
+
+def mps_score_sample_gram(cores, idx, out=None, status=None):
+    """Sample-space Gram of the score rows of an MPS Born machine (bornvi_mps_score_sample_gram), after
+    mps_environments(cores, len(idx)): -> (T float64 [B, B], status int32 [1]), T[b, b'] = o_b . o_b' / B with o_b the
+    centred score row of sample b (the column b of mps_score_rows), computed from the samples' left and right vectors on
+    the fp64 matrix cores without forming a row.  T == T.T bitwise; two calls are bitwise equal.  status: 0, or 2 when some
+    psi(idx_b) is 0 or not finite (that sample's row and column are all 0.0).  2 <= B <= 1024."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    n, D, B = _mps_args(cores, int(idx.numel()))
+    if not SCORE_ROWS_MIN_BATCH <= B <= SAMPLE_GRAM_MAX_BATCH:
+        raise BornviError(f"mps_score_sample_gram: {SCORE_ROWS_MIN_BATCH} ... {SAMPLE_GRAM_MAX_BATCH} samples, got {B}")
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    if out is None:
+        out = torch.empty((B, B), dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", B * B)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(status, torch.int32, dev, "status", 1)
+    env = _mps_sampled_ws(h, dev, n, D, B)
+    ws = _ws(dev, _cached_size(h, "bornvi_mps_score_sample_gram_workspace_bytes", n, D, B), f"mps_sample_gram_{n}_{D}_{B}")
+    h.call("bornvi_mps_score_sample_gram", n, D, B, _ptr(cores), _ptr(idx), _ptr(out), _ptr(status), _ptr(env), env.numel(),
+           _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out, status
+
+
 def paramshift_states_bytes(n, count, include_base=True):
     """Bytes of the rows paramshift_states writes: 16 (count + base) 2^n."""
     return 16 * (int(count) + (1 if include_base else 0)) << int(n)

@@ -1305,6 +1305,31 @@ int bornvi_mps_score_rows(bornvi_handle h, int n, int D, long long B, const doub
   return BORNVI_OK;
 }
 
+static bool valid_sample_gram(int n, int D, long long B) { return valid_mps_sample(n, D, B) && B >= 2 && B <= SAMPLE_GRAM_MAX_B; }
+static const char* const SAMPLE_GRAM_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 32, 2 <= B <= 1024)";
+
+size_t bornvi_mps_score_sample_gram_workspace_bytes(bornvi_handle h, int n, int D, long long B) {
+  if (!h) return 0;
+  if (!valid_sample_gram(n, D, B)) { fail(h, BORNVI_ERR_UNSUPPORTED, SAMPLE_GRAM_RANGE); return 0; }
+  return mps_sample_gram_workspace_bytes(n, D, B);
+}
+
+int bornvi_mps_score_sample_gram(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, double* T,
+                                 int* status, void* env_workspace, size_t env_workspace_bytes, void* workspace,
+                                 size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_sample_gram(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, SAMPLE_GRAM_RANGE);
+  if (!cores || !idx || !T || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!env_workspace || env_workspace_bytes < mps_sample_workspace_bytes(n, D, B))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, "the environments' workspace is too small");
+  if (!workspace || workspace_bytes < mps_sample_gram_workspace_bytes(n, D, B))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_score_sample_gram(n, D, B, cores, idx, T, status, env_workspace, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 static bool valid_score_fisher(int R, int nblocks) { return R >= 1 && R <= 1024 && nblocks >= 1 && nblocks <= 65535; }
 static const char* const SCORE_FISHER_RANGE = "unsupported size (1 <= R <= 1024, 1 <= nblocks <= 65535)";
 

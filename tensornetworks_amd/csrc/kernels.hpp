@@ -115,8 +115,16 @@ hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, 
                                 double* grad_cores, int* status, void* ws, hipStream_t st);
 hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores, const long long* idx, int k_begin, int k_count,
                                  long long ld, double* rows, int* status, void* ws, hipStream_t st);
+hipError_t launch_mps_score_mu(int n, int D, long long B, const double* cores, void* ws, const double** hdr, const double** mu,
+                               hipStream_t st);
 hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
                                       hipStream_t st);
+
+// ---- sample-space Gram of the sampled MPS's score rows (kernels_mps_sample_gram.hip): T = O O^T / B without the rows ----
+constexpr long long SAMPLE_GRAM_MAX_B = 1024;        // what bornvi_spd_solve factors
+size_t mps_sample_gram_workspace_bytes(int n, int D, long long B);
+hipError_t launch_mps_score_sample_gram(int n, int D, long long B, const double* cores, const long long* idx, double* T, int* status,
+                                        void* env_ws, void* ws, hipStream_t st);
 
 // ---- sampled KSD: scores of p at sampled states, pairwise Stein kernel row sums (kernels_ksd_sampled.hip) ----
 constexpr long long STEIN_PAIRS_MAX_B = 1ll << 17;   // B^2 is the cost: 1.7e10 pairs at the cap

@@ -57,12 +57,12 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "mps_sample_dev.hpp"
 #include "philox_dev.hpp"
 
 namespace bornvi {
 
 namespace {
-constexpr int MS_LANES = 64;               // sampler and score kernels: one wave per workgroup
 constexpr int MS_MAX_WG = 256;             // score kernel: workgroups (= workspace slices and partials) at most
 constexpr int ENV_THREADS = 256;
 constexpr int MS_DMAX = 32;
@@ -106,35 +106,6 @@ __device__ __forceinline__ double ms_wave_max(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
   return v;
-}
-
-// exponent of the exact power-of-two rescaling: ilogb of a positive finite largest magnitude, else 0 (nothing to rescale)
-__device__ __forceinline__ int ms_exponent(double mx) { return (mx > 0.0 && isfinite(mx)) ? ilogb(mx) : 0; }
-
-template <int DP>
-__device__ __forceinline__ int ms_rescale(double (&v)[DP]) {
-  double mx = 0.0;
-#pragma unroll
-  for (int a = 0; a < DP; ++a) mx = fmax(mx, fabs(v[a]));
-  const int e = ms_exponent(mx);
-#pragma unroll
-  for (int a = 0; a < DP; ++a) v[a] = ldexp(v[a], -e);
-  return e;
-}
-
-// A_k[s] zero-padded to DP x DP in LDS, As[s][a][b]; optionally a D x D matrix M the same way
-template <int DP>
-__device__ __forceinline__ void ms_load_site(const double* cores, int k, int D, double* As, const double* M, double* Ms) {
-  const double* A = cores + (long long)(k - 1) * 2 * D * D;
-  for (int i = threadIdx.x; i < 2 * DP * DP; i += MS_LANES) {
-    const int s = i / (DP * DP), a = (i / DP) % DP, b = i % DP;
-    As[i] = (a < D && b < D) ? A[(s * D + a) * D + b] : 0.0;
-  }
-  if (M)
-    for (int i = threadIdx.x; i < DP * DP; i += MS_LANES) {
-      const int a = i / DP, b = i % DP;
-      Ms[i] = (a < D && b < D) ? M[a * D + b] : 0.0;
-    }
 }
 
 // ---- environments ----------------------------------------------------------------------------------------------
@@ -709,14 +680,27 @@ hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores,
   ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
+  const double* hdr = nullptr;
+  const double* mu = nullptr;
+  e = launch_mps_score_mu(n, D, B, cores, ws, &hdr, &mu, st);
+  if (e != hipSuccess) return e;
+  MS_DISPATCH(S.DP, (mps_score_rows_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
+                        cores, n, D, S.DS, B, ld / MS_LANES, idx, hdr, mu,
+                        k_begin, k_count, ld, rows, status, (double*)(base + S.r), (int*)(base + S.er))));
+  return hipGetLastError();
+}
+
+// mu alone, for kernels_mps_sample_gram.hip: the launch of launch_mps_score_rows into the same region, and where the header
+// (log Z, E^_0[0, 0], eE[0]) and mu lie in the workspace
+hipError_t launch_mps_score_mu(int n, int D, long long B, const double* cores, void* ws, const double** hdr, const double** mu,
+                               hipStream_t st) {
+  const MsLayout S = ms_layout(n, D, B);
+  char* base = ws_align(ws);
   mps_score_mu_kernel<<<(unsigned)n, ENV_THREADS, 0, st>>>(cores, D, (const double*)(base + S.E), (const double*)(base + S.L),
                                                           (const int*)(base + S.eE), (const int*)(base + S.eL),
                                                           (const double*)(base + S.hdr), (double*)(base + S.mu));
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  MS_DISPATCH(S.DP, (mps_score_rows_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
-                        cores, n, D, S.DS, B, ld / MS_LANES, idx, (const double*)(base + S.hdr), (const double*)(base + S.mu),
-                        k_begin, k_count, ld, rows, status, (double*)(base + S.r), (int*)(base + S.er))));
+  *hdr = (const double*)(base + S.hdr);
+  *mu = (const double*)(base + S.mu);
   return hipGetLastError();
 }
 

@@ -33,6 +33,15 @@ same SYRK core (backend.score_fisher_gram) and the same Cholesky body, one workg
 (backend.spd_solve_batched).  blocks='site' keeps the n diagonal blocks of 2 D^2 x 2 D^2, blocks='full' the whole matrix
 of P = 2 n D^2.  F is singular (scale and gauge of every core leave q unchanged): the damping is what makes the solve
 succeed, and a block whose factorisation fails keeps its plain gradient.  DESIGN.md section 6i.
+
+`SampleSpaceFisherPreconditioner` is the same full-matrix step solved in sample space (minSR).  The
+trainers' gradient is O^T w with O the B x P matrix of the score rows, and
+
+  (O^T O / B + damping I)^-1 O^T w = O^T u,   (T + damping I) u = w,   T = O O^T / B,
+
+so the exact blocks='full' step needs a B x B Gram (backend.mps_score_sample_gram, from the samples' left and right vectors:
+no row is formed), one backend.spd_solve of size B <= 1024 and one more backend.mps_score_vjp with the weights u.  P is not
+limited.  Duplicate samples make T singular: the damping must be positive.
 """
 import numpy as np
 import torch
@@ -159,21 +168,24 @@ class SampledFisherPreconditioner:
     @classmethod
     def coerce(cls, spec):
         """What the sampled trainers' `natural_gradient` keyword accepts: None / False -> None, True -> the defaults, a
-        number -> that damping, 'site' / 'full' -> that block structure, a SampledFisherPreconditioner -> itself."""
+        number -> that damping, 'site' / 'full' -> that block structure, a SampledFisherPreconditioner -> itself;
+        'sample' -> SampleSpaceFisherPreconditioner(), an instance of it -> itself."""
         if spec is None or spec is False:
             return None
         if spec is True:
             return cls()
-        if isinstance(spec, cls):
+        if isinstance(spec, (cls, SampleSpaceFisherPreconditioner)):
             return spec
         if isinstance(spec, str):
             if spec in cls.BLOCKS:
                 return cls(blocks=spec)
-            raise ValueError(f"natural_gradient: the strings accepted are 'site' and 'full', got {spec!r}")
+            if spec == "sample":
+                return SampleSpaceFisherPreconditioner()
+            raise ValueError(f"natural_gradient: the strings accepted are 'site', 'full' and 'sample', got {spec!r}")
         if isinstance(spec, (int, float, np.integer, np.floating)):
             return cls(damping=spec)
-        raise ValueError("natural_gradient must be None, True, a damping, 'site', 'full' or a SampledFisherPreconditioner, "
-                         f"got {spec!r}")
+        raise ValueError("natural_gradient must be None, True, a damping, 'site', 'full', 'sample', a SampledFisherPreconditioner "
+                         f"or a SampleSpaceFisherPreconditioner, got {spec!r}")
 
     def plan(self, n, D, B):
         """(block size R, number of blocks, sites per chunk) for cores [n, 2, D, D] and B samples; every ValueError of the
@@ -240,3 +252,62 @@ class SampledFisherPreconditioner:
                 backend.spd_solve_batched(self._F[:cnt], g[k0:k0 + cnt], self.damping, out=self._delta[k0:k0 + cnt],
                                           info=self.info[k0:k0 + cnt])
         return self._delta.reshape(cores.shape), self.info
+
+
+class SampleSpaceFisherPreconditioner:
+    """delta = (F^ + damping I)^-1 O^T w for ALL P = 2 n D^2 parameters at once, solved as a B x B system in sample space
+    (module docstring): what SampledFisherPreconditioner(blocks='full') computes, at any P, for B <= 1024 samples.  It
+    takes the weights w of the gradient, not the gradient.  It owns T, u, delta, info and status, reused across calls (a
+    captured step writes into the same tensors)."""
+    MAX_SAMPLES = backend.SAMPLE_GRAM_MAX_BATCH
+
+    def __init__(self, damping=1e-3):
+        if isinstance(damping, bool) or not isinstance(damping, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(damping) or not damping > 0:
+            raise ValueError(f"damping must be a finite number > 0 (repeated samples make the sample-space Gram singular), "
+                             f"got {damping!r}")
+        self.damping = float(damping)
+        self.info = None          # int32 [1] of the last call (backend.spd_solve's codes)
+        self.status = None        # int32 [1]: the Gram's and the second score_vjp's status words or-ed
+        self._key = None
+        self._T = self._u = self._delta = self._logq = self._status_vjp = None
+
+    def plan(self, n, D, B):
+        """(B, 1, n): the size of the system, one block, every site at once; every ValueError of the shape is raised here,
+        without touching the GPU."""
+        n, D, B = int(n), int(D), int(B)
+        if not 1 <= n <= backend.MPS_SAMPLED_MAX_N:
+            raise ValueError(f"natural_gradient: 1 ... {backend.MPS_SAMPLED_MAX_N} sites, got {n}")
+        if not 1 <= D <= backend.MPS_MAX_BOND:
+            raise ValueError(f"natural_gradient: bond dimension 1 ... {backend.MPS_MAX_BOND}, got {D}")
+        if B < backend.SCORE_ROWS_MIN_BATCH:
+            raise ValueError(f"natural_gradient='sample': at least {backend.SCORE_ROWS_MIN_BATCH} samples, got {B}")
+        if B > self.MAX_SAMPLES:
+            raise ValueError(f"natural_gradient='sample': {B} samples; the device solve holds at most {self.MAX_SAMPLES} "
+                             f"(the system is B x B)")
+        return B, 1, n
+
+    def precondition_weights(self, cores, idx, w):
+        """After backend.mps_environments(cores, len(idx)): -> (delta float64 [n, 2, D, D], info int32 [1]) for the weights
+        w float64 [B] of the gradient sum_b w_b grad log q(z_b); where info != 0 the solve left u = w and delta is that
+        plain gradient bit for bit."""
+        n, D, B = backend._mps_args(cores, int(idx.numel()))
+        self.plan(n, D, B)
+        dev = cores.device
+        if tuple(w.shape) != (B,) or w.dtype != torch.float64 or w.device != dev:
+            raise ValueError(f"w: expected float64 ({B},) on {dev}, got {w.dtype} {tuple(w.shape)} on {w.device}")
+        key = (n, D, B, dev)
+        if self._key != key:
+            self._T = torch.empty((B, B), dtype=torch.float64, device=dev)
+            self._u = torch.empty(B, dtype=torch.float64, device=dev)
+            self._delta = torch.empty(tuple(cores.shape), dtype=torch.float64, device=dev)
+            self._logq = torch.empty(B, dtype=torch.float64, device=dev)
+            self.info = torch.empty(1, dtype=torch.int32, device=dev)
+            self.status = torch.empty(1, dtype=torch.int32, device=dev)
+            self._status_vjp = torch.empty(1, dtype=torch.int32, device=dev)
+            self._key = key
+        backend.mps_score_sample_gram(cores, idx, out=self._T, status=self.status)
+        backend.spd_solve(self._T, w.contiguous(), self.damping, out=self._u, info=self.info)
+        backend.mps_score_vjp(cores, idx, self._u, out=self._delta, out_logq=self._logq, status=self._status_vjp)
+        self.status |= self._status_vjp
+        return self._delta, self.info

@@ -7,6 +7,8 @@ guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every e
 With `natural_gradient` (natural_gradient.SampledFisherPreconditioner.coerce says what it accepts) the gradient is replaced,
 before the guard and the clip, by delta = (F^ + damping I)^-1 grad, F^ the Fisher estimate from the epoch's own samples;
 history['natgrad_info'] counts the blocks per epoch whose factorisation failed (they keep the plain gradient).
+natural_gradient='sample' (SampleSpaceFisherPreconditioner) is the full-matrix step solved in sample space: it takes the
+weights w and returns delta = sum_b u_b grad log q(z_b) with (T + damping I) u = w, for num_samples <= 1024.
 
 A subclass supplies
   LOSS_KEYS                     the history keys it fills per epoch, MIN_SAMPLES / MAX_SAMPLES and their wording,
@@ -23,7 +25,7 @@ from . import backend
 from .bayesian_network import pack_network
 from .born_machine_mps_sampled import SampledMPSBornMachine
 from .ksd_vi import guarded_update, make_optimizer
-from .natural_gradient import SampledFisherPreconditioner
+from .natural_gradient import SampledFisherPreconditioner, SampleSpaceFisherPreconditioner
 
 
 class SampledTrainer:
@@ -87,8 +89,11 @@ class SampledTrainer:
         sampler's and the gradient's status words or-ed).  Nothing is read back to the host."""
         cores, idx, logq, st_s = self.draw(epoch)
         loss, w = self.sample_weights(idx, logq)
-        grad, _, st_g = backend.mps_score_vjp(cores, idx, w.contiguous())
         self.last_idx = idx
+        if isinstance(self.natural_gradient, SampleSpaceFisherPreconditioner):      # delta = O^T u: the plain O^T w need not run
+            grad, _ = self.natural_gradient.precondition_weights(cores, idx, w.contiguous())
+            return loss, grad, logq.mean(), st_s | self.natural_gradient.status
+        grad, _, st_g = backend.mps_score_vjp(cores, idx, w.contiguous())
         if self.natural_gradient is not None:
             grad, _ = self.natural_gradient.precondition(cores, idx, grad)
             return loss, grad, logq.mean(), st_s | st_g | self.natural_gradient.status
