@@ -541,6 +541,45 @@ int bornvi_mps_score_sample_gram(bornvi_handle h, int n, int D, long long B, con
                                  int* status, void* env_workspace, size_t env_workspace_bytes, void* workspace,
                                  size_t workspace_bytes, bornvi_stream stream);
 
+/* ---- the same natural gradient without any matrix: conjugate gradients on
+ * (O^T O / B + damping I) delta = g, one product v -> O^T (O v) / B per iteration.  O^T w is bornvi_mps_score_vjp.
+ * bornvi_mps_score_jvp, after bornvi_mps_environments on env_workspace (the (n, D, B) workspace of
+ * bornvi_mps_sample_workspace_bytes), writes O v scaled: for the samples idx dev [B] and a direction v dev [n, 2, D, D]
+ * float64 (the cores' layout),
+ *   t_b = scale <grad log q(z_b), v> = scale (2 dpsi_b / psi_b - sum_k <mu_k, V_k>),  dpsi_b = sum_k l_b,k-1^T V_k[z_bk] r_b,k,
+ * t dev [B] float64; mu as in bornvi_mps_score_rows.  One left-to-right sweep of (l, dl), dl <- dl A_k[z] + l V_k[z], both
+ * rescaled by the same power of two after every site; <mu_k, V_k> is added in index order per site, then the sites in
+ * order.  t_b's bits depend on (cores, v, scale, the sample) only: not on B, the grid or the tile; two calls are bitwise
+ * equal.  A sample with psi = 0 or not finite gets t_b = 0.0 and status (dev [1] int32) becomes 2, else 0.  2 <= B <= 2^24,
+ * 1 <= n <= 63, 1 <= D <= 32; anything else, a short workspace included, is BORNVI_ERR_UNSUPPORTED before any launch; scale
+ * must be finite.  It rewrites the mu region of env_workspace (as bornvi_mps_score_rows does) and the per-workgroup weight
+ * sums bornvi_mps_score_vjp keeps there between its own two launches.  No atomics, no allocation or synchronisation
+ * (capturable). */
+int bornvi_mps_score_jvp(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, const double* v,
+                         double scale, double* t, int* status, void* env_workspace, size_t env_workspace_bytes,
+                         bornvi_stream stream);
+
+/* The conjugate-gradient recurrence for (F + damping I) x = g, the product F p left to the caller between the calls; every
+ * vector dev [P] float64, state dev [8] float64 (rr = r^T r, rr0 = g^T g, iterations done, done flag, relres = sqrt(rr / rr0),
+ * fallback flag, two spare words).  One workgroup each; every dot product is a fixed-order reduction, so two solves are
+ * bitwise equal.
+ * bornvi_cg_init: x = 0, r = p = g, the state.  g = 0 sets the done flag (x = 0 is the solution); a non-finite entry of g
+ * sets the done and the fallback flag; info (dev [1] int32) becomes the fallback flag.
+ * bornvi_cg_step, given Fp = F p (without the damping): writes nothing once the done flag is set.  Otherwise
+ * q = Fp + damping p and alpha = rr / p^T q; where p^T q is not positive and finite the iteration freezes (done; x stays the
+ * last iterate; at iteration 0 the fallback flag is set); else x += alpha p, r -= alpha q, rr' = r^T r, p = r + (rr' / rr) p,
+ * one more iteration counted, and done once rr' <= rel_tol^2 rr0.
+ * bornvi_cg_finish: where the fallback flag is set or x is not finite, x = g bit for bit and info = 1; else info = 0 (an
+ * unconverged x too: every iterate from x_0 = 0 is a descent direction).  iters dev [1] int32, relres dev [1] float64.
+ * 1 <= P <= 2^31 - 1, damping > 0 and finite, rel_tol >= 0 and finite, else BORNVI_ERR_INVALID.  No atomics, no allocation or
+ * synchronisation (capturable): the launch sequence of a solve does not depend on the data. */
+int bornvi_cg_init(bornvi_handle h, long long P, const double* g, double* x, double* r, double* p, double* state, int* info,
+                   bornvi_stream stream);
+int bornvi_cg_step(bornvi_handle h, long long P, double damping, double rel_tol, const double* Fp, double* x, double* r,
+                   double* p, double* state, bornvi_stream stream);
+int bornvi_cg_finish(bornvi_handle h, long long P, const double* g, double* x, const double* state, int* info, int* iters,
+                     double* relres, bornvi_stream stream);
+
 /* ---- quantum natural gradient: the Fubini-Study metric instead of the classical Fisher matrix (what PennyLane's
  * QNGOptimizer preconditions with; no reference counterpart).  Every parameter enters exactly one gate exp(-i theta s / 2),
  * so d_a psi = 1/2 psi(theta + pi e_a).

@@ -8,7 +8,8 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
            "SampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
-           "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "generate_all_binary_outcomes", "calculate_tvd"]
+           "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "CGFisherPreconditioner",
+           "generate_all_binary_outcomes", "calculate_tvd"]
 
 
 def __getattr__(name):
@@ -51,4 +52,7 @@ def __getattr__(name):
     if name == "SampleSpaceFisherPreconditioner":
         from .natural_gradient import SampleSpaceFisherPreconditioner
         return SampleSpaceFisherPreconditioner
+    if name == "CGFisherPreconditioner":
+        from .natural_gradient import CGFisherPreconditioner
+        return CGFisherPreconditioner
     raise AttributeError(name)

@@ -1029,6 +1029,121 @@ def mps_score_sample_gram(cores, idx, out=None, status=None):
     return out, status
 
 
+# ---- matrix-free natural gradient of the sampled MPS Born machine: O v, and conjugate gradients around a product ----
+CG_MAX_PARAMS = (1 << 31) - 1
+CG_STATE_DOUBLES = 8
+
+
+def mps_score_jvp(cores, idx, v, scale=1.0, out=None, status=None):
+    """Per-sample directional derivative of log q of an MPS Born machine (bornvi_mps_score_jvp), after
+    mps_environments(cores, len(idx)): v float64 [n, 2, D, D] -> (t float64 [B], status int32 [1]),
+    t_b = scale <grad log q(idx_b), v>: the product O v of the centred score rows (mps_score_rows) with v, without forming a
+    row; mps_score_vjp is its transpose.  t_b's bits depend on (cores, v, scale, idx_b) only; two calls are bitwise equal.
+    status: 0, or 2 when some psi(idx_b) is 0 or not finite (that t_b is 0.0).  B >= 2."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    n, D, B = _mps_args(cores, int(idx.numel()))
+    if B < SCORE_ROWS_MIN_BATCH:
+        raise BornviError(f"mps_score_jvp: at least {SCORE_ROWS_MIN_BATCH} samples, got {B}")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(scale):
+        raise BornviError(f"scale must be a finite number, got {scale!r}")
+    if not torch.is_tensor(v) or tuple(v.shape) != tuple(cores.shape):
+        raise BornviError(f"v: expected a tensor of the cores' shape {tuple(cores.shape)}, got "
+                          f"{tuple(v.shape) if torch.is_tensor(v) else type(v)}")
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    _chk(v, torch.float64, dev, "v", cores.numel())
+    if out is None:
+        out = torch.empty(B, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", B)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(status, torch.int32, dev, "status", 1)
+    env = _mps_sampled_ws(h, dev, n, D, B)
+    h.call("bornvi_mps_score_jvp", n, D, B, _ptr(cores), _ptr(idx), _ptr(v), float(scale), _ptr(out), _ptr(status), _ptr(env),
+           env.numel(), _ext.stream_ptr(dev))
+    return out, status
+
+
+def _cg_vectors(g, named):
+    """P and the device of g float64 [P] (any shape, contiguous); every (name, tensor) of `named` must match it."""
+    if not torch.is_tensor(g) or g.numel() < 1:
+        raise BornviError("cg: g must be a tensor with at least one element")
+    P, dev = int(g.numel()), g.device
+    if P > CG_MAX_PARAMS:
+        raise BornviError(f"cg: 1 ... 2^31 - 1 elements, got {P}")
+    _chk(g, torch.float64, dev, "g")
+    for name, t in named:
+        if not torch.is_tensor(t):
+            raise BornviError(f"cg: {name} must be a tensor")
+        _chk(t, torch.float64, dev, name, P)
+    return P, dev
+
+
+def cg_init(g, x=None, r=None, p=None, state=None, info=None):
+    """Start of conjugate gradients on (F + damping I) x = g (bornvi_cg_init): g float64 [P] (any shape) ->
+    (x = 0, r = g, p = g, state float64 [8], info int32 [1]).  state: rr = r^T r, rr0 = g^T g, iterations, done flag, relres,
+    fallback flag.  g = 0 sets done; a non-finite g sets done and fallback (info = 1).  x, r, p, state, info: destinations."""
+    if torch.is_tensor(g):
+        x, r, p = (torch.empty_like(g) if t is None else t for t in (x, r, p))
+    P, dev = _cg_vectors(g, (("x", x), ("r", r), ("p", p)))
+    if state is None:
+        state = torch.empty(CG_STATE_DOUBLES, dtype=torch.float64, device=dev)
+    else:
+        _chk(state, torch.float64, dev, "state", CG_STATE_DOUBLES)
+    if info is None:
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(info, torch.int32, dev, "info", 1)
+    _ext.handle_for(dev).call("bornvi_cg_init", P, _ptr(g), _ptr(x), _ptr(r), _ptr(p), _ptr(state), _ptr(info), _ext.stream_ptr(dev))
+    return x, r, p, state, info
+
+
+def cg_step(Fp, x, r, p, state, damping, rel_tol=0.0):
+    """One conjugate-gradient iteration in place (bornvi_cg_step), Fp = F p without the damping: q = Fp + damping p,
+    alpha = rr / p^T q, x += alpha p, r -= alpha q, p = r + (rr' / rr) p; done once rr' <= rel_tol^2 rr0.  Writes nothing once
+    the done flag of `state` is set; freezes (and, at iteration 0, asks for the fallback) where p^T q is not positive and
+    finite.  Returns state."""
+    P, dev = _cg_vectors(Fp, (("x", x), ("r", r), ("p", p)))
+    _chk_positive(damping, "damping")
+    _chk_positive(rel_tol, "rel_tol", allow_zero=True)
+    if not torch.is_tensor(state):
+        raise BornviError("cg: state must be a tensor")
+    _chk(state, torch.float64, dev, "state", CG_STATE_DOUBLES)
+    _ext.handle_for(dev).call("bornvi_cg_step", P, float(damping), float(rel_tol), _ptr(Fp), _ptr(x), _ptr(r), _ptr(p), _ptr(state),
+                              _ext.stream_ptr(dev))
+    return state
+
+
+def cg_finish(g, x, state, info=None, iters=None, relres=None):
+    """End of a conjugate-gradient solve (bornvi_cg_finish) -> (x, info int32 [1], iters int32 [1], relres float64 [1]):
+    x = g bit for bit and info = 1 where the fallback flag of `state` is set or x is not finite, else info = 0 (converged
+    or not: relres = sqrt(rr / rr0) says).  info, iters, relres: destinations."""
+    P, dev = _cg_vectors(g, (("x", x),))
+    if not torch.is_tensor(state):
+        raise BornviError("cg: state must be a tensor")
+    _chk(state, torch.float64, dev, "state", CG_STATE_DOUBLES)
+    if info is None:
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(info, torch.int32, dev, "info", 1)
+    if iters is None:
+        iters = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        _chk(iters, torch.int32, dev, "iters", 1)
+    if relres is None:
+        relres = torch.empty(1, dtype=torch.float64, device=dev)
+    else:
+        _chk(relres, torch.float64, dev, "relres", 1)
+    _ext.handle_for(dev).call("bornvi_cg_finish", P, _ptr(g), _ptr(x), _ptr(state), _ptr(info), _ptr(iters), _ptr(relres),
+                              _ext.stream_ptr(dev))
+    return x, info, iters, relres
+
+
 def paramshift_states_bytes(n, count, include_base=True):
     """Bytes of the rows paramshift_states writes: 16 (count + base) 2^n."""
     return 16 * (int(count) + (1 if include_base else 0)) << int(n)

@@ -1330,6 +1330,57 @@ int bornvi_mps_score_sample_gram(bornvi_handle h, int n, int D, long long B, con
   return BORNVI_OK;
 }
 
+int bornvi_mps_score_jvp(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, const double* v,
+                         double scale, double* t, int* status, void* env_workspace, size_t env_workspace_bytes,
+                         bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_sample(n, D, B) || B < 2) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= D <= 32, 2 <= B <= 2^24)");
+  if (!cores || !idx || !v || !t || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!std::isfinite(scale)) return fail(h, BORNVI_ERR_INVALID, "scale must be finite");
+  // a short workspace is refused like a size: nothing is launched
+  if (!env_workspace || env_workspace_bytes < mps_sample_workspace_bytes(n, D, B))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, "the environments' workspace is too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_score_jvp(n, D, B, cores, idx, v, scale, t, status, env_workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+// ---- conjugate gradients around a caller's product (kernels_cg.hip) ------------------------------------------------
+static bool valid_cg(long long P) { return P >= 1 && P <= 2147483647ll; }
+static const char* const CG_RANGE = "bad argument (1 <= P <= 2^31 - 1)";
+
+int bornvi_cg_init(bornvi_handle h, long long P, const double* g, double* x, double* r, double* p, double* state, int* info,
+                   bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_cg(P)) return fail(h, BORNVI_ERR_INVALID, CG_RANGE);
+  if (!g || !x || !r || !p || !state || !info) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_cg_init(P, g, x, r, p, state, info, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_cg_step(bornvi_handle h, long long P, double damping, double rel_tol, const double* Fp, double* x, double* r, double* p,
+                   double* state, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_cg(P)) return fail(h, BORNVI_ERR_INVALID, CG_RANGE);
+  if (!(damping > 0.0) || !std::isfinite(damping)) return fail(h, BORNVI_ERR_INVALID, "damping must be finite and > 0");
+  if (!(rel_tol >= 0.0) || !std::isfinite(rel_tol)) return fail(h, BORNVI_ERR_INVALID, "rel_tol must be finite and >= 0");
+  if (!Fp || !x || !r || !p || !state) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_cg_step(P, damping, rel_tol, Fp, x, r, p, state, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_cg_finish(bornvi_handle h, long long P, const double* g, double* x, const double* state, int* info, int* iters,
+                     double* relres, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_cg(P)) return fail(h, BORNVI_ERR_INVALID, CG_RANGE);
+  if (!g || !x || !state || !info || !iters || !relres) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_cg_finish(P, g, x, state, info, iters, relres, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 static bool valid_score_fisher(int R, int nblocks) { return R >= 1 && R <= 1024 && nblocks >= 1 && nblocks <= 65535; }
 static const char* const SCORE_FISHER_RANGE = "unsupported size (1 <= R <= 1024, 1 <= nblocks <= 65535)";
 

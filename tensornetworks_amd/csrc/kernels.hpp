@@ -117,8 +117,18 @@ hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores,
                                  long long ld, double* rows, int* status, void* ws, hipStream_t st);
 hipError_t launch_mps_score_mu(int n, int D, long long B, const double* cores, void* ws, const double** hdr, const double** mu,
                                hipStream_t st);
+hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, const long long* idx, const double* v, double scale,
+                                double* t, int* status, void* ws, hipStream_t st);
 hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
                                       hipStream_t st);
+
+// ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
+constexpr int CG_STATE_DOUBLES = 8;      // rr, rr0, iterations, done, relres, fallback, 2 spare
+hipError_t launch_cg_init(long long P, const double* g, double* x, double* r, double* p, double* state, int* info, hipStream_t st);
+hipError_t launch_cg_step(long long P, double damping, double rel_tol, const double* Fp, double* x, double* r, double* p,
+                          double* state, hipStream_t st);
+hipError_t launch_cg_finish(long long P, const double* g, double* x, const double* state, int* info, int* iters, double* relres,
+                            hipStream_t st);
 
 // ---- sample-space Gram of the sampled MPS's score rows (kernels_mps_sample_gram.hip): T = O O^T / B without the rows ----
 constexpr long long SAMPLE_GRAM_MAX_B = 1024;        // what bornvi_spd_solve factors

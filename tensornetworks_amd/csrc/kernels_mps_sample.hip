@@ -47,6 +47,18 @@
 //   each store contiguous over the 64 lanes.  A sample with psi = 0 (or not finite) gets an all-zero column and status 2;
 //   the columns B .. ld - 1 are written as 0.0.  Sites outside the range are swept and not written.
 //
+// bornvi_mps_score_jvp: the per-sample directional derivative of log q along v [n, 2, D, D],
+//   t_b = scale <grad log q(z_b), v> = scale (2 dpsi_b / psi_b - c),   dpsi_b = sum_k l_{b,k-1}^T V_k[z_bk] r_{b,k},   c = sum_k <mu_k, V_k>.
+//   mps_score_mu_kernel forms mu into the workspace as for the score rows; mps_jvp_dot_kernel, one workgroup per site, adds
+//   the site's 2 D^2 products mu V in index order (one fma chain) into wpart[k - 1]; every workgroup of the sweep adds the n
+//   partials in site order.  mps_score_jvp_kernel has the grid and the tiles of mps_score_kernel (one sample per lane, one wave
+//   per workgroup, workgroup g walks the tiles g, g + G, ...) and one sweep, left to right, of the pair (l, dl):
+//     dl <- dl A_k[z] + l V_k[z]  (one fma chain per entry: the D terms of dl A, then the D terms of l V),   l <- l A_k[z],
+//   A_k[.] and V_k[.] zero-padded in LDS, each lane reading the matrices of its own z (at most two addresses per read); after
+//   every site l *= 2^-e as everywhere (ms_rescale) and dl *= 2^-e with the same e, so 2 dl_n[0] / l_n[0] carries no exponent.
+//   No right vector, no slice of the workspace.  t_b depends on (cores, v, scale, z_b) only.  A sample with psi = 0 (or not
+//   finite) gets t_b = 0.0 and sets the status word to 2.
+//
 // bornvi_bn_logjoint_samples: logp_b = sum_v log max(CPT_v[parents][value], p_floor), one lane per sample, nodes in order.
 //
 // No atomics, no allocation, no synchronisation: capturable, and two calls are bitwise equal.  The status word is cleared
@@ -595,6 +607,89 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_rows_kernel(const double* 
   }
 }
 
+// ---- score jvp (matrix-free natural gradient) --------------------------------------------------------------------
+// grid n: cpart[k - 1] = sum_i mu[k - 1][i] v[k - 1][i], i = (s D + a) D + c in order: one fma chain of 2 D^2 terms
+__global__ __launch_bounds__(ENV_THREADS) void mps_jvp_dot_kernel(const double* __restrict__ mu, const double* __restrict__ v, int D,
+                                                                  double* __restrict__ cpart) {
+  __shared__ double Ms[2 * MS_DMAX * MS_DMAX];
+  __shared__ double Vs[2 * MS_DMAX * MS_DMAX];
+  const int R = 2 * D * D, t = threadIdx.x;
+  const size_t off = (size_t)blockIdx.x * R;
+  for (int i = t; i < R; i += ENV_THREADS) {
+    Ms[i] = mu[off + i];
+    Vs[i] = v[off + i];
+  }
+  __syncthreads();
+  if (t == 0) {
+    double acc = 0.0;
+    for (int i = 0; i < R; ++i) acc = fma(Ms[i], Vs[i], acc);
+    cpart[blockIdx.x] = acc;
+  }
+}
+
+template <int DP>
+__global__ __launch_bounds__(MS_LANES) void mps_score_jvp_kernel(const double* __restrict__ cores, const double* __restrict__ vdir,
+                                                                 int n, int D, long long B, long long ntiles,
+                                                                 const long long* __restrict__ idx, const double* __restrict__ hdr,
+                                                                 const double* __restrict__ cpart, double scale,
+                                                                 double* __restrict__ tout, int* status) {
+  __shared__ double As[2 * DP * DP];
+  __shared__ double Vs[2 * DP * DP];
+  const int lane = threadIdx.x;
+  const double Zh = hdr[1];
+  const bool Zok = Zh > 0.0 && isfinite(Zh);
+  double cdot = 0.0;                                       // (uniform) the sites in order
+  for (int k = 0; k < n; ++k) cdot += cpart[k];
+#pragma unroll 1
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long long b = tile * MS_LANES + lane;
+    const bool active = b < B;
+    const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
+    double l[DP], dl[DP];
+#pragma unroll
+    for (int a = 0; a < DP; ++a) {
+      l[a] = a == 0 ? 1.0 : 0.0;
+      dl[a] = 0.0;
+    }
+#pragma unroll 1
+    for (int k = 1; k <= n; ++k) {
+      __syncthreads();
+      ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
+      ms_load_site<DP>(vdir, k, D, Vs, nullptr, nullptr);
+      __syncthreads();
+      const int s = (int)((z >> (n - k)) & 1ull);
+      const double* Az = As + s * DP * DP;
+      const double* Vz = Vs + s * DP * DP;
+      double ln[DP], dn[DP];
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+        double a0 = 0.0, d0 = 0.0;
+#pragma unroll
+        for (int a = 0; a < DP; ++a) {
+          const double av = Az[a * DP + c];
+          a0 = fma(l[a], av, a0);
+          d0 = fma(dl[a], av, d0);
+        }
+#pragma unroll
+        for (int a = 0; a < DP; ++a) d0 = fma(l[a], Vz[a * DP + c], d0);
+        ln[c] = a0;
+        dn[c] = d0;
+      }
+#pragma unroll
+      for (int a = 0; a < DP; ++a) l[a] = ln[a];
+      const int e = ms_rescale<DP>(l);
+#pragma unroll
+      for (int a = 0; a < DP; ++a) dl[a] = ldexp(dn[a], -e);
+    }
+    const double p0 = l[0];
+    const bool good = p0 != 0.0 && isfinite(p0) && Zok;
+    if (active) {
+      tout[b] = good ? scale * ((dl[0] + dl[0]) / p0 - cdot) : 0.0;
+      if (!good) *status = 2;
+    }
+  }
+}
+
 // ---- log joint of samples --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bn_logjoint_kernel(bornvi_bn_desc bn, int n, long long B, const long long* __restrict__ idx,
                                                           double p_floor, double* __restrict__ logp) {
@@ -687,6 +782,30 @@ hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores,
   MS_DISPATCH(S.DP, (mps_score_rows_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
                         cores, n, D, S.DS, B, ld / MS_LANES, idx, hdr, mu,
                         k_begin, k_count, ld, rows, status, (double*)(base + S.r), (int*)(base + S.er))));
+  return hipGetLastError();
+}
+
+// after launch_mps_environments: mu into the workspace's mu region (as launch_mps_score_rows), the n site partials of
+// c = <mu, v> into its wpart region (MS_MAX_WG doubles >= n), then the tangent sweep
+hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, const long long* idx, const double* v, double scale,
+                                double* t, int* status, void* ws, hipStream_t st) {
+  static_assert(MS_MAX_WG >= 63, "the site partials of c live in the wpart region");
+  const MsLayout S = ms_layout(n, D, B);
+  char* base = ws_align(ws);
+  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const double* hdr = nullptr;
+  const double* mu = nullptr;
+  e = launch_mps_score_mu(n, D, B, cores, ws, &hdr, &mu, st);
+  if (e != hipSuccess) return e;
+  double* cpart = (double*)(base + S.wpart);
+  mps_jvp_dot_kernel<<<(unsigned)n, ENV_THREADS, 0, st>>>(mu, v, D, cpart);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const long long ntiles = (B + MS_LANES - 1) / MS_LANES;
+  MS_DISPATCH(S.DP, (mps_score_jvp_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(cores, v, n, D, B, ntiles, idx, hdr, cpart, scale, t,
+                                                                                 status)));
   return hipGetLastError();
 }
 

@@ -42,6 +42,12 @@ trainers' gradient is O^T w with O the B x P matrix of the score rows, and
 so the exact blocks='full' step needs a B x B Gram (backend.mps_score_sample_gram, from the samples' left and right vectors:
 no row is formed), one backend.spd_solve of size B <= 1024 and one more backend.mps_score_vjp with the weights u.  P is not
 limited.  Duplicate samples make T singular: the damping must be positive.
+
+`CGFisherPreconditioner` solves the same full-matrix system with no matrix at all: conjugate
+gradients on (O^T O / B + damping I) delta = g, one product p -> O^T (O p) / B per iteration, O p from
+backend.mps_score_jvp (a tangent sweep, one sample per lane) and O^T t from backend.mps_score_vjp, the recurrence on the
+device (backend.cg_init / cg_step / cg_finish).  Neither P nor B is limited by a factorisation: every (n, D, B) the sampler
+accepts.  It always launches max_iters iterations; those after convergence write nothing.
 """
 import numpy as np
 import torch
@@ -169,23 +175,26 @@ class SampledFisherPreconditioner:
     def coerce(cls, spec):
         """What the sampled trainers' `natural_gradient` keyword accepts: None / False -> None, True -> the defaults, a
         number -> that damping, 'site' / 'full' -> that block structure, a SampledFisherPreconditioner -> itself;
-        'sample' -> SampleSpaceFisherPreconditioner(), an instance of it -> itself."""
+        'sample' -> SampleSpaceFisherPreconditioner(), 'cg' -> CGFisherPreconditioner(), an instance of either -> itself."""
         if spec is None or spec is False:
             return None
         if spec is True:
             return cls()
-        if isinstance(spec, (cls, SampleSpaceFisherPreconditioner)):
+        if isinstance(spec, (cls, SampleSpaceFisherPreconditioner, CGFisherPreconditioner)):
             return spec
         if isinstance(spec, str):
             if spec in cls.BLOCKS:
                 return cls(blocks=spec)
             if spec == "sample":
                 return SampleSpaceFisherPreconditioner()
-            raise ValueError(f"natural_gradient: the strings accepted are 'site', 'full' and 'sample', got {spec!r}")
+            if spec == "cg":
+                return CGFisherPreconditioner()
+            raise ValueError(f"natural_gradient: the strings accepted are 'site', 'full', 'sample' and 'cg', got {spec!r}")
         if isinstance(spec, (int, float, np.integer, np.floating)):
             return cls(damping=spec)
-        raise ValueError("natural_gradient must be None, True, a damping, 'site', 'full', 'sample', a SampledFisherPreconditioner "
-                         f"or a SampleSpaceFisherPreconditioner, got {spec!r}")
+        raise ValueError("natural_gradient must be None, True, a damping, 'site', 'full', 'sample', 'cg', a "
+                         "SampledFisherPreconditioner, a SampleSpaceFisherPreconditioner or a CGFisherPreconditioner, "
+                         f"got {spec!r}")
 
     def plan(self, n, D, B):
         """(block size R, number of blocks, sites per chunk) for cores [n, 2, D, D] and B samples; every ValueError of the
@@ -311,3 +320,73 @@ class SampleSpaceFisherPreconditioner:
         backend.mps_score_vjp(cores, idx, self._u, out=self._delta, out_logq=self._logq, status=self._status_vjp)
         self.status |= self._status_vjp
         return self._delta, self.info
+
+
+class CGFisherPreconditioner:
+    """delta ~ (F^ + damping I)^-1 grad for ALL P = 2 n D^2 parameters at once by conjugate gradients, F^ never formed
+    (module docstring): what SampledFisherPreconditioner(blocks='full') solves, at any P and any number of samples.
+    precondition always launches max_iters iterations of mps_score_jvp -> mps_score_vjp -> cg_step, so a captured epoch
+    replays; the iterations after rr <= rel_tol^2 rr0 write nothing.  An unconverged delta is returned as it is (info 0:
+    every CG iterate from 0 is a descent direction; `relres` says how far it got); info 1 means delta is the plain gradient
+    (a non-finite gradient or iterate, or no positive curvature at the first step).  It owns x, r, p, F p, t and the
+    scalars, reused across calls (a captured step writes into the same tensors)."""
+    MAX_ITERS = 32
+    REL_TOL = 1e-6
+
+    def __init__(self, damping=1e-3, max_iters=MAX_ITERS, rel_tol=REL_TOL):
+        if isinstance(damping, bool) or not isinstance(damping, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(damping) or not damping > 0:
+            raise ValueError(f"damping must be a finite number > 0 (F^ is singular along every gauge direction), got {damping!r}")
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1:
+            raise ValueError(f"max_iters must be an integer >= 1, got {max_iters!r}")
+        if isinstance(rel_tol, bool) or not isinstance(rel_tol, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(rel_tol) or not rel_tol >= 0:
+            raise ValueError(f"rel_tol must be a finite number >= 0, got {rel_tol!r}")
+        self.damping, self.max_iters, self.rel_tol = float(damping), int(max_iters), float(rel_tol)
+        self.info = None          # int32 [1] of the last call: 0, or 1 where delta is the plain gradient
+        self.iters = None         # int32 [1]: the iterations the last call took
+        self.relres = None        # float64 [1]: sqrt(r^T r / g^T g) of the recurrence at the end of the last call
+        self.status = None        # int32 [1]: the jvp's and the vjp's status words or-ed
+        self._key = None
+        self._x = self._r = self._p = self._Fp = self._t = self._logq = self._state = self._status_vjp = None
+
+    def plan(self, n, D, B):
+        """(P, 1, n): the size of the system, one block, every site at once; every ValueError of the shape is raised here,
+        without touching the GPU."""
+        n, D, B = int(n), int(D), int(B)
+        if not 1 <= n <= backend.MPS_SAMPLED_MAX_N:
+            raise ValueError(f"natural_gradient: 1 ... {backend.MPS_SAMPLED_MAX_N} sites, got {n}")
+        if not 1 <= D <= backend.MPS_MAX_BOND:
+            raise ValueError(f"natural_gradient: bond dimension 1 ... {backend.MPS_MAX_BOND}, got {D}")
+        if not backend.SCORE_ROWS_MIN_BATCH <= B <= backend.MPS_SAMPLED_MAX_BATCH:
+            raise ValueError(f"natural_gradient='cg': {backend.SCORE_ROWS_MIN_BATCH} ... 2^24 samples, got {B}")
+        return 2 * n * D * D, 1, n
+
+    def precondition(self, cores, idx, grad):
+        """After backend.mps_environments(cores, len(idx)): -> (delta float64 [n, 2, D, D], info int32 [1])."""
+        n, D, B = backend._mps_args(cores, int(idx.numel()))
+        self.plan(n, D, B)
+        dev = cores.device
+        if tuple(grad.shape) != tuple(cores.shape) or grad.dtype != cores.dtype or grad.device != dev:
+            raise ValueError(f"grad: expected float64 {tuple(cores.shape)} on {dev}, got {grad.dtype} {tuple(grad.shape)} on {grad.device}")
+        key = (n, D, B, dev)
+        if self._key != key:
+            self._x, self._r, self._p, self._Fp = (torch.empty(tuple(cores.shape), dtype=torch.float64, device=dev) for _ in range(4))
+            self._t = torch.empty(B, dtype=torch.float64, device=dev)
+            self._logq = torch.empty(B, dtype=torch.float64, device=dev)
+            self._state = torch.empty(backend.CG_STATE_DOUBLES, dtype=torch.float64, device=dev)
+            self.info = torch.empty(1, dtype=torch.int32, device=dev)
+            self.iters = torch.empty(1, dtype=torch.int32, device=dev)
+            self.relres = torch.empty(1, dtype=torch.float64, device=dev)
+            self.status = torch.empty(1, dtype=torch.int32, device=dev)
+            self._status_vjp = torch.empty(1, dtype=torch.int32, device=dev)
+            self._key = key
+        g = grad.contiguous()
+        backend.cg_init(g, self._x, self._r, self._p, self._state, self.info)
+        for _ in range(self.max_iters):
+            backend.mps_score_jvp(cores, idx, self._p, scale=1.0 / B, out=self._t, status=self.status)
+            backend.mps_score_vjp(cores, idx, self._t, out=self._Fp, out_logq=self._logq, status=self._status_vjp)
+            backend.cg_step(self._Fp, self._x, self._r, self._p, self._state, self.damping, self.rel_tol)
+        backend.cg_finish(g, self._x, self._state, self.info, self.iters, self.relres)
+        self.status |= self._status_vjp           # both words depend on the samples only: the last iteration's are every one's
+        return self._x, self.info

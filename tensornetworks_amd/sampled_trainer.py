@@ -9,6 +9,8 @@ before the guard and the clip, by delta = (F^ + damping I)^-1 grad, F^ the Fishe
 history['natgrad_info'] counts the blocks per epoch whose factorisation failed (they keep the plain gradient).
 natural_gradient='sample' (SampleSpaceFisherPreconditioner) is the full-matrix step solved in sample space: it takes the
 weights w and returns delta = sum_b u_b grad log q(z_b) with (T + damping I) u = w, for num_samples <= 1024.
+natural_gradient='cg' (CGFisherPreconditioner) solves the same full-matrix system by conjugate gradients without a matrix, at
+any bond dimension and any num_samples; history['natgrad_iters'] then holds the iterations each epoch took.
 
 A subclass supplies
   LOSS_KEYS                     the history keys it fills per epoch, MIN_SAMPLES / MAX_SAMPLES and their wording,
@@ -25,7 +27,7 @@ from . import backend
 from .bayesian_network import pack_network
 from .born_machine_mps_sampled import SampledMPSBornMachine
 from .ksd_vi import guarded_update, make_optimizer
-from .natural_gradient import SampledFisherPreconditioner, SampleSpaceFisherPreconditioner
+from .natural_gradient import CGFisherPreconditioner, SampledFisherPreconditioner, SampleSpaceFisherPreconditioner
 
 
 class SampledTrainer:
@@ -129,6 +131,9 @@ class SampledTrainer:
             history['tvd'], history['kl'] = [], []
         if self.natural_gradient is not None:
             history['natgrad_info'] = []
+        cg = isinstance(self.natural_gradient, CGFisherPreconditioner)
+        if cg:
+            history['natgrad_iters'] = []
         grad_norm = None
         for epoch in range(num_epochs):
             opt.zero_grad()
@@ -142,6 +147,8 @@ class SampledTrainer:
             history['status'].append(int(st_t.item()))
             if self.natural_gradient is not None:
                 history['natgrad_info'].append(int((self.natural_gradient.info != 0).sum().item()))
+            if cg:
+                history['natgrad_iters'].append(int(self.natural_gradient.iters.item()))
             if exact:
                 tvd, kl = self.exact_report(true_posterior_for_tvd)
                 history['tvd'].append(tvd)
