@@ -342,7 +342,8 @@ int bornvi_ksd_grad_finish(bornvi_handle h, int n, const double* shifted, int n_
  * of (seed, *epoch_dev, id, draw index) through Philox4x32-10 (kernels_shots.hip states the exact function), so they do
  * not depend on how the rows are batched or sharded.  epoch_dev: int64 in device memory, read by the kernels (a graph
  * replay sees the value current at replay time; its low 32 bits enter the counter).  A probability-0 entry is never
- * drawn; a row of zeros yields zeros.  1 <= shots <= 2^31 - 1.  Workspace: bornvi_shots_workspace_bytes(h, n, B). */
+ * drawn (the pick rule tests the entry's value, not only its cdf: csrc/shots_dev.hpp), so every row with a positive
+ * entry sums to exactly S; a row of zeros yields zeros.  1 <= shots <= 2^31 - 1.  Workspace: bornvi_shots_workspace_bytes(h, n, B). */
 size_t bornvi_shots_workspace_bytes(bornvi_handle h, int n, int B);
 int bornvi_shots_histogram(bornvi_handle h, int n, int B, const double* probs, double* freq, long long shots,
                            unsigned long long seed, const long long* epoch_dev, int include_base, int p_begin,

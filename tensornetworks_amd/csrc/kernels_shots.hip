@@ -8,11 +8,16 @@
 //   draws 2m and 2m + 1 of that (level, block) take u = ((w1:w0) >> 11) 2^-53 and u = ((w3:w2) >> 11) 2^-53, in [0, 1).
 // A row of 2^n outcomes is cut into blocks of 2^12; the block masses form the row of the next level (2^(n-12) entries,
 // cut again while longer than one block).  The top level holds one block and gets all S draws; a block with m draws
-// (its count at the level above) draws m outcomes from its own contents:  x = first i with cdf[i] > u cdf[last]
-// (cdf = inclusive prefix sums of the block), or the block's last non-zero entry if no cdf[i] exceeds it (rounding).
+// (its count at the level above) draws m outcomes from its own contents by rule R (shots_dev.hpp): with cdf the block's
+// inclusive prefix sums in the scan's order and lo0 the first i with cdf[i] > u cdf[last], the outcome is the first
+// i >= lo0 whose value is positive, or the block's last positive entry if there is none; a block without a positive
+// entry counts nothing.  (Where zero entries never raise the cdf -- dyadic rows, any single running sum -- this is
+// "first i with cdf[i] > u cdf[last]".  The scan is not one running sum: at a thread boundary a zero entry's cdf can
+// exceed its predecessor's by an ulp, and only the positivity mask keeps such an entry, or a zero-mass block, undrawn.)
 // Given the counts of the level above, the draws inside a block are conditionally i.i.d. from the block's normalised
 // contents, so the level-0 counts are one exact multinomial sample of the row: no normal or Poisson approximation.
-// A probability-0 outcome is never drawn; a row whose entries are all zero yields zeros.
+// A probability-0 outcome is never drawn, so every row with a positive entry sums to exactly S; a row whose entries are
+// all zero yields zeros.
 //
 // Traffic: the mass kernel reads every row once, the draw kernel reads it once more and writes the frequencies
 // (in place allowed: a workgroup reads its whole block into LDS before it writes it): 3 B 2^n 8 bytes.
@@ -21,11 +26,12 @@
 
 #include "kernels.hpp"
 #include "philox_dev.hpp"
+#include "shots_dev.hpp"
 
 namespace bornvi {
 
 namespace {
-constexpr int SH_BLOCK_BITS = 12, SH_BLOCK = 1 << SH_BLOCK_BITS;
+constexpr int SH_BLOCK_BITS = SHOTS_BLOCK_BITS, SH_BLOCK = SHOTS_BLOCK;
 constexpr int SH_THREADS = 512, SH_EPT = SH_BLOCK / SH_THREADS;     // draw kernel: 8 consecutive entries per thread in the scan
 constexpr int SM_THREADS = 256, SM_EPT = SH_BLOCK / SM_THREADS;     // mass kernel
 
@@ -71,6 +77,7 @@ __global__ __launch_bounds__(SH_THREADS) void shots_draw_kernel(const double* sr
   __shared__ double cdf[SH_BLOCK];
   __shared__ int hist[SH_BLOCK];
   __shared__ double tsum[2][SH_THREADS];
+  __shared__ uint32_t pos[SHOTS_MASK_WORDS];      // bit i: entry i is positive; thread t owns byte t (its 8 entries)
   __shared__ int lastnz;
   const int t = threadIdx.x;
   const long long g = blockIdx.x;
@@ -82,18 +89,26 @@ __global__ __launch_bounds__(SH_THREADS) void shots_draw_kernel(const double* sr
     cdf[i] = src[base + i];
     hist[i] = 0;
   }
-  if (t == 0) lastnz = -1;
+  if (t == 0) {
+    lastnz = -1;
+    pos[SHOTS_MASK_WORDS - 1] = 0u;
+  }
   __syncthreads();
   // inclusive scan: 8 consecutive entries per thread, then a scan of the 512 thread totals
   const int c0 = t * SH_EPT, c1 = min(c0 + SH_EPT, blk);
   double run = 0.0;
   int nz = -1;
+  uint32_t mybits = 0u;
   for (int i = c0; i < c1; ++i) {
     const double v = cdf[i];
-    if (v > 0.0) nz = i;
+    if (v > 0.0) {
+      nz = i;
+      mybits |= 1u << (i - c0);
+    }
     run += v;
     cdf[i] = run;
   }
+  reinterpret_cast<unsigned char*>(pos)[t] = (unsigned char)mybits;     // little-endian: bit (8t + k) & 31 of word t >> 2
   if (nz >= 0) atomicMax(&lastnz, nz);
   tsum[0][t] = run;
   __syncthreads();
@@ -110,29 +125,20 @@ __global__ __launch_bounds__(SH_THREADS) void shots_draw_kernel(const double* sr
   }
   __syncthreads();
 
-  if (m > 0) {
+  const int last = lastnz;
+  if (m > 0 && last >= 0) {
     const double total = cdf[blk - 1];
-    const int last = lastnz;
     const uint32_t cid = circuit_id(row, include_base, p_begin, p_stride);
     const uint32_t ep = (uint32_t)(unsigned long long)(*epoch_dev);
     const uint32_t lb = ((uint32_t)level << 24) | (uint32_t)b;
     const int npairs = (int)(((long long)m + 1) >> 1);
     for (int pr = t; pr < npairs; pr += SH_THREADS) {
       const uint4 w = philox4x32_10(make_uint4((uint32_t)pr, lb, cid, ep), seed_lo, seed_hi);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (2 * pr + h >= m) break;
-        const double u = h ? unit53(w.z, w.w) : unit53(w.x, w.y);
-        const double x = u * total;
-        int lo = 0, hi = blk;                 // first i with cdf[i] > x
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (cdf[mid] > x) hi = mid;
-          else lo = mid + 1;
-        }
-        if (lo >= blk) lo = last;
-        if (lo >= 0) atomicAdd(&hist[lo], 1);
-      }
+      const double x[2] = {unit53(w.x, w.y) * total, unit53(w.z, w.w) * total};
+      int pick[2];                            // both draws of the call are searched together; an odd m drops the last
+      shots_pick<2>(cdf, pos, blk, last, x, pick);
+      atomicAdd(&hist[pick[0]], 1);
+      if (2 * pr + 1 < m) atomicAdd(&hist[pick[1]], 1);
     }
   }
   __syncthreads();

@@ -1,7 +1,9 @@
 """Finite-shot KSD training on the GPU: the sampler (bornvi_shots_histogram) against the NumPy mirror of its documented
-draw function (tests/shots_mirror.py) bit for bit on dyadic rows, its invariants and statistics, and the shots mode of
-QuantumBornMachine / KSDVariationalInference (eager, graph replay, train(), two ranks).  Every seed is fixed: each
-statistical check is deterministic, with thresholds at about the 1e-6 level of its null distribution."""
+draw function (tests/shots_mirror.py) bit for bit on dyadic rows, draw for draw against extended-precision inversion on
+rows that are not dyadic (sparse and peaked, one dominant outcome, 30 orders of magnitude and unnormalised, a circuit's own
+|psi|^2), its invariants and statistics, and the shots mode of QuantumBornMachine / KSDVariationalInference (eager, graph
+replay, train(), two ranks).  Every seed is fixed: each statistical check is deterministic, with thresholds at about the
+1e-6 level of its null distribution."""
 import os
 
 import numpy as np
@@ -143,6 +145,94 @@ def test_mean_histogram_converges_to_q(dev):
     se = np.sqrt(qq * (1 - qq) / (8 * E * S))
     z = np.abs(mean - qq)[qq > 0] / se[qq > 0]
     assert z.max() < 6.0, z.max()                                  # 64 bins, family-wise ~1e-6
+
+
+# ---- rows that are not dyadic: every draw against exact inversion -----------------------------------------------------------
+# sm.histogram_exact forms masses and cdfs in extended precision and counts the draws whose u lies within 2^-40 of a boundary
+# (about 100 times what the kernels' order of summation can move one: tests/test_shots_host.py derives it).  With no such
+# draw, the kernel's counts must equal the reference's exactly.  The synthetic inputs are the ones that host module has
+# already shown to be free of undecided draws.
+CASES = {c[0]: c for c in sm.synthetic_cases()}
+
+
+def _equals_exact(probs, n, S, seed, epoch, dev, **ids):
+    """Asserts freq == exact counts / S for one call; returns the number of draws compared."""
+    got = _sample(probs, n, S, seed, epoch, dev, **ids)
+    want, undecided = sm.histogram_exact(probs, S, seed, epoch, **ids)
+    assert undecided == 0
+    assert np.array_equal(got, want / S)
+    c = np.rint(got * S).astype(np.int64)
+    has_mass = (np.asarray(probs) > 0).any(axis=1)
+    assert (c.sum(axis=1) == np.where(has_mass, S, 0)).all()         # every row with a positive entry sums to S
+    assert (c[np.asarray(probs) == 0] == 0).all()                    # probability 0: never drawn
+    return int(c.sum())
+
+
+@pytest.mark.parametrize("n,kind", [(n, k) for n in sm.REAL_N for k in "abcd" if k != "d" or n >= 3])
+def test_real_rows_equal_exact_inversion(dev, n, kind):
+    if kind == "d":                                                  # the device's own |psi|^2 of a hardware-efficient circuit,
+        probs = _hw_q(n, 2, 40 + n, dev).cpu().numpy()[None]         # read back: the reference's input bit for bit
+        assert abs(probs.sum() - 1.0) < 1e-12
+    else:
+        probs = sm.real_rows(kind, n)
+    draws = sum(_equals_exact(probs, n, S, sm.REAL_SEED, sm.REAL_EPOCH, dev) for S in sm.REAL_SHOTS)
+    print(f"n = {n}, kind ({kind}): undecided 0, {draws} draws compared")
+
+
+def test_full_top_block_dyadic_equals_mirror(dev):
+    """n = 24: the top level is exactly one full block of 4096 masses."""
+    name, make, S, seed, epoch, ids = CASES["n24-dyadic"]
+    probs = make()
+    want = sm.histogram(probs, S, seed, epoch)
+    assert np.array_equal(_sample(probs, 24, S, seed, epoch, dev), want / S) and want.sum() == S
+    print(f"n = 24 dyadic: bitwise, {S} draws compared")
+
+
+def test_full_top_block_sparse_equals_exact_inversion(dev):
+    name, make, S, seed, epoch, ids = CASES["n24-sparse"]
+    probs = make()
+    assert (probs == 0).mean() > 0.98
+    draws = _equals_exact(probs, 24, S, seed, epoch, dev)
+    print(f"n = 24, 99 % zeros: undecided 0, {draws} draws compared")
+
+
+def test_power_of_two_scaling_keeps_every_bit(dev):
+    """Every add and the product u * total scale exactly by a power of two as long as nothing goes subnormal or overflows:
+    a row times 2^-600 or 2^+600 gives the bits of the unscaled row's frequencies."""
+    freqs, draws = [], 0
+    for e in sm.SCALES:
+        name, make, S, seed, epoch, ids = CASES[f"scale-2^{e:+.0f}"]
+        probs = make()
+        assert np.isfinite(probs).all() and probs[probs > 0].min() > 2.0 ** -400 * probs.sum() > 0
+        assert probs[probs > 0].min() > 2.0 ** -1000 and probs.sum() < 2.0 ** 1000
+        draws += _equals_exact(probs, 13, S, seed, epoch, dev)
+        freqs.append(_sample(probs, 13, S, seed, epoch, dev))
+    assert np.array_equal(freqs[0], freqs[1]) and np.array_equal(freqs[0], freqs[2])
+    print(f"scaled rows: undecided 0, {draws} draws compared")
+
+
+@pytest.mark.parametrize("kind", ["a", "c"])
+def test_real_rows_strided_ids_equal_exact_inversion(dev, kind):
+    name, make, S, seed, epoch, ids = CASES[f"strided-{kind}"]
+    assert ids == dict(include_base=False, p_begin=5, p_stride=3)
+    draws = _equals_exact(make(), 9, S, seed, epoch, dev, **ids)
+    print(f"strided ids, kind ({kind}): undecided 0, {draws} draws compared")
+
+
+def test_batch_equals_rows_sampled_one_call_each(dev):
+    name, make, S, seed, epoch, ids = CASES["mixed-batch"]
+    probs = make()
+    n = 13
+    draws = _equals_exact(probs, n, S, seed, epoch, dev)
+    batch = _sample(probs, n, S, seed, epoch, dev)
+    for r in range(len(probs)):
+        if r == 0:
+            alone = _sample(probs[:1], n, S, seed, epoch, dev)[0]
+        else:                                                        # row r is shift (r - 1) & 1 of parameter (r - 1) >> 1:
+            pair = np.stack([probs[0], probs[r]]) if (r - 1) & 1 else probs[r:r + 1]      # the - shift is a call's row 1
+            alone = _sample(pair, n, S, seed, epoch, dev, include_base=False, p_begin=(r - 1) >> 1)[-1]
+        assert np.array_equal(alone, batch[r]), r
+    print(f"batch of {len(probs)}: undecided 0, {draws} draws compared")
 
 
 def _vi(n, L, dev, shots=None, seed=0, ansatz="hardware_efficient", init="small_random", **kw):
