@@ -115,6 +115,7 @@ hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, 
                                 double* grad_cores, int* status, void* ws, hipStream_t st);
 hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores, const long long* idx, int k_begin, int k_count,
                                  long long ld, double* rows, int* status, void* ws, hipStream_t st);
+hipError_t launch_ms_clear_status(int* status, hipStream_t st);      // the one-lane clear in front of every status writer
 hipError_t launch_mps_score_mu(int n, int D, long long B, const double* cores, void* ws, const double** hdr, const double** mu,
                                hipStream_t st);
 hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, const long long* idx, const double* v, double scale,

@@ -9,55 +9,57 @@
 //   its largest magnitude (exact), and the running sum of the e's is stored beside it:  true E_k = E^_k 2^eE[k].
 //   log Z = log E^_0[0, 0] + eE[0] ln 2.
 //
-// bornvi_mps_sample: one sample per lane, one wave per workgroup; l (DP doubles, DP = 2, 4, 8, 16, 32 >= D) in registers,
-//   A_k[0], A_k[1], E^_k zero-padded in LDS and read as broadcasts.  For k = 1 .. n:
-//     u_s = l A_k[s],  m_s = u_s E^_k u_s^T = sum_d u_s[d] (sum_c u_s[c] E^_k[c][d]),  z_k = [U_k (m_0 + m_1) >= m_0],  l = u_{z_k}
-//   then l *= 2^-e (e = ilogb of its largest magnitude), the e's summed in el.  The common factor 2^eE[k] of both m_s drops out.
+// The lanes' vectors l^, r^, their steps and exponents, the right-to-left sweep, the amplitude test, the site factor and the
+// environment term mu are defined in mps_sample_dev.hpp, once, and named here by the helper that computes them.
+//
+// bornvi_mps_sample: one sample per lane, one wave per workgroup; l^ in registers, A_k[0], A_k[1], E^_k zero-padded in LDS
+//   and read as broadcasts.  For k = 1 .. n:
+//     u_s = l A_k[s] (ms_row_dot's chain, the two s in one loop),  m_s = u_s E^_k u_s^T = sum_d u_s[d] (sum_c u_s[c] E^_k[c][d]),  z_k = [U_k (m_0 + m_1) >= m_0],
+//   then l = u_{z_k} rescaled (ms_rescale), the exponents summed in el.  The common factor 2^eE[k] of both m_s drops out.
 //   U_k: Philox4x32-10 (philox_dev.hpp), key = (seed & 0xffffffff, seed >> 32),
 //     counter = (b, ceil(k / 2) - 1, 0xffffffff, epoch & 0xffffffff) -> w0 .. w3;
 //     odd k: U_k = ((w1:w0) >> 11) 2^-53,  even k: U_k = ((w3:w2) >> 11) 2^-53   (the call of k - 1).
 //   (0xffffffff is no circuit id of the shots path: those are 0 .. 2 P + 2 for P circuit parameters.)  A draw depends on
 //   (seed, epoch, b, k) and on the sample's own earlier bits only: not on B, the grid or the tiling.
 //   If m_0 + m_1 is 0 or not finite the status word becomes 1, the sample's remaining bits are 0 and its logq is NaN.
-//   logq = 2 log|l_n[0]| - log E^_0[0, 0] + (2 el - eE[0]) ln 2.
+//   logq = ms_logq(l^_n[0], el).
 //
 // bornvi_mps_score_vjp: grad = sum_b w_b grad log q(z_b) = sum_b (2 w_b / psi_b) l_{b,k-1}^T (x) r_{b,k}^T at [k, z_{b,k}]
-//                              - (sum_b w_b) 2 L_{k-1} A_k[s] E_k / Z.
-//   One wave per workgroup and a tile of 64 samples at a time, one sample per lane; at most MS_MAX_WG workgroups, each
-//   walking the tiles wg, wg + G, ...  Right-to-left sweep: r_k = A_{k+1}[z_{k+1}] r_{k+1} in registers (rescaled like l,
-//   exponent er_k), r^_1 .. r^_{n-1} and their exponents stored in the workgroup's slice of the workspace; psi = r^_0[0] 2^er_0.
-//   Left-to-right sweep: X[b][a] = 2 w_b / r^_0[0] * 2^(el_{k-1} + er_k - er_0) * l^_{k-1}[a] goes to LDS and
+//                              - (sum_b w_b) mu[k].
+//   mps_score_kernel: one wave per workgroup and a tile of 64 samples at a time, one sample per lane; at most MS_MAX_WG
+//   workgroups, each walking the tiles wg, wg + G, ...  ms_right_sweep with MsSliceStore: r^_1 .. r^_{n-1} and their exponents
+//   go to the workgroup's slice of the workspace; logq = ms_logq(r^_0[0], er_0).  Left to right (ms_left_step):
+//   X[b][a] = cf l^_{k-1}[a], cf = ms_site_factor with g = 2 w_b / r^_0[0], goes to LDS and
 //   dA_k[s] += X_s^T R_k (X_s: the rows with z_{b,k} = s, others 0) runs on v_mfma_f64_16x16x4_f64, 16 steps of 4 samples,
 //   the B operand read straight from the slice ([sample][DS], 16 consecutive doubles of 4 rows per step, the layout of
 //   kernels_mps.hip's dA_k); the workgroup adds the tile into its own partial [n, 2, D, D] (first tile: stores).
 //   mps_score_finish_kernel, one workgroup per site: the partials in workgroup order, sum_b w_b (per tile a butterfly over the
-//   64 lanes, tiles in order, then the workgroups' totals: 64-lane butterflies of lane-strided sums, waves in order) and the
-//   environment term, T_s = A_s E^_k and M_s = L^_{k-1} T_s as fma chains in index order, scaled by 2^(eL[k-1] + eE[k] - eE[0]) / E^_0[0, 0].
-//   A sample with psi = 0 (or not finite) gets logq = -inf (NaN), weight 0 in the first term, and sets the status word to 2.
+//   64 lanes, tiles in order, then the workgroups' totals: 64-lane butterflies of lane-strided sums, waves in order) and
+//   mu[k] by ms_env_stage and ms_env_entry.
+//   A sample that fails ms_amplitude_ok gets logq = -inf (NaN), weight 0 in the first term, and sets the status word to 2.
 //
 // bornvi_mps_score_rows: the per-sample score rows of the sampled Fisher estimate,
-//   o_b[k, s, a, c] = 2 [z_{b,k} = s] l_{b,k-1}[a] r_{b,k}[c] / psi_b - mu[k, s, a, c],   mu = 2 L_{k-1} A_k[s] E_k / Z,
+//   o_b[k, s, a, c] = 2 [z_{b,k} = s] l_{b,k-1}[a] r_{b,k}[c] / psi_b - mu[k, s, a, c],
 //   rows[k - 1 - k_begin][(s D + a) D + c][b], leading dimension ld (a power of two >= max(B, 64): what the Gram takes).
-//   mps_score_mu_kernel, one workgroup per site, forms mu by mps_score_finish_kernel's expression, in its order and with
-//   its scaling exponents, into the workspace.  mps_score_rows_kernel has the shape of mps_score_kernel (one sample per
-//   lane, one wave per workgroup, workgroup g walks the 64-column tiles g, g + G, ... of the ld columns; the same
-//   right-to-left sweep into the workgroup's slice); on the way back l^_{k-1} and r^_k of the lane's sample go to LDS
-//   ([a][lane]: conflict free) and for the sites k_begin < k <= k_begin + k_count the lane writes its 2 D^2 entries
-//     (cf l^[a]) r^[c] - mu  (z = s),   0 - mu  (z != s),   cf = (2 / r^_0[0]) 2^(el_{k-1} + er_k - er_0),
-//   each store contiguous over the 64 lanes.  A sample with psi = 0 (or not finite) gets an all-zero column and status 2;
+//   mps_score_mu_kernel, one workgroup per site: mu by ms_env_stage and ms_env_entry into the workspace.
+//   mps_score_rows_kernel: one sample per lane, one wave per workgroup, workgroup g walks the 64-column tiles g, g + G, ... of
+//   the ld columns; ms_right_sweep with MsSliceStore; left to right (ms_left_step) l^_{k-1} and r^_k of the lane's sample go
+//   to LDS ([a][lane]: conflict free) and for the sites k_begin < k <= k_begin + k_count the lane writes its 2 D^2 entries
+//     (cf l^[a]) r^[c] - mu  (z = s),   0 - mu  (z != s),   cf = ms_site_factor with g = 2 / r^_0[0],
+//   each store contiguous over the 64 lanes.  A sample that fails ms_amplitude_ok gets an all-zero column and status 2;
 //   the columns B .. ld - 1 are written as 0.0.  Sites outside the range are swept and not written.
 //
 // bornvi_mps_score_jvp: the per-sample directional derivative of log q along v [n, 2, D, D],
 //   t_b = scale <grad log q(z_b), v> = scale (2 dpsi_b / psi_b - c),   dpsi_b = sum_k l_{b,k-1}^T V_k[z_bk] r_{b,k},   c = sum_k <mu_k, V_k>.
-//   mps_score_mu_kernel forms mu into the workspace as for the score rows; mps_jvp_dot_kernel, one workgroup per site, adds
-//   the site's 2 D^2 products mu V in index order (one fma chain) into wpart[k - 1]; every workgroup of the sweep adds the n
-//   partials in site order.  mps_score_jvp_kernel has the grid and the tiles of mps_score_kernel (one sample per lane, one wave
-//   per workgroup, workgroup g walks the tiles g, g + G, ...) and one sweep, left to right, of the pair (l, dl):
+//   mps_score_mu_kernel forms mu into the workspace; mps_jvp_dot_kernel, one workgroup per site, adds the site's 2 D^2
+//   products mu V in index order (one fma chain) into wpart[k - 1]; every workgroup of the sweep adds the n partials in site
+//   order.  mps_score_jvp_kernel has mps_score_kernel's grid and tiles and one sweep, left to right, of the pair (l, dl):
 //     dl <- dl A_k[z] + l V_k[z]  (one fma chain per entry: the D terms of dl A, then the D terms of l V),   l <- l A_k[z],
+//   ms_row_dot's chain written out so that l A and dl A share one loop and each A entry is read once for both,
 //   A_k[.] and V_k[.] zero-padded in LDS, each lane reading the matrices of its own z (at most two addresses per read); after
-//   every site l *= 2^-e as everywhere (ms_rescale) and dl *= 2^-e with the same e, so 2 dl_n[0] / l_n[0] carries no exponent.
-//   No right vector, no slice of the workspace.  t_b depends on (cores, v, scale, z_b) only.  A sample with psi = 0 (or not
-//   finite) gets t_b = 0.0 and sets the status word to 2.
+//   every site l is rescaled (ms_rescale) and dl *= 2^-e with the same e, so 2 dl_n[0] / l_n[0] carries no exponent.
+//   No right vector, no slice of the workspace.  t_b depends on (cores, v, scale, z_b) only.  A sample that fails
+//   ms_amplitude_ok (on l^_n[0]) gets t_b = 0.0 and sets the status word to 2.
 //
 // bornvi_bn_logjoint_samples: logp_b = sum_v log max(CPT_v[parents][value], p_floor), one lane per sample, nodes in order.
 //
@@ -76,10 +78,7 @@ namespace bornvi {
 
 namespace {
 constexpr int MS_MAX_WG = 256;             // score kernel: workgroups (= workspace slices and partials) at most
-constexpr int ENV_THREADS = 256;
-constexpr int MS_DMAX = 32;
 constexpr uint32_t MS_PHILOX_DOMAIN = 0xffffffffu;
-constexpr double MS_LN2 = 0.693147180559945309417232121458;
 
 typedef double ms_d4 __attribute__((ext_vector_type(4)));
 
@@ -90,7 +89,7 @@ struct MsLayout {
 
 MsLayout ms_layout(int n, int D, long long B) {
   MsLayout S;
-  S.DP = D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32;
+  S.DP = ms_dp(D);
   S.DS = (D + 1) & ~1;
   const long long tiles = (B + MS_LANES - 1) / MS_LANES;
   S.G = (int)(tiles < MS_MAX_WG ? tiles : MS_MAX_WG);
@@ -109,11 +108,6 @@ MsLayout ms_layout(int n, int D, long long B) {
   return S;
 }
 
-__device__ __forceinline__ double ms_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 __device__ __forceinline__ double ms_wave_max(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
@@ -121,18 +115,18 @@ __device__ __forceinline__ double ms_wave_max(double v) {
 }
 
 // ---- environments ----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(ENV_THREADS) void mps_env_kernel(const double* __restrict__ cores, int n, int D, double* __restrict__ E,
+__global__ __launch_bounds__(MS_ENV_THREADS) void mps_env_kernel(const double* __restrict__ cores, int n, int D, double* __restrict__ E,
                                                               double* __restrict__ L, int* __restrict__ eE, int* __restrict__ eL,
                                                               double* __restrict__ hdr, double* __restrict__ logZ_out) {
   __shared__ double As[2 * MS_DMAX * MS_DMAX];
   __shared__ double X[MS_DMAX * MS_DMAX];
   __shared__ double T[2 * MS_DMAX * MS_DMAX];
-  __shared__ double red[ENV_THREADS / 64];
+  __shared__ double red[MS_ENV_THREADS / 64];
   const bool right = blockIdx.x == 0;
   double* out = right ? E : L;
   int* eo = right ? eE : eL;
   const int DD = D * D, t = threadIdx.x;
-  for (int i = t; i < DD; i += ENV_THREADS) {
+  for (int i = t; i < DD; i += MS_ENV_THREADS) {
     X[i] = i == 0 ? 1.0 : 0.0;
     out[(long long)(right ? n : 0) * DD + i] = X[i];
   }
@@ -142,9 +136,9 @@ __global__ __launch_bounds__(ENV_THREADS) void mps_env_kernel(const double* __re
     const int k = right ? n - step : step + 1;       // the site whose matrices this step uses
     const int dst = right ? k - 1 : k;
     __syncthreads();
-    for (int i = t; i < 2 * DD; i += ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+    for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
     __syncthreads();
-    for (int i = t; i < 2 * DD; i += ENV_THREADS) {
+    for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
       const int s = i / DD, a = (i % DD) / D, d = i % D;
       double acc = 0.0;
       for (int c = 0; c < D; ++c) acc = fma(right ? As[s * DD + a * D + c] : As[s * DD + c * D + a], X[c * D + d], acc);
@@ -155,7 +149,7 @@ __global__ __launch_bounds__(ENV_THREADS) void mps_env_kernel(const double* __re
     double mx = 0.0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int i = t + ENV_THREADS * j;
+      const int i = t + MS_ENV_THREADS * j;
       v[j] = 0.0;
       if (i < DD) {
         const int a = i / D, b = i % D;
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(ENV_THREADS) void mps_env_kernel(const double* __re
     ex += e;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int i = t + ENV_THREADS * j;
+      const int i = t + MS_ENV_THREADS * j;
       if (i < DD) {
         const double x = ldexp(v[j], -e);
         X[i] = x;
@@ -212,8 +206,7 @@ __global__ __launch_bounds__(MS_LANES) void mps_sample_kernel(const double* __re
   const bool active = b < B;
   const uint32_t ep = (uint32_t)(unsigned long long)(*epoch_dev);
   double l[DP];
-#pragma unroll
-  for (int a = 0; a < DP; ++a) l[a] = a == 0 ? 1.0 : 0.0;
+  ms_fill<DP>(l, 1.0);
   int el = 0;
   unsigned long long z = 0;
   bool dead = false;
@@ -225,7 +218,7 @@ __global__ __launch_bounds__(MS_LANES) void mps_sample_kernel(const double* __re
     __syncthreads();
     if (k & 1) w = philox4x32_10(make_uint4((uint32_t)b, (uint32_t)((k + 1) / 2 - 1), MS_PHILOX_DOMAIN, ep), seed_lo, seed_hi);
     const double U = (k & 1) ? unit53(w.x, w.y) : unit53(w.z, w.w);
-    double u0[DP], u1[DP];
+    double u0[DP], u1[DP];           // ms_row_dot's chains, both s in one loop: see mps_sample_dev.hpp
 #pragma unroll
     for (int c = 0; c < DP; ++c) {
       double a0 = 0.0, a1 = 0.0;
@@ -263,11 +256,27 @@ __global__ __launch_bounds__(MS_LANES) void mps_sample_kernel(const double* __re
   }
   if (active) {
     idx[b] = (long long)z;
-    logq[b] = dead ? __builtin_nan("") : (2.0 * log(fabs(l[0])) - log(hdr[1])) + (2.0 * (double)el - hdr[2]) * MS_LN2;
+    logq[b] = dead ? __builtin_nan("") : ms_logq(l[0], el, hdr[1], hdr[2]);
   }
 }
 
 // ---- score gradient --------------------------------------------------------------------------------------------
+// ms_right_sweep's store of the score and rows kernels: r^_k and er_k into slot k of the workgroup's slice, k = 1 .. n - 1
+template <int DP>
+struct MsSliceStore {
+  double* rsl;
+  int* esl;
+  int n, DS, lane;
+  __device__ __forceinline__ void operator()(int k, const double (&r)[DP], int er) const {
+    if (k >= n) return;
+    double* dst = rsl + ((size_t)k * MS_LANES + lane) * DS;
+#pragma unroll
+    for (int a = 0; a < DP; ++a)
+      if (a < DS) dst[a] = r[a];
+    esl[k * MS_LANES + lane] = er;
+  }
+};
+
 template <int DP>
 __global__ __launch_bounds__(MS_LANES) void mps_score_kernel(const double* __restrict__ cores, int n, int D, int DS, long long B,
                                                              long long ntiles, const long long* __restrict__ idx,
@@ -284,7 +293,7 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_kernel(const double* __res
   int* esl = erws + (size_t)blockIdx.x * n * MS_LANES;
   double* part = parts + (size_t)blockIdx.x * n * 2 * D * D;
   const double Zh = hdr[1], eE0 = hdr[2];
-  const bool Zok = Zh > 0.0 && isfinite(Zh);
+  const bool Zok = ms_norm_ok(Zh);
   double wacc = 0.0;
   bool first = true;
 #pragma unroll 1
@@ -294,56 +303,27 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_kernel(const double* __res
     const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
     const double wv = active ? wgt[b] : 0.0;
     wacc += ms_wave_sum(wv);
-    // right to left: r_k for k = n - 1 .. 0
+    // right to left: r^_1 .. r^_{n-1} and their exponents into the slice
     double r[DP];
-#pragma unroll
-    for (int a = 0; a < DP; ++a) r[a] = a == 0 ? 1.0 : 0.0;
-    int er = 0;
-#pragma unroll 1
-    for (int k = n; k >= 1; --k) {
-      if (k < n) {
-        double* dst = rsl + ((size_t)k * MS_LANES + lane) * DS;
-#pragma unroll
-        for (int a = 0; a < DP; ++a)
-          if (a < DS) dst[a] = r[a];
-        esl[k * MS_LANES + lane] = er;
-      }
-      __syncthreads();
-      ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
-      __syncthreads();
-      const double* Az = As + (int)((z >> (n - k)) & 1ull) * DP * DP;
-      double rn[DP];
-#pragma unroll
-      for (int a = 0; a < DP; ++a) {
-        double acc = 0.0;
-#pragma unroll
-        for (int c = 0; c < DP; ++c) acc = fma(Az[a * DP + c], r[c], acc);
-        rn[a] = acc;
-      }
-#pragma unroll
-      for (int a = 0; a < DP; ++a) r[a] = rn[a];
-      er += ms_rescale<DP>(r);
-    }
+    const int er0 = ms_right_sweep<DP>(cores, n, D, z, As, r, MsSliceStore<DP>{rsl, esl, n, DS, lane});
     const double r0 = r[0];
-    const int er0 = er;
-    const bool good = r0 != 0.0 && isfinite(r0) && Zok;
+    const bool good = ms_amplitude_ok(r0, Zok);
     if (active) {
-      logq[b] = (2.0 * log(fabs(r0)) - log(Zh)) + (2.0 * (double)er0 - eE0) * MS_LN2;
+      logq[b] = ms_logq(r0, er0, Zh, eE0);
       if (!good) *status = 2;
     }
     const double g = good ? (wv + wv) / r0 : 0.0;
     // left to right
     double l[DP];
-#pragma unroll
-    for (int a = 0; a < DP; ++a) l[a] = a == 0 ? 1.0 : 0.0;
+    ms_fill<DP>(l, 1.0);
     int el = 0;
 #pragma unroll 1
     for (int k = 1; k <= n; ++k) {
       __syncthreads();
       ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
-      const int s = (int)((z >> (n - k)) & 1ull);
+      const int s = ms_bit(z, n, k);
       const int erk = k < n ? esl[k * MS_LANES + lane] : 0;
-      const double cf = ldexp(g, el + erk - er0);
+      const double cf = ms_site_factor(g, el, erk, er0);
 #pragma unroll
       for (int a = 0; a < DP; ++a) Xs[lane * XP + a] = cf * l[a];
       Zs[lane] = s;
@@ -395,26 +375,14 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_kernel(const double* __res
                 *p = first ? acc[q][ta][tb][i] : *p + acc[q][ta][tb][i];
               }
             }
-      // l_k = l_{k-1} A_k[z_k]
-      const double* Az = As + s * DP * DP;
-      double ln[DP];
-#pragma unroll
-      for (int c = 0; c < DP; ++c) {
-        double a0 = 0.0;
-#pragma unroll
-        for (int a = 0; a < DP; ++a) a0 = fma(l[a], Az[a * DP + c], a0);
-        ln[c] = a0;
-      }
-#pragma unroll
-      for (int a = 0; a < DP; ++a) l[a] = ln[a];
-      el += ms_rescale<DP>(l);
+      el += ms_left_step<DP>(l, As + s * DP * DP);
     }
   }
   if (lane == 0) wpart[blockIdx.x] = wacc;
 }
 
-// grid n: grad[k - 1] = the workgroups' partials in order - (sum_b w_b) 2 L_{k-1} A_k[s] E_k / Z
-__global__ __launch_bounds__(ENV_THREADS) void mps_score_finish_kernel(const double* __restrict__ cores, int n, int D, int G,
+// grid n: grad[k - 1] = the workgroups' partials in order - (sum_b w_b) mu[k - 1] (ms_env_stage, ms_env_entry)
+__global__ __launch_bounds__(MS_ENV_THREADS) void mps_score_finish_kernel(const double* __restrict__ cores, int n, int D, int G,
                                                                        const double* __restrict__ parts,
                                                                        const double* __restrict__ wpart, const double* __restrict__ E,
                                                                        const double* __restrict__ L, const int* __restrict__ eE,
@@ -424,44 +392,28 @@ __global__ __launch_bounds__(ENV_THREADS) void mps_score_finish_kernel(const dou
   __shared__ double Em[MS_DMAX * MS_DMAX];
   __shared__ double Lm[MS_DMAX * MS_DMAX];
   __shared__ double T[2 * MS_DMAX * MS_DMAX];
-  __shared__ double red[ENV_THREADS / 64];
+  __shared__ double red[MS_ENV_THREADS / 64];
   const int k = blockIdx.x + 1, t = threadIdx.x, DD = D * D;
   double wv = 0.0;
-  for (int i = t; i < G; i += ENV_THREADS) wv += wpart[i];
+  for (int i = t; i < G; i += MS_ENV_THREADS) wv += wpart[i];
   wv = ms_wave_sum(wv);
   if ((t & 63) == 0) red[t >> 6] = wv;
-  for (int i = t; i < 2 * DD; i += ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
-  for (int i = t; i < DD; i += ENV_THREADS) {
-    Em[i] = E[(long long)k * DD + i];
-    Lm[i] = L[(long long)(k - 1) * DD + i];
-  }
-  __syncthreads();
+  ms_env_stage(cores, k, D, E, L, As, Em, Lm, T);      // its barriers publish red too
   const double W = ((red[0] + red[1]) + red[2]) + red[3];
-  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
-    const int s = i / DD, c = (i % DD) / D, d = i % D;
-    double acc = 0.0;
-    for (int e = 0; e < D; ++e) acc = fma(As[s * DD + c * D + e], Em[e * D + d], acc);
-    T[i] = acc;
-  }
-  __syncthreads();
   const int ex = eL[k - 1] + eE[k] - eE[0];
   const double Zh = hdr[1];
   const size_t stride = (size_t)n * 2 * DD;
-  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
-    const int s = i / DD, a = (i % DD) / D, d = i % D;
-    double m = 0.0;
-    for (int c = 0; c < D; ++c) m = fma(Lm[a * D + c], T[s * DD + c * D + d], m);
+  for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
     double sum = 0.0;
     const double* p = parts + (size_t)(k - 1) * 2 * DD + i;
     for (int g = 0; g < G; ++g) sum += p[g * stride];
-    const double env = ldexp(m / Zh, ex);
-    grad[(size_t)(k - 1) * 2 * DD + i] = sum - W * (env + env);
+    grad[(size_t)(k - 1) * 2 * DD + i] = sum - W * ms_env_entry(Lm, T, D, i, Zh, ex);
   }
 }
 
 // ---- score rows (sampled Fisher estimate) ----------------------------------------------------------------------
-// grid n: mu[k - 1][s][a][d] = 2 (L_{k-1} A_k[s] E_k)[a][d] / Z, the environment term of mps_score_finish_kernel
-__global__ __launch_bounds__(ENV_THREADS) void mps_score_mu_kernel(const double* __restrict__ cores, int D, const double* __restrict__ E,
+// grid n: mu[k - 1] = the environment term (ms_env_stage, ms_env_entry)
+__global__ __launch_bounds__(MS_ENV_THREADS) void mps_score_mu_kernel(const double* __restrict__ cores, int D, const double* __restrict__ E,
                                                                    const double* __restrict__ L, const int* __restrict__ eE,
                                                                    const int* __restrict__ eL, const double* __restrict__ hdr,
                                                                    double* __restrict__ mu) {
@@ -470,28 +422,10 @@ __global__ __launch_bounds__(ENV_THREADS) void mps_score_mu_kernel(const double*
   __shared__ double Lm[MS_DMAX * MS_DMAX];
   __shared__ double T[2 * MS_DMAX * MS_DMAX];
   const int k = blockIdx.x + 1, t = threadIdx.x, DD = D * D;
-  for (int i = t; i < 2 * DD; i += ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
-  for (int i = t; i < DD; i += ENV_THREADS) {
-    Em[i] = E[(long long)k * DD + i];
-    Lm[i] = L[(long long)(k - 1) * DD + i];
-  }
-  __syncthreads();
-  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
-    const int s = i / DD, c = (i % DD) / D, d = i % D;
-    double acc = 0.0;
-    for (int e = 0; e < D; ++e) acc = fma(As[s * DD + c * D + e], Em[e * D + d], acc);
-    T[i] = acc;
-  }
-  __syncthreads();
+  ms_env_stage(cores, k, D, E, L, As, Em, Lm, T);
   const int ex = eL[k - 1] + eE[k] - eE[0];
   const double Zh = hdr[1];
-  for (int i = t; i < 2 * DD; i += ENV_THREADS) {
-    const int s = i / DD, a = (i % DD) / D, d = i % D;
-    double m = 0.0;
-    for (int c = 0; c < D; ++c) m = fma(Lm[a * D + c], T[s * DD + c * D + d], m);
-    const double env = ldexp(m / Zh, ex);
-    mu[(size_t)(k - 1) * 2 * DD + i] = env + env;
-  }
+  for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) mu[(size_t)(k - 1) * 2 * DD + i] = ms_env_entry(Lm, T, D, i, Zh, ex);
 }
 
 template <int DP>
@@ -507,8 +441,7 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_rows_kernel(const double* 
   const int lane = threadIdx.x, DD = D * D, R = 2 * DD;
   double* rsl = rws + (size_t)blockIdx.x * n * MS_LANES * DS;
   int* esl = erws + (size_t)blockIdx.x * n * MS_LANES;
-  const double Zh = hdr[1];
-  const bool Zok = Zh > 0.0 && isfinite(Zh);
+  const bool Zok = ms_norm_ok(hdr[1]);
 #pragma unroll 1
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long b = tile * MS_LANES + lane;            // b < ld: the tiles cover the ld columns exactly
@@ -519,56 +452,27 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_rows_kernel(const double* 
     }
     const bool active = b < B;
     const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
-    // right to left: r_k for k = n - 1 .. 0 (as mps_score_kernel)
+    // right to left: r^_1 .. r^_{n-1} and their exponents into the slice
     double r[DP];
-#pragma unroll
-    for (int a = 0; a < DP; ++a) r[a] = a == 0 ? 1.0 : 0.0;
-    int er = 0;
-#pragma unroll 1
-    for (int k = n; k >= 1; --k) {
-      if (k < n) {
-        double* dst = rsl + ((size_t)k * MS_LANES + lane) * DS;
-#pragma unroll
-        for (int a = 0; a < DP; ++a)
-          if (a < DS) dst[a] = r[a];
-        esl[k * MS_LANES + lane] = er;
-      }
-      __syncthreads();
-      ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
-      __syncthreads();
-      const double* Az = As + (int)((z >> (n - k)) & 1ull) * DP * DP;
-      double rn[DP];
-#pragma unroll
-      for (int a = 0; a < DP; ++a) {
-        double acc = 0.0;
-#pragma unroll
-        for (int c = 0; c < DP; ++c) acc = fma(Az[a * DP + c], r[c], acc);
-        rn[a] = acc;
-      }
-#pragma unroll
-      for (int a = 0; a < DP; ++a) r[a] = rn[a];
-      er += ms_rescale<DP>(r);
-    }
+    const int er0 = ms_right_sweep<DP>(cores, n, D, z, As, r, MsSliceStore<DP>{rsl, esl, n, DS, lane});
     const double r0 = r[0];
-    const int er0 = er;
-    const bool good = active && r0 != 0.0 && isfinite(r0) && Zok;
+    const bool good = active && ms_amplitude_ok(r0, Zok);
     if (active && !good) *status = 2;
     const double g = good ? 2.0 / r0 : 0.0;
     // left to right
     double l[DP];
-#pragma unroll
-    for (int a = 0; a < DP; ++a) l[a] = a == 0 ? 1.0 : 0.0;
+    ms_fill<DP>(l, 1.0);
     int el = 0;
 #pragma unroll 1
     for (int k = 1; k <= n; ++k) {
       const bool wanted = k - 1 >= k_begin && k - 1 < k_begin + k_count;
       __syncthreads();
       ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
-      const int s = (int)((z >> (n - k)) & 1ull);
+      const int s = ms_bit(z, n, k);
       if (wanted) {
         for (int i = lane; i < R; i += MS_LANES) Mu[i] = mu[(size_t)(k - 1) * R + i];
         const int erk = k < n ? esl[k * MS_LANES + lane] : 0;
-        const double cf = ldexp(g, el + erk - er0);
+        const double cf = ms_site_factor(g, el, erk, er0);
         const double* src = rsl + ((size_t)k * MS_LANES + lane) * DS;
 #pragma unroll
         for (int a = 0; a < DP; ++a) {
@@ -590,32 +494,20 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_rows_kernel(const double* 
           }
         }
       }
-      // l_k = l_{k-1} A_k[z_k]
-      const double* Az = As + s * DP * DP;
-      double ln[DP];
-#pragma unroll
-      for (int c = 0; c < DP; ++c) {
-        double a0 = 0.0;
-#pragma unroll
-        for (int a = 0; a < DP; ++a) a0 = fma(l[a], Az[a * DP + c], a0);
-        ln[c] = a0;
-      }
-#pragma unroll
-      for (int a = 0; a < DP; ++a) l[a] = ln[a];
-      el += ms_rescale<DP>(l);
+      el += ms_left_step<DP>(l, As + s * DP * DP);
     }
   }
 }
 
 // ---- score jvp (matrix-free natural gradient) --------------------------------------------------------------------
 // grid n: cpart[k - 1] = sum_i mu[k - 1][i] v[k - 1][i], i = (s D + a) D + c in order: one fma chain of 2 D^2 terms
-__global__ __launch_bounds__(ENV_THREADS) void mps_jvp_dot_kernel(const double* __restrict__ mu, const double* __restrict__ v, int D,
+__global__ __launch_bounds__(MS_ENV_THREADS) void mps_jvp_dot_kernel(const double* __restrict__ mu, const double* __restrict__ v, int D,
                                                                   double* __restrict__ cpart) {
   __shared__ double Ms[2 * MS_DMAX * MS_DMAX];
   __shared__ double Vs[2 * MS_DMAX * MS_DMAX];
   const int R = 2 * D * D, t = threadIdx.x;
   const size_t off = (size_t)blockIdx.x * R;
-  for (int i = t; i < R; i += ENV_THREADS) {
+  for (int i = t; i < R; i += MS_ENV_THREADS) {
     Ms[i] = mu[off + i];
     Vs[i] = v[off + i];
   }
@@ -636,8 +528,7 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_jvp_kernel(const double* _
   __shared__ double As[2 * DP * DP];
   __shared__ double Vs[2 * DP * DP];
   const int lane = threadIdx.x;
-  const double Zh = hdr[1];
-  const bool Zok = Zh > 0.0 && isfinite(Zh);
+  const bool Zok = ms_norm_ok(hdr[1]);
   double cdot = 0.0;                                       // (uniform) the sites in order
   for (int k = 0; k < n; ++k) cdot += cpart[k];
 #pragma unroll 1
@@ -646,21 +537,18 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_jvp_kernel(const double* _
     const bool active = b < B;
     const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
     double l[DP], dl[DP];
-#pragma unroll
-    for (int a = 0; a < DP; ++a) {
-      l[a] = a == 0 ? 1.0 : 0.0;
-      dl[a] = 0.0;
-    }
+    ms_fill<DP>(l, 1.0);
+    ms_fill<DP>(dl, 0.0);
 #pragma unroll 1
     for (int k = 1; k <= n; ++k) {
       __syncthreads();
       ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
       ms_load_site<DP>(vdir, k, D, Vs, nullptr, nullptr);
       __syncthreads();
-      const int s = (int)((z >> (n - k)) & 1ull);
+      const int s = ms_bit(z, n, k);
       const double* Az = As + s * DP * DP;
       const double* Vz = Vs + s * DP * DP;
-      double ln[DP], dn[DP];
+      double ln[DP], dn[DP];           // ms_row_dot's chains, l A and dl A in one loop: see mps_sample_dev.hpp
 #pragma unroll
       for (int c = 0; c < DP; ++c) {
         double a0 = 0.0, d0 = 0.0;
@@ -676,13 +564,13 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_jvp_kernel(const double* _
         dn[c] = d0;
       }
 #pragma unroll
-      for (int a = 0; a < DP; ++a) l[a] = ln[a];
-      const int e = ms_rescale<DP>(l);
+      for (int a = 0; a < DP; ++a) l[a] = ln[a];           // ms_take's two lines: through the call the DP = 16 kernel waits
+      const int e = ms_rescale<DP>(l);                     // on its LDS reads more often and is a quarter slower
 #pragma unroll
       for (int a = 0; a < DP; ++a) dl[a] = ldexp(dn[a], -e);
     }
     const double p0 = l[0];
-    const bool good = p0 != 0.0 && isfinite(p0) && Zok;
+    const bool good = ms_amplitude_ok(p0, Zok);
     if (active) {
       tout[b] = good ? scale * ((dl[0] + dl[0]) / p0 - cdot) : 0.0;
       if (!good) *status = 2;
@@ -716,22 +604,19 @@ __global__ __launch_bounds__(256) void bn_logjoint_kernel(bornvi_bn_desc bn, int
   logp[b] = bad ? __builtin_nan("") : sum;
 }
 
-#define MS_DISPATCH(DPV, CALL)                        \
-  switch (DPV) {                                      \
-    case 2: { constexpr int DP = 2; CALL; } break;    \
-    case 4: { constexpr int DP = 4; CALL; } break;    \
-    case 8: { constexpr int DP = 8; CALL; } break;    \
-    case 16: { constexpr int DP = 16; CALL; } break;  \
-    default: { constexpr int DP = 32; CALL; } break;  \
-  }
 }  // namespace
+
+hipError_t launch_ms_clear_status(int* status, hipStream_t st) {
+  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
+  return hipGetLastError();
+}
 
 size_t mps_sample_workspace_bytes(int n, int D, long long B) { return ms_layout(n, D, B).total + 256; }
 
 hipError_t launch_mps_environments(int n, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
   char* base = ws_align(ws);
-  mps_env_kernel<<<2, ENV_THREADS, 0, st>>>(cores, n, D, (double*)(base + S.E), (double*)(base + S.L), (int*)(base + S.eE),
+  mps_env_kernel<<<2, MS_ENV_THREADS, 0, st>>>(cores, n, D, (double*)(base + S.E), (double*)(base + S.L), (int*)(base + S.eE),
                                            (int*)(base + S.eL), (double*)(base + S.hdr), logZ_out);
   return hipGetLastError();
 }
@@ -740,8 +625,7 @@ hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, uns
                              long long* idx, double* logq, int* status, void* ws, hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
   char* base = ws_align(ws);
-  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_ms_clear_status(status, st);
   if (e != hipSuccess) return e;
   const unsigned grid = (unsigned)((B + MS_LANES - 1) / MS_LANES);
   MS_DISPATCH(S.DP, (mps_sample_kernel<DP><<<grid, MS_LANES, 0, st>>>(cores, n, D, B, (const double*)(base + S.E),
@@ -754,14 +638,13 @@ hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, 
                                 double* grad_cores, int* status, void* ws, hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
   char* base = ws_align(ws);
-  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_ms_clear_status(status, st);
   if (e != hipSuccess) return e;
   const long long ntiles = (B + MS_LANES - 1) / MS_LANES;
   MS_DISPATCH(S.DP, (mps_score_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
                         cores, n, D, S.DS, B, ntiles, idx, w, (const double*)(base + S.hdr), logq, status, (double*)(base + S.r),
                         (int*)(base + S.er), (double*)(base + S.parts), (double*)(base + S.wpart))));
-  mps_score_finish_kernel<<<(unsigned)n, ENV_THREADS, 0, st>>>(cores, n, D, S.G, (const double*)(base + S.parts),
+  mps_score_finish_kernel<<<(unsigned)n, MS_ENV_THREADS, 0, st>>>(cores, n, D, S.G, (const double*)(base + S.parts),
                                                               (const double*)(base + S.wpart), (const double*)(base + S.E),
                                                               (const double*)(base + S.L), (const int*)(base + S.eE),
                                                               (const int*)(base + S.eL), (const double*)(base + S.hdr), grad_cores);
@@ -772,8 +655,7 @@ hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores,
                                  long long ld, double* rows, int* status, void* ws, hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
   char* base = ws_align(ws);
-  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_ms_clear_status(status, st);
   if (e != hipSuccess) return e;
   const double* hdr = nullptr;
   const double* mu = nullptr;
@@ -785,22 +667,21 @@ hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores,
   return hipGetLastError();
 }
 
-// after launch_mps_environments: mu into the workspace's mu region (as launch_mps_score_rows), the n site partials of
+// after launch_mps_environments: mu into the workspace's mu region (launch_mps_score_mu), the n site partials of
 // c = <mu, v> into its wpart region (MS_MAX_WG doubles >= n), then the tangent sweep
 hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, const long long* idx, const double* v, double scale,
                                 double* t, int* status, void* ws, hipStream_t st) {
   static_assert(MS_MAX_WG >= 63, "the site partials of c live in the wpart region");
   const MsLayout S = ms_layout(n, D, B);
   char* base = ws_align(ws);
-  ms_clear_status_kernel<<<1, 64, 0, st>>>(status);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_ms_clear_status(status, st);
   if (e != hipSuccess) return e;
   const double* hdr = nullptr;
   const double* mu = nullptr;
   e = launch_mps_score_mu(n, D, B, cores, ws, &hdr, &mu, st);
   if (e != hipSuccess) return e;
   double* cpart = (double*)(base + S.wpart);
-  mps_jvp_dot_kernel<<<(unsigned)n, ENV_THREADS, 0, st>>>(mu, v, D, cpart);
+  mps_jvp_dot_kernel<<<(unsigned)n, MS_ENV_THREADS, 0, st>>>(mu, v, D, cpart);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const long long ntiles = (B + MS_LANES - 1) / MS_LANES;
@@ -809,13 +690,13 @@ hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, 
   return hipGetLastError();
 }
 
-// mu alone, for kernels_mps_sample_gram.hip: the launch of launch_mps_score_rows into the same region, and where the header
+// mu alone: the launch that the score rows, the jvp and kernels_mps_sample_gram.hip share, and where the header
 // (log Z, E^_0[0, 0], eE[0]) and mu lie in the workspace
 hipError_t launch_mps_score_mu(int n, int D, long long B, const double* cores, void* ws, const double** hdr, const double** mu,
                                hipStream_t st) {
   const MsLayout S = ms_layout(n, D, B);
   char* base = ws_align(ws);
-  mps_score_mu_kernel<<<(unsigned)n, ENV_THREADS, 0, st>>>(cores, D, (const double*)(base + S.E), (const double*)(base + S.L),
+  mps_score_mu_kernel<<<(unsigned)n, MS_ENV_THREADS, 0, st>>>(cores, D, (const double*)(base + S.E), (const double*)(base + S.L),
                                                           (const int*)(base + S.eE), (const int*)(base + S.eL),
                                                           (const double*)(base + S.hdr), (double*)(base + S.mu));
   *hdr = (const double*)(base + S.hdr);

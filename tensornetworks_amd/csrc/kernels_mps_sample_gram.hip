@@ -4,18 +4,19 @@
 //   B T_bb' = sum_k [z_bk = z_b'k] (x_bk . x_b'k)(r_bk . r_b'k) - m_b - m_b' + M,
 //   x_bk = (2 / psi_b) l_{b,k-1},   m_b = sum_k x_bk^T mu_k[z_bk] r_bk,   M = sum_{k,s} ||mu_k[s]||_F^2.
 //
-// bornvi_mps_score_sample_gram = the status word's clear + mps_score_mu_kernel (kernels_mps_sample.hip, into the mu region of
-// the environments' workspace) + three kernels:
-//   mps_gram_vectors_kernel<DP>: the shape of mps_score_rows_kernel (one sample per lane, one wave per workgroup, workgroup g
-//     owns the samples 64 g .. 64 g + 63).  The right-to-left sweep stores r^_k (k = n: e0) and its exponent er_k for every
-//     site; the left-to-right sweep keeps l^ in registers and stores x^_bk = cf l^_{k-1}, cf = (2 / r^_0[0]) 2^(el_{k-1} + er_k
-//     - er_0) as in mps_score_rows_kernel, and adds the site's m term: one fma chain over (a, c) of (x^[a] r^[c]) mu[s][a][c],
-//     the sites added in order.  Layout of both vector sets: [site][fragment of 16 samples][component, D4 = D rounded up to 4,
-//     zero padded][sample in the fragment]: step j of a 16-sample fragment is 64 consecutive doubles, lane (fr, fk) reading
-//     component 4 j + fk of sample fr, which is what v_mfma_f64_16x16x4_f64 takes as A and as B without a transpose.
-//     A sample with psi = 0 (or not finite) gets zero vectors, m_b = 0, alive = 0 and sets the status word to 2; so do the
+// bornvi_mps_score_sample_gram = the status word's clear (launch_ms_clear_status) + mps_score_mu_kernel (kernels_mps_sample.hip,
+// into the mu region of the environments' workspace) + three kernels; l^, r^, their exponents and the site factor are
+// mps_sample_dev.hpp's:
+//   mps_gram_vectors_kernel<DP>: one sample per lane, one wave per workgroup, workgroup g owns the samples 64 g .. 64 g + 63.
+//     ms_right_sweep stores r^_k (k = n: e0) and its exponent er_k for every site; the left-to-right sweep (ms_left_step)
+//     keeps l^ in registers and stores x^_bk = cf l^_{k-1}, cf = ms_site_factor with g = 2 / r^_0[0], and adds the site's m
+//     term: one fma chain over (a, c) of (x^[a] r^[c]) mu[s][a][c], the sites added in order.  Layout of both vector sets:
+//     [site][fragment of 16 samples][component, D4 = D rounded up to 4, zero padded][sample in the fragment]: step j of a
+//     16-sample fragment is 64 consecutive doubles, lane (fr, fk) reading component 4 j + fk of sample fr, which is what
+//     v_mfma_f64_16x16x4_f64 takes as A and as B without a transpose.
+//     A sample that fails ms_amplitude_ok gets zero vectors, m_b = 0, alive = 0 and sets the status word to 2; so do the
 //     padding samples B .. 64 ceil(B / 64) - 1 (without the status).
-//   mps_gram_mu_norm_kernel: M, one workgroup; lane t squares the entries t, t + 256, ... in one fma chain, then a butterfly
+//   mps_gram_mu_norm_kernel: M, one workgroup; lane t squares the entries t, t + 256, ... in one fma chain, then ms_wave_sum
 //     over the 64 lanes and the four waves in order.
 //   mps_sample_gram_kernel: one wave per 32 x 32 tile on or above the diagonal (2 x 2 fragments).  Per site the wave forms the
 //     two dot-product tiles x . x' and r . r' of every fragment pair on the matrix cores (D4 / 4 steps each, components in
@@ -49,7 +50,7 @@ struct SgLayout {
 
 SgLayout sg_layout(int n, int D, long long B) {
   SgLayout S;
-  S.DP = D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32;
+  S.DP = ms_dp(D);
   S.D4 = (D + 3) & ~3;
   S.Bp = (B + SG_LANES - 1) / SG_LANES * SG_LANES;
   S.nfrag = (int)(S.Bp / SG_FRAG);
@@ -85,45 +86,23 @@ __global__ __launch_bounds__(SG_LANES) void mps_gram_vectors_kernel(const double
   const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
   const size_t site = (size_t)Bp * D4;                               // doubles of one site's vectors
   const size_t at = (size_t)(b / SG_FRAG) * D4 * SG_FRAG + (size_t)(b % SG_FRAG);
-  const double Zh = hdr[1];
-  const bool Zok = Zh > 0.0 && isfinite(Zh);
-  // right to left: r_k for k = n .. 1, stored; then r_0 (as mps_score_kernel)
+  const bool Zok = ms_norm_ok(hdr[1]);
+  // right to left: r^_k and er_k of every site k = n .. 1 in the fragment layout
   double r[DP];
-#pragma unroll
-  for (int a = 0; a < DP; ++a) r[a] = a == 0 ? 1.0 : 0.0;
-  int er = 0;
-#pragma unroll 1
-  for (int k = n; k >= 1; --k) {
+  const int er0 = ms_right_sweep<DP>(cores, n, D, z, As, r, [&](int k, const double (&rk)[DP], int er) {
     double* dst = rv + (size_t)(k - 1) * site + at;
 #pragma unroll
     for (int a = 0; a < DV; ++a)
-      if (a < D4) dst[a * SG_FRAG] = sg_component<DP>(r, a);
+      if (a < D4) dst[a * SG_FRAG] = sg_component<DP>(rk, a);
     erw[(size_t)(k - 1) * Bp + b] = er;
-    __syncthreads();
-    ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
-    __syncthreads();
-    const double* Az = As + (int)((z >> (n - k)) & 1ull) * DP * DP;
-    double rn[DP];
-#pragma unroll
-    for (int a = 0; a < DP; ++a) {
-      double acc = 0.0;
-#pragma unroll
-      for (int c = 0; c < DP; ++c) acc = fma(Az[a * DP + c], r[c], acc);
-      rn[a] = acc;
-    }
-#pragma unroll
-    for (int a = 0; a < DP; ++a) r[a] = rn[a];
-    er += ms_rescale<DP>(r);
-  }
+  });
   const double r0 = r[0];
-  const int er0 = er;
-  const bool good = active && r0 != 0.0 && isfinite(r0) && Zok;
+  const bool good = active && ms_amplitude_ok(r0, Zok);
   if (active && !good) *status = 2;
   const double g = good ? 2.0 / r0 : 0.0;
   // left to right
   double l[DP];
-#pragma unroll
-  for (int a = 0; a < DP; ++a) l[a] = a == 0 ? 1.0 : 0.0;
+  ms_fill<DP>(l, 1.0);
   int el = 0;
   double m = 0.0;
 #pragma unroll 1
@@ -132,8 +111,8 @@ __global__ __launch_bounds__(SG_LANES) void mps_gram_vectors_kernel(const double
     ms_load_site<DP>(cores, k, D, As, nullptr, nullptr);
     for (int i = lane; i < R; i += SG_LANES) Mu[i] = mu[(size_t)(k - 1) * R + i];
     __syncthreads();
-    const int s = (int)((z >> (n - k)) & 1ull);
-    const double cf = ldexp(g, el + erw[(size_t)(k - 1) * Bp + b] - er0);
+    const int s = ms_bit(z, n, k);
+    const double cf = ms_site_factor(g, el, erw[(size_t)(k - 1) * Bp + b], er0);
     double* xd = xv + (size_t)(k - 1) * site + at;
     double* rd = rv + (size_t)(k - 1) * site + at;
     double rr[DP];
@@ -157,19 +136,7 @@ __global__ __launch_bounds__(SG_LANES) void mps_gram_vectors_kernel(const double
       }
     }
     m += ms;
-    // l_k = l_{k-1} A_k[z_k]
-    const double* Az = As + s * DP * DP;
-    double ln[DP];
-#pragma unroll
-    for (int c = 0; c < DP; ++c) {
-      double a0 = 0.0;
-#pragma unroll
-      for (int a = 0; a < DP; ++a) a0 = fma(l[a], Az[a * DP + c], a0);
-      ln[c] = a0;
-    }
-#pragma unroll
-    for (int a = 0; a < DP; ++a) l[a] = ln[a];
-    el += ms_rescale<DP>(l);
+    el += ms_left_step<DP>(l, As + s * DP * DP);
   }
   mv[b] = good ? m : 0.0;
   alive[b] = good ? 1 : 0;
@@ -182,8 +149,7 @@ __global__ __launch_bounds__(SG_NORM_THREADS) void mps_gram_mu_norm_kernel(const
   const int t = threadIdx.x;
   double acc = 0.0;
   for (int i = t; i < count; i += SG_NORM_THREADS) acc = fma(mu[i], mu[i], acc);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  acc = ms_wave_sum(acc);
   if ((t & 63) == 0) red[t >> 6] = acc;
   __syncthreads();
   if (t == 0) M[0] = ((red[0] + red[1]) + red[2]) + red[3];
@@ -289,18 +255,6 @@ __global__ __launch_bounds__(SG_LANES) void mps_sample_gram_kernel(int n, int D4
   }
 }
 
-__global__ __launch_bounds__(64) void sg_clear_status_kernel(int* status) {
-  if (threadIdx.x == 0) *status = 0;
-}
-
-#define SG_DISPATCH(DPV, CALL)                        \
-  switch (DPV) {                                      \
-    case 2: { constexpr int DP = 2; CALL; } break;    \
-    case 4: { constexpr int DP = 4; CALL; } break;    \
-    case 8: { constexpr int DP = 8; CALL; } break;    \
-    case 16: { constexpr int DP = 16; CALL; } break;  \
-    default: { constexpr int DP = 32; CALL; } break;  \
-  }
 }  // namespace
 
 size_t mps_sample_gram_workspace_bytes(int n, int D, long long B) { return sg_layout(n, D, B).total + 256; }
@@ -309,8 +263,7 @@ hipError_t launch_mps_score_sample_gram(int n, int D, long long B, const double*
                                         void* env_ws, void* ws, hipStream_t st) {
   const SgLayout S = sg_layout(n, D, B);
   char* base = ws_align(ws);
-  sg_clear_status_kernel<<<1, 64, 0, st>>>(status);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_ms_clear_status(status, st);
   if (e != hipSuccess) return e;
   const double* hdr = nullptr;
   const double* mu = nullptr;
@@ -318,7 +271,7 @@ hipError_t launch_mps_score_sample_gram(int n, int D, long long B, const double*
   if (e != hipSuccess) return e;
   double* xv = (double*)(base + S.x);
   double* rv = (double*)(base + S.r);
-  SG_DISPATCH(S.DP, (mps_gram_vectors_kernel<DP><<<(unsigned)(S.Bp / SG_LANES), SG_LANES, 0, st>>>(
+  MS_DISPATCH(S.DP, (mps_gram_vectors_kernel<DP><<<(unsigned)(S.Bp / SG_LANES), SG_LANES, 0, st>>>(
                         cores, n, D, S.D4, B, S.Bp, idx, hdr, mu, xv, rv, (int*)(base + S.er), (double*)(base + S.m),
                         (int*)(base + S.alive), status)));
   e = hipGetLastError();
