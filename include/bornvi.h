@@ -560,6 +560,43 @@ int bornvi_mps_score_jvp(bornvi_handle h, int n, int D, long long B, const doubl
                          double scale, double* t, int* status, void* env_workspace, size_t env_workspace_bytes,
                          bornvi_stream stream);
 
+/* ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip): what q says about parts
+ * of z, from its environments in O(n D^3) per query; cores, n and D as in the sampled section above.
+ * An evidence is a pair of int64 words (mask, value): a set mask bit clamps that site (tuple position p = bit n - 1 - p) to
+ * the value's bit; value bits outside the mask are ignored; bits at or above n must be 0 in both words (the kernels never
+ * look at them).  The clamped environments E^(j)_{k-1} = sum_{s allowed at k} A_k[s] E^(j)_k A_k[s]^T run the step of
+ * bornvi_mps_environments (same fma chains, same power-of-two rescale and exponent), a disallowed s contributing no term.
+ * bornvi_mps_log_marginals: Q evidences mask, value dev [Q] -> logm dev [Q] float64, the log probability of each partial
+ * assignment.  One workgroup per query and one for the empty mask, the normaliser:
+ *   logm_j = (log E^^(j)_0[0,0] - log E^_0[0,0]) + (e_j - e) ln 2,
+ * so an empty evidence gives exactly 0.0 and one with all n sites clamped log q of that state.  Evidence of probability
+ * zero gives -inf, an environment that is not finite NaN; either sets status (dev [1] int32) to 1, else 0.  1 <= Q <= 2^16.
+ * bornvi_mps_sample_clamped: B exact draws from q(. | evidence), mask and value dev [1] (read by the kernels: capturable).
+ * idx dev [B]; logq dev [B] = log q(z | evidence) (exactly 0.0 when all n sites are clamped: set, not computed); logm dev [1] = the evidence's log
+ * marginal.  The sampler is bornvi_mps_sample's against the clamped environments: a free site decides as there, from the
+ * same uniform (the Philox counter does not depend on the mask); a clamped site takes the evidence's bit.  A sample whose
+ * chosen branch has a conditional mass that is not positive and finite is dead: status 1, logq NaN, its clamped positions
+ * keep the evidence's bits and its free positions from there on are 0.  With an empty mask idx and logq are bitwise those
+ * of bornvi_mps_environments + bornvi_mps_sample at the same (cores, seed, epoch).  Draws do not depend on B.
+ * bornvi_mps_marginals: m1 dev [n], m1[i] = q(z_i = 1), and, where m2 is not NULL, m2 dev [n, n], m2[i][j] = q(z_i = 1,
+ * z_j = 1).  It runs both unclamped sweeps itself, into its own workspace (no call of bornvi_mps_environments is needed
+ * and none is disturbed), then one workgroup per site i:  m1[i] = <L_{i-1}, A_i[1] E_i A_i[1]^T> / Z, and
+ * M = A_i[1]^T L_{i-1} A_i[1] carried through j = i + 1 .. n with m2[i][j] = <M, A_j[1] E_j A_j[1]^T> / Z, M rescaled by exact
+ * powers of two.  The lower triangle is a copy of the upper and the diagonal is m1: m2 == m2^T bitwise.
+ * All three: anything outside the ranges, a short workspace included, is BORNVI_ERR_UNSUPPORTED before any launch; no
+ * atomics (two calls are bitwise equal), no allocation or synchronisation (capturable).  Workspace:
+ * bornvi_mps_query_workspace_bytes(h, n, D, Q), with Q = 1 for the sampler and the marginals. */
+size_t bornvi_mps_query_workspace_bytes(bornvi_handle h, int n, int D, int Q);
+int bornvi_mps_log_marginals(bornvi_handle h, int n, int D, int Q, const double* cores, const long long* mask,
+                             const long long* value, double* logm, int* status, void* workspace, size_t workspace_bytes,
+                             bornvi_stream stream);
+int bornvi_mps_sample_clamped(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* mask,
+                              const long long* value, unsigned long long seed, const long long* epoch_dev, long long* idx,
+                              double* logq, double* logm, int* status, void* workspace, size_t workspace_bytes,
+                              bornvi_stream stream);
+int bornvi_mps_marginals(bornvi_handle h, int n, int D, const double* cores, double* m1, double* m2, void* workspace,
+                         size_t workspace_bytes, bornvi_stream stream);
+
 /* The conjugate-gradient recurrence for (F + damping I) x = g, the product F p left to the caller between the calls; every
  * vector dev [P] float64, state dev [8] float64 (rr = r^T r, rr0 = g^T g, iterations done, done flag, relres = sqrt(rr / rr0),
  * fallback flag, two spare words).  One workgroup each; every dot product is a fixed-order reduction, so two solves are

@@ -717,6 +717,90 @@ def mps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
     return out, out_logq, status
 
 
+# ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ----------------------------------------------
+MPS_QUERY_MAX_QUERIES = 1 << 16
+
+
+def _mps_query_ws(h, dev, n, D, Q):
+    return _ws(dev, _cached_size(h, "bornvi_mps_query_workspace_bytes", n, D, Q), f"mps_query_{n}_{D}_{Q}")
+
+
+def _out(t, dtype, dev, name, numel):
+    if t is None:
+        return torch.empty(numel, dtype=dtype, device=dev)
+    _chk(t, dtype, dev, name, numel)
+    return t
+
+
+def mps_log_marginals(cores, mask, value, out=None, status=None):
+    """Log probabilities of partial assignments under an MPS Born machine (bornvi_mps_log_marginals): mask, value int64 [Q]
+    on the GPU (a set mask bit clamps tuple position p = bit n - 1 - p to the value's bit), 1 <= Q <= 2^16 ->
+    (logm float64 [Q], status int32 [1]: 0, or 1 when some evidence has probability zero (logm -inf) or met a non-finite
+    environment (NaN)).  An empty mask gives exactly 0.0, a full one log q of that state.  Needs no mps_environments."""
+    n, D, _ = _mps_args(cores, 1)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    if not torch.is_tensor(mask) or not torch.is_tensor(value) or mask.dim() != 1 or mask.shape != value.shape:
+        raise BornviError("mask, value: expected two [Q] int64 tensors")
+    Q = int(mask.numel())
+    if not 1 <= Q <= MPS_QUERY_MAX_QUERIES:
+        raise BornviError(f"number of queries: 1 ... 2^16 per call, got {Q}")
+    _chk(mask, torch.int64, dev, "mask", Q)
+    _chk(value, torch.int64, dev, "value", Q)
+    out = _out(out, torch.float64, dev, "out", Q)
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _mps_query_ws(h, dev, n, D, Q)
+    h.call("bornvi_mps_log_marginals", n, D, Q, _ptr(cores), _ptr(mask), _ptr(value), _ptr(out), _ptr(status), _ptr(ws), ws.numel(),
+           _ext.stream_ptr(dev))
+    return out, status
+
+
+def mps_sample_clamped(cores, num_samples, mask, value, seed, epoch, out_idx=None, out_logq=None, out_logm=None, status=None):
+    """Exact draws from q(. | evidence) of an MPS Born machine (bornvi_mps_sample_clamped): mask, value int64 [1] on the
+    GPU -> (idx int64 [B], logq float64 [B] = log q(idx | evidence), logm float64 [1] = the evidence's log marginal,
+    status int32 [1]: 0, or 1 when a sample died (logq NaN) or the evidence has probability zero).  seed and epoch as
+    mps_sample: with an empty mask idx and logq are mps_environments + mps_sample's bit for bit.  Needs no mps_environments."""
+    n, D, B = _mps_args(cores, num_samples)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise BornviError(f"seed must be an integer, got {seed!r}")
+    _chk(epoch, torch.int64, dev, "epoch", 1)
+    if not torch.is_tensor(mask) or not torch.is_tensor(value):
+        raise BornviError("mask, value: expected two [1] int64 tensors")
+    _chk(mask, torch.int64, dev, "mask", 1)
+    _chk(value, torch.int64, dev, "value", 1)
+    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
+    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
+    out_logm = _out(out_logm, torch.float64, dev, "out_logm", 1)
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _mps_query_ws(h, dev, n, D, 1)
+    h.call("bornvi_mps_sample_clamped", n, D, B, _ptr(cores), _ptr(mask), _ptr(value), int(seed) & ((1 << 64) - 1), _ptr(epoch),
+           _ptr(out_idx), _ptr(out_logq), _ptr(out_logm), _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out_idx, out_logq, out_logm, status
+
+
+def mps_marginals(cores, want_pairs=False, out_m1=None, out_m2=None):
+    """Exact marginals of an MPS Born machine (bornvi_mps_marginals): -> (m1 float64 [n], m1[i] = q(z_i = 1), m2 float64
+    [n, n] or None, m2[i, j] = q(z_i = 1, z_j = 1): symmetric bit for bit, its diagonal m1).  Runs its own environment
+    sweeps in its own workspace: no mps_environments is needed and none is disturbed."""
+    n, D, _ = _mps_args(cores, 1)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    out_m1 = _out(out_m1, torch.float64, dev, "out_m1", n)
+    if want_pairs:
+        out_m2 = _out(out_m2, torch.float64, dev, "out_m2", n * n).view(n, n)
+    elif out_m2 is not None:
+        raise BornviError("out_m2 given without want_pairs")
+    ws = _mps_query_ws(h, dev, n, D, 1)
+    h.call("bornvi_mps_marginals", n, D, _ptr(cores), _ptr(out_m1), _ptr(out_m2) if want_pairs else None, _ptr(ws), ws.numel(),
+           _ext.stream_ptr(dev))
+    return out_m1, out_m2
+
+
 def bn_descriptor(packed, dev):
     """(device arrays, BnDesc) of bayesian_network.pack_network's dict; the arrays must outlive every call that uses the
     descriptor.  A network with a summed-out node is refused by bn_logjoint_samples, not here."""

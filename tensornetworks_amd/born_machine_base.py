@@ -3,6 +3,8 @@ machine (born_machine_mps.py) and the sampled MPS machine (born_machine_mps_samp
 
   indices_to_bits / bits_to_indices   outcome index <-> bit row (tuple position 0 = the most significant bit), with the
                                       validation of bit rows and its message; exact up to n = 63 (shifts reach 1 << 62)
+  pack_evidence                       a partial assignment {position: value} -> the (mask, value) words of the sampled MPS's
+                                      queries, in the same bit layout
   EnumeratedBornMachine               the surface over the 2^n table of q that the classical trainers use: fixed
                                       probabilities, all_outcome_tuples, sample, get_prob_dict, get_log_q_z_x, entropy.
                                       A family supplies how q is computed (_probabilities, _entropy) and its two ends of a
@@ -12,6 +14,7 @@ machine (born_machine_mps.py) and the sampled MPS machine (born_machine_mps_samp
 import math
 from typing import Any, NamedTuple, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -39,6 +42,46 @@ def bits_to_indices(z_samples, n, device=None):
     if row is not None:
         raise ValueError(f"Sample {tuple(row.tolist())} is not a valid outcome.")
     return (z << torch.arange(n - 1, -1, -1, device=z.device)).sum(dim=1)
+
+
+MAX_EVIDENCE_QUERIES = 1 << 16      # what one bornvi_mps_log_marginals call takes
+
+
+def pack_evidence(evidence, n):
+    """(mask, value): int64 tensors [Q] of the evidence words of the sampled MPS's queries, in the outcome index's own layout:
+    tuple position p is bit n - 1 - p; a set mask bit clamps that position to the value's bit.  `evidence` is a dict
+    {position: 0 or 1} (Q = 1), a non-empty sequence of such dicts, or a (mask, value) pair of int64 tensors (kept where
+    they are; checked where the host can see them: on the CPU).  Every error is a ValueError raised on the host."""
+    if isinstance(evidence, (tuple, list)) and len(evidence) == 2 and all(torch.is_tensor(e) for e in evidence):
+        mask, value = evidence
+        if mask.dtype != torch.int64 or value.dtype != torch.int64 or mask.shape != value.shape or mask.dim() > 1:
+            raise ValueError("evidence (mask, value): two int64 tensors of one shape [Q]")
+        mask, value = mask.reshape(-1), value.reshape(-1)
+        if not 1 <= mask.numel() <= MAX_EVIDENCE_QUERIES:
+            raise ValueError(f"evidence: 1 ... 2^16 queries per call, got {mask.numel()}")
+        if mask.device.type == "cpu" and bool((((mask | value) >> n) != 0).any()):
+            raise ValueError(f"evidence (mask, value): bits at or above n = {n} must be 0")
+        return mask.contiguous(), value.contiguous()
+    queries = [evidence] if isinstance(evidence, dict) else evidence
+    if isinstance(queries, (str, bytes)) or not hasattr(queries, "__len__") or not hasattr(queries, "__iter__"):
+        raise ValueError(f"evidence: a dict {{position: 0 or 1}}, a sequence of such dicts or a (mask, value) pair, got {evidence!r}")
+    if not 1 <= len(queries) <= MAX_EVIDENCE_QUERIES:
+        raise ValueError(f"evidence: 1 ... 2^16 queries per call, got {len(queries)}")
+    masks, values = [], []
+    for q in queries:
+        if not isinstance(q, dict):
+            raise ValueError(f"evidence: every query is a dict {{position: 0 or 1}}, got {q!r}")
+        m = v = 0
+        for pos, val in q.items():
+            if isinstance(pos, bool) or not isinstance(pos, (int, np.integer)) or not 0 <= int(pos) < n:
+                raise ValueError(f"evidence: position {pos!r} is outside 0 ... {n - 1}")
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or int(val) not in (0, 1):
+                raise ValueError(f"evidence: the value at position {pos!r} must be 0 or 1, got {val!r}")
+            m |= 1 << (n - 1 - int(pos))
+            v |= int(val) << (n - 1 - int(pos))
+        masks.append(m)
+        values.append(v)
+    return torch.tensor(masks, dtype=torch.int64), torch.tensor(values, dtype=torch.int64)
 
 
 class EpochForward(NamedTuple):

@@ -6,14 +6,16 @@ An exact draw z ~ q costs O(n D^2) (ancestral sampling against the right environ
 grad log q(z) for a given z (bornvi_mps_environments / bornvi_mps_sample / bornvi_mps_score_vjp).
 A sample is an int64 outcome index, idx = sum_k z_k 2^(n-k) (tuple position 0 = the most significant bit), or a float32
 bit row; the conversion, like the `cores` parameter, its checks, initialisations and messages, is born_machine_base's, shared
-with MPSBornMachine.  For n <= 26 the enumerated q is still there (probabilities64 / get_probabilities, through
+with MPSBornMachine.  The fitted q is read out exactly, at any n, by marginals / pair_marginals / log_marginal / sample_given (DESIGN.md section
+6l): an evidence is a partial assignment {tuple position: 0 or 1}.
+For n <= 26 the enumerated q is still there (probabilities64 / get_probabilities, through
 backend.mps_probs); above that those raise.
 """
 import torch
 import torch.nn as nn
 
 from . import backend
-from .born_machine_base import MPSCores, bits_to_indices, indices_to_bits, new_mps_cores
+from .born_machine_base import MPSCores, bits_to_indices, indices_to_bits, new_mps_cores, pack_evidence
 from .born_machine_mps import _MPSProbs
 
 
@@ -83,6 +85,46 @@ class SampledMPSBornMachine(MPSCores, nn.Module):
         if x_condition is not None:
             raise ValueError("x_condition provided but Born machine is not conditional.")
         return self.log_prob(self.indices_of(z_samples)).to(z_samples.device)
+
+    # ---- exact queries: detached, on the compute device -----------------------------------
+    def _evidence(self, evidence, single=False):
+        """(mask, value) int64 [Q] on the compute device; every argument error is raised before any GPU call."""
+        mask, value = pack_evidence(evidence, self.num_latent_vars)
+        if single and mask.numel() != 1:
+            raise ValueError(f"sample_given takes one evidence, got {mask.numel()}")
+        dev = backend.compute_device(self.cores.device)
+        return mask.to(dev), value.to(dev)
+
+    def marginals(self):
+        """float64 [n]: q(z_k = 1), exact."""
+        return backend.mps_marginals(self.kernel_input()[0])[0]
+
+    def pair_marginals(self):
+        """(float64 [n], float64 [n, n]): q(z_i = 1) and q(z_i = 1, z_j = 1), exact; the matrix is symmetric bit for bit and
+        its diagonal is the first result."""
+        return backend.mps_marginals(self.kernel_input()[0], want_pairs=True)
+
+    def log_marginal(self, evidence):
+        """float64 [Q]: the log probability of each partial assignment (-inf where it is impossible under q).  evidence: a
+        dict {position: 0 or 1}, a sequence of such dicts (at most 2^16), or a (mask, value) pair of int64 tensors."""
+        mask, value = self._evidence(evidence)
+        return backend.mps_log_marginals(self.kernel_input()[0], mask, value)[0]
+
+    def sample_given(self, evidence, num_samples, seed=None, epoch=0):
+        """(idx int64 [num], logq_cond float64 [num] = log q(idx | evidence), log_marginal float64 [1] of the evidence):
+        exact draws from q(. | evidence).  A pure function of (cores, evidence, seed, epoch); a free position gets the
+        uniform it gets in sample_indices."""
+        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+            raise ValueError(f"num_samples must be a positive integer, got {num_samples!r}")
+        if isinstance(epoch, bool) or not isinstance(epoch, int):
+            raise ValueError(f"epoch must be an integer, got {epoch!r}")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+            raise ValueError(f"seed must be an integer, got {seed!r}")
+        mask, value = self._evidence(evidence, single=True)
+        cores, _ = self.kernel_input()
+        ep = torch.tensor([epoch], dtype=torch.int64, device=cores.device)
+        idx, logq, logm, _ = backend.mps_sample_clamped(cores, num_samples, mask, value, self.seed if seed is None else seed, ep)
+        return idx, logq, logm
 
     # ---- the enumerated distribution, where it exists ------------------------------------------------------------
     def probabilities64(self, x_condition=None):

@@ -1345,6 +1345,52 @@ int bornvi_mps_score_jvp(bornvi_handle h, int n, int D, long long B, const doubl
   return BORNVI_OK;
 }
 
+// ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ---------------------------------------------
+static bool valid_mps_query(int n, int D, long long Q) { return n >= 1 && n <= 63 && D >= 1 && D <= 32 && Q >= 1 && Q <= MPS_QUERY_MAX_Q; }
+static const char* const MPS_QUERY_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 32, 1 <= Q <= 2^16)";
+
+size_t bornvi_mps_query_workspace_bytes(bornvi_handle h, int n, int D, int Q) {
+  if (!h) return 0;
+  if (!valid_mps_query(n, D, Q)) { fail(h, BORNVI_ERR_UNSUPPORTED, MPS_QUERY_RANGE); return 0; }
+  return mps_query_workspace_bytes(n, D, Q);
+}
+
+int bornvi_mps_log_marginals(bornvi_handle h, int n, int D, int Q, const double* cores, const long long* mask, const long long* value,
+                             double* logm, int* status, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_query(n, D, Q)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_QUERY_RANGE);
+  if (!cores || !mask || !value || !logm || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!workspace || workspace_bytes < mps_query_workspace_bytes(n, D, Q)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_log_marginals(n, D, Q, cores, mask, value, logm, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_mps_sample_clamped(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* mask,
+                              const long long* value, unsigned long long seed, const long long* epoch_dev, long long* idx, double* logq,
+                              double* logm, int* status, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_sample(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_SAMPLE_RANGE);
+  if (!cores || !mask || !value || !epoch_dev || !idx || !logq || !logm || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < mps_query_workspace_bytes(n, D, 1)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_sample_clamped(n, D, B, cores, mask, value, seed, epoch_dev, idx, logq, logm, status, workspace,
+                                      (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_mps_marginals(bornvi_handle h, int n, int D, const double* cores, double* m1, double* m2, void* workspace,
+                         size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_query(n, D, 1)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_QUERY_RANGE);
+  if (!cores || !m1) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < mps_query_workspace_bytes(n, D, 1)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_marginals(n, D, cores, m1, m2, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 // ---- conjugate gradients around a caller's product (kernels_cg.hip) ------------------------------------------------
 static bool valid_cg(long long P) { return P >= 1 && P <= 2147483647ll; }
 static const char* const CG_RANGE = "bad argument (1 <= P <= 2^31 - 1)";

@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_mps_sample_gram.hip", "kernels_ksd_sampled.hip", "kernels_cg.hip", "plan.cpp"]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_mps_sample_gram.hip", "kernels_mps_query.hip", "kernels_ksd_sampled.hip", "kernels_cg.hip", "plan.cpp"]
 HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "shots_dev.hpp", "mps_sample_dev.hpp", "syrk_f64.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
@@ -67,6 +67,10 @@ RESOURCE_BUDGET = {
     "mps_sample_gram_kernel": (0, 0),             # accumulators and the 16 xor-ed index words likewise, no scratch
     "mps_jvp_dot_kernel": (0, 0),                 # matrix-free natural gradient: the tangent sweep holds l, dl and their two
     "mps_score_jvp_kernel": (0, 0),               # products (4 x 32 doubles, 256 of a lone wave's 512 VGPRs), no scratch
+    "mps_query_env_kernel": (0, 0),               # posterior queries (kernels_mps_query.hip): the environment step's and the
+    "mps_query_logm_kernel": (0, 0),              # sampler's own code, so their budgets
+    "mps_sample_clamped_kernel": (0, 0),
+    "mps_marginals_kernel": (0, 0),
     "cg_init_kernel": (0, 0),                     # the CG recurrence (kernels_cg.hip)
     "cg_step_kernel": (0, 0),
     "cg_finish_kernel": (0, 0),

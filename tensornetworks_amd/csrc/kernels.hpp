@@ -109,6 +109,8 @@ hipError_t launch_mps_vjp(int n, int D, const double* cores, const double* g, do
 // ---- sampled MPS Born machine (kernels_mps_sample.hip): environments, exact sampler, score gradient, log joint of samples
 size_t mps_sample_workspace_bytes(int n, int D, long long B);
 hipError_t launch_mps_environments(int n, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st);
+hipError_t launch_mps_environments_into(int n, int D, const double* cores, double* E, double* L, int* eE, int* eL, double* hdr,
+                                        hipStream_t st);
 hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, unsigned long long seed, const long long* epoch_dev,
                              long long* idx, double* logq, int* status, void* ws, hipStream_t st);
 hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
@@ -122,6 +124,16 @@ hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, 
                                 double* t, int* status, void* ws, hipStream_t st);
 hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
                                       hipStream_t st);
+
+// ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip): log-marginals, clamped sampler, marginals ----
+constexpr int MPS_QUERY_MAX_Q = 1 << 16;
+size_t mps_query_workspace_bytes(int n, int D, int Q);
+hipError_t launch_mps_log_marginals(int n, int D, int Q, const double* cores, const long long* mask, const long long* value,
+                                    double* logm, int* status, void* ws, hipStream_t st);
+hipError_t launch_mps_sample_clamped(int n, int D, long long B, const double* cores, const long long* mask, const long long* value,
+                                     unsigned long long seed, const long long* epoch_dev, long long* idx, double* logq, double* logm,
+                                     int* status, void* ws, hipStream_t st);
+hipError_t launch_mps_marginals(int n, int D, const double* cores, double* m1, double* m2, void* ws, hipStream_t st);
 
 // ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
 constexpr int CG_STATE_DOUBLES = 8;      // rr, rr0, iterations, done, relres, fallback, 2 spare

@@ -16,6 +16,7 @@
 //   and read as broadcasts.  For k = 1 .. n:
 //     u_s = l A_k[s] (ms_row_dot's chain, the two s in one loop),  m_s = u_s E^_k u_s^T = sum_d u_s[d] (sum_c u_s[c] E^_k[c][d]),  z_k = [U_k (m_0 + m_1) >= m_0],
 //   then l = u_{z_k} rescaled (ms_rescale), the exponents summed in el.  The common factor 2^eE[k] of both m_s drops out.
+//   (The loop is ms_sample_sweep: the clamped sampler of kernels_mps_query.hip runs the same one.)
 //   U_k: Philox4x32-10 (philox_dev.hpp), key = (seed & 0xffffffff, seed >> 32),
 //     counter = (b, ceil(k / 2) - 1, 0xffffffff, epoch & 0xffffffff) -> w0 .. w3;
 //     odd k: U_k = ((w1:w0) >> 11) 2^-53,  even k: U_k = ((w3:w2) >> 11) 2^-53   (the call of k - 1).
@@ -78,7 +79,6 @@ namespace bornvi {
 
 namespace {
 constexpr int MS_MAX_WG = 256;             // score kernel: workgroups (= workspace slices and partials) at most
-constexpr uint32_t MS_PHILOX_DOMAIN = 0xffffffffu;
 
 typedef double ms_d4 __attribute__((ext_vector_type(4)));
 
@@ -108,12 +108,6 @@ MsLayout ms_layout(int n, int D, long long B) {
   return S;
 }
 
-__device__ __forceinline__ double ms_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
-
 // ---- environments ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MS_ENV_THREADS) void mps_env_kernel(const double* __restrict__ cores, int n, int D, double* __restrict__ E,
                                                               double* __restrict__ L, int* __restrict__ eE, int* __restrict__ eL,
@@ -138,43 +132,7 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_env_kernel(const double* _
     __syncthreads();
     for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
     __syncthreads();
-    for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
-      const int s = i / DD, a = (i % DD) / D, d = i % D;
-      double acc = 0.0;
-      for (int c = 0; c < D; ++c) acc = fma(right ? As[s * DD + a * D + c] : As[s * DD + c * D + a], X[c * D + d], acc);
-      T[i] = acc;
-    }
-    __syncthreads();
-    double v[4];
-    double mx = 0.0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = t + MS_ENV_THREADS * j;
-      v[j] = 0.0;
-      if (i < DD) {
-        const int a = i / D, b = i % D;
-        double acc = 0.0;
-        for (int s = 0; s < 2; ++s)
-          for (int d = 0; d < D; ++d) acc = fma(T[s * DD + a * D + d], right ? As[s * DD + b * D + d] : As[s * DD + d * D + b], acc);
-        v[j] = acc;
-        mx = fmax(mx, fabs(acc));
-      }
-    }
-    mx = ms_wave_max(mx);
-    if ((t & 63) == 0) red[t >> 6] = mx;
-    __syncthreads();
-    mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-    const int e = ms_exponent(mx);
-    ex += e;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = t + MS_ENV_THREADS * j;
-      if (i < DD) {
-        const double x = ldexp(v[j], -e);
-        X[i] = x;
-        out[(long long)dst * DD + i] = x;
-      }
-    }
+    ex += ms_env_step(right, D, 3, As, X, T, red, out + (long long)dst * DD);
     if (t == 0) eo[dst] = ex;
   }
   __syncthreads();
@@ -206,54 +164,10 @@ __global__ __launch_bounds__(MS_LANES) void mps_sample_kernel(const double* __re
   const bool active = b < B;
   const uint32_t ep = (uint32_t)(unsigned long long)(*epoch_dev);
   double l[DP];
-  ms_fill<DP>(l, 1.0);
-  int el = 0;
-  unsigned long long z = 0;
-  bool dead = false;
-  uint4 w = make_uint4(0, 0, 0, 0);
-#pragma unroll 1
-  for (int k = 1; k <= n; ++k) {
-    __syncthreads();
-    ms_load_site<DP>(cores, k, D, As, E + (long long)k * D * D, Es);
-    __syncthreads();
-    if (k & 1) w = philox4x32_10(make_uint4((uint32_t)b, (uint32_t)((k + 1) / 2 - 1), MS_PHILOX_DOMAIN, ep), seed_lo, seed_hi);
-    const double U = (k & 1) ? unit53(w.x, w.y) : unit53(w.z, w.w);
-    double u0[DP], u1[DP];           // ms_row_dot's chains, both s in one loop: see mps_sample_dev.hpp
-#pragma unroll
-    for (int c = 0; c < DP; ++c) {
-      double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-      for (int a = 0; a < DP; ++a) {
-        a0 = fma(l[a], As[a * DP + c], a0);
-        a1 = fma(l[a], As[DP * DP + a * DP + c], a1);
-      }
-      u0[c] = a0;
-      u1[c] = a1;
-    }
-    double m0 = 0.0, m1 = 0.0;
-#pragma unroll
-    for (int d = 0; d < DP; ++d) {
-      double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-      for (int c = 0; c < DP; ++c) {
-        const double e = Es[c * DP + d];
-        t0 = fma(u0[c], e, t0);
-        t1 = fma(u1[c], e, t1);
-      }
-      m0 = fma(t0, u0[d], m0);
-      m1 = fma(t1, u1[d], m1);
-    }
-    const double tot = m0 + m1;
-    if (!dead && !(tot > 0.0 && isfinite(tot))) {
-      dead = true;
-      if (active) *status = 1;
-    }
-    const bool bit = !dead && (U * tot >= m0);
-    z = (z << 1) | (bit ? 1ull : 0ull);
-#pragma unroll
-    for (int a = 0; a < DP; ++a) l[a] = bit ? u1[a] : u0[a];
-    el += ms_rescale<DP>(l);
-  }
+  int el;
+  unsigned long long z;
+  bool dead;
+  ms_sample_sweep<DP, false>(cores, n, D, b, active, E, seed_lo, seed_hi, ep, 0ull, 0ull, As, Es, z, l, el, dead, status);
   if (active) {
     idx[b] = (long long)z;
     logq[b] = dead ? __builtin_nan("") : ms_logq(l[0], el, hdr[1], hdr[2]);
@@ -618,6 +532,13 @@ hipError_t launch_mps_environments(int n, int D, long long B, const double* core
   char* base = ws_align(ws);
   mps_env_kernel<<<2, MS_ENV_THREADS, 0, st>>>(cores, n, D, (double*)(base + S.E), (double*)(base + S.L), (int*)(base + S.eE),
                                            (int*)(base + S.eL), (double*)(base + S.hdr), logZ_out);
+  return hipGetLastError();
+}
+
+// the same launch into a caller's own arrays (kernels_mps_query.hip keeps them in the query workspace)
+hipError_t launch_mps_environments_into(int n, int D, const double* cores, double* E, double* L, int* eE, int* eL, double* hdr,
+                                        hipStream_t st) {
+  mps_env_kernel<<<2, MS_ENV_THREADS, 0, st>>>(cores, n, D, E, L, eE, eL, hdr, nullptr);
   return hipGetLastError();
 }
 

@@ -5,7 +5,7 @@
 //   A_k[0], A_k[1] zero-padded to DP x DP in LDS (ms_load_site) and read as broadcasts.  z_k is bit n - k of the index word.
 // Products: an entry of x A (ms_row_dot) or of A r (ms_dot_col) is one fma chain in index order that continues from the
 //   accumulator it is given; the left and right steps are built on them.  Two kernels write this chain out themselves,
-//   because each runs two chains in one loop with their terms alternating, around one shared load: the sampler (u_0 and
+//   because each runs two chains in one loop with their terms alternating, around one shared load: the sampler's sweep (u_0 and
 //   u_1 share l[a]) and the jvp (l A and dl A share the entry of A).  Routed through ms_row_dot they give the same bits
 //   but are slower (profiles/sampled_sweep_core_variants.jsonl).
 // Steps: l <- l A_k[z_k] (ms_left_step), r <- A_k[z_k] r (ms_right_step); the new vector is taken times 2^-e (ms_take), e =
@@ -19,10 +19,19 @@
 // Environment term (ms_env_stage, ms_env_entry; a workgroup of MS_ENV_THREADS per site): mu[k - 1][s][a][d] =
 //   2 (L_{k-1} A_k[s] E_k)[a][d] / Z as T_s = A_s E^_k, M_s = L^_{k-1} T_s, fma chains in index order through LDS, then
 //   2^(eL[k-1] + eE[k] - eE[0]) / E^_0[0, 0].
+// Environment step (ms_env_step; a workgroup of MS_ENV_THREADS, the matrix X and the site's A in LDS): X <- sum_s A[s] X A[s]^T
+//   (right) or sum_s A[s]^T X A[s] (left) over the ALLOWED s (bit s of `allowed`; a clamped site allows one, a disallowed s
+//   contributes no term), as T_s = A_s X (A_s^T X), X' = sum_s T_s A_s^T (T_s A_s), every entry one fma chain in index order
+//   (c, then s outer / d inner), then times 2^-e, e = ilogb of the largest magnitude, e returned.  mps_env_kernel's step
+//   (allowed = 3) and the clamped environments of kernels_mps_query.hip are this one function.
+// Sampler sweep (ms_sample_sweep): the site loop of bornvi_mps_sample, stated in kernels_mps_sample.hip, and with CLAMP the
+//   same loop under an evidence (mask, value): a clamped site takes the evidence's bit and ignores U_k.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+
+#include "philox_dev.hpp"
 
 namespace bornvi {
 
@@ -45,6 +54,12 @@ inline int ms_dp(int D) { return D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 
 __device__ __forceinline__ double ms_wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+__device__ __forceinline__ double ms_wave_max(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
   return v;
 }
 
@@ -177,6 +192,121 @@ __device__ __forceinline__ double ms_env_entry(const double* Lm, const double* T
   for (int c = 0; c < D; ++c) m = fma(Lm[a * D + c], T[s * DD + c * D + d], m);
   const double env = ldexp(m / Zh, ex);
   return env + env;
+}
+
+// One environment step of a workgroup of MS_ENV_THREADS.  As: the site's A[s][.][.] as stored (pitch D), X: the D x D matrix,
+// both in LDS and published by a barrier; T (2 D D doubles) and red (MS_ENV_THREADS / 64) are scratch.  X becomes the new
+// matrix times 2^-e and, where out is not null, goes to out too; e is returned.  X is published by the caller's next barrier.
+__device__ __forceinline__ int ms_env_step(bool right, int D, int allowed, const double* As, double* X, double* T, double* red,
+                                           double* out) {
+  const int DD = D * D, t = threadIdx.x;
+  for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
+    const int s = i / DD, a = (i % DD) / D, d = i % D;
+    if (!((allowed >> s) & 1)) continue;
+    double acc = 0.0;
+    for (int c = 0; c < D; ++c) acc = fma(right ? As[s * DD + a * D + c] : As[s * DD + c * D + a], X[c * D + d], acc);
+    T[i] = acc;
+  }
+  __syncthreads();
+  double v[4];
+  double mx = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = t + MS_ENV_THREADS * j;
+    v[j] = 0.0;
+    if (i < DD) {
+      const int a = i / D, b = i % D;
+      double acc = 0.0;
+      for (int s = 0; s < 2; ++s) {
+        if (!((allowed >> s) & 1)) continue;
+        for (int d = 0; d < D; ++d) acc = fma(T[s * DD + a * D + d], right ? As[s * DD + b * D + d] : As[s * DD + d * D + b], acc);
+      }
+      v[j] = acc;
+      mx = fmax(mx, fabs(acc));
+    }
+  }
+  mx = ms_wave_max(mx);
+  if ((t & 63) == 0) red[t >> 6] = mx;
+  __syncthreads();
+  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  const int e = ms_exponent(mx);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = t + MS_ENV_THREADS * j;
+    if (i < DD) {
+      const double x = ldexp(v[j], -e);
+      X[i] = x;
+      if (out) out[i] = x;
+    }
+  }
+  return e;
+}
+
+constexpr uint32_t MS_PHILOX_DOMAIN = 0xffffffffu;
+
+// The sampler's site loop for the lane's sample b (one wave per workgroup; As 2 DP DP and Es DP DP doubles of LDS) against the
+// environments E [n + 1, D, D]: leaves the index word z, l^_n and its exponent el, and whether the sample died.  CLAMP: a site
+// whose bit of `mask` is set takes that bit of `value`, ignores U_k and kills the sample when the m_s of that branch is not
+// positive and finite; a dead sample's free bits are 0 and its clamped bits the evidence's.  The Philox counter does not
+// depend on the mask: a free site sees the same U_k whatever else is clamped.
+template <int DP, bool CLAMP>
+__device__ __forceinline__ void ms_sample_sweep(const double* __restrict__ cores, int n, int D, long long b, bool active,
+                                                const double* __restrict__ E, uint32_t seed_lo, uint32_t seed_hi, uint32_t ep,
+                                                unsigned long long mask, unsigned long long value, double* As, double* Es,
+                                                unsigned long long& z_out, double (&l)[DP], int& el_out, bool& dead_out, int* status) {
+  ms_fill<DP>(l, 1.0);
+  int el = 0;
+  unsigned long long z = 0;
+  bool dead = false;
+  uint4 w = make_uint4(0, 0, 0, 0);
+#pragma unroll 1
+  for (int k = 1; k <= n; ++k) {
+    __syncthreads();
+    ms_load_site<DP>(cores, k, D, As, E + (long long)k * D * D, Es);
+    __syncthreads();
+    if (k & 1) w = philox4x32_10(make_uint4((uint32_t)b, (uint32_t)((k + 1) / 2 - 1), MS_PHILOX_DOMAIN, ep), seed_lo, seed_hi);
+    const double U = (k & 1) ? unit53(w.x, w.y) : unit53(w.z, w.w);
+    double u0[DP], u1[DP];           // ms_row_dot's chains, both s in one loop: see the head of this file
+#pragma unroll
+    for (int c = 0; c < DP; ++c) {
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int a = 0; a < DP; ++a) {
+        a0 = fma(l[a], As[a * DP + c], a0);
+        a1 = fma(l[a], As[DP * DP + a * DP + c], a1);
+      }
+      u0[c] = a0;
+      u1[c] = a1;
+    }
+    double m0 = 0.0, m1 = 0.0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+        const double e = Es[c * DP + d];
+        t0 = fma(u0[c], e, t0);
+        t1 = fma(u1[c], e, t1);
+      }
+      m0 = fma(t0, u0[d], m0);
+      m1 = fma(t1, u1[d], m1);
+    }
+    const bool clamped = CLAMP && ((mask >> (n - k)) & 1ull);
+    const bool ev = (value >> (n - k)) & 1ull;
+    const double tot = clamped ? (ev ? m1 : m0) : m0 + m1;
+    if (!dead && !(tot > 0.0 && isfinite(tot))) {
+      dead = true;
+      if (active) *status = 1;
+    }
+    const bool bit = clamped ? ev : (!dead && (U * tot >= m0));
+    z = (z << 1) | (bit ? 1ull : 0ull);
+#pragma unroll
+    for (int a = 0; a < DP; ++a) l[a] = bit ? u1[a] : u0[a];
+    el += ms_rescale<DP>(l);
+  }
+  z_out = z;
+  el_out = el;
+  dead_out = dead;
 }
 
 }  // namespace bornvi

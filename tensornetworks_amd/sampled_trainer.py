@@ -162,6 +162,37 @@ class SampledTrainer:
                 print(msg)
         return history
 
+    # ---- the fitted posterior, read out exactly (SampledMPSBornMachine's queries by variable name) ------------------
+    def _evidence_by_name(self, evidence):
+        """{name: value} (or a sequence of such dicts) -> the same with tuple positions, through latent_vars_names."""
+        if isinstance(evidence, dict):
+            out = {}
+            for name, val in evidence.items():
+                if name in self.observed_vars_names:
+                    raise ValueError(f"{name!r} is an observed variable: the posterior is already conditioned on it")
+                if name not in self.latent_vars_names:
+                    raise ValueError(f"{name!r} is not a latent variable of this trainer")
+                out[self.latent_vars_names.index(name)] = val
+            return out
+        if isinstance(evidence, (list, tuple)):
+            return [self._evidence_by_name(e) if isinstance(e, dict) else e for e in evidence]
+        return evidence
+
+    def posterior_marginals(self):
+        """{name: q(z = 1)} of the current cores, exact."""
+        m1 = self.born_machine.marginals().cpu().tolist()
+        return dict(zip(self.latent_vars_names, m1))
+
+    def posterior_log_marginal(self, evidence):
+        """float64 [Q] on the compute device: log q of {name: value, ...}, or of each dict of a list."""
+        return self.born_machine.log_marginal(self._evidence_by_name(evidence))
+
+    def posterior_sample_given(self, evidence, num_samples, seed=None, epoch=0):
+        """(idx, logq_cond, log_marginal) of SampledMPSBornMachine.sample_given, the evidence by variable name."""
+        if not isinstance(evidence, dict):
+            raise ValueError(f"evidence: a dict {{name: 0 or 1}}, got {evidence!r}")
+        return self.born_machine.sample_given(self._evidence_by_name(evidence), num_samples, seed=seed, epoch=epoch)
+
     def exact_report(self, posterior):
         """(TVD, KL(q || posterior)) of the current cores against a posterior table [2^n], by enumeration (n <= 26)."""
         with torch.no_grad():
