@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
 SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_mps_sample_gram.hip", "kernels_mps_query.hip", "kernels_ksd_sampled.hip", "kernels_cg.hip", "plan.cpp"]
-HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "shots_dev.hpp", "mps_sample_dev.hpp", "syrk_f64.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
+HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "shots_dev.hpp", "mps_sample_dev.hpp", "syrk_f64.hpp", "reduce_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-I" + os.path.join(REPO, "include"), "-I" + HERE,

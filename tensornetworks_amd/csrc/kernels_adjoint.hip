@@ -17,16 +17,11 @@
 
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_adj(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 struct C2 { double re, im; };
 __device__ __forceinline__ C2 cmul(C2 a, C2 b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
@@ -121,7 +116,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void adj_rot_backward_kernel(double2* 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const double v = wave_sum_adj(g[e]);
+    const double v = wave_sum(g[e]);
     if (lane == 0) red[wave][e] = v;
   }
   __syncthreads();

@@ -8,15 +8,16 @@
 // with respect to q back onto w: dL/dq = y / L (0 where the clamp is active; y = K_p q) + lambda (log c + [q >= 1e-10]),
 // c = max(q, 1e-10); then the softmax VJP q (g - sum q g), or for mode 1 sign(w) (g - sum q g) / sum |w| (sign(0) = 0).
 //
-// Every reduction over a row is two-level and in a fixed order: each of the G workgroups of a row writes its partial to
-// the workspace, the next kernel reduces the row's G partials (each workgroup redundantly, in the same order).  No
-// atomics; results are bitwise reproducible.  256-thread workgroups (four waves of 64), grid-stride over a contiguous
-// chunk of the row with float4 loads where the row allows them.
+// Every reduction over a row is two-level and in the fixed order of reduce_dev.hpp: each of the G
+// workgroups of a row writes its partial to the workspace, the next kernel reduces the row's G partials (each workgroup
+// redundantly, in the same order).  256-thread workgroups (four waves of 64), grid-stride over a contiguous chunk of the
+// row with float4 loads where the row allows them.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -27,20 +28,8 @@ constexpr long long BT_PER_WG = 4096;     // target entries per workgroup
 constexpr long long BT_MAX_WG = 1024;     // workgroups per row at most
 constexpr float BT_CLAMP = 1e-10f;        // the reference's clamp(min=1e-10) on a float32 tensor
 
-struct BtGeom {
-  long long chunk;   // entries per workgroup (a multiple of 4)
-  int G;             // workgroups per row
-};
-
-BtGeom bt_geom(long long N) {
-  long long G = (N + BT_PER_WG - 1) / BT_PER_WG;
-  if (G > BT_MAX_WG) G = BT_MAX_WG;
-  if (G < 1) G = 1;
-  long long chunk = (N + G - 1) / G;
-  chunk = (chunk + 3) & ~3ll;
-  G = (N + chunk - 1) / chunk;
-  return {chunk, (int)G};
-}
+// a row's workgroups: chunks of a multiple of 4 entries
+ChunkGeom bt_geom(long long N) { return chunk_geom(N, BT_PER_WG, BT_MAX_WG, 4); }
 
 // Online (max, sum of exp(w - max)) pair.  Symmetric in its two arguments (so the shuffle butterfly gives every lane the
 // same value) and NaN-sticky (a NaN logit reaches every q, as in torch.softmax).
@@ -62,25 +51,6 @@ __device__ __forceinline__ void sm_combine(float& M, double& S, float m, double 
   } else {
     S += s * exp((double)m - (double)M);
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// Block sum, fixed order: butterfly within each wave, then the four wave totals in order.  Every thread gets the result.
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-  v = wave_sum(v);
-  const int t = threadIdx.x;
-  __syncthreads();
-  if ((t & 63) == 0) lds[t >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-#pragma unroll
-  for (int i = 0; i < BT_WAVES; ++i) tot += lds[i];
-  return tot;
 }
 
 __device__ __forceinline__ void block_softmax_stats(float& M, double& S, float* ldsm, double* ldss) {
@@ -113,10 +83,10 @@ __device__ __forceinline__ void row_stats(const double* __restrict__ part, int G
     for (int k = t; k < G; k += BT_THREADS) sm_combine(M, S, (float)part[2 * k], part[2 * k + 1]);
     block_softmax_stats(M, S, ldsm, ldss);
   } else {
-    double s = 0.0;
+    double s = 0.0;      // (this loop and the entropy kernel's are sum_partials written out: reduce_dev.hpp says why)
     for (int k = t; k < G; k += BT_THREADS) s += part[2 * k + 1];
     M = 0.0f;
-    S = block_sum(s, ldss);
+    S = block_sum<BT_WAVES>(s, ldss);
   }
 }
 
@@ -149,7 +119,7 @@ __global__ __launch_bounds__(BT_THREADS) void born_table_stats_kernel(const floa
   if (mode == 0) {
     block_softmax_stats(M, S, ldsm, ldss);
   } else {
-    S = block_sum(S, ldss);
+    S = block_sum<BT_WAVES>(S, ldss);
   }
   if (threadIdx.x == 0) {
     double* p = part + 2 * (row * gridDim.x + g);
@@ -204,7 +174,7 @@ __global__ __launch_bounds__(BT_THREADS) void born_table_probs_kernel(const floa
     }
   }
   if (hpart) {
-    h = block_sum(h, ldss);
+    h = block_sum<BT_WAVES>(h, ldss);
     if (threadIdx.x == 0) hpart[row * G + g] = h;
   }
 }
@@ -216,7 +186,7 @@ __global__ __launch_bounds__(BT_THREADS) void born_table_entropy_kernel(const do
   const long long row = blockIdx.x;
   double s = 0.0;
   for (int k = threadIdx.x; k < G; k += BT_THREADS) s += hpart[row * G + k];
-  s = block_sum(s, ldss);
+  s = block_sum<BT_WAVES>(s, ldss);
   if (threadIdx.x == 0) H[row] = (float)(-s);
 }
 
@@ -270,8 +240,8 @@ __global__ __launch_bounds__(BT_THREADS) void born_table_vjp_stats_kernel(const 
       if (mode == 1) sw += (double)fabsf(wr[i]);
     }
   }
-  sqg = block_sum(sqg, ldss);
-  if (mode == 1) sw = block_sum(sw, ldss);
+  sqg = block_sum<BT_WAVES>(sqg, ldss);
+  if (mode == 1) sw = block_sum<BT_WAVES>(sw, ldss);
   if (threadIdx.x == 0) {
     double* p = part + 2 * (row * gridDim.x + g);
     p[0] = sqg;
@@ -302,8 +272,8 @@ __global__ __launch_bounds__(BT_THREADS) void born_table_vjp_kernel(const float*
     c += pr[2 * k];
     sw += pr[2 * k + 1];
   }
-  c = block_sum(c, ldss);
-  if (mode == 1) sw = block_sum(sw, ldss);
+  c = block_sum<BT_WAVES>(c, ldss);
+  if (mode == 1) sw = block_sum<BT_WAVES>(sw, ldss);
   const double inv_s = 1.0 / sw;
   const double a = ksd_scale(ksd2, row);
   const float* __restrict__ wr = w + row * N;
@@ -336,14 +306,14 @@ __global__ __launch_bounds__(BT_THREADS) void born_table_vjp_kernel(const float*
 }  // namespace
 
 size_t born_table_workspace_bytes(int n, long long rows) {
-  const BtGeom gm = bt_geom(1ll << n);
+  const ChunkGeom gm = bt_geom(1ll << n);
   return (size_t)rows * gm.G * 3 * sizeof(double) + 512;
 }
 
 hipError_t launch_born_table_probs(int n, long long rows, int mode, const float* w, float* q32, double* q64, float* H,
                                    void* ws, hipStream_t st) {
   const long long N = 1ll << n;
-  const BtGeom gm = bt_geom(N);
+  const ChunkGeom gm = bt_geom(N);
   const int vec = (N % 4 == 0) && ((((uintptr_t)w) | ((uintptr_t)q32) | ((uintptr_t)q64)) & 15) == 0;
   double* part = (double*)ws_align(ws);
   double* hpart = H ? part + 2 * rows * gm.G : nullptr;
@@ -357,7 +327,7 @@ hipError_t launch_born_table_probs(int n, long long rows, int mode, const float*
 hipError_t launch_born_table_vjp(int n, long long rows, int mode, const float* w, const double* q64, const double* y,
                                  const double* ksd2, double lam, float* grad, double* loss_out, void* ws, hipStream_t st) {
   const long long N = 1ll << n;
-  const BtGeom gm = bt_geom(N);
+  const ChunkGeom gm = bt_geom(N);
   const int vec = (N % 4 == 0) &&
                   ((((uintptr_t)w) | ((uintptr_t)q64) | ((uintptr_t)y) | ((uintptr_t)grad)) & 15) == 0;
   double* part = (double*)ws_align(ws);

@@ -7,8 +7,8 @@
 //
 // Each entry point is one workgroup of CG_THREADS threads; thread t owns the elements t, t + CG_THREADS, ... of every
 // vector (P <= 2 * 63 * 32^2 = 129 024 for an MPS: at most 126 elements per thread), so no element is read by a thread that
-// did not write it and a step needs no fence.  Every dot product is one fixed-order reduction: the thread's elements in
-// order, a butterfly over the 64 lanes of the wave, the 16 waves in order.  q is not stored: fma(damping, p, Fp) is
+// did not write it and a step needs no fence.  Every dot product is one fixed-order reduction (reduce_dev.hpp, DESIGN.md
+// section 4.6): the thread's elements in order, then block_sum over the 16 waves.  q is not stored: fma(damping, p, Fp) is
 // evaluated again, to the same bits, where r is updated.
 //
 // The launch sequence of a solve never depends on the data.  Once the done flag is set (converged: rr' <= rel_tol^2 rr0;
@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -29,19 +30,6 @@ namespace {
 constexpr int CG_THREADS = 1024;
 constexpr int CG_WAVES = CG_THREADS / 64;
 enum { CG_RR = 0, CG_RR0 = 1, CG_ITERS = 2, CG_DONE = 3, CG_RELRES = 4, CG_FALLBACK = 5 };
-
-// the workgroup's sum of v: the lanes of a wave by butterfly, then the waves in order (every thread gets the same bits)
-__device__ __forceinline__ double cg_block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();                                   // red may still be read from the reduction before
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < CG_WAVES; ++w) s += red[w];
-  return s;
-}
 
 __global__ __launch_bounds__(CG_THREADS) void cg_init_kernel(long long P, const double* __restrict__ g, double* __restrict__ x,
                                                              double* __restrict__ r, double* __restrict__ p,
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(CG_THREADS) void cg_init_kernel(long long P, const 
     acc = fma(gi, gi, acc);
     bad |= !isfinite(gi);
   }
-  const double rr = cg_block_sum(acc, red);
+  const double rr = block_sum<CG_WAVES>(acc, red);
   const int anybad = __syncthreads_or(bad);
   if (t == 0) {
     state[CG_RR] = rr;
@@ -85,7 +73,7 @@ __global__ __launch_bounds__(CG_THREADS) void cg_step_kernel(long long P, double
     const double pi = p[i];
     acc = fma(pi, fma(damping, pi, Fp[i]), acc);
   }
-  const double pq = cg_block_sum(acc, red);
+  const double pq = block_sum<CG_WAVES>(acc, red);
   if (!(pq > 0.0) || !isfinite(pq)) {                // (uniform) no step: x stays the last iterate
     __syncthreads();                                 // every thread has read the state
     if (t == 0) {
@@ -104,7 +92,7 @@ __global__ __launch_bounds__(CG_THREADS) void cg_step_kernel(long long P, double
     r[i] = ri;
     acc = fma(ri, ri, acc);
   }
-  const double rr1 = cg_block_sum(acc, red);
+  const double rr1 = block_sum<CG_WAVES>(acc, red);
   const double beta = rr1 / rr;
   for (long long i = t; i < P; i += CG_THREADS) p[i] = fma(beta, p[i], r[i]);
   if (t == 0) {

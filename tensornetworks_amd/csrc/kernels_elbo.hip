@@ -8,15 +8,16 @@
 //   entropy  = -sum_z q_z l_z
 // One read of q, one read of log_p, one write of w: 24 bytes per entry, memory-bound.
 //
-// Reductions as in kernels_born_table.hip: each of the G workgroups of a row adds its contiguous chunk (at most 16 entries
-// per thread, then a butterfly within each wave, then the four wave totals in order) and writes its two partials to the
-// workspace; a finishing launch adds a row's G partials in the same fixed way.  No atomics: bitwise reproducible.
-// 256-thread workgroups (four waves of 64), double2 accesses where the pointers allow them.
+// Reductions as in kernels_born_table.hip, in the fixed order of reduce_dev.hpp: each of the G
+// workgroups of a row adds its contiguous chunk (at most 16 entries per thread) and writes its two partials to the
+// workspace; a finishing launch adds a row's G partials in the same fixed way.  256-thread workgroups (four waves of 64),
+// double2 accesses where the pointers allow them.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -26,38 +27,8 @@ constexpr int EL_WAVES = EL_THREADS / 64;
 constexpr long long EL_PER_WG = 4096;     // target entries per workgroup: 16 per thread
 constexpr long long EL_MAX_WG = 1024;     // workgroups per row at most (n > 22: longer chunks)
 
-struct ElGeom {
-  long long chunk;   // entries per workgroup (a multiple of 4)
-  int G;             // workgroups per row
-};
-
-ElGeom el_geom(long long N) {
-  long long G = (N + EL_PER_WG - 1) / EL_PER_WG;
-  if (G > EL_MAX_WG) G = EL_MAX_WG;
-  long long chunk = (N + G - 1) / G;
-  chunk = (chunk + 3) & ~3ll;
-  G = (N + chunk - 1) / chunk;
-  return {chunk, (int)G};
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// Block sum, fixed order: butterfly within each wave, then the four wave totals in order.  Every thread gets the result.
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-  v = wave_sum(v);
-  const int t = threadIdx.x;
-  __syncthreads();
-  if ((t & 63) == 0) lds[t >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-#pragma unroll
-  for (int i = 0; i < EL_WAVES; ++i) tot += lds[i];
-  return tot;
-}
+// a row's workgroups: chunks of a multiple of 4 entries
+ChunkGeom el_geom(long long N) { return chunk_geom(N, EL_PER_WG, EL_MAX_WG, 4); }
 
 // One entry: returns w, adds the entry's loss and q log c terms.  The clamp is written so that a NaN q stays NaN.
 __device__ __forceinline__ double elbo_entry(double q, double lp, double q_floor, double& loss, double& qlogq) {
@@ -96,8 +67,8 @@ __global__ __launch_bounds__(EL_THREADS) void elbo_weights_kernel(const double* 
       if (wr) wr[i] = o;
     }
   }
-  loss = block_sum(loss, lds);
-  qlogq = block_sum(qlogq, lds);
+  loss = block_sum<EL_WAVES>(loss, lds);
+  qlogq = block_sum<EL_WAVES>(qlogq, lds);
   if (threadIdx.x == 0) {
     double* p = part + 2 * (row * gridDim.x + g);
     p[0] = loss;
@@ -115,8 +86,8 @@ __global__ __launch_bounds__(EL_THREADS) void elbo_finish_kernel(const double* _
     loss += pr[2 * k];
     qlogq += pr[2 * k + 1];
   }
-  loss = block_sum(loss, lds);
-  qlogq = block_sum(qlogq, lds);
+  loss = block_sum<EL_WAVES>(loss, lds);
+  qlogq = block_sum<EL_WAVES>(qlogq, lds);
   if (threadIdx.x == 0) {
     neg_elbo[blockIdx.x] = loss;
     if (entropy) entropy[blockIdx.x] = -qlogq;
@@ -126,14 +97,14 @@ __global__ __launch_bounds__(EL_THREADS) void elbo_finish_kernel(const double* _
 }  // namespace
 
 size_t elbo_workspace_bytes(int n, long long rows) {
-  const ElGeom gm = el_geom(1ll << n);
+  const ChunkGeom gm = el_geom(1ll << n);
   return (size_t)rows * gm.G * 2 * sizeof(double) + 512;
 }
 
 hipError_t launch_elbo_weights(int n, long long rows, const double* q, const double* log_p, double q_floor, double* w,
                                double* neg_elbo, double* entropy, void* ws, hipStream_t st) {
   const long long N = 1ll << n;
-  const ElGeom gm = el_geom(N);
+  const ChunkGeom gm = el_geom(N);
   const int vec = (N % 2 == 0) && ((((uintptr_t)q) | ((uintptr_t)log_p) | ((uintptr_t)w)) & 15) == 0;
   double* part = (double*)ws_align(ws);
   elbo_weights_kernel<<<dim3((unsigned)gm.G, (unsigned)rows), EL_THREADS, 0, st>>>(q, log_p, N, gm.chunk, vec, q_floor, w, part);

@@ -47,6 +47,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 #include "syrk_f64.hpp"
 
 namespace bornvi {
@@ -222,12 +223,6 @@ __global__ __launch_bounds__(syrk::THREADS) void score_gram_finish_kernel(const 
 
 // ------------------------------------------------------------------------------------------------ SPD solve
 constexpr int SS_NB = 16, SS_PITCH = 17, SS_MAX_P = 1024;
-
-__device__ __forceinline__ double ss_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 struct SsLds {
   double* pan;    // [P][SS_PITCH]
@@ -406,7 +401,7 @@ __global__ __launch_bounds__(1024) void spd_solve_kernel(const double* __restric
       }
 #pragma unroll
       for (int c = 0; c < SS_NB; ++c) {
-        const double w = ss_wave_sum(pr[c]);
+        const double w = wave_sum(pr[c]);
         if ((t & 63) == 0) L.red[(t >> 6) * SS_NB + c] = w;
       }
       for (int idx = t; idx < SS_NB * SS_NB; idx += nt) {

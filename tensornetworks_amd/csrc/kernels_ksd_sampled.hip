@@ -33,6 +33,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(KP_THREADS) void stein_pairs_kernel(int n, long lon
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    double v = rs[r];
+    double v = rs[r];     // (a 16-lane sum written out: as a call the kernel's instruction stream differs, profiles/reduce_core_isa.txt)
 #pragma unroll
     for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off);
     const long long row = wrow0 + fk + 4 * r;
@@ -299,8 +300,7 @@ __global__ __launch_bounds__(KP_THREADS) void stein_pairs_finish_kernel(long lon
     r[b] = sum;
     acc += sum;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  acc = wave_sum(acc);
   if ((t & 63) == 0) red[t >> 6] = acc;
   __syncthreads();
   if (t == 0) total[0] = ((red[0] + red[1]) + red[2]) + red[3];

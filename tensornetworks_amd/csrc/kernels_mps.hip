@@ -26,13 +26,14 @@
 //   parents per workgroup up to level 19, 2^(k-11) above), so the traffic counts it as a read of its own.
 //   Last level: psi(2p + s) = V_{n-1}[p, :] . A_n[s][:, 0] and the workgroup's partial of Z; a second launch adds the Z
 //   partials (every workgroup adds all of them in the same fixed order) and writes q = psi^2 / Z.
-// Every long sum is fixed-order partials plus a finishing step: no atomics, two calls are bitwise equal.  No allocation, no
-// synchronisation (capturable).  Fragment layout of the f64 MFMA as in syrk_f64.hpp.
+// Every long sum is fixed-order partials plus a finishing step (reduce_dev.hpp): no atomics, two calls
+// are bitwise equal.  No allocation, no synchronisation (capturable).  Fragment layout of the f64 MFMA as in syrk_f64.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -61,42 +62,7 @@ __host__ __device__ inline long long mps_part_off(int k, int n, int D) {   // do
 }
 __host__ __device__ inline long long mps_voff(int k, int DS) { return (long long)DS * ((1ll << k) - 1); }   // doubles before V_k
 
-struct MpsQGeom {
-  long long chunk;
-  int G;
-};
-MpsQGeom mps_qgeom(long long N) {
-  long long G = (N + MPS_Q_PER_WG - 1) / MPS_Q_PER_WG;
-  if (G > MPS_MAX_PART) G = MPS_MAX_PART;
-  const long long chunk = (N + G - 1) / G;
-  return {chunk, (int)((N + chunk - 1) / chunk)};
-}
-
-__device__ __forceinline__ double mps_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// Block sum, fixed order: butterfly within each wave, then the four wave totals in order.  Every thread gets the result.
-__device__ __forceinline__ double mps_block_sum(double v, double* lds) {
-  v = mps_wave_sum(v);
-  const int t = threadIdx.x;
-  __syncthreads();
-  if ((t & 63) == 0) lds[t >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-#pragma unroll
-  for (int i = 0; i < MPS_WAVES; ++i) tot += lds[i];
-  return tot;
-}
-
-// Sum of `count` partials, the same fixed order in every workgroup that asks.
-__device__ __forceinline__ double mps_sum_partials(const double* part, int count, double* lds) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < count; i += MPS_THREADS) v += part[i];
-  return mps_block_sum(v, lds);
-}
+ChunkGeom mps_qgeom(long long N) { return chunk_geom(N, MPS_Q_PER_WG, MPS_MAX_PART, 1); }
 
 // G_n[z, 0]
 __device__ __forceinline__ double mps_gamma(double psi, double g, double c, double Z) {
@@ -328,7 +294,7 @@ __global__ __launch_bounds__(MPS_THREADS) void mps_fwd_fused_kernel(const double
     mps_load_col<DP>(cores, n, D, As);
     __syncthreads();
     double z = mps_psi_level<DP>(As, V + mps_voff(n - 1, DS), psi, 0, 1ll << (n - 1), D, DS);
-    z = mps_block_sum(z, lds);
+    z = block_sum<MPS_WAVES>(z, lds);
     if (threadIdx.x == 0) zpart[0] = z;
   }
 }
@@ -354,7 +320,7 @@ __global__ __launch_bounds__(MPS_THREADS) void mps_psi_kernel(const double* __re
   __syncthreads();
   const long long p0 = blockIdx.x * chunk;
   double z = mps_psi_level<DP>(col, Vp, psi, p0, p0 + chunk, D, DS);
-  z = mps_block_sum(z, lds);
+  z = block_sum<MPS_WAVES>(z, lds);
   if (threadIdx.x == 0) zpart[blockIdx.x] = z;
 }
 
@@ -364,7 +330,7 @@ __global__ __launch_bounds__(MPS_THREADS) void mps_q_kernel(const double* __rest
                                                             float* __restrict__ q32, double* __restrict__ psi_out,
                                                             double* __restrict__ Z_out, double* __restrict__ hdr) {
   __shared__ double lds[MPS_WAVES];
-  const double Z = mps_sum_partials(zpart, nz, lds);
+  const double Z = sum_partials<MPS_THREADS>(zpart, nz, lds);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     hdr[0] = Z;
     if (Z_out) Z_out[0] = Z;
@@ -395,7 +361,7 @@ __global__ __launch_bounds__(MPS_THREADS) void mps_gstats_kernel(const double* _
     const double q = good ? (ps * ps) / Z : __builtin_nan("");
     v = fma(q, g[i], v);
   }
-  v = mps_block_sum(v, lds);
+  v = block_sum<MPS_WAVES>(v, lds);
   if (threadIdx.x == 0) cpart[blockIdx.x] = v;
 }
 
@@ -411,7 +377,7 @@ __global__ __launch_bounds__(MPS_THREADS) void mps_bwd_fused_kernel(const double
   __shared__ double lds[MPS_WAVES];
   double c = 0.0, Z = 1.0;
   if (ktop == n) {
-    c = mps_sum_partials(cpart, nc, lds);
+    c = sum_partials<MPS_THREADS>(cpart, nc, lds);
     Z = hdr[0];
   }
   for (int k = ktop; k >= 1; --k) {
@@ -446,7 +412,7 @@ __global__ __launch_bounds__(MPS_THREADS) void mps_bwd_level_kernel(const double
   __shared__ double lds[MPS_WAVES];
   double c = 0.0, Z = 1.0;
   if (TOP) {
-    c = mps_sum_partials(cpart, nc, lds);
+    c = sum_partials<MPS_THREADS>(cpart, nc, lds);
     Z = hdr[0];
   }
   mps_load_core<DP, false>(cores, k, D, As);
@@ -486,7 +452,7 @@ struct MpsLayout {
 
 MpsLayout mps_layout(int n, int D) {
   MpsLayout L;
-  L.DP = D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32;
+  L.DP = bond_dp(D);
   L.DS = (D + 1) & ~1;
   const size_t N = (size_t)1 << n;
   size_t o = 0;
@@ -501,15 +467,6 @@ MpsLayout mps_layout(int n, int D) {
   L.total = o;
   return L;
 }
-
-#define MPS_DISPATCH(DPV, CALL)                 \
-  switch (DPV) {                                \
-    case 2: { constexpr int DP = 2; CALL; } break;   \
-    case 4: { constexpr int DP = 4; CALL; } break;   \
-    case 8: { constexpr int DP = 8; CALL; } break;   \
-    case 16: { constexpr int DP = 16; CALL; } break; \
-    default: { constexpr int DP = 32; CALL; } break; \
-  }
 }  // namespace
 
 size_t mps_workspace_bytes(int n, int D) { return mps_layout(n, D).total + 256; }
@@ -525,20 +482,20 @@ hipError_t launch_mps_probs(int n, int D, const double* cores, double* q64, floa
   const int DS = L.DS;
   const int kmax = (n - 1 < MPS_FUSED) ? n - 1 : MPS_FUSED;
   const int last = mps_level_fused(n, n) ? 1 : 0;
-  MPS_DISPATCH(L.DP, (mps_fwd_fused_kernel<DP><<<1, MPS_THREADS, 0, st>>>(cores, n, D, DS, kmax, last, V, psi, zpart)));
+  BOND_DISPATCH(L.DP, (mps_fwd_fused_kernel<DP><<<1, MPS_THREADS, 0, st>>>(cores, n, D, DS, kmax, last, V, psi, zpart)));
   for (int k = kmax + 1; k <= n - 1; ++k) {
     const long long nwg = mps_nwg(k, n), chunk = (1ll << (k - 1)) / nwg;
-    MPS_DISPATCH(L.DP, (mps_fwd_level_kernel<DP><<<(unsigned)nwg, MPS_THREADS, 0, st>>>(cores, k, D, DS, chunk, V + mps_voff(k - 1, DS),
+    BOND_DISPATCH(L.DP, (mps_fwd_level_kernel<DP><<<(unsigned)nwg, MPS_THREADS, 0, st>>>(cores, k, D, DS, chunk, V + mps_voff(k - 1, DS),
                                                                                        V + mps_voff(k, DS))));
   }
   const long long nz = mps_nwg(n, n);
   if (!last) {
     const long long chunk = (1ll << (n - 1)) / nz;
-    MPS_DISPATCH(L.DP, (mps_psi_kernel<DP><<<(unsigned)nz, MPS_THREADS, 0, st>>>(cores, n, D, DS, chunk, V + mps_voff(n - 1, DS), psi,
+    BOND_DISPATCH(L.DP, (mps_psi_kernel<DP><<<(unsigned)nz, MPS_THREADS, 0, st>>>(cores, n, D, DS, chunk, V + mps_voff(n - 1, DS), psi,
                                                                                 zpart)));
   }
   const long long N = 1ll << n;
-  const MpsQGeom qg = mps_qgeom(N);
+  const ChunkGeom qg = mps_qgeom(N);
   mps_q_kernel<<<(unsigned)qg.G, MPS_THREADS, 0, st>>>(psi, zpart, (int)nz, N, qg.chunk, q64, q32, psi_out, Z_out, hdr);
   return hipGetLastError();
 }
@@ -555,7 +512,7 @@ hipError_t launch_mps_vjp(int n, int D, const double* cores, const double* g, do
   double* parts = (double*)(base + L.parts);
   const int DS = L.DS;
   const long long N = 1ll << n;
-  const MpsQGeom qg = mps_qgeom(N);
+  const ChunkGeom qg = mps_qgeom(N);
   mps_gstats_kernel<<<(unsigned)qg.G, MPS_THREADS, 0, st>>>(psi, hdr, g, N, qg.chunk, cpart);
   int k = n;
   for (; k >= 1 && !mps_level_fused(k, n); --k) {
@@ -564,14 +521,14 @@ hipError_t launch_mps_vjp(int n, int D, const double* cores, const double* g, do
     double* Gp = ((n - k) & 1) ? Gb : Ga;
     double* part = parts + mps_part_off(k, n, D);
     if (k == n) {
-      MPS_DISPATCH(L.DP, (mps_bwd_level_kernel<DP, true><<<(unsigned)nwg, MPS_THREADS, 0, st>>>(
+      BOND_DISPATCH(L.DP, (mps_bwd_level_kernel<DP, true><<<(unsigned)nwg, MPS_THREADS, 0, st>>>(
                              cores, k, D, DS, chunk, V + mps_voff(k - 1, DS), nullptr, Gp, psi, hdr, g, cpart, qg.G, part)));
     } else {
-      MPS_DISPATCH(L.DP, (mps_bwd_level_kernel<DP, false><<<(unsigned)nwg, MPS_THREADS, 0, st>>>(
+      BOND_DISPATCH(L.DP, (mps_bwd_level_kernel<DP, false><<<(unsigned)nwg, MPS_THREADS, 0, st>>>(
                              cores, k, D, DS, chunk, V + mps_voff(k - 1, DS), Gc, Gp, nullptr, nullptr, nullptr, nullptr, 0, part)));
     }
   }
-  MPS_DISPATCH(L.DP, (mps_bwd_fused_kernel<DP><<<1, MPS_THREADS, 0, st>>>(cores, n, D, DS, k, V, psi, hdr, g, cpart, qg.G, Ga, Gb, parts)));
+  BOND_DISPATCH(L.DP, (mps_bwd_fused_kernel<DP><<<1, MPS_THREADS, 0, st>>>(cores, n, D, DS, k, V, psi, hdr, g, cpart, qg.G, Ga, Gb, parts)));
   mps_finish_kernel<<<dim3((unsigned)n, (unsigned)((2 * D * D + 63) / 64)), MPS_THREADS, 0, st>>>(parts, n, D, grad_cores);
   return hipGetLastError();
 }

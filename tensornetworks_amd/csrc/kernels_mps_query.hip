@@ -243,9 +243,9 @@ hipError_t launch_mps_sample_clamped(int n, int D, long long B, const double* co
   mps_query_env_kernel<<<2, MS_ENV_THREADS, 0, st>>>(cores, n, D, 1, mask, value, pairs, (double*)(base + S.E), (int*)(base + S.eE));
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int DPV = ms_dp(D);
+  const int DPV = bond_dp(D);
   const unsigned grid = (unsigned)((B + MS_LANES - 1) / MS_LANES);
-  MS_DISPATCH(DPV, (mps_sample_clamped_kernel<DP><<<grid, MS_LANES, 0, st>>>(cores, n, D, B, (const double*)(base + S.E), pairs, mask,
+  BOND_DISPATCH(DPV, (mps_sample_clamped_kernel<DP><<<grid, MS_LANES, 0, st>>>(cores, n, D, B, (const double*)(base + S.E), pairs, mask,
                                                                              value, (uint32_t)seed, (uint32_t)(seed >> 32), epoch_dev,
                                                                              idx, logq, logm, status)));
   return hipGetLastError();

@@ -89,7 +89,7 @@ struct MsLayout {
 
 MsLayout ms_layout(int n, int D, long long B) {
   MsLayout S;
-  S.DP = ms_dp(D);
+  S.DP = bond_dp(D);
   S.DS = (D + 1) & ~1;
   const long long tiles = (B + MS_LANES - 1) / MS_LANES;
   S.G = (int)(tiles < MS_MAX_WG ? tiles : MS_MAX_WG);
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(MS_LANES) void mps_score_kernel(const double* __res
     const bool active = b < B;
     const unsigned long long z = active ? (unsigned long long)idx[b] : 0ull;
     const double wv = active ? wgt[b] : 0.0;
-    wacc += ms_wave_sum(wv);
+    wacc += wave_sum(wv);
     // right to left: r^_1 .. r^_{n-1} and their exponents into the slice
     double r[DP];
     const int er0 = ms_right_sweep<DP>(cores, n, D, z, As, r, MsSliceStore<DP>{rsl, esl, n, DS, lane});
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_score_finish_kernel(const 
   const int k = blockIdx.x + 1, t = threadIdx.x, DD = D * D;
   double wv = 0.0;
   for (int i = t; i < G; i += MS_ENV_THREADS) wv += wpart[i];
-  wv = ms_wave_sum(wv);
+  wv = wave_sum(wv);
   if ((t & 63) == 0) red[t >> 6] = wv;
   ms_env_stage(cores, k, D, E, L, As, Em, Lm, T);      // its barriers publish red too
   const double W = ((red[0] + red[1]) + red[2]) + red[3];
@@ -549,7 +549,7 @@ hipError_t launch_mps_sample(int n, int D, long long B, const double* cores, uns
   hipError_t e = launch_ms_clear_status(status, st);
   if (e != hipSuccess) return e;
   const unsigned grid = (unsigned)((B + MS_LANES - 1) / MS_LANES);
-  MS_DISPATCH(S.DP, (mps_sample_kernel<DP><<<grid, MS_LANES, 0, st>>>(cores, n, D, B, (const double*)(base + S.E),
+  BOND_DISPATCH(S.DP, (mps_sample_kernel<DP><<<grid, MS_LANES, 0, st>>>(cores, n, D, B, (const double*)(base + S.E),
                                                                       (const double*)(base + S.hdr), (uint32_t)seed,
                                                                       (uint32_t)(seed >> 32), epoch_dev, idx, logq, status)));
   return hipGetLastError();
@@ -562,7 +562,7 @@ hipError_t launch_mps_score_vjp(int n, int D, long long B, const double* cores, 
   hipError_t e = launch_ms_clear_status(status, st);
   if (e != hipSuccess) return e;
   const long long ntiles = (B + MS_LANES - 1) / MS_LANES;
-  MS_DISPATCH(S.DP, (mps_score_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
+  BOND_DISPATCH(S.DP, (mps_score_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
                         cores, n, D, S.DS, B, ntiles, idx, w, (const double*)(base + S.hdr), logq, status, (double*)(base + S.r),
                         (int*)(base + S.er), (double*)(base + S.parts), (double*)(base + S.wpart))));
   mps_score_finish_kernel<<<(unsigned)n, MS_ENV_THREADS, 0, st>>>(cores, n, D, S.G, (const double*)(base + S.parts),
@@ -582,7 +582,7 @@ hipError_t launch_mps_score_rows(int n, int D, long long B, const double* cores,
   const double* mu = nullptr;
   e = launch_mps_score_mu(n, D, B, cores, ws, &hdr, &mu, st);
   if (e != hipSuccess) return e;
-  MS_DISPATCH(S.DP, (mps_score_rows_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
+  BOND_DISPATCH(S.DP, (mps_score_rows_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(
                         cores, n, D, S.DS, B, ld / MS_LANES, idx, hdr, mu,
                         k_begin, k_count, ld, rows, status, (double*)(base + S.r), (int*)(base + S.er))));
   return hipGetLastError();
@@ -606,7 +606,7 @@ hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, 
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const long long ntiles = (B + MS_LANES - 1) / MS_LANES;
-  MS_DISPATCH(S.DP, (mps_score_jvp_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(cores, v, n, D, B, ntiles, idx, hdr, cpart, scale, t,
+  BOND_DISPATCH(S.DP, (mps_score_jvp_kernel<DP><<<(unsigned)S.G, MS_LANES, 0, st>>>(cores, v, n, D, B, ntiles, idx, hdr, cpart, scale, t,
                                                                                  status)));
   return hipGetLastError();
 }

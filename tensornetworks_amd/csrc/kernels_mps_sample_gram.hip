@@ -16,7 +16,7 @@
 //     v_mfma_f64_16x16x4_f64 takes as A and as B without a transpose.
 //     A sample that fails ms_amplitude_ok gets zero vectors, m_b = 0, alive = 0 and sets the status word to 2; so do the
 //     padding samples B .. 64 ceil(B / 64) - 1 (without the status).
-//   mps_gram_mu_norm_kernel: M, one workgroup; lane t squares the entries t, t + 256, ... in one fma chain, then ms_wave_sum
+//   mps_gram_mu_norm_kernel: M, one workgroup; lane t squares the entries t, t + 256, ... in one fma chain, then wave_sum
 //     over the 64 lanes and the four waves in order.
 //   mps_sample_gram_kernel: one wave per 32 x 32 tile on or above the diagonal (2 x 2 fragments).  Per site the wave forms the
 //     two dot-product tiles x . x' and r . r' of every fragment pair on the matrix cores (D4 / 4 steps each, components in
@@ -50,7 +50,7 @@ struct SgLayout {
 
 SgLayout sg_layout(int n, int D, long long B) {
   SgLayout S;
-  S.DP = ms_dp(D);
+  S.DP = bond_dp(D);
   S.D4 = (D + 3) & ~3;
   S.Bp = (B + SG_LANES - 1) / SG_LANES * SG_LANES;
   S.nfrag = (int)(S.Bp / SG_FRAG);
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(SG_NORM_THREADS) void mps_gram_mu_norm_kernel(const
   const int t = threadIdx.x;
   double acc = 0.0;
   for (int i = t; i < count; i += SG_NORM_THREADS) acc = fma(mu[i], mu[i], acc);
-  acc = ms_wave_sum(acc);
+  acc = wave_sum(acc);
   if ((t & 63) == 0) red[t >> 6] = acc;
   __syncthreads();
   if (t == 0) M[0] = ((red[0] + red[1]) + red[2]) + red[3];
@@ -271,7 +271,7 @@ hipError_t launch_mps_score_sample_gram(int n, int D, long long B, const double*
   if (e != hipSuccess) return e;
   double* xv = (double*)(base + S.x);
   double* rv = (double*)(base + S.r);
-  MS_DISPATCH(S.DP, (mps_gram_vectors_kernel<DP><<<(unsigned)(S.Bp / SG_LANES), SG_LANES, 0, st>>>(
+  BOND_DISPATCH(S.DP, (mps_gram_vectors_kernel<DP><<<(unsigned)(S.Bp / SG_LANES), SG_LANES, 0, st>>>(
                         cores, n, D, S.D4, B, S.Bp, idx, hdr, mu, xv, rv, (int*)(base + S.er), (double*)(base + S.m),
                         (int*)(base + S.alive), status)));
   e = hipGetLastError();

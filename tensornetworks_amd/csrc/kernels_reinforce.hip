@@ -19,8 +19,8 @@
 // no sample hit cost no store.  Adds go through a small per-workgroup LDS table first (a peaked q puts most samples of
 // a workgroup on a few outcomes: they become one global add each); what does not find a slot is added directly.
 //
-// The mean is a two-level float64 sum in a fixed order over sample positions (per-workgroup partials in the workspace,
-// reduced by every workgroup of the next kernel in the same order): bitwise repeatable; permuting the samples changes
+// The mean is a two-level float64 sum in the fixed order of reduce_dev.hpp over sample positions (per-workgroup partials in
+// the workspace, reduced by every workgroup of the next kernel in the same order): bitwise repeatable; permuting the samples changes
 // its last bits.  A non-finite raw_b (log_p may hold +-inf) makes mean and baseline non-finite as in the reference;
 // no add is made then, dLdq is all zeros, loss = NaN and found_inf = 1.
 #include <hip/hip_runtime.h>
@@ -28,6 +28,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -39,19 +40,7 @@ constexpr long long RF_OUTCOMES_PER_WG = 4096;  // target outcomes per workgroup
 constexpr long long RF_MAX_WG = 1024;           // partials per level at most
 constexpr int RF_SLOT_BITS = 10, RF_SLOTS = 1 << RF_SLOT_BITS;   // LDS pre-aggregation table of a workgroup
 
-struct RfGeom {
-  long long chunk;
-  int G;
-};
-
-RfGeom rf_geom(long long count, long long per_wg) {
-  long long G = (count + per_wg - 1) / per_wg;
-  if (G > RF_MAX_WG) G = RF_MAX_WG;
-  if (G < 1) G = 1;
-  const long long chunk = (count + G - 1) / G;
-  G = (count + chunk - 1) / chunk;
-  return {chunk, (int)G};
-}
+ChunkGeom rf_geom(long long count, long long per_wg) { return chunk_geom(count, per_wg, RF_MAX_WG, 1); }
 
 // scalars handed from kernel to kernel through the workspace
 struct RfScalars {
@@ -60,41 +49,6 @@ struct RfScalars {
   double inv_scale;   // 2^-e
   int bad;            // 1: a weight is not finite (no adds were made)
 };
-
-__device__ __forceinline__ double rf_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// Block sum, fixed order: butterfly within each wave, then the wave totals in order.  Every thread gets the result.
-__device__ __forceinline__ double rf_block_sum(double v, double* lds) {
-  v = rf_wave_sum(v);
-  const int t = threadIdx.x;
-  __syncthreads();
-  if ((t & 63) == 0) lds[t >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-#pragma unroll
-  for (int i = 0; i < RF_WAVES; ++i) tot += lds[i];
-  return tot;
-}
-
-// max that keeps a NaN (fmax would drop it)
-__device__ __forceinline__ double rf_max(double a, double b) { return (a != a || b != b) ? NAN : (a > b ? a : b); }
-
-__device__ __forceinline__ double rf_block_max(double v, double* lds) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = rf_max(v, __shfl_xor(v, off));
-  const int t = threadIdx.x;
-  __syncthreads();
-  if ((t & 63) == 0) lds[t >> 6] = v;
-  __syncthreads();
-  double m = 0.0;
-#pragma unroll
-  for (int i = 0; i < RF_WAVES; ++i) m = rf_max(m, lds[i]);
-  return m;
-}
 
 // raw reward of sample b; 0 for an index outside the table (never dereferenced: "no sample")
 __device__ __forceinline__ double raw_reward(const long long* __restrict__ idx, const float* __restrict__ logit,
@@ -125,10 +79,10 @@ __global__ __launch_bounds__(RF_THREADS) void reinforce_stats_kernel(const long 
     long long i;
     const double r = raw_reward(idx, logit, log_p, N, b, i);
     s += r;
-    m = rf_max(m, fabs(r));
+    m = max_nan(m, fabs(r));
   }
-  s = rf_block_sum(s, lds);
-  m = rf_block_max(m, lds);
+  s = block_sum<RF_WAVES>(s, lds);
+  m = block_max_nan<RF_WAVES>(m, lds);
   if (threadIdx.x == 0) {
     part[2 * g] = s;
     part[2 * g + 1] = m;
@@ -156,10 +110,10 @@ __global__ __launch_bounds__(RF_THREADS) void reinforce_scatter_kernel(const lon
   double s = 0.0, m = 0.0;
   for (int k = t; k < G; k += RF_THREADS) {
     s += part[2 * k];
-    m = rf_max(m, part[2 * k + 1]);
+    m = max_nan(m, part[2 * k + 1]);
   }
-  s = rf_block_sum(s, lds);
-  m = rf_block_max(m, lds);      // (its barriers also publish the cleared table)
+  s = block_sum<RF_WAVES>(s, lds);
+  m = block_max_nan<RF_WAVES>(m, lds);      // (its barriers also publish the cleared table)
   const double mean = s / (double)B;
   const double base = first ? mean : decay * baseline[0] + (1.0 - decay) * mean;
   const double W = m + fabs(base) + fabs(coef);
@@ -218,7 +172,7 @@ __global__ __launch_bounds__(RF_THREADS) void reinforce_finish_kernel(const floa
     // the clamp passes no gradient below the floor
     acc[i] = __double_as_longlong((q >= q_floor || q != q) ? s / (Bd * (double)q) : 0.0);
   }
-  l = rf_block_sum(l, lds);
+  l = block_sum<RF_WAVES>(l, lds);
   if (threadIdx.x == 0) lpart[g] = l;
 }
 
@@ -228,9 +182,7 @@ __global__ __launch_bounds__(RF_THREADS) void reinforce_loss_kernel(const double
                                                                     double* __restrict__ baseline, float* __restrict__ loss,
                                                                     float* __restrict__ found_inf) {
   __shared__ double lds[RF_WAVES];
-  double l = 0.0;
-  for (int k = threadIdx.x; k < Gz; k += RF_THREADS) l += lpart[k];
-  l = rf_block_sum(l, lds);
+  const double l = sum_partials<RF_THREADS>(lpart, Gz, lds);
   if (threadIdx.x == 0) {
     const float lf = sc->bad ? NAN : (float)(l / (double)B);
     loss[0] = lf;
@@ -242,7 +194,7 @@ __global__ __launch_bounds__(RF_THREADS) void reinforce_loss_kernel(const double
 }  // namespace
 
 size_t reinforce_workspace_bytes(int n, long long B) {
-  const RfGeom gs = rf_geom(B, RF_SAMPLES_PER_WG), gz = rf_geom(1ll << n, RF_OUTCOMES_PER_WG);
+  const ChunkGeom gs = rf_geom(B, RF_SAMPLES_PER_WG), gz = rf_geom(1ll << n, RF_OUTCOMES_PER_WG);
   return 256 + (size_t)(2 * gs.G + gz.G) * sizeof(double) + 512;
 }
 
@@ -250,7 +202,7 @@ hipError_t launch_reinforce_step(int n, long long B, const long long* idx, const
                                  const float* q32, double* baseline, int first, double decay, double coef, double q_floor,
                                  double* dLdq, float* loss, float* found_inf, void* ws, hipStream_t st) {
   const long long N = 1ll << n;
-  const RfGeom gs = rf_geom(B, RF_SAMPLES_PER_WG), gz = rf_geom(N, RF_OUTCOMES_PER_WG);
+  const ChunkGeom gs = rf_geom(B, RF_SAMPLES_PER_WG), gz = rf_geom(N, RF_OUTCOMES_PER_WG);
   char* w = ws_align(ws);
   RfScalars* sc = (RfScalars*)w;
   double* part = (double*)(w + 256);

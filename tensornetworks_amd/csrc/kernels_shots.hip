@@ -26,6 +26,7 @@
 
 #include "kernels.hpp"
 #include "philox_dev.hpp"
+#include "reduce_dev.hpp"
 #include "shots_dev.hpp"
 
 namespace bornvi {
@@ -55,8 +56,7 @@ __global__ __launch_bounds__(SM_THREADS) void shots_mass_kernel(const double* __
   double s = 0.0;
 #pragma unroll
   for (int i = 0; i < SM_EPT; ++i) s += p[t + i * SM_THREADS];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  s = wave_sum(s);
   if ((t & 63) == 0) part[t >> 6] = s;
   __syncthreads();
   if (t == 0) {

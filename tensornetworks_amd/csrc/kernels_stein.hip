@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -453,12 +454,6 @@ hipError_t launch_kp_pairs(int n, double length_scale, long long M, const long l
 // ------------------------------------------------------------------------------------------------
 constexpr int QF_ROWS = 4;
 constexpr int QF_WAVES = 4;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(64 * QF_WAVES) void quadform_kernel(const double* __restrict__ K, const double* __restrict__ q,
                                                                  double* __restrict__ y, double* __restrict__ partials, long long N,

@@ -1,7 +1,9 @@
 // The sampled-MPS kernels' one definition of their site sweeps (kernels_mps_sample.hip, kernels_mps_sample_gram.hip), so that
 // l^, r^, their exponents and mu are the same bits in every kernel because they are the same code.
 //
-// Vectors: one sample per lane, DP doubles (DP = ms_dp(D) = 2, 4, 8, 16, 32 >= D, zero padded) in registers; a site's matrices
+// Wave sums and maxima, the padded bond dimension and its dispatch macro come from reduce_dev.hpp.
+//
+// Vectors: one sample per lane, DP doubles (DP = bond_dp(D) = 2, 4, 8, 16, 32 >= D, zero padded) in registers; a site's matrices
 //   A_k[0], A_k[1] zero-padded to DP x DP in LDS (ms_load_site) and read as broadcasts.  z_k is bit n - k of the index word.
 // Products: an entry of x A (ms_row_dot) or of A r (ms_dot_col) is one fma chain in index order that continues from the
 //   accumulator it is given; the left and right steps are built on them.  Two kernels write this chain out themselves,
@@ -32,6 +34,7 @@
 #include <cmath>
 
 #include "philox_dev.hpp"
+#include "reduce_dev.hpp"
 
 namespace bornvi {
 
@@ -39,29 +42,6 @@ constexpr int MS_LANES = 64;               // sampler, score and Gram-vector ker
 constexpr int MS_ENV_THREADS = 256;        // environment kernels: one workgroup per site (or per direction)
 constexpr int MS_DMAX = 32;
 constexpr double MS_LN2 = 0.693147180559945309417232121458;
-
-inline int ms_dp(int D) { return D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
-
-#define MS_DISPATCH(DPV, CALL)                        \
-  switch (DPV) {                                      \
-    case 2: { constexpr int DP = 2; CALL; } break;    \
-    case 4: { constexpr int DP = 4; CALL; } break;    \
-    case 8: { constexpr int DP = 8; CALL; } break;    \
-    case 16: { constexpr int DP = 16; CALL; } break;  \
-    default: { constexpr int DP = 32; CALL; } break;  \
-  }
-
-__device__ __forceinline__ double ms_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-__device__ __forceinline__ double ms_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
 
 // exponent of the exact power-of-two rescaling: ilogb of a positive finite largest magnitude, else 0 (nothing to rescale)
 __device__ __forceinline__ int ms_exponent(double mx) { return (mx > 0.0 && isfinite(mx)) ? ilogb(mx) : 0; }
@@ -225,7 +205,7 @@ __device__ __forceinline__ int ms_env_step(bool right, int D, int allowed, const
       mx = fmax(mx, fabs(acc));
     }
   }
-  mx = ms_wave_max(mx);
+  mx = wave_max(mx);
   if ((t & 63) == 0) red[t >> 6] = mx;
   __syncthreads();
   mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
