@@ -597,6 +597,38 @@ int bornvi_mps_sample_clamped(bornvi_handle h, int n, int D, long long B, const 
 int bornvi_mps_marginals(bornvi_handle h, int n, int D, const double* cores, double* m1, double* m2, void* workspace,
                          size_t workspace_bytes, bornvi_stream stream);
 
+/* ---- amortised inference: draws from the network, and the gradient of log-marginals.
+ * bornvi_bn_sample: B exact ancestral draws from the network itself.  role[v] is the tuple position 0 .. n - 1 of node v in
+ * the output word (each position taken once) or -3: such a node is drawn, because its children need it, and dropped.
+ * Observed roles (-1, -2) and a node listed before one of its parents (a parent index not below the node's own) are
+ * BORNVI_ERR_UNSUPPORTED: role, n_parents and parents are read back from the device for that, except while `stream` is being
+ * captured, where the kernel writes NaN to logp and 1 to status instead.  Node v of sample b takes
+ *   bit = U (t0 + t1) >= t0,  t_s = CPT_v[parents][s] as stored
+ * (a value of probability 0 is never drawn), U the 53-bit uniform of Philox4x32-10 with counter (b, v >> 1, 0xfffffffe,
+ * *epoch_dev) and key seed, even v the words (x, y), odd v (z, w): a sample depends on (network, seed, epoch, b) only, not on
+ * B.  idx dev [B] int64: the kept nodes' bits, tuple position p at bit n - 1 - p.  logp dev [B] float64: the sum over all V
+ * nodes, in descriptor order, of log of the chosen factor, unfloored; with no dropped node and every factor >= p_floor it is
+ * bit for bit what bornvi_bn_logjoint_samples writes for idx.  status dev [1] int32: 0, or 1 when some sample met a row whose
+ * t0 + t1 is not positive and finite (its logp is NaN, its remaining bits 0).  1 <= n <= 63, 1 <= B <= 2^24, else
+ * BORNVI_ERR_UNSUPPORTED before any launch.  No allocation, no synchronisation outside the descriptor check: capturable. */
+int bornvi_bn_sample(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, unsigned long long seed,
+                     const long long* epoch_dev, long long* idx, double* logp, int* status, bornvi_stream stream);
+/* bornvi_mps_log_marginals_vjp: grad_cores dev [n, 2, D, D] = sum_j c_j grad log q(evidence_j), c dev [Q] float64, the
+ * evidences as for bornvi_mps_log_marginals, and logm dev [Q]: bit for bit what that call returns for the same queries.
+ *   log q(e_j) = log m_j - log Z,  d m_j / d A_k[s] = 2 L^(j)_{k-1} A_k[s] E^(j)_k for s allowed at site k, 0 otherwise,
+ * L^(j) the clamped left environments; minus (sum_j c_j) times the same expression of the empty mask.  G workgroups (the
+ * geometry call: a function of Q only) take the queries g, g + G, ... in order and add each query's term into their own
+ * partial in the workspace; one more takes the empty mask; a finishing launch adds the G partials in order: no atomics,
+ * two calls are bitwise equal, a query's logm depends neither on Q nor on its slot.  An evidence whose mass is 0 or not
+ * finite contributes nothing (its weight stays out of sum_j c_j too), gets logm -inf or NaN and sets status (dev [1] int32)
+ * to 1, else 0.  1 <= n <= 63, 1 <= D <= 32, 1 <= Q <= 2^16; anything else, a short workspace included, is
+ * BORNVI_ERR_UNSUPPORTED before any launch.  No allocation or synchronisation (capturable). */
+size_t bornvi_mps_log_marginals_vjp_workspace_bytes(bornvi_handle h, int n, int D, int Q);
+int bornvi_mps_log_marginals_vjp_geometry(int Q, int* G);
+int bornvi_mps_log_marginals_vjp(bornvi_handle h, int n, int D, int Q, const double* cores, const long long* mask,
+                                 const long long* value, const double* c, double* grad_cores, double* logm, int* status,
+                                 void* workspace, size_t workspace_bytes, bornvi_stream stream);
+
 /* The conjugate-gradient recurrence for (F + damping I) x = g, the product F p left to the caller between the calls; every
  * vector dev [P] float64, state dev [8] float64 (rr = r^T r, rr0 = g^T g, iterations done, done flag, relres = sqrt(rr / rr0),
  * fallback flag, two spare words).  One workgroup each; every dot product is a fixed-order reduction, so two solves are

@@ -9,7 +9,7 @@ __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachin
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
            "SampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
            "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "CGFisherPreconditioner",
-           "generate_all_binary_outcomes", "calculate_tvd"]
+           "AmortisedMPSInference", "generate_all_binary_outcomes", "calculate_tvd"]
 
 
 def __getattr__(name):
@@ -55,4 +55,7 @@ def __getattr__(name):
     if name == "CGFisherPreconditioner":
         from .natural_gradient import CGFisherPreconditioner
         return CGFisherPreconditioner
+    if name == "AmortisedMPSInference":
+        from .amortised_vi_sampled import AmortisedMPSInference
+        return AmortisedMPSInference
     raise AttributeError(name)

@@ -830,6 +830,70 @@ def bn_logjoint_samples(desc, n, idx, p_floor=1e-30, out=None):
     return out
 
 
+# ---- amortised inference: draws from the network, gradient of log-marginals -------------------
+def bn_sample(desc, n, num_samples, seed, epoch, out_idx=None, out_logp=None, status=None):
+    """Exact ancestral draws from the network (bornvi_bn_sample): desc from bn_descriptor of
+    bayesian_network.pack_network_for_sampling's dict, epoch an int64 device tensor [1] -> (idx int64 [B]: the kept nodes'
+    bits, tuple position p at bit n - 1 - p, logp float64 [B] = log p of the whole draw, dropped nodes included, status
+    int32 [1]: 0, or 1 when a sample met a CPT row whose sum is not positive and finite).  A draw is a pure function of
+    (network, seed, epoch, b)."""
+    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
+    B = num_samples
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MPS_SAMPLED_MAX_BATCH:
+        raise BornviError(f"number of samples: 1 ... 2^24 per call, got {B!r}")
+    B = int(B)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise BornviError(f"seed must be an integer, got {seed!r}")
+    if not torch.is_tensor(epoch):
+        raise BornviError("epoch: expected an int64 device tensor [1]")
+    dev = epoch.device
+    h = _ext.handle_for(dev)
+    _chk(epoch, torch.int64, dev, "epoch", 1)
+    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
+    out_logp = _out(out_logp, torch.float64, dev, "out_logp", B)
+    status = _out(status, torch.int32, dev, "status", 1)
+    h.call("bornvi_bn_sample", C.byref(desc), int(n), B, int(seed) & ((1 << 64) - 1), _ptr(epoch), _ptr(out_idx), _ptr(out_logp),
+           _ptr(status), _ext.stream_ptr(dev))
+    return out_idx, out_logp, status
+
+
+def mps_log_marginals_vjp_groups(Q):
+    """The workgroups that take queries in mps_log_marginals_vjp = the partials per gradient entry: a function of Q only."""
+    G = C.c_int(0)
+    if _ext.lib().bornvi_mps_log_marginals_vjp_geometry(int(Q), C.byref(G)) != 0:
+        raise BornviError(f"number of queries: 1 ... 2^16 per call, got {Q}")
+    return int(G.value)
+
+
+def mps_log_marginals_vjp(cores, mask, value, c, out=None, out_logm=None, status=None):
+    """Gradient of weighted log-marginals of an MPS Born machine (bornvi_mps_log_marginals_vjp): mask, value int64 [Q] as
+    for mps_log_marginals, c float64 [Q] -> (grad float64 [n, 2, D, D] = sum_j c_j grad log q(evidence_j), logm float64
+    [Q]: mps_log_marginals' bits, status int32 [1]: 0, or 1 when some evidence is impossible or met a non-finite
+    environment; such an evidence contributes nothing).  Needs no mps_environments."""
+    n, D, _ = _mps_args(cores, 1)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    if not torch.is_tensor(mask) or not torch.is_tensor(value) or mask.dim() != 1 or mask.shape != value.shape:
+        raise BornviError("mask, value: expected two [Q] int64 tensors")
+    Q = int(mask.numel())
+    if not 1 <= Q <= MPS_QUERY_MAX_QUERIES:
+        raise BornviError(f"number of queries: 1 ... 2^16 per call, got {Q}")
+    _chk(mask, torch.int64, dev, "mask", Q)
+    _chk(value, torch.int64, dev, "value", Q)
+    _chk(c, torch.float64, dev, "c", Q)
+    if out is None:
+        out = torch.empty(cores.shape, dtype=torch.float64, device=dev)
+    else:
+        _chk(out, torch.float64, dev, "out", cores.numel())
+    out_logm = _out(out_logm, torch.float64, dev, "out_logm", Q)
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _ws(dev, _cached_size(h, "bornvi_mps_log_marginals_vjp_workspace_bytes", n, D, Q), f"mps_logm_vjp_{n}_{D}_{Q}")
+    h.call("bornvi_mps_log_marginals_vjp", n, D, Q, _ptr(cores), _ptr(mask), _ptr(value), _ptr(c), _ptr(out), _ptr(out_logm),
+           _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out, out_logm, status
+
+
 # ---- sampled KSD: scores of p at sampled states, pairwise Stein kernel row sums -----------------------------
 STEIN_PAIRS_MAX_BATCH = 1 << 17
 

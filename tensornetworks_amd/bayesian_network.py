@@ -204,3 +204,46 @@ def pack_network(bn, latent_names, x_dict):
             flat.extend([float(row[0]), float(row[1])])
     return {"role": role, "n_parents": n_par, "parents": par, "cpt_off": off,
             "cpt": np.asarray(flat, np.float64)}
+
+
+def pack_network_for_sampling(bn, site_names):
+    """``pack_network``'s arrays for ``bornvi_bn_sample``, the ancestral sampler of the network itself: ``role[v]`` is the
+    tuple position of node v in ``site_names`` (position 0 = MSB of the outcome index) or ROLE_HIDDEN: such a node is drawn,
+    because its children need it, and dropped from the sample.  Nothing is observed.  The nodes must be in topological
+    order (every parent listed before its child), names of ``site_names`` must be nodes and must not repeat; every error is
+    a ValueError raised here, on the host."""
+    site_names = list(site_names)
+    if len(set(site_names)) != len(site_names):
+        raise ValueError(f"site_names: a name is repeated in {site_names}")
+    index = {nm: i for i, nm in enumerate(bn.nodes)}
+    for nm in site_names:
+        if nm not in index:
+            raise ValueError(f"site_names: {nm!r} is not a node of the network")
+    if not 1 <= len(site_names) <= 63:
+        raise ValueError(f"site_names: 1 ... 63 names, got {len(site_names)}")
+    if len(bn.nodes) > 64:
+        raise ValueError(f"the sampler takes networks of at most 64 nodes, got {len(bn.nodes)}")
+    for nm in bn.nodes:
+        for p in (bn.parents[nm] if nm in bn.parents else []):
+            if p not in index:
+                raise ValueError(f"parent {p!r} of node {nm!r} is not a node of the network")
+            if index[p] >= index[nm]:
+                raise ValueError(f"node {nm!r} is listed before its parent {p!r}: the sampler needs topological order")
+    packed = pack_network(bn, site_names, {})
+    check_sampling_pack(packed, len(site_names))
+    return packed
+
+
+def check_sampling_pack(packed, n):
+    """What ``bornvi_bn_sample`` asks of a packed network, checked on the host: roles 0 .. n - 1, each once, or ROLE_HIDDEN
+    (an observed role is refused), and every parent index below the node's own.  Raises ValueError."""
+    role, n_par, par = packed["role"], packed["n_parents"], packed["parents"]
+    if ((role == ROLE_OBSERVED0) | (role == ROLE_OBSERVED1)).any():
+        raise ValueError("an observed node (role -1 or -2) cannot be drawn: give it a tuple position or ROLE_HIDDEN")
+    kept = role[role != ROLE_HIDDEN]
+    if sorted(kept.tolist()) != list(range(n)):
+        raise ValueError(f"roles must be the tuple positions 0 ... {n - 1}, each once, or ROLE_HIDDEN; got {role.tolist()}")
+    for v in range(len(role)):
+        for p in par[v, :n_par[v]]:
+            if not 0 <= int(p) < v:
+                raise ValueError(f"node {v} has parent index {int(p)}: the sampler needs every parent index below the node's own")

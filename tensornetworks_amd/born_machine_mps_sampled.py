@@ -110,6 +110,18 @@ class SampledMPSBornMachine(MPSCores, nn.Module):
         mask, value = self._evidence(evidence)
         return backend.mps_log_marginals(self.kernel_input()[0], mask, value)[0]
 
+    def log_marginal_vjp(self, evidence, weights):
+        """(grad float64 [n, 2, D, D] = sum_j weights_j grad log q(evidence_j), logm float64 [Q]) on the compute device: the
+        counterpart of score_vjp for partial assignments.  evidence as log_marginal takes it; an
+        impossible evidence contributes nothing and has logm -inf."""
+        mask, value = self._evidence(evidence)
+        cores, _ = self.kernel_input()
+        if not torch.is_tensor(weights) or weights.numel() != mask.numel():
+            raise ValueError(f"weights: a tensor of {mask.numel()} numbers, one per evidence")
+        w = weights.reshape(-1).to(device=cores.device, dtype=torch.float64).contiguous()
+        grad, logm, _ = backend.mps_log_marginals_vjp(cores, mask, value, w)
+        return grad, logm
+
     def sample_given(self, evidence, num_samples, seed=None, epoch=0):
         """(idx int64 [num], logq_cond float64 [num] = log q(idx | evidence), log_marginal float64 [1] of the evidence):
         exact draws from q(. | evidence).  A pure function of (cores, evidence, seed, epoch); a free position gets the

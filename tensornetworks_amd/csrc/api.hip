@@ -888,6 +888,53 @@ int bornvi_bn_score_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, lo
   return BORNVI_OK;
 }
 
+// The descriptor checks of bornvi_bn_sample, with the same read-back: every role a tuple position 0 .. n - 1, each taken once,
+// or -3 (drawn and dropped); an observed role and a node listed before one of its parents are refused as unsupported.
+static int check_sampling_descriptor(bornvi_handle h, const bornvi_bn_desc* bn, int n, bornvi_stream stream) {
+  if (bn->num_nodes < 1 || bn->num_nodes > 64 || bn->max_parents < 1 || bn->max_parents > 64 || !bn->role || !bn->n_parents ||
+      !bn->parents || !bn->cpt_off || !bn->cpt)
+    return fail(h, BORNVI_ERR_INVALID, "bad network descriptor");
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+  if (cap != hipStreamCaptureStatusNone) return BORNVI_OK;
+  const int V = bn->num_nodes, P = bn->max_parents;
+  int32_t role[64], npar[64];
+  std::vector<int32_t> par((size_t)V * P);
+  HIPCHK(h, hipMemcpy(role, bn->role, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(npar, bn->n_parents, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(par.data(), bn->parents, sizeof(int32_t) * V * P, hipMemcpyDeviceToHost));
+  unsigned long long seen = 0;
+  for (int v = 0; v < V; ++v) {
+    if (role[v] == -1 || role[v] == -2)
+      return fail(h, BORNVI_ERR_UNSUPPORTED, "an observed node (role -1, -2) cannot be drawn: give it a tuple position or role -3");
+    if (role[v] != -3) {
+      if (role[v] < 0 || role[v] >= n || ((seen >> role[v]) & 1ull))
+        return fail(h, BORNVI_ERR_INVALID, "bad network descriptor: role out of range or tuple position taken twice");
+      seen |= 1ull << role[v];
+    }
+    if (npar[v] < 0 || npar[v] > P) return fail(h, BORNVI_ERR_INVALID, "bad network descriptor: parent count out of range");
+    for (int p = 0; p < npar[v]; ++p) {
+      const int pa = par[(size_t)v * P + p];
+      if (pa < 0 || pa >= V) return fail(h, BORNVI_ERR_INVALID, "bad network descriptor: parent index out of range");
+      if (pa >= v) return fail(h, BORNVI_ERR_UNSUPPORTED, "nodes must be in topological order: every parent index below the node's own");
+    }
+  }
+  if (seen != (n == 64 ? ~0ull : (1ull << n) - 1ull))
+    return fail(h, BORNVI_ERR_INVALID, "bad network descriptor: a tuple position 0 .. n - 1 has no node");
+  return BORNVI_OK;
+}
+
+int bornvi_bn_sample(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, unsigned long long seed,
+                     const long long* epoch_dev, long long* idx, double* logp, int* status, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
+  if (!bn || !epoch_dev || !idx || !logp || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  DEVICE_SCOPE(h);
+  if (int rc = check_sampling_descriptor(h, bn, n, stream)) return rc;
+  HIPCHK(h, launch_bn_sample(*bn, n, B, seed, epoch_dev, idx, logp, status, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 static bool stein_pairs_supported(int n, long long B, double length_scale) {
   return n >= 1 && n <= 63 && B >= 2 && B <= STEIN_PAIRS_MAX_B && std::isfinite(length_scale) && (double)n * length_scale >= 1.0;
 }
@@ -1364,6 +1411,33 @@ int bornvi_mps_log_marginals(bornvi_handle h, int n, int D, int Q, const double*
   if (!workspace || workspace_bytes < mps_query_workspace_bytes(n, D, Q)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_mps_log_marginals(n, D, Q, cores, mask, value, logm, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+size_t bornvi_mps_log_marginals_vjp_workspace_bytes(bornvi_handle h, int n, int D, int Q) {
+  if (!h) return 0;
+  if (!valid_mps_query(n, D, Q)) { fail(h, BORNVI_ERR_UNSUPPORTED, MPS_QUERY_RANGE); return 0; }
+  return mps_log_marginals_vjp_workspace_bytes(n, D, Q);
+}
+
+int bornvi_mps_log_marginals_vjp_geometry(int Q, int* G) {
+  if (!G) return BORNVI_ERR_INVALID;
+  if (Q < 1 || Q > MPS_QUERY_MAX_Q) return BORNVI_ERR_UNSUPPORTED;
+  *G = mps_log_marginals_vjp_groups(Q);
+  return BORNVI_OK;
+}
+
+int bornvi_mps_log_marginals_vjp(bornvi_handle h, int n, int D, int Q, const double* cores, const long long* mask,
+                                 const long long* value, const double* c, double* grad_cores, double* logm, int* status,
+                                 void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_query(n, D, Q)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_QUERY_RANGE);
+  if (!cores || !mask || !value || !c || !grad_cores || !logm || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!workspace || workspace_bytes < mps_log_marginals_vjp_workspace_bytes(n, D, Q))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_log_marginals_vjp(n, D, Q, cores, mask, value, c, grad_cores, logm, status, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

@@ -71,6 +71,9 @@ RESOURCE_BUDGET = {
     "mps_query_logm_kernel": (0, 0),              # sampler's own code, so their budgets
     "mps_sample_clamped_kernel": (0, 0),
     "mps_marginals_kernel": (0, 0),
+    "mps_logm_vjp_kernel": (0, 0),                # gradient of log-marginals: the environment step's code in both directions
+    "mps_logm_vjp_finish_kernel": (0, 0),
+    "bn_sample_kernel": (0, 0),                   # ancestral draws from the network: the node values are one 64-bit register
     "cg_init_kernel": (0, 0),                     # the CG recurrence (kernels_cg.hip)
     "cg_step_kernel": (0, 0),
     "cg_finish_kernel": (0, 0),

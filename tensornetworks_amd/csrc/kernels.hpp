@@ -124,6 +124,8 @@ hipError_t launch_mps_score_jvp(int n, int D, long long B, const double* cores, 
                                 double* t, int* status, void* ws, hipStream_t st);
 hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
                                       hipStream_t st);
+hipError_t launch_bn_sample(const bornvi_bn_desc& bn, int n, long long B, unsigned long long seed, const long long* epoch_dev,
+                            long long* idx, double* logp, int* status, hipStream_t st);
 
 // ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip): log-marginals, clamped sampler, marginals ----
 constexpr int MPS_QUERY_MAX_Q = 1 << 16;
@@ -134,6 +136,11 @@ hipError_t launch_mps_sample_clamped(int n, int D, long long B, const double* co
                                      unsigned long long seed, const long long* epoch_dev, long long* idx, double* logq, double* logm,
                                      int* status, void* ws, hipStream_t st);
 hipError_t launch_mps_marginals(int n, int D, const double* cores, double* m1, double* m2, void* ws, hipStream_t st);
+// the gradient of weighted log-marginals: groups = the workgroups that take queries = the partials per entry
+size_t mps_log_marginals_vjp_workspace_bytes(int n, int D, int Q);
+int mps_log_marginals_vjp_groups(int Q);
+hipError_t launch_mps_log_marginals_vjp(int n, int D, int Q, const double* cores, const long long* mask, const long long* value,
+                                        const double* c, double* grad, double* logm, int* status, void* ws, hipStream_t st);
 
 // ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
 constexpr int CG_STATE_DOUBLES = 8;      // rr, rr0, iterations, done, relres, fallback, 2 spare

@@ -28,6 +28,8 @@
 //   one ldexp.  mq_inner: T = A[1] E and G = T A[1]^T as D-term fma chains through LDS, then per row a the chain
 //   sum_b X[a][b] G[a][b] and the rows added in order.  m2[j][i] is stored from the value of m2[i][j] and m2[i][i] from m1[i].
 //
+// bornvi_mps_log_marginals_vjp: the gradient of weighted log-marginals, stated above its kernels below.
+//
 // No atomics, no allocation, no synchronisation: capturable, and two calls are bitwise equal.
 #include <hip/hip_runtime.h>
 
@@ -214,7 +216,165 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_marginals_kernel(const dou
   }
 }
 
+// ---- gradient of weighted log-marginals -----------------------------------------------------
+// grad = sum_j c_j grad log q(evidence_j),  log q(e_j) = log m_j - log Z,  m_j = E^(j)_0[0, 0],
+//   d m_j / d A_k[s] = 2 L^(j)_{k-1} A_k[s] E^(j)_k  for s allowed at site k, 0 for a disallowed s,
+// L^(j) the clamped LEFT environments (L_0 = e0 e0^T, L_k = sum_{s allowed} A_k[s]^T L_{k-1} A_k[s]); minus (sum_j c_j) times
+// the same expression of the empty mask (Z is the empty evidence's mass).
+//
+// mps_logm_vjp_kernel, grid G + 1 of MS_ENV_THREADS: workgroup g < G = min(Q, MQ_VJP_MAX_WG) takes the queries g, g + G, ... in
+// that order, workgroup G the empty mask with weight 1.  Per query:
+//   right sweep: mps_query_env_kernel's loop (ms_env_step, right), the stack E^^(j)_k, k = n .. 0, into the workgroup's own
+//     slot of the workspace and its exponents into LDS; the pair (E^^(j)_0[0, 0], e_j) into the pair table, so that logm comes
+//     out of mps_query_logm_kernel bit for bit as bornvi_mps_log_marginals gives it;
+//   left sweep, k = 1 .. n, L^ in LDS:  T_s = A_s E^^_k, M_s = L^_{k-1} T_s (ms_env_stage's and ms_env_entry's fma chains, in
+//     index order) for the allowed s; the entry is M_s (c_j / E^^(j)_0[0, 0]) 2^(eL + eE[k] - e_j), doubled, and is added to the
+//     workgroup's own partial [n, 2, D, D]: entry i of a site always by thread i mod MS_ENV_THREADS, so no atomics and no barrier
+//     guard it; then ms_env_step (left) with the same allowed set.
+//   A query whose mass is not positive and finite, or whose weight is 0.0, takes no left sweep and adds nothing, and an
+//   impossible one's weight stays out of the workgroup's weight sum.
+// mps_logm_vjp_finish_kernel: per entry the partials of workgroups 0 .. G - 1 in order, minus W times the empty mask's entry,
+//   W the workgroups' weight sums by sum_partials.
+constexpr int MQ_VJP_MAX_WG = 256;      // one per compute unit of the MI355X
+
+__host__ __device__ inline int mq_vjp_groups(int Q) { return Q < MQ_VJP_MAX_WG ? Q : MQ_VJP_MAX_WG; }
+
+struct MqVjpLayout {
+  size_t parts, stacks, wpart, pairs, total;
+  int G;
+};
+
+MqVjpLayout mq_vjp_layout(int n, int D, int Q) {
+  MqVjpLayout S;
+  S.G = mq_vjp_groups(Q);
+  size_t o = 0;
+  S.parts = o;  o += ws_round((size_t)(S.G + 1) * n * 2 * D * D * sizeof(double));     // slot G: the empty mask's term
+  S.stacks = o; o += ws_round((size_t)(S.G + 1) * (n + 1) * D * D * sizeof(double));
+  S.wpart = o;  o += ws_round((size_t)(S.G + 1) * sizeof(double));
+  S.pairs = o;  o += ws_round((size_t)(Q + 1) * 2 * sizeof(double));
+  S.total = o;
+  return S;
+}
+
+__global__ __launch_bounds__(MS_ENV_THREADS) void mps_logm_vjp_kernel(const double* __restrict__ cores, int n, int D, int Q, int G,
+                                                                   const long long* __restrict__ mask,
+                                                                   const long long* __restrict__ value,
+                                                                   const double* __restrict__ c, double* __restrict__ pairs,
+                                                                   double* parts, double* stacks, double* __restrict__ wpart) {
+  __shared__ double As[2 * MS_DMAX * MS_DMAX];
+  __shared__ double X[MS_DMAX * MS_DMAX];
+  __shared__ double Em[MS_DMAX * MS_DMAX];
+  __shared__ double T[2 * MS_DMAX * MS_DMAX];
+  __shared__ double red[MS_ENV_THREADS / 64];
+  __shared__ int eEs[64];
+  const int g = blockIdx.x, DD = D * D, t = threadIdx.x;
+  double* part = parts + (size_t)g * n * 2 * DD;
+  double* stack = stacks + (size_t)g * (n + 1) * DD;
+  for (int k = 0; k < n; ++k)
+    for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) part[(size_t)k * 2 * DD + i] = 0.0;
+  double wsum = 0.0;
+  const int first = g < G ? g : Q, step = g < G ? G : 1;      // workgroup G: the one "query" Q, the empty mask
+  for (int j = first; j <= Q && (j < Q || g == G); j += step) {
+    const unsigned long long mk = j < Q ? (unsigned long long)mask[j] : 0ull;
+    const unsigned long long vl = j < Q ? (unsigned long long)value[j] : 0ull;
+    const double cj = j < Q ? c[j] : 1.0;
+    __syncthreads();                                           // the query before this one is done with X, As and eEs
+    for (int i = t; i < DD; i += MS_ENV_THREADS) {
+      X[i] = i == 0 ? 1.0 : 0.0;
+      stack[(size_t)n * DD + i] = X[i];
+    }
+    if (t == 0) eEs[n] = 0;
+    int ex = 0;
+    for (int k = n; k >= 1; --k) {
+      const int allowed = ms_bit(mk, n, k) ? 1 << ms_bit(vl, n, k) : 3;
+      __syncthreads();
+      for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+      __syncthreads();
+      ex += ms_env_step(true, D, allowed, As, X, T, red, stack + (size_t)(k - 1) * DD);
+      if (t == 0) eEs[k - 1] = ex;
+    }
+    __syncthreads();                                           // publishes X, the stack and eEs
+    const double aj = X[0];
+    if (t == 0) {
+      pairs[2 * j] = aj;
+      pairs[2 * j + 1] = (double)ex;
+    }
+    const bool possible = aj > 0.0 && isfinite(aj);
+    if (possible) wsum += cj;
+    if (!possible || cj == 0.0) continue;                      // the same decision in every thread
+    const double f = cj / aj;
+    __syncthreads();                                           // every thread has read X[0]
+    for (int i = t; i < DD; i += MS_ENV_THREADS) X[i] = i == 0 ? 1.0 : 0.0;
+    int eL = 0;
+    for (int k = 1; k <= n; ++k) {
+      const int allowed = ms_bit(mk, n, k) ? 1 << ms_bit(vl, n, k) : 3;
+      __syncthreads();                                         // the step before is done with As and T
+      for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+      for (int i = t; i < DD; i += MS_ENV_THREADS) Em[i] = stack[(size_t)k * DD + i];
+      __syncthreads();
+      for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
+        const int s = i / DD, a = (i % DD) / D, d = i % D;
+        if (!((allowed >> s) & 1)) continue;
+        double acc = 0.0;
+        for (int e = 0; e < D; ++e) acc = fma(As[s * DD + a * D + e], Em[e * D + d], acc);
+        T[i] = acc;
+      }
+      __syncthreads();
+      const int sh = eL + eEs[k] - ex;
+      for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
+        const int s = i / DD, a = (i % DD) / D, d = i % D;
+        if (!((allowed >> s) & 1)) continue;
+        double m = 0.0;
+        for (int e = 0; e < D; ++e) m = fma(X[a * D + e], T[s * DD + e * D + d], m);
+        const double term = ldexp(m * f, sh);
+        part[(size_t)(k - 1) * 2 * DD + i] += term + term;
+      }
+      __syncthreads();                                         // T is the step's scratch
+      if (k < n) eL += ms_env_step(false, D, allowed, As, X, T, red, nullptr);
+    }
+  }
+  if (t == 0) wpart[g] = wsum;
+}
+
+__global__ __launch_bounds__(MS_ENV_THREADS) void mps_logm_vjp_finish_kernel(long long count, int G, const double* __restrict__ parts,
+                                                                          const double* __restrict__ wpart,
+                                                                          double* __restrict__ grad) {
+  __shared__ double red[MS_ENV_THREADS / 64];
+  const double W = sum_partials<MS_ENV_THREADS>(wpart, G, red);
+  const long long i = (long long)blockIdx.x * MS_ENV_THREADS + threadIdx.x;
+  if (i >= count) return;
+  double sum = 0.0;
+  for (int g = 0; g < G; ++g) sum += parts[(size_t)g * count + i];
+  grad[i] = sum - W * parts[(size_t)G * count + i];
+}
+
 }  // namespace
+
+size_t mps_log_marginals_vjp_workspace_bytes(int n, int D, int Q) { return mq_vjp_layout(n, D, Q).total + 256; }
+
+int mps_log_marginals_vjp_groups(int Q) { return mq_vjp_groups(Q); }
+
+hipError_t launch_mps_log_marginals_vjp(int n, int D, int Q, const double* cores, const long long* mask, const long long* value,
+                                        const double* c, double* grad, double* logm, int* status, void* ws, hipStream_t st) {
+  const MqVjpLayout S = mq_vjp_layout(n, D, Q);
+  char* base = ws_align(ws);
+  hipError_t e = launch_ms_clear_status(status, st);
+  if (e != hipSuccess) return e;
+  double* pairs = (double*)(base + S.pairs);
+  double* parts = (double*)(base + S.parts);
+  double* wpart = (double*)(base + S.wpart);
+  mps_logm_vjp_kernel<<<(unsigned)(S.G + 1), MS_ENV_THREADS, 0, st>>>(cores, n, D, Q, S.G, mask, value, c, pairs, parts,
+                                                                    (double*)(base + S.stacks), wpart);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const long long count = (long long)n * 2 * D * D;
+  mps_logm_vjp_finish_kernel<<<(unsigned)((count + MS_ENV_THREADS - 1) / MS_ENV_THREADS), MS_ENV_THREADS, 0, st>>>(count, S.G, parts,
+                                                                                                                 wpart, grad);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  mps_query_logm_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, st>>>(Q, pairs, logm, status);
+  return hipGetLastError();
+}
 
 size_t mps_query_workspace_bytes(int n, int D, int Q) { return mq_layout(n, D, Q).total + 256; }
 

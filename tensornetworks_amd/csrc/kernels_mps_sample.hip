@@ -63,6 +63,7 @@
 //   ms_amplitude_ok (on l^_n[0]) gets t_b = 0.0 and sets the status word to 2.
 //
 // bornvi_bn_logjoint_samples: logp_b = sum_v log max(CPT_v[parents][value], p_floor), one lane per sample, nodes in order.
+// bornvi_bn_sample: exact ancestral draws from the network itself, stated above bn_sample_kernel.
 //
 // No atomics, no allocation, no synchronisation: capturable, and two calls are bitwise equal.  The status word is cleared
 // by a one-lane kernel in front of the launch (a kernel node like the others when the calls are captured into a graph, so
@@ -518,6 +519,52 @@ __global__ __launch_bounds__(256) void bn_logjoint_kernel(bornvi_bn_desc bn, int
   logp[b] = bad ? __builtin_nan("") : sum;
 }
 
+// ---- exact ancestral draws from the network -------------------------------------------------
+// One sample per lane, the values of all V <= 64 nodes in one 64-bit register (bit v = node v), nodes in descriptor order
+// (topological: every parent index is below the node's own).  Node v:  t_s = CPT_v[parents][s] as stored,
+// bit = U (t0 + t1) >= t0 (the MPS sampler's rule: a value of probability 0 is never drawn), U = unit53 of
+// Philox4x32-10 with counter (b, v >> 1, BN_PHILOX_DOMAIN, epoch): even v the words (x, y), odd v (z, w).  logp is
+// bn_logjoint_kernel's sum, the chosen factor unfloored.  role, n_parents, parents and cpt_off are the same for every lane
+// (scalar loads); the CPT row is a gather from a table of at most a few KB that stays in cache.
+constexpr uint32_t BN_PHILOX_DOMAIN = 0xfffffffeu;
+
+__global__ __launch_bounds__(256) void bn_sample_kernel(bornvi_bn_desc bn, int n, long long B, uint32_t seed_lo, uint32_t seed_hi,
+                                                        const long long* __restrict__ epoch_dev, long long* __restrict__ idx,
+                                                        double* __restrict__ logp, int* status) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const uint32_t ep = (uint32_t)(unsigned long long)(*epoch_dev);
+  unsigned long long vals = 0, z = 0;   // bit v = value of node v; the kept nodes' bits by tuple position
+  bool bad = false, dead = false;
+  double sum = 0.0;
+  uint4 w = make_uint4(0, 0, 0, 0);
+  for (int v = 0; v < bn.num_nodes; ++v) {
+    if (!(v & 1)) w = philox4x32_10(make_uint4((uint32_t)b, (uint32_t)(v >> 1), BN_PHILOX_DOMAIN, ep), seed_lo, seed_hi);
+    const double U = (v & 1) ? unit53(w.z, w.w) : unit53(w.x, w.y);
+    int cfg = 0;
+    int np = bn.n_parents[v];
+    if (np < 0 || np > bn.max_parents) { bad = true; np = 0; }
+    for (int p = 0; p < np; ++p) {
+      const int pa = bn.parents[v * bn.max_parents + p];
+      if (pa < 0 || pa >= v) bad = true;       // not topological: the host refuses it where it can look
+      cfg = cfg * 2 + (int)((vals >> (pa & 63)) & 1ull);
+    }
+    const double* row = bn.cpt + bn.cpt_off[v] + 2 * cfg;
+    const double t0 = row[0], t1 = row[1];
+    const double tot = t0 + t1;
+    if (!(tot > 0.0 && isfinite(tot))) dead = true;
+    const bool bit = !dead && (U * tot >= t0);
+    vals |= (bit ? 1ull : 0ull) << v;
+    sum += log(bit ? t1 : t0);
+    const int role = bn.role[v];
+    if (role >= 0 && role < n) z |= (bit ? 1ull : 0ull) << (n - 1 - role);
+    else if (role != -3) bad = true;           // an observed node: the host refuses it where it can look
+  }
+  idx[b] = (long long)z;
+  logp[b] = (bad || dead) ? __builtin_nan("") : sum;
+  if (bad || dead) *status = 1;
+}
+
 }  // namespace
 
 hipError_t launch_ms_clear_status(int* status, hipStream_t st) {
@@ -628,6 +675,15 @@ hipError_t launch_mps_score_mu(int n, int D, long long B, const double* cores, v
 hipError_t launch_bn_logjoint_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* logp,
                                       hipStream_t st) {
   bn_logjoint_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(bn, n, B, idx, p_floor, logp);
+  return hipGetLastError();
+}
+
+hipError_t launch_bn_sample(const bornvi_bn_desc& bn, int n, long long B, unsigned long long seed, const long long* epoch_dev,
+                            long long* idx, double* logp, int* status, hipStream_t st) {
+  hipError_t e = launch_ms_clear_status(status, st);
+  if (e != hipSuccess) return e;
+  bn_sample_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(bn, n, B, (uint32_t)seed, (uint32_t)(seed >> 32), epoch_dev, idx, logp,
+                                                               status);
   return hipGetLastError();
 }
 
