@@ -30,7 +30,7 @@
  *       ELBO weights, Fisher matrix ............................... 1 <= n <= 30;
  *       probability-table Born machine ............................ 0 <= n <= 30;
  *       matrix-product-state Born machine (bond 1 <= D <= 32) ..... 1 <= n <= 26;
- *       sampled MPS calls, log joint and scores of samples,
+ *       sampled MPS calls, the MPS canonicaliser, log joint and scores of samples,
  *       pairwise Stein kernel row sums (n * length_scale >= 1) ..... 1 <= n <= 63;
  *       un-fused gate application ................................. 1 <= n <= 40.
  */
@@ -596,6 +596,33 @@ int bornvi_mps_sample_clamped(bornvi_handle h, int n, int D, long long B, const 
                               bornvi_stream stream);
 int bornvi_mps_marginals(bornvi_handle h, int n, int D, const double* cores, double* m1, double* m2, void* workspace,
                          size_t workspace_bytes, bornvi_stream stream);
+
+/* ---- canonical form, bond spectra and truncation (kernels_mps_canon.hip); cores, n and D as in the
+ * sampled section above.  bornvi_mps_canonicalise brings the MPS to canonical form with two orthogonalising sweeps of one
+ * workgroup and reads the Schmidt values at every bond on the way back:
+ *   left, k = 1 .. n - 1:  [C A_k[0]; C A_k[1]] = Q (S V^T) (one-sided Jacobi), A_k <- the blocks of Q, C <- S V^T over its
+ *     Frobenius norm, whose log is accumulated (C_0 = e0 e0^T);
+ *   right, k = n .. 2:  [A_k[0] R, A_k[1] R] = U S W, the values of S (sorted descending, ties by index, over their norm) are
+ *     the Schmidt values of bond k - 1; the D_out largest stay, then more go from the small end for as long as the dropped
+ *     squares sum to <= cutoff, at least one stays; A_k <- the kept rows of W's blocks, R <- U S on the kept values over its
+ *     Frobenius norm (R_n = e0 e0^T); at last R goes into site 1.
+ * cores_out dev [n, 2, D_out, D_out]: psi_out = +psi_in / sqrt(Z) when nothing is cut, sites 2 .. n right-canonical (sum_s
+ * A_k[s] A_k[s]^T = I on the kept block), its own Z is 1; rows >= 1 of the first core, columns >= 1 of the last and
+ * everything outside the kept blocks are exactly 0.0.  schmidt dev [n - 1, D]: all D values of every bond, descending,
+ * sum of squares 1, a value the rank rule found null exactly 0.0.  discarded dev [n - 1]: the sum of the dropped squares.
+ * rank dev [n - 1] int32: the values kept.  log_norm dev [1] = log Z of the INPUT cores.  status dev [1] int32: 1 when
+ * the input held a non-finite entry or Z is not positive and finite (cores_out and log_norm are NaN), 4 when a
+ * factorisation used all 30 sweeps without converging (outputs as computed), else 0.  With n = 1 there are no bonds
+ * (schmidt, discarded and rank may be NULL) and the one core is normalised.
+ * The rank rule: a column pair is skipped when either squared norm is <= (D 2^-52)^2 times the largest squared column
+ * norm of the matrix under factorisation, and such a column's singular value is exactly 0.0.
+ * 1 <= n <= 63, 1 <= D <= 32, 1 <= D_out <= D, cutoff finite and >= 0: anything else, a short workspace included, is
+ * BORNVI_ERR_UNSUPPORTED before any launch.  No atomics (two calls are bitwise equal), no allocation or synchronisation
+ * (capturable).  The first int of the aligned workspace holds the largest sweep count of the call's factorisations. */
+size_t bornvi_mps_canon_workspace_bytes(bornvi_handle h, int n, int D);
+int bornvi_mps_canonicalise(bornvi_handle h, int n, int D, int D_out, double cutoff, const double* cores, double* cores_out,
+                            double* schmidt, double* discarded, int* rank, double* log_norm, int* status, void* workspace,
+                            size_t workspace_bytes, bornvi_stream stream);
 
 /* ---- amortised inference: draws from the network, and the gradient of log-marginals.
  * bornvi_bn_sample: B exact ancestral draws from the network itself.  role[v] is the tuple position 0 .. n - 1 of node v in

@@ -152,6 +152,9 @@ _PROTOS = {
                                             C.c_size_t, C.c_void_p]),
     "bornvi_mps_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    "bornvi_mps_canon_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "bornvi_mps_canonicalise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bornvi_bn_sample": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_longlong, C.c_ulonglong, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "bornvi_mps_log_marginals_vjp_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

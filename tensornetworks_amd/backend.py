@@ -801,6 +801,36 @@ def mps_marginals(cores, want_pairs=False, out_m1=None, out_m2=None):
     return out_m1, out_m2
 
 
+# ---- canonical form, bond spectra and truncation (kernels_mps_canon.hip) -----------------------
+def mps_canonicalise(cores, bond_dim_out=None, cutoff=0.0):
+    """Canonical form of an MPS Born machine (bornvi_mps_canonicalise): cores float64 [n, 2, D, D] on the GPU, 1 <= n <= 63 ->
+    (cores_out float64 [n, 2, D_out, D_out]: psi_out = psi / sqrt(Z) up to what is cut, sites 2 .. n right-canonical;
+    schmidt float64 [n - 1, D]: the Schmidt values of every bond, descending, sum of squares 1; discarded float64 [n - 1]:
+    the sum of the dropped squares; rank int32 [n - 1]: the values kept; log_norm float64 [1] = log Z of the input; status
+    int32 [1]: 0, 1 (non-finite input or Z: cores_out NaN) or 4 (a factorisation did not converge)).  bond_dim_out (default
+    D): the D_out largest values of a bond stay; then more go from the small end while the dropped squares sum to <= cutoff."""
+    n, D, _ = _mps_args(cores, 1)
+    Do = D if bond_dim_out is None else bond_dim_out
+    if isinstance(Do, bool) or not isinstance(Do, (int, np.integer)) or not 1 <= int(Do) <= D:
+        raise BornviError(f"bond_dim_out must be an integer in 1 ... {D} (the cores' bond dimension), got {bond_dim_out!r}")
+    Do = int(Do)
+    _chk_positive(cutoff, "cutoff", allow_zero=True)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    _chk(cores, torch.float64, dev, "cores")
+    out = torch.empty(n, 2, Do, Do, dtype=torch.float64, device=dev)
+    schmidt = torch.empty(n - 1, D, dtype=torch.float64, device=dev)
+    discarded = torch.empty(n - 1, dtype=torch.float64, device=dev)
+    rank = torch.empty(n - 1, dtype=torch.int32, device=dev)
+    log_norm = torch.empty(1, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = _ws(dev, _cached_size(h, "bornvi_mps_canon_workspace_bytes", n, D), f"mps_canon_{n}_{D}")
+    h.call("bornvi_mps_canonicalise", n, D, Do, float(cutoff), _ptr(cores), _ptr(out), _ptr(schmidt) if n > 1 else None,
+           _ptr(discarded) if n > 1 else None, _ptr(rank) if n > 1 else None, _ptr(log_norm), _ptr(status), _ptr(ws), ws.numel(),
+           _ext.stream_ptr(dev))
+    return out, schmidt, discarded, rank, log_norm, status
+
+
 def bn_descriptor(packed, dev):
     """(device arrays, BnDesc) of bayesian_network.pack_network's dict; the arrays must outlive every call that uses the
     descriptor.  A network with a summed-out node is refused by bn_logjoint_samples, not here."""

@@ -10,6 +10,8 @@ machine (born_machine_mps.py) and the sampled MPS machine (born_machine_mps_samp
                                       A family supplies how q is computed (_probabilities, _entropy) and its two ends of a
                                       training epoch: epoch_forward -> EpochForward, epoch_backward -> (loss, grads)
   new_mps_cores / MPSCores            the MPS families' constructor checks, initialisations and move to the compute device
+                                      and, on MPSCores, the canonical-form surface: bond_spectrum,
+                                      bond_entropies, canonical_cores, canonicalise_, compress_, expand_
 """
 import math
 from typing import Any, NamedTuple, Optional
@@ -226,3 +228,81 @@ class MPSCores:
         home = self.cores.device
         cores = self.cores.detach() if detach else self.cores
         return cores.to(device=backend.compute_device(home), dtype=torch.float64).contiguous(), home
+
+    # ---- canonical form, bond spectra, truncation and growth (backend.mps_canonicalise) ----------
+    # Everything returned is detached and on the compute device; every argument error is raised before any GPU call.
+    @staticmethod
+    def _check_cut(bond_dim, cutoff, D):
+        if bond_dim is not None and (isinstance(bond_dim, bool) or not isinstance(bond_dim, int) or not 1 <= bond_dim <= D):
+            raise ValueError(f"bond_dim must be None or an integer in 1 ... {D} (the current bond dimension), got {bond_dim!r}")
+        if isinstance(cutoff, bool) or not isinstance(cutoff, (int, float)) or not math.isfinite(cutoff) or cutoff < 0:
+            raise ValueError(f"cutoff must be a finite number >= 0, got {cutoff!r}")
+
+    def _canonical(self, bond_dim, cutoff):
+        self._check_cut(bond_dim, cutoff, self.bond_dim)
+        out, schmidt, discarded, rank, log_norm, status = backend.mps_canonicalise(MPSCores.kernel_input(self, detach=True)[0], bond_dim,
+                                                                                  float(cutoff))
+        return out, schmidt, {"rank": rank, "discarded": discarded, "log_norm": log_norm, "status": status}
+
+    def bond_spectrum(self):
+        """float64 [n - 1, D]: the Schmidt values of every bond of the current cores, descending, zero-padded; the squares
+        of a bond sum to 1.  A value the factorisation's rank rule found null is exactly 0.0."""
+        return self._canonical(None, 0.0)[1]
+
+    def bond_entropies(self):
+        """float64 [n - 1]: -sum s^2 log s^2 over a bond's Schmidt values, a zero value contributing 0."""
+        p = self.bond_spectrum() ** 2
+        return -(p * torch.log(torch.where(p > 0, p, torch.ones_like(p)))).sum(dim=1)
+
+    def canonical_cores(self, bond_dim=None, cutoff=0.0):
+        """(cores_out float64 [n, 2, D', D'], report) with D' = bond_dim (default: the current D): the same q in canonical
+        form (sites 2 .. n right-canonical, Z = 1), each bond cut to its bond_dim largest Schmidt values and then further
+        from the small end while the dropped squares sum to <= cutoff.  report = {'rank' int32 [n - 1], 'discarded' float64
+        [n - 1], 'log_norm' float64 [1] (log Z of the current cores), 'status' int32 [1]: 0, 1 (non-finite cores or Z) or 4
+        (a factorisation did not converge)}.  The machine is not changed."""
+        out, _, report = self._canonical(bond_dim, cutoff)
+        return out, report
+
+    def canonicalise_(self):
+        """Replaces the parameter's data by its canonical form, in place (the same nn.Parameter, the same D): q is unchanged,
+        Z = 1.  Returns canonical_cores' report."""
+        out, _, report = self._canonical(None, 0.0)
+        with torch.no_grad():
+            self.cores.data.copy_(out.to(device=self.cores.device, dtype=self.cores.dtype))
+        return report
+
+    def compress_(self, bond_dim=None, cutoff=0.0):
+        """Cuts the bonds as canonical_cores does and makes `cores` a NEW nn.Parameter [n, 2, D', D']: D' = bond_dim when
+        given (at most the current D; D itself cuts by `cutoff` alone), else the largest kept rank.  Returns the report.  An optimiser built on the
+        old parameter is stale: build a new one (the trainers build theirs inside train(), so train -> compress_ -> train
+        works as it stands)."""
+        out, _, report = self._canonical(bond_dim, cutoff)
+        if bond_dim is None:
+            rank = report["rank"]
+            bond_dim = int(rank.max().item()) if rank.numel() else 1
+        new = out[:, :, :bond_dim, :bond_dim].contiguous()
+        self.cores = nn.Parameter(new.to(device=self.cores.device, dtype=self.cores.dtype))
+        return report
+
+    def expand_(self, bond_dim, noise=0.0, seed=0):
+        """Grows the bond dimension to bond_dim (current D < bond_dim <= 32) on the host: `cores` becomes a NEW nn.Parameter
+        whose leading [D, D] blocks are the old cores and whose other entries are noise * torch.randn of a CPU generator
+        seeded by seed -- except the first core's rows >= 1 and the last core's columns >= 1, which stay 0.  With noise =
+        0.0 psi is unchanged as a function.  As after compress_, an optimiser built on the old parameter is stale."""
+        D, n = self.bond_dim, int(self.cores.shape[0])
+        if isinstance(bond_dim, bool) or not isinstance(bond_dim, int) or not D < bond_dim <= backend.MPS_MAX_BOND:
+            raise ValueError(f"expand_: bond_dim must be an integer in {D + 1} ... {backend.MPS_MAX_BOND}, got {bond_dim!r}")
+        if isinstance(noise, bool) or not isinstance(noise, (int, float)) or not math.isfinite(noise) or noise < 0:
+            raise ValueError(f"noise must be a finite number >= 0, got {noise!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed must be an integer, got {seed!r}")
+        new = torch.zeros(n, 2, bond_dim, bond_dim, dtype=torch.float64)
+        new[:, :, :D, :D] = self.cores.detach().to(device="cpu", dtype=torch.float64)
+        if noise != 0.0:
+            gen = torch.Generator().manual_seed(seed)
+            fresh = torch.ones(n, 2, bond_dim, bond_dim, dtype=torch.bool)
+            fresh[:, :, :D, :D] = False
+            fresh[0, :, 1:, :] = False
+            fresh[n - 1, :, :, 1:] = False
+            new = new + noise * torch.randn(n, 2, bond_dim, bond_dim, dtype=torch.float64, generator=gen) * fresh
+        self.cores = nn.Parameter(new.to(device=self.cores.device, dtype=self.cores.dtype).contiguous())

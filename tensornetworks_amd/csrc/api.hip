@@ -1465,6 +1465,32 @@ int bornvi_mps_marginals(bornvi_handle h, int n, int D, const double* cores, dou
   return BORNVI_OK;
 }
 
+// ---- canonical form, bond spectra and truncation (kernels_mps_canon.hip) -------------------------------------------
+static bool valid_mps_canon(int n, int D) { return n >= 1 && n <= 63 && D >= 1 && D <= 32; }
+static const char* const MPS_CANON_RANGE = "unsupported size (1 <= n <= 63, 1 <= D_out <= D <= 32, cutoff finite and >= 0)";
+
+size_t bornvi_mps_canon_workspace_bytes(bornvi_handle h, int n, int D) {
+  if (!h) return 0;
+  if (!valid_mps_canon(n, D)) { fail(h, BORNVI_ERR_UNSUPPORTED, MPS_CANON_RANGE); return 0; }
+  return mps_canon_workspace_bytes(n, D);
+}
+
+int bornvi_mps_canonicalise(bornvi_handle h, int n, int D, int D_out, double cutoff, const double* cores, double* cores_out,
+                            double* schmidt, double* discarded, int* rank, double* log_norm, int* status, void* workspace,
+                            size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_canon(n, D) || D_out < 1 || D_out > D || !(cutoff >= 0.0) || !std::isfinite(cutoff))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_CANON_RANGE);
+  if (!cores || !cores_out || !log_norm || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (n > 1 && (!schmidt || !discarded || !rank)) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!workspace || workspace_bytes < mps_canon_workspace_bytes(n, D)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_canonicalise(n, D, D_out, cutoff, cores, cores_out, schmidt, discarded, rank, log_norm, status, workspace,
+                                    (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
 // ---- conjugate gradients around a caller's product (kernels_cg.hip) ------------------------------------------------
 static bool valid_cg(long long P) { return P >= 1 && P <= 2147483647ll; }
 static const char* const CG_RANGE = "bad argument (1 <= P <= 2^31 - 1)";

@@ -142,6 +142,11 @@ int mps_log_marginals_vjp_groups(int Q);
 hipError_t launch_mps_log_marginals_vjp(int n, int D, int Q, const double* cores, const long long* mask, const long long* value,
                                         const double* c, double* grad, double* logm, int* status, void* ws, hipStream_t st);
 
+// ---- canonical form, bond spectra and truncation of an MPS (kernels_mps_canon.hip): one workgroup, two Jacobi sweeps ----
+size_t mps_canon_workspace_bytes(int n, int D);
+hipError_t launch_mps_canonicalise(int n, int D, int D_out, double cutoff, const double* cores, double* cores_out, double* schmidt,
+                                   double* discarded, int* rank, double* log_norm, int* status, void* ws, hipStream_t st);
+
 // ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
 constexpr int CG_STATE_DOUBLES = 8;      // rr, rr0, iterations, done, relres, fallback, 2 spare
 hipError_t launch_cg_init(long long P, const double* g, double* x, double* r, double* p, double* state, int* info, hipStream_t st);
