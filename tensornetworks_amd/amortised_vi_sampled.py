@@ -9,7 +9,7 @@ No observation enters the training.  The fitted q then answers q(z | x) exactly 
 SampledMPSBornMachine (log_marginal, sample_given): posterior_sample, posterior_log_prob, posterior_marginals, log_evidence.
 With at most 16 observed sites the 'conditional' query list is all 2^c evidences of those sites with the weights
 count_j / B (the counts are integers, added on the device); with more there is one query per sample and num_samples <= 2^16.
-The optimiser, the NaN/Inf guard and the clip are the other trainers' make_optimizer and guarded_update (ksd_vi.py).
+The optimiser, the NaN/Inf guard and the clip are SampledTrainer's (make_sampled_optimizer, host_update: sampled_trainer.py).
 """
 import math
 
@@ -18,7 +18,7 @@ import torch
 from . import backend
 from .bayesian_network import pack_network_for_sampling
 from .born_machine_mps_sampled import SampledMPSBornMachine
-from .ksd_vi import guarded_update, make_optimizer
+from .sampled_trainer import checked_config, host_update, make_sampled_optimizer
 from .utils import generate_all_binary_outcomes
 
 
@@ -28,13 +28,8 @@ class AmortisedMPSInference:
     OBJECTIVES = ('joint', 'conditional')
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu'):
-        cfg = dict(born_machine_config or {})
-        unknown = set(cfg) - {'bond_dim', 'num_samples', 'seed', 'init_method', 'site_order'}
-        if unknown:
-            raise ValueError(f"born_machine_config: unknown keys {sorted(unknown)}")
-        B = cfg.get('num_samples', 1024)
-        if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= backend.MPS_SAMPLED_MAX_BATCH:
-            raise ValueError(f"num_samples must be an integer in 1 ... 2^24, got {B!r}")
+        cfg, B = checked_config(born_machine_config, ('bond_dim', 'num_samples', 'seed', 'init_method', 'site_order'), 1,
+                                backend.MPS_SAMPLED_MAX_BATCH, "1 ... 2^24")
         self.bn = bayesian_network
         self.latent_vars_names = list(latent_vars_names)
         self.observed_vars_names = list(observed_vars_names)
@@ -139,20 +134,13 @@ class AmortisedMPSInference:
         after every update (read-outs there leave the run unchanged).  History: loss, grad_norm, status."""
         self._check_objective(objective)
         bm = self.born_machine
-        opt, sched = make_optimizer(bm.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas)
-        if optimizer_type != "adam":
-            if isinstance(sgd_momentum, bool) or not isinstance(sgd_momentum, (int, float)) or not 0 <= sgd_momentum < 1:
-                raise ValueError(f"sgd_momentum must be a number in [0, 1), got {sgd_momentum!r}")
-            for group in opt.param_groups:
-                group['momentum'] = float(sgd_momentum)
+        opt, sched = make_sampled_optimizer(bm, lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas, sgd_momentum)
         history = {'loss': [], 'grad_norm': [], 'status': []}
         grad_norm = None
         for epoch in range(num_epochs):
             opt.zero_grad()
             loss_t, grad, st_t = self.loss_and_grad(epoch, objective)
-            loss = float(loss_t.item())                       # the epoch's host synchronisation
-            grads = [(bm.cores, grad.to(device=bm.cores.device, dtype=bm.cores.dtype))]
-            grad_norm = guarded_update(bm, opt, sched, loss, grads, gradient_clip_norm, grad_norm)
+            loss, grad_norm = host_update(loss_t, grad, bm, opt, sched, gradient_clip_norm, grad_norm)
             history['loss'].append(loss)
             history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
             history['status'].append(int(st_t.item()))

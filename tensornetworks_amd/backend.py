@@ -80,6 +80,42 @@ def _chk(t, dtype, dev, name, numel=None):
         raise BornviError(f"{name}: expected {int(numel)} elements, got {t.numel()} (shape {tuple(t.shape)})")
 
 
+def _out(t, dtype, dev, name, shape):
+    """The optional output `t`, checked for the element count of `shape` (an int or a tuple), or a new tensor of that shape."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    _chk(t, dtype, dev, name, np.prod(shape))
+    return t
+
+
+def _seed_word(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise BornviError(f"seed must be an integer, got {seed!r}")
+    return int(seed) & ((1 << 64) - 1)
+
+
+def _sample_count(B):
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MPS_SAMPLED_MAX_BATCH:
+        raise BornviError(f"number of samples: 1 ... 2^24 per call, got {B!r}")
+    return int(B)
+
+
+def _evidence_args(mask, value, dev, count=None):
+    """Checks a list of evidences (mask, value int64 [Q], 1 <= Q <= 2^16), or with `count` one of exactly that many -> Q."""
+    if count is not None:
+        if not torch.is_tensor(mask) or not torch.is_tensor(value):
+            raise BornviError(f"mask, value: expected two [{count}] int64 tensors")
+    else:
+        if not torch.is_tensor(mask) or not torch.is_tensor(value) or mask.dim() != 1 or mask.shape != value.shape:
+            raise BornviError("mask, value: expected two [Q] int64 tensors")
+        count = int(mask.numel())
+        if not 1 <= count <= MPS_QUERY_MAX_QUERIES:
+            raise BornviError(f"number of queries: 1 ... 2^16 per call, got {count}")
+    _chk(mask, torch.int64, dev, "mask", count)
+    _chk(value, torch.int64, dev, "value", count)
+    return count
+
+
 # Largest n of the circuit engines (circuits, parameter shift, fused dot, adjoint) and of the matrix-free Stein mat-vec:
 # the planner's tile and workgroup indices are 16 bits and its tiles hold at most 2^13 amplitudes (include/bornvi.h).
 CIRCUIT_MAX_N = 29
@@ -592,9 +628,7 @@ def _mps_args(cores, num_samples=_ENUMERATED):
         raise BornviError(f"cores: bond dimension 1 ... {MPS_MAX_BOND}, got {D}")
     if B is _ENUMERATED:
         return n, D
-    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MPS_SAMPLED_MAX_BATCH:
-        raise BornviError(f"number of samples: 1 ... 2^24 per call, got {B!r}")
-    return n, D, int(B)
+    return n, D, _sample_count(B)
 
 
 def mps_probs(cores, want_q32=True, want_psi=False):
@@ -666,23 +700,13 @@ def mps_sample(cores, num_samples, seed, epoch, out_idx=None, out_logq=None, sta
     dev = cores.device
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-        raise BornviError(f"seed must be an integer, got {seed!r}")
+    seed = _seed_word(seed)
     _chk(epoch, torch.int64, dev, "epoch", 1)
-    if out_idx is None:
-        out_idx = torch.empty(B, dtype=torch.int64, device=dev)
-    else:
-        _chk(out_idx, torch.int64, dev, "out_idx", B)
-    if out_logq is None:
-        out_logq = torch.empty(B, dtype=torch.float64, device=dev)
-    else:
-        _chk(out_logq, torch.float64, dev, "out_logq", B)
-    if status is None:
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-    else:
-        _chk(status, torch.int32, dev, "status", 1)
+    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
+    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
+    status = _out(status, torch.int32, dev, "status", 1)
     ws = _mps_sampled_ws(h, dev, n, D, B)
-    h.call("bornvi_mps_sample", n, D, B, _ptr(cores), int(seed) & ((1 << 64) - 1), _ptr(epoch), _ptr(out_idx), _ptr(out_logq),
+    h.call("bornvi_mps_sample", n, D, B, _ptr(cores), seed, _ptr(epoch), _ptr(out_idx), _ptr(out_logq),
            _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
     return out_idx, out_logq, status
 
@@ -699,18 +723,9 @@ def mps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
     _chk(cores, torch.float64, dev, "cores")
     _chk(idx, torch.int64, dev, "idx", B)
     _chk(w, torch.float64, dev, "w", B)
-    if out is None:
-        out = torch.empty(cores.shape, dtype=torch.float64, device=dev)
-    else:
-        _chk(out, torch.float64, dev, "out", cores.numel())
-    if out_logq is None:
-        out_logq = torch.empty(B, dtype=torch.float64, device=dev)
-    else:
-        _chk(out_logq, torch.float64, dev, "out_logq", B)
-    if status is None:
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-    else:
-        _chk(status, torch.int32, dev, "status", 1)
+    out = _out(out, torch.float64, dev, "out", tuple(cores.shape))
+    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
+    status = _out(status, torch.int32, dev, "status", 1)
     ws = _mps_sampled_ws(h, dev, n, D, B)
     h.call("bornvi_mps_score_vjp", n, D, B, _ptr(cores), _ptr(idx), _ptr(w), _ptr(out_logq), _ptr(out), _ptr(status), _ptr(ws),
            ws.numel(), _ext.stream_ptr(dev))
@@ -725,13 +740,6 @@ def _mps_query_ws(h, dev, n, D, Q):
     return _ws(dev, _cached_size(h, "bornvi_mps_query_workspace_bytes", n, D, Q), f"mps_query_{n}_{D}_{Q}")
 
 
-def _out(t, dtype, dev, name, numel):
-    if t is None:
-        return torch.empty(numel, dtype=dtype, device=dev)
-    _chk(t, dtype, dev, name, numel)
-    return t
-
-
 def mps_log_marginals(cores, mask, value, out=None, status=None):
     """Log probabilities of partial assignments under an MPS Born machine (bornvi_mps_log_marginals): mask, value int64 [Q]
     on the GPU (a set mask bit clamps tuple position p = bit n - 1 - p to the value's bit), 1 <= Q <= 2^16 ->
@@ -741,13 +749,7 @@ def mps_log_marginals(cores, mask, value, out=None, status=None):
     dev = cores.device
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")
-    if not torch.is_tensor(mask) or not torch.is_tensor(value) or mask.dim() != 1 or mask.shape != value.shape:
-        raise BornviError("mask, value: expected two [Q] int64 tensors")
-    Q = int(mask.numel())
-    if not 1 <= Q <= MPS_QUERY_MAX_QUERIES:
-        raise BornviError(f"number of queries: 1 ... 2^16 per call, got {Q}")
-    _chk(mask, torch.int64, dev, "mask", Q)
-    _chk(value, torch.int64, dev, "value", Q)
+    Q = _evidence_args(mask, value, dev)
     out = _out(out, torch.float64, dev, "out", Q)
     status = _out(status, torch.int32, dev, "status", 1)
     ws = _mps_query_ws(h, dev, n, D, Q)
@@ -765,19 +767,15 @@ def mps_sample_clamped(cores, num_samples, mask, value, seed, epoch, out_idx=Non
     dev = cores.device
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-        raise BornviError(f"seed must be an integer, got {seed!r}")
+    seed = _seed_word(seed)
     _chk(epoch, torch.int64, dev, "epoch", 1)
-    if not torch.is_tensor(mask) or not torch.is_tensor(value):
-        raise BornviError("mask, value: expected two [1] int64 tensors")
-    _chk(mask, torch.int64, dev, "mask", 1)
-    _chk(value, torch.int64, dev, "value", 1)
+    _evidence_args(mask, value, dev, 1)
     out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
     out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
     out_logm = _out(out_logm, torch.float64, dev, "out_logm", 1)
     status = _out(status, torch.int32, dev, "status", 1)
     ws = _mps_query_ws(h, dev, n, D, 1)
-    h.call("bornvi_mps_sample_clamped", n, D, B, _ptr(cores), _ptr(mask), _ptr(value), int(seed) & ((1 << 64) - 1), _ptr(epoch),
+    h.call("bornvi_mps_sample_clamped", n, D, B, _ptr(cores), _ptr(mask), _ptr(value), seed, _ptr(epoch),
            _ptr(out_idx), _ptr(out_logq), _ptr(out_logm), _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
     return out_idx, out_logq, out_logm, status
 
@@ -852,10 +850,7 @@ def bn_logjoint_samples(desc, n, idx, p_floor=1e-30, out=None):
     h = _ext.handle_for(dev)
     B = int(idx.numel())
     _chk(idx, torch.int64, dev, "idx")
-    if out is None:
-        out = torch.empty(B, dtype=torch.float64, device=dev)
-    else:
-        _chk(out, torch.float64, dev, "out", B)
+    out = _out(out, torch.float64, dev, "out", B)
     h.call("bornvi_bn_logjoint_samples", C.byref(desc), int(n), B, _ptr(idx), float(p_floor), _ptr(out), _ext.stream_ptr(dev))
     return out
 
@@ -868,12 +863,8 @@ def bn_sample(desc, n, num_samples, seed, epoch, out_idx=None, out_logp=None, st
     int32 [1]: 0, or 1 when a sample met a CPT row whose sum is not positive and finite).  A draw is a pure function of
     (network, seed, epoch, b)."""
     _chk_n(n, 1, MPS_SAMPLED_MAX_N)
-    B = num_samples
-    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MPS_SAMPLED_MAX_BATCH:
-        raise BornviError(f"number of samples: 1 ... 2^24 per call, got {B!r}")
-    B = int(B)
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-        raise BornviError(f"seed must be an integer, got {seed!r}")
+    B = _sample_count(num_samples)
+    seed = _seed_word(seed)
     if not torch.is_tensor(epoch):
         raise BornviError("epoch: expected an int64 device tensor [1]")
     dev = epoch.device
@@ -882,7 +873,7 @@ def bn_sample(desc, n, num_samples, seed, epoch, out_idx=None, out_logp=None, st
     out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
     out_logp = _out(out_logp, torch.float64, dev, "out_logp", B)
     status = _out(status, torch.int32, dev, "status", 1)
-    h.call("bornvi_bn_sample", C.byref(desc), int(n), B, int(seed) & ((1 << 64) - 1), _ptr(epoch), _ptr(out_idx), _ptr(out_logp),
+    h.call("bornvi_bn_sample", C.byref(desc), int(n), B, seed, _ptr(epoch), _ptr(out_idx), _ptr(out_logp),
            _ptr(status), _ext.stream_ptr(dev))
     return out_idx, out_logp, status
 
@@ -904,18 +895,9 @@ def mps_log_marginals_vjp(cores, mask, value, c, out=None, out_logm=None, status
     dev = cores.device
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")
-    if not torch.is_tensor(mask) or not torch.is_tensor(value) or mask.dim() != 1 or mask.shape != value.shape:
-        raise BornviError("mask, value: expected two [Q] int64 tensors")
-    Q = int(mask.numel())
-    if not 1 <= Q <= MPS_QUERY_MAX_QUERIES:
-        raise BornviError(f"number of queries: 1 ... 2^16 per call, got {Q}")
-    _chk(mask, torch.int64, dev, "mask", Q)
-    _chk(value, torch.int64, dev, "value", Q)
+    Q = _evidence_args(mask, value, dev)
     _chk(c, torch.float64, dev, "c", Q)
-    if out is None:
-        out = torch.empty(cores.shape, dtype=torch.float64, device=dev)
-    else:
-        _chk(out, torch.float64, dev, "out", cores.numel())
+    out = _out(out, torch.float64, dev, "out", tuple(cores.shape))
     out_logm = _out(out_logm, torch.float64, dev, "out_logm", Q)
     status = _out(status, torch.int32, dev, "status", 1)
     ws = _ws(dev, _cached_size(h, "bornvi_mps_log_marginals_vjp_workspace_bytes", n, D, Q), f"mps_logm_vjp_{n}_{D}_{Q}")
@@ -941,10 +923,7 @@ def bn_score_samples(desc, n, idx, p_floor=1e-30, out=None, want_logp=False):
     h = _ext.handle_for(dev)
     B = int(idx.numel())
     _chk(idx, torch.int64, dev, "idx")
-    if out is None:
-        out = torch.empty((B, int(n)), dtype=torch.float64, device=dev)
-    else:
-        _chk(out, torch.float64, dev, "out", B * int(n))
+    out = _out(out, torch.float64, dev, "out", (B, int(n)))
     logp = torch.empty(B, dtype=torch.float64, device=dev) if want_logp else None
     h.call("bornvi_bn_score_samples", C.byref(desc), int(n), B, _ptr(idx), float(p_floor), _ptr(out),
            _ptr(logp) if logp is not None else None, _ext.stream_ptr(dev))
@@ -1123,14 +1102,8 @@ def mps_score_rows(cores, idx, k_begin=0, k_count=None, out=None, status=None):
     _chk(cores, torch.float64, dev, "cores")
     _chk(idx, torch.int64, dev, "idx", B)
     ld, R = score_rows_ld(B), 2 * D * D
-    if out is None:
-        out = torch.empty((k_count, R, ld), dtype=torch.float64, device=dev)
-    else:
-        _chk(out, torch.float64, dev, "out", k_count * R * ld)
-    if status is None:
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-    else:
-        _chk(status, torch.int32, dev, "status", 1)
+    out = _out(out, torch.float64, dev, "out", (k_count, R, ld))
+    status = _out(status, torch.int32, dev, "status", 1)
     ws = _mps_sampled_ws(h, dev, n, D, B)
     h.call("bornvi_mps_score_rows", n, D, B, _ptr(cores), _ptr(idx), k_begin, k_count, ld, _ptr(out), _ptr(status), _ptr(ws),
            ws.numel(), _ext.stream_ptr(dev))
@@ -1192,14 +1165,8 @@ def mps_score_sample_gram(cores, idx, out=None, status=None):
     h = _ext.handle_for(dev)
     _chk(cores, torch.float64, dev, "cores")
     _chk(idx, torch.int64, dev, "idx", B)
-    if out is None:
-        out = torch.empty((B, B), dtype=torch.float64, device=dev)
-    else:
-        _chk(out, torch.float64, dev, "out", B * B)
-    if status is None:
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-    else:
-        _chk(status, torch.int32, dev, "status", 1)
+    out = _out(out, torch.float64, dev, "out", (B, B))
+    status = _out(status, torch.int32, dev, "status", 1)
     env = _mps_sampled_ws(h, dev, n, D, B)
     ws = _ws(dev, _cached_size(h, "bornvi_mps_score_sample_gram_workspace_bytes", n, D, B), f"mps_sample_gram_{n}_{D}_{B}")
     h.call("bornvi_mps_score_sample_gram", n, D, B, _ptr(cores), _ptr(idx), _ptr(out), _ptr(status), _ptr(env), env.numel(),
@@ -1233,14 +1200,8 @@ def mps_score_jvp(cores, idx, v, scale=1.0, out=None, status=None):
     _chk(cores, torch.float64, dev, "cores")
     _chk(idx, torch.int64, dev, "idx", B)
     _chk(v, torch.float64, dev, "v", cores.numel())
-    if out is None:
-        out = torch.empty(B, dtype=torch.float64, device=dev)
-    else:
-        _chk(out, torch.float64, dev, "out", B)
-    if status is None:
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-    else:
-        _chk(status, torch.int32, dev, "status", 1)
+    out = _out(out, torch.float64, dev, "out", B)
+    status = _out(status, torch.int32, dev, "status", 1)
     env = _mps_sampled_ws(h, dev, n, D, B)
     h.call("bornvi_mps_score_jvp", n, D, B, _ptr(cores), _ptr(idx), _ptr(v), float(scale), _ptr(out), _ptr(status), _ptr(env),
            env.numel(), _ext.stream_ptr(dev))

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(MC_THREADS) void mps_canon_kernel(const double* __r
   double logacc = 0.0;
   for (int i = t; i < DD; i += MC_THREADS) Cm[i] = i == 0 ? 1.0 : 0.0;
 
-  // ---- left sweep ----
+  // ---- left sweep ----  (site loads and C A_k[s] stay written out, not ms_load_site_wg's: profiles/mps_env_core_isa.txt)
   for (int k = 1; k < n; ++k) {
     __syncthreads();
     for (int i = t; i < 2 * DD; i += MC_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];

@@ -4,10 +4,8 @@
 // of words (mask, value): a set mask bit clamps that site to the value's bit; value bits outside the mask and bits at or
 // above n are never looked at.
 //
-// Clamped environments:  E^(j)_n = e0 e0^T,  E^(j)_{k-1} = sum_{s allowed at k} A_k[s] E^(j)_k A_k[s]^T; a clamped site allows
-//   one s, a free site both.  The step is ms_env_step (mps_sample_dev.hpp), mps_env_kernel's own: the same fma chains in the
-//   same order, the same 2^-e rescale and running exponent; a disallowed s contributes no term.  With an empty mask the
-//   result is therefore mps_env_kernel's right sweep bit for bit.
+// Clamped environments:  E^(j)_n = e0 e0^T,  E^(j)_{k-1} = sum_{s allowed at k} A_k[s] E^(j)_k A_k[s]^T; a clamped site allows one
+//   s, a free site both (ms_allowed).  The sweep is ms_env_sweep, its step mps_env_kernel's ms_env_step: an empty mask gives that kernel's bits.
 //
 // bornvi_mps_log_marginals: mps_query_env_kernel, one workgroup per query and one more (the last) for the empty mask; each
 //   leaves (E^^(j)_0[0, 0], e_j) in the workspace's pair table and nothing of size Q n D^2 is stored.  mps_query_logm_kernel:
@@ -69,24 +67,12 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_query_env_kernel(const dou
   __shared__ double X[MS_DMAX * MS_DMAX];
   __shared__ double T[2 * MS_DMAX * MS_DMAX];
   __shared__ double red[MS_ENV_THREADS / 64];
-  const int j = blockIdx.x, DD = D * D, t = threadIdx.x;
+  const int j = blockIdx.x, t = threadIdx.x;
   const unsigned long long mk = j < Q ? (unsigned long long)mask[j] : 0ull;
   const unsigned long long vl = j < Q ? (unsigned long long)value[j] : 0ull;
   double* out = (j == 0 && stackE) ? stackE : nullptr;
-  for (int i = t; i < DD; i += MS_ENV_THREADS) {
-    X[i] = i == 0 ? 1.0 : 0.0;
-    if (out) out[(long long)n * DD + i] = X[i];
-  }
-  if (out && t == 0) stackeE[n] = 0;
-  int ex = 0;
-  for (int k = n; k >= 1; --k) {
-    const int allowed = ms_bit(mk, n, k) ? 1 << ms_bit(vl, n, k) : 3;
-    __syncthreads();
-    for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
-    __syncthreads();
-    ex += ms_env_step(true, D, allowed, As, X, T, red, out ? out + (long long)(k - 1) * DD : nullptr);
-    if (out && t == 0) stackeE[k - 1] = ex;
-  }
+  const int ex = ms_env_sweep(cores, n, D, [&](int k) { return ms_allowed(mk, vl, n, k); }, As, X, T, red, out,
+                              [&](int slot, int e) { if (out && t == 0) stackeE[slot] = e; });
   __syncthreads();
   if (t == 0) {
     pairs[2 * j] = X[0];
@@ -148,7 +134,7 @@ __global__ __launch_bounds__(MS_LANES) void mps_sample_clamped_kernel(const doub
 __device__ __forceinline__ double mq_inner(int D, const double* X, const double* A1, const double* Em, double* T, double* G, double* R) {
   const int DD = D * D, t = threadIdx.x;
   __syncthreads();
-  for (int i = t; i < DD; i += MS_ENV_THREADS) {
+  for (int i = t; i < DD; i += MS_ENV_THREADS) {        // ms_mul_AX's chain for s = 1 alone: profiles/mps_env_core_isa.txt
     const int a = i / D, d = i % D;
     double acc = 0.0;
     for (int e = 0; e < D; ++e) acc = fma(A1[a * D + e], Em[e * D + d], acc);
@@ -189,7 +175,7 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_marginals_kernel(const dou
   const int i = blockIdx.x + 1, DD = D * D, t = threadIdx.x;
   const double Zh = hdr[1];
   const int eZ = eE[0];
-  for (int x = t; x < 2 * DD; x += MS_ENV_THREADS) As[x] = cores[(long long)(i - 1) * 2 * DD + x];
+  ms_load_site_wg(cores, i, D, As);
   for (int x = t; x < DD; x += MS_ENV_THREADS) {
     X[x] = L[(long long)(i - 1) * DD + x];
     Em[x] = E[(long long)i * DD + x];
@@ -204,7 +190,7 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_marginals_kernel(const dou
   int eM = eL[i - 1] + ms_env_step(false, D, 2, As, X, T, red, nullptr);
   for (int j = i + 1; j <= n; ++j) {
     __syncthreads();
-    for (int x = t; x < 2 * DD; x += MS_ENV_THREADS) As[x] = cores[(long long)(j - 1) * 2 * DD + x];
+    ms_load_site_wg(cores, j, D, As);
     for (int x = t; x < DD; x += MS_ENV_THREADS) Em[x] = E[(long long)j * DD + x];
     const double s2 = mq_inner(D, X, As + DD, Em, T, T + DD, R);
     const double v2 = ldexp(s2 / Zh, eM + eE[j] - eZ);
@@ -224,17 +210,14 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_marginals_kernel(const dou
 //
 // mps_logm_vjp_kernel, grid G + 1 of MS_ENV_THREADS: workgroup g < G = min(Q, MQ_VJP_MAX_WG) takes the queries g, g + G, ... in
 // that order, workgroup G the empty mask with weight 1.  Per query:
-//   right sweep: mps_query_env_kernel's loop (ms_env_step, right), the stack E^^(j)_k, k = n .. 0, into the workgroup's own
-//     slot of the workspace and its exponents into LDS; the pair (E^^(j)_0[0, 0], e_j) into the pair table, so that logm comes
-//     out of mps_query_logm_kernel bit for bit as bornvi_mps_log_marginals gives it;
-//   left sweep, k = 1 .. n, L^ in LDS:  T_s = A_s E^^_k, M_s = L^_{k-1} T_s (ms_env_stage's and ms_env_entry's fma chains, in
-//     index order) for the allowed s; the entry is M_s (c_j / E^^(j)_0[0, 0]) 2^(eL + eE[k] - e_j), doubled, and is added to the
-//     workgroup's own partial [n, 2, D, D]: entry i of a site always by thread i mod MS_ENV_THREADS, so no atomics and no barrier
-//     guard it; then ms_env_step (left) with the same allowed set.
-//   A query whose mass is not positive and finite, or whose weight is 0.0, takes no left sweep and adds nothing, and an
-//   impossible one's weight stays out of the workgroup's weight sum.
-// mps_logm_vjp_finish_kernel: per entry the partials of workgroups 0 .. G - 1 in order, minus W times the empty mask's entry,
-//   W the workgroups' weight sums by sum_partials.
+//   right sweep: ms_env_sweep, mps_query_env_kernel's call, the stack E^^(j)_k into the workgroup's own slot of the workspace, its
+//     exponents into LDS, (E^^(j)_0[0, 0], e_j) into the pair table: logm is mps_query_logm_kernel's, bornvi_mps_log_marginals' bits;
+//   left sweep, k = 1 .. n, L^ in LDS:  T_s = A_s E^^_k (ms_mul_AX), M_s = L^_{k-1} T_s (ms_env_chain) for the allowed s; the entry
+//     is M_s (c_j / E^^(j)_0[0, 0]) 2^(eL + eE[k] - e_j), doubled, and is added to the workgroup's own partial [n, 2, D, D]: entry i of a
+//     site always by thread i mod MS_ENV_THREADS, so no atomics and no barrier guard it; then ms_env_step (left), the same allowed set.
+//   A query whose mass is not positive and finite, or whose weight is 0.0, takes no left sweep and adds nothing, and an impossible
+//   one's weight stays out of the workgroup's weight sum.  mps_logm_vjp_finish_kernel: per entry the partials of workgroups
+//   0 .. G - 1 in order, minus W times the empty mask's entry, W the workgroups' weight sums by sum_partials.
 constexpr int MQ_VJP_MAX_WG = 256;      // one per compute unit of the MI355X
 
 __host__ __device__ inline int mq_vjp_groups(int Q) { return Q < MQ_VJP_MAX_WG ? Q : MQ_VJP_MAX_WG; }
@@ -278,21 +261,9 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_logm_vjp_kernel(const doub
     const unsigned long long mk = j < Q ? (unsigned long long)mask[j] : 0ull;
     const unsigned long long vl = j < Q ? (unsigned long long)value[j] : 0ull;
     const double cj = j < Q ? c[j] : 1.0;
+    const auto allowed_of = [&](int k) { return ms_allowed(mk, vl, n, k); };
     __syncthreads();                                           // the query before this one is done with X, As and eEs
-    for (int i = t; i < DD; i += MS_ENV_THREADS) {
-      X[i] = i == 0 ? 1.0 : 0.0;
-      stack[(size_t)n * DD + i] = X[i];
-    }
-    if (t == 0) eEs[n] = 0;
-    int ex = 0;
-    for (int k = n; k >= 1; --k) {
-      const int allowed = ms_bit(mk, n, k) ? 1 << ms_bit(vl, n, k) : 3;
-      __syncthreads();
-      for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
-      __syncthreads();
-      ex += ms_env_step(true, D, allowed, As, X, T, red, stack + (size_t)(k - 1) * DD);
-      if (t == 0) eEs[k - 1] = ex;
-    }
+    const int ex = ms_env_sweep(cores, n, D, allowed_of, As, X, T, red, stack, [&](int slot, int e) { if (t == 0) eEs[slot] = e; });
     __syncthreads();                                           // publishes X, the stack and eEs
     const double aj = X[0];
     if (t == 0) {
@@ -307,26 +278,17 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_logm_vjp_kernel(const doub
     for (int i = t; i < DD; i += MS_ENV_THREADS) X[i] = i == 0 ? 1.0 : 0.0;
     int eL = 0;
     for (int k = 1; k <= n; ++k) {
-      const int allowed = ms_bit(mk, n, k) ? 1 << ms_bit(vl, n, k) : 3;
+      const int allowed = allowed_of(k);
       __syncthreads();                                         // the step before is done with As and T
-      for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+      ms_load_site_wg(cores, k, D, As);
       for (int i = t; i < DD; i += MS_ENV_THREADS) Em[i] = stack[(size_t)k * DD + i];
       __syncthreads();
-      for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
-        const int s = i / DD, a = (i % DD) / D, d = i % D;
-        if (!((allowed >> s) & 1)) continue;
-        double acc = 0.0;
-        for (int e = 0; e < D; ++e) acc = fma(As[s * DD + a * D + e], Em[e * D + d], acc);
-        T[i] = acc;
-      }
+      ms_mul_AX(D, allowed, As, Em, T);
       __syncthreads();
       const int sh = eL + eEs[k] - ex;
       for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
-        const int s = i / DD, a = (i % DD) / D, d = i % D;
-        if (!((allowed >> s) & 1)) continue;
-        double m = 0.0;
-        for (int e = 0; e < D; ++e) m = fma(X[a * D + e], T[s * DD + e * D + d], m);
-        const double term = ldexp(m * f, sh);
+        if (!((allowed >> (i / DD)) & 1)) continue;
+        const double term = ldexp(ms_env_chain(X, T, D, i) * f, sh);          // its own scaling: not ms_env_entry's rounding
         part[(size_t)(k - 1) * 2 * DD + i] += term + term;
       }
       __syncthreads();                                         // T is the step's scratch

@@ -127,13 +127,13 @@ __global__ __launch_bounds__(MS_ENV_THREADS) void mps_env_kernel(const double* _
   }
   if (t == 0) eo[right ? n : 0] = 0;
   int ex = 0;
-  for (int step = 0; step < n; ++step) {
+  for (int step = 0; step < n; ++step) {            // its own text, not ms_env_sweep: the direction is a run-time value (profiles/mps_env_core_isa.txt)
     const int k = right ? n - step : step + 1;       // the site whose matrices this step uses
     const int dst = right ? k - 1 : k;
     __syncthreads();
     for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
     __syncthreads();
-    ex += ms_env_step(right, D, 3, As, X, T, red, out + (long long)dst * DD);
+    ex += ms_env_step<true>(right, D, 3, As, X, T, red, out + (long long)dst * DD);
     if (t == 0) eo[dst] = ex;
   }
   __syncthreads();

@@ -1,5 +1,5 @@
-// The sampled-MPS kernels' one definition of their site sweeps (kernels_mps_sample.hip, kernels_mps_sample_gram.hip), so that
-// l^, r^, their exponents and mu are the same bits in every kernel because they are the same code.
+// The sampled-MPS kernels' one definition of their site sweeps (kernels_mps_sample.hip, _sample_gram.hip, _query.hip), so that
+// l^, r^, the environments, their exponents and mu are the same bits in every kernel because they are the same code.
 //
 // Wave sums and maxima, the padded bond dimension and its dispatch macro come from reduce_dev.hpp.
 //
@@ -18,14 +18,19 @@
 // Amplitude (ms_norm_ok, ms_amplitude_ok, ms_site_factor): a sample counts when r^_0[0] is finite and not 0 and E^_0[0, 0] is
 //   finite and positive; its factor at site k is g 2^(el_{k-1} + er_k - er_0), g = 2 w_b / r^_0[0] or 2 / r^_0[0] (0 when it does not count).
 //   log q = 2 log|psi| - log Z with the exponents kept apart (ms_logq).
-// Environment term (ms_env_stage, ms_env_entry; a workgroup of MS_ENV_THREADS per site): mu[k - 1][s][a][d] =
-//   2 (L_{k-1} A_k[s] E_k)[a][d] / Z as T_s = A_s E^_k, M_s = L^_{k-1} T_s, fma chains in index order through LDS, then
-//   2^(eL[k-1] + eE[k] - eE[0]) / E^_0[0, 0].
-// Environment step (ms_env_step; a workgroup of MS_ENV_THREADS, the matrix X and the site's A in LDS): X <- sum_s A[s] X A[s]^T
-//   (right) or sum_s A[s]^T X A[s] (left) over the ALLOWED s (bit s of `allowed`; a clamped site allows one, a disallowed s
-//   contributes no term), as T_s = A_s X (A_s^T X), X' = sum_s T_s A_s^T (T_s A_s), every entry one fma chain in index order
-//   (c, then s outer / d inner), then times 2^-e, e = ilogb of the largest magnitude, e returned.  mps_env_kernel's step
-//   (allowed = 3) and the clamped environments of kernels_mps_query.hip are this one function.
+// Workgroup level (MS_ENV_THREADS threads, D x D matrices of pitch D in LDS): ms_allowed, the s allowed at site k under an evidence
+//   as bits (3: free);  ms_load_site_wg;  ms_mul_AX: T[s] = A[s] X for the allowed s, and ms_env_chain: entry (s D + a) D + d of L T[s],
+//   one fma chain in index order each.  ms_mul_AX takes s = [i >= D D], the others divide i by D D: the same indices, each form the
+//   one at which its callers meet their timings (profiles/mps_env_core_isa.txt).
+// Environment term (ms_env_stage, ms_env_entry; one workgroup per site): mu[k - 1][s][a][d] = 2 (L_{k-1} A_k[s] E_k)[a][d] / Z
+//   as T_s = A_s E^_k (ms_mul_AX), M_s = L^_{k-1} T_s (ms_env_chain), then 2^(eL[k-1] + eE[k] - eE[0]) / E^_0[0, 0].
+// Environment step (ms_env_step): X <- sum_s A[s] X A[s]^T (right) or sum_s A[s]^T X A[s] (left) over the ALLOWED s, as T_s = A_s X
+//   (A_s^T X), X' = sum_s T_s A_s^T (T_s A_s), each entry one fma chain in index order (c, then s outer / d inner), then times 2^-e.
+//   T_s is ms_mul_AX on the right where `right` is a literal, and one loop with a select where it is a run-time value (ANY_DIR,
+//   mps_env_kernel): split, that kernel misses its timing, and unsplit the literal callers miss theirs (mps_env_core_isa.txt).
+// Environment sweep (ms_env_sweep): X = e0 e0^T (slot n, exponent 0); for k = n .. 1 the workgroup loads site k and steps (right) with
+//   allowed_of(k) into slot k - 1 of `out` (the stack, or null); store(slot, exponent sum) runs in every thread.  The clamped sweeps of
+//   kernels_mps_query.hip; mps_env_kernel, either direction by a run-time choice, keeps its own loop.
 // Sampler sweep (ms_sample_sweep): the site loop of bornvi_mps_sample, stated in kernels_mps_sample.hip, and with CLAMP the
 //   same loop under an evidence (mask, value): a clamped site takes the evidence's bit and ignores U_k.
 #pragma once
@@ -145,48 +150,61 @@ __device__ __forceinline__ double ms_site_factor(double g, int el, int erk, int 
 __device__ __forceinline__ double ms_logq(double a0, int e, double Zh, double eE0) {
   return (2.0 * log(fabs(a0)) - log(Zh)) + (2.0 * (double)e - eE0) * MS_LN2;
 }
-
-// site k's A (as stored, pitch D), E^_k, L^_{k-1} into LDS and T[s][c][d] = sum_e A[s][c][e] E^_k[e][d]; ends on a barrier
+__device__ __forceinline__ int ms_allowed(unsigned long long mask, unsigned long long value, int n, int k) {
+  return ms_bit(mask, n, k) ? 1 << ms_bit(value, n, k) : 3;
+}
+__device__ __forceinline__ void ms_load_site_wg(const double* cores, int k, int D, double* As) {
+  for (int DD = D * D, i = threadIdx.x; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+}
+__device__ __forceinline__ void ms_mul_AX(int D, int allowed, const double* As, const double* X, double* T) {      // T: the caller's next barrier
+  for (int DD = D * D, i = threadIdx.x; i < 2 * DD; i += MS_ENV_THREADS) {
+    const int s = i >= DD, r = i - s * DD, a = r / D, d = r % D;      // s is 0 or 1: a literal allowed = 3 leaves no test behind
+    if (!((allowed >> s) & 1)) continue;
+    double acc = 0.0;
+    for (int c = 0; c < D; ++c) acc = fma(As[s * DD + a * D + c], X[c * D + d], acc);
+    T[i] = acc;
+  }
+}
+__device__ __forceinline__ double ms_env_chain(const double* Lm, const double* T, int D, int i) {
+  const int DD = D * D, s = i / DD, a = (i % DD) / D, d = i % D;
+  double m = 0.0;
+  for (int c = 0; c < D; ++c) m = fma(Lm[a * D + c], T[s * DD + c * D + d], m);
+  return m;
+}
+// site k's A, E^_k, L^_{k-1} into LDS and T[s] = A[s] E^_k; ends on a barrier
 __device__ __forceinline__ void ms_env_stage(const double* cores, int k, int D, const double* E, const double* L, double* As, double* Em,
                                              double* Lm, double* T) {
-  const int t = threadIdx.x, DD = D * D;
-  for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) As[i] = cores[(long long)(k - 1) * 2 * DD + i];
+  const int DD = D * D, t = threadIdx.x;
+  ms_load_site_wg(cores, k, D, As);
   for (int i = t; i < DD; i += MS_ENV_THREADS) {
     Em[i] = E[(long long)k * DD + i];
     Lm[i] = L[(long long)(k - 1) * DD + i];
   }
   __syncthreads();
-  for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
-    const int s = i / DD, c = (i % DD) / D, d = i % D;
-    double acc = 0.0;
-    for (int e = 0; e < D; ++e) acc = fma(As[s * DD + c * D + e], Em[e * D + d], acc);
-    T[i] = acc;
-  }
+  ms_mul_AX(D, 3, As, Em, T);
   __syncthreads();
 }
 
 // entry i = (s D + a) D + d of mu[k - 1], after ms_env_stage; ex = eL[k - 1] + eE[k] - eE[0], Zh = E^_0[0, 0]
 __device__ __forceinline__ double ms_env_entry(const double* Lm, const double* T, int D, int i, double Zh, int ex) {
-  const int DD = D * D, s = i / DD, a = (i % DD) / D, d = i % D;
-  double m = 0.0;
-  for (int c = 0; c < D; ++c) m = fma(Lm[a * D + c], T[s * DD + c * D + d], m);
-  const double env = ldexp(m / Zh, ex);
+  const double env = ldexp(ms_env_chain(Lm, T, D, i) / Zh, ex);
   return env + env;
 }
 
-// One environment step of a workgroup of MS_ENV_THREADS.  As: the site's A[s][.][.] as stored (pitch D), X: the D x D matrix,
-// both in LDS and published by a barrier; T (2 D D doubles) and red (MS_ENV_THREADS / 64) are scratch.  X becomes the new
-// matrix times 2^-e and, where out is not null, goes to out too; e is returned.  X is published by the caller's next barrier.
+// As, X in LDS, published by a barrier; T (2 D D), red (one a wave): scratch.  The new X, times 2^-e, goes to out too where not null; e returned.
+template <bool ANY_DIR = false>
 __device__ __forceinline__ int ms_env_step(bool right, int D, int allowed, const double* As, double* X, double* T, double* red,
                                            double* out) {
   const int DD = D * D, t = threadIdx.x;
-  for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {
-    const int s = i / DD, a = (i % DD) / D, d = i % D;
-    if (!((allowed >> s) & 1)) continue;
-    double acc = 0.0;
-    for (int c = 0; c < D; ++c) acc = fma(right ? As[s * DD + a * D + c] : As[s * DD + c * D + a], X[c * D + d], acc);
-    T[i] = acc;
-  }
+  if (!ANY_DIR && right) ms_mul_AX(D, allowed, As, X, T);
+  else
+    for (int i = t; i < 2 * DD; i += MS_ENV_THREADS) {      // T_s = A_s^T X (A_s X)
+      const int s = i / DD, a = (i % DD) / D, d = i % D;
+      if (!((allowed >> s) & 1)) continue;
+      double acc = 0.0;
+      for (int c = 0; c < D; ++c) acc = fma(right ? As[s * DD + a * D + c] : As[s * DD + c * D + a], X[c * D + d], acc);
+      T[i] = acc;
+    }
   __syncthreads();
   double v[4];
   double mx = 0.0;
@@ -220,6 +238,26 @@ __device__ __forceinline__ int ms_env_step(bool right, int D, int allowed, const
     }
   }
   return e;
+}
+
+template <class Allowed, class Store>
+__device__ __forceinline__ int ms_env_sweep(const double* cores, int n, int D, Allowed&& allowed_of, double* As, double* X, double* T,
+                                            double* red, double* out, Store&& store) {
+  const int DD = D * D, t = threadIdx.x;
+  for (int i = t; i < DD; i += MS_ENV_THREADS) {
+    X[i] = i == 0 ? 1.0 : 0.0;
+    if (out) out[(long long)n * DD + i] = X[i];
+  }
+  store(n, 0);
+  int ex = 0;
+  for (int k = n; k >= 1; --k) {
+    __syncthreads();
+    ms_load_site_wg(cores, k, D, As);
+    __syncthreads();
+    ex += ms_env_step(true, D, allowed_of(k), As, X, T, red, out ? out + (long long)(k - 1) * DD : nullptr);
+    store(k - 1, ex);
+  }
+  return ex;
 }
 
 constexpr uint32_t MS_PHILOX_DOMAIN = 0xffffffffu;

@@ -30,6 +30,38 @@ from .ksd_vi import guarded_update, make_optimizer
 from .natural_gradient import CGFisherPreconditioner, SampledFisherPreconditioner, SampleSpaceFisherPreconditioner
 
 
+def checked_config(born_machine_config, allowed_keys, min_samples, max_samples, samples_range):
+    """(born_machine_config as a dict, its num_samples, default 1024), with the caller's own allowed keys and sample range."""
+    cfg = dict(born_machine_config or {})
+    unknown = set(cfg) - set(allowed_keys)
+    if unknown:
+        raise ValueError(f"born_machine_config: unknown keys {sorted(unknown)}")
+    B = cfg.get('num_samples', 1024)
+    if isinstance(B, bool) or not isinstance(B, int) or not min_samples <= B <= max_samples:
+        raise ValueError(f"num_samples must be an integer in {samples_range}, got {B!r}")
+    return cfg, B
+
+
+def make_sampled_optimizer(born_machine, lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas, sgd_momentum):
+    """make_optimizer's (optimiser, scheduler) for the machine's parameters; optimizer_type="sgd" takes the checked momentum."""
+    opt, sched = make_optimizer(born_machine.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas)
+    if optimizer_type != "adam":
+        if isinstance(sgd_momentum, bool) or not isinstance(sgd_momentum, (int, float)) or not 0 <= sgd_momentum < 1:
+            raise ValueError(f"sgd_momentum must be a number in [0, 1), got {sgd_momentum!r}")
+        for group in opt.param_groups:
+            group['momentum'] = float(sgd_momentum)
+    return opt, sched
+
+
+def host_update(loss_t, grad, born_machine, opt, sched, gradient_clip_norm, grad_norm):
+    """The epoch's host part: the loss read back, then guarded_update on the cores -> (loss as a float, grad_norm)."""
+    loss = float(loss_t.item())                       # the epoch's host synchronisation
+    cores = born_machine.cores
+    grad_norm = guarded_update(born_machine, opt, sched, loss, [(cores, grad.to(device=cores.device, dtype=cores.dtype))],
+                               gradient_clip_norm, grad_norm)
+    return loss, grad_norm
+
+
 class SampledTrainer:
     LOSS_KEYS = ()
     MIN_SAMPLES = 1
@@ -38,13 +70,8 @@ class SampledTrainer:
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu',
                  p_floor=1e-30, natural_gradient=None):
-        cfg = dict(born_machine_config or {})
-        unknown = set(cfg) - {'bond_dim', 'num_samples', 'seed', 'init_method'}
-        if unknown:
-            raise ValueError(f"born_machine_config: unknown keys {sorted(unknown)}")
-        B = cfg.get('num_samples', 1024)
-        if isinstance(B, bool) or not isinstance(B, int) or not self.MIN_SAMPLES <= B <= self.MAX_SAMPLES:
-            raise ValueError(f"num_samples must be an integer in {self.SAMPLES_RANGE}, got {B!r}")
+        cfg, B = checked_config(born_machine_config, ('bond_dim', 'num_samples', 'seed', 'init_method'), self.MIN_SAMPLES,
+                                self.MAX_SAMPLES, self.SAMPLES_RANGE)
         if isinstance(p_floor, bool) or not isinstance(p_floor, (int, float)) or not np.isfinite(p_floor) or not p_floor > 0:
             raise ValueError(f"p_floor must be a positive finite number, got {p_floor!r}")
         self.bn = bayesian_network
@@ -119,12 +146,7 @@ class SampledTrainer:
             raise ValueError("Keys in x_observation_dict must match self.observed_vars_names.")
         bm = self.born_machine
         self._prepare_observation(x_observation_dict)
-        opt, sched = make_optimizer(bm.parameters(), lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas)
-        if optimizer_type != "adam":
-            if isinstance(sgd_momentum, bool) or not isinstance(sgd_momentum, (int, float)) or not 0 <= sgd_momentum < 1:
-                raise ValueError(f"sgd_momentum must be a number in [0, 1), got {sgd_momentum!r}")
-            for group in opt.param_groups:
-                group['momentum'] = float(sgd_momentum)
+        opt, sched = make_sampled_optimizer(bm, lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas, sgd_momentum)
         exact = true_posterior_for_tvd is not None and self.num_latent_vars <= backend.MPS_MAX_N
         history = {k: [] for k in self.LOSS_KEYS + ('grad_norm', 'logq_mean', 'status')}
         if exact:
@@ -138,9 +160,7 @@ class SampledTrainer:
         for epoch in range(num_epochs):
             opt.zero_grad()
             loss_t, grad, lq_t, st_t = self.loss_and_grad(epoch)
-            loss = float(loss_t.item())                       # the epoch's host synchronisation
-            grads = [(bm.cores, grad.to(device=bm.cores.device, dtype=bm.cores.dtype))]
-            grad_norm = guarded_update(bm, opt, sched, loss, grads, gradient_clip_norm, grad_norm)
+            loss, grad_norm = host_update(loss_t, grad, bm, opt, sched, gradient_clip_norm, grad_norm)
             self.record_loss(history, loss)
             history['grad_norm'].append(grad_norm.item() if grad_norm is not None else 0.0)
             history['logq_mean'].append(float(lq_t.item()))
