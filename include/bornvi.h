@@ -20,19 +20,21 @@
  *   - outcome index i <-> bitstring bin(i).zfill(n): bit position 0 of the tuple is the MOST
  *     significant bit of i and is wire 0 of the circuit (utils.py:77-91).
  *   - accepted n per entry point (anything else is refused with BORNVI_ERR_UNSUPPORTED or
- *     BORNVI_ERR_INVALID before any launch):
+ *     BORNVI_ERR_INVALID before any launch); the BORNVI_* limits are defined below, once, for the
+ *     library and for every binding (the Python one reads this file):
  *       circuits, parameter shift (probs, grad, fused dot), adjoint engine,
- *       matrix-free Stein mat-vec ................................. 1 <= n <= 29
+ *       matrix-free Stein mat-vec ................................. 1 <= n <= BORNVI_CIRCUIT_MAX_N
  *         (plan tile and workgroup indices are 16 bits, tiles at most 2^13 amplitudes;
  *          the 8-amplitude kernel runs n <= 27, the larger states the generic pass kernel);
- *       dense Gram and quadratic forms ............................ 1 <= n <= 17;
+ *       dense Gram and quadratic forms ............................ 1 <= n <= BORNVI_DENSE_MAX_N;
  *       score from CPTs, k_p pairs, gradient assembly, shots,
- *       ELBO weights, Fisher matrix ............................... 1 <= n <= 30;
- *       probability-table Born machine ............................ 0 <= n <= 30;
- *       matrix-product-state Born machine (bond 1 <= D <= 32) ..... 1 <= n <= 26;
+ *       ELBO weights, Fisher matrix ............................... 1 <= n <= BORNVI_TABLE_MAX_N;
+ *       probability-table Born machine ............................ 0 <= n <= BORNVI_TABLE_MAX_N;
+ *       matrix-product-state Born machine
+ *         (bond 1 <= D <= BORNVI_MPS_MAX_BOND) .................... 1 <= n <= BORNVI_MPS_MAX_N;
  *       sampled MPS calls, the MPS canonicaliser, log joint and scores of samples,
- *       pairwise Stein kernel row sums (n * length_scale >= 1) ..... 1 <= n <= 63;
- *       un-fused gate application ................................. 1 <= n <= 40.
+ *       pairwise Stein kernel row sums (n * length_scale >= 1) ..... 1 <= n <= BORNVI_MPS_SAMPLED_MAX_N;
+ *       un-fused gate application ................................. 1 <= n <= BORNVI_GATE_MAX_N.
  */
 #ifndef BORNVI_H
 #define BORNVI_H
@@ -49,6 +51,33 @@ extern "C" {
 #endif
 
 #define BORNVI_VERSION 100 /* 0.1.0 */
+
+/* ---- limits: each accepted range is stated here and nowhere else.  The library's argument checks, the kernels' own
+ * bounds and the Python binding (which parses these lines) all use these names.  Plain decimal integers, so that a
+ * binding can read them without evaluating C. */
+#define BORNVI_CIRCUIT_MAX_N 29               /* circuits, parameter shift, adjoint engine, matrix-free mat-vec: n - 13 <= 16 */
+#define BORNVI_DENSE_MAX_N 17                 /* dense Gram and quadratic forms: 8 * 4^n bytes */
+#define BORNVI_DENSE_MAX_LD_PAD 4096          /* the `_ld` calls: 2^n <= ld <= 2^n + this, ld even */
+#define BORNVI_TABLE_MAX_N 30                 /* everything that walks a table of 2^n entries */
+#define BORNVI_GATE_MAX_N 40                  /* un-fused gate application */
+#define BORNVI_BN_MAX_NODES 64                /* nodes of a network descriptor: one bit each of a 64-bit word */
+#define BORNVI_BORN_TABLE_MAX_ROWS 65535      /* 2^16 - 1: rows of the probability-table Born machine */
+#define BORNVI_ELBO_MAX_ROWS 65535            /* 2^16 - 1: rows of bornvi_elbo_weights */
+#define BORNVI_REINFORCE_MAX_BATCH 16777216   /* 2^24: samples of bornvi_reinforce_step */
+#define BORNVI_SHOTS_MAX 2147483647           /* 2^31 - 1: shots of bornvi_shots_histogram */
+#define BORNVI_MPS_MAX_N 26                   /* the enumerated MPS Born machine */
+#define BORNVI_MPS_MAX_BOND 32                /* bond dimension D of every MPS call */
+#define BORNVI_MPS_SAMPLED_MAX_N 63           /* the sampled MPS calls and the per-sample network calls: an int64 outcome index */
+#define BORNVI_MPS_SAMPLED_MAX_BATCH 16777216 /* 2^24: samples per call, and the largest score-row pitch ld */
+#define BORNVI_SCORE_MIN_LD 64                /* score-row pitch: a power of two, >= this and >= B */
+#define BORNVI_MPS_QUERY_MAX_QUERIES 65536    /* 2^16: evidences per log-marginal call */
+#define BORNVI_STEIN_PAIRS_MAX_B 131072       /* 2^17: samples of the pairwise Stein kernel; B^2 is the cost, 1.7e10 pairs here */
+#define BORNVI_FISHER_MAX_PARAMS 1024         /* rows of a Fisher / QFI / score Gram block, order of an SPD solve */
+#define BORNVI_SAMPLE_GRAM_MAX_BATCH 1024     /* samples of the sample-space Gram: what bornvi_spd_solve factors */
+#define BORNVI_SPD_BATCHED_MAX_SYSTEMS 65535  /* 2^16 - 1: systems of bornvi_spd_solve_batched */
+#define BORNVI_SCORE_FISHER_MAX_BLOCKS 65535  /* 2^16 - 1: blocks of bornvi_score_fisher_gram */
+#define BORNVI_CG_MAX_PARAMS 2147483647       /* 2^31 - 1: vector length of the CG recurrence */
+#define BORNVI_CG_STATE_DOUBLES 8             /* doubles of the CG state the caller allocates and the kernels write */
 
 typedef struct bornvi_ctx* bornvi_handle;
 typedef void* bornvi_stream; /* hipStream_t */
@@ -97,9 +126,10 @@ const char* bornvi_last_error(bornvi_handle h);
  * bornvi_paramshift_probs* a shifted circuit starts from the base circuit's state at the first pass
  * its parameter touches instead of |0..0> -- the rows are bit-identical, fewer passes are run). */
 int bornvi_set_option(bornvi_handle h, const char* name, long long value);
-/* Current value of a planner / engine option ("reg_wires": 3 = the pass kernel with 8 amplitudes per thread and four waves
- * per SIMD where the plan is eligible, 4 = 16 per thread; "read_map", "contig_out", "tile_bits", "tile_bits_multi", "low_bits",
- * "prefix_share", "grad_engine", "fast_path", "direct_stages", "zero_support", "alternate_walk", "batched_quadform"). */
+/* Current value of a planner / engine option: every name bornvi_set_option takes can be read back (one table in the
+ * library drives both calls; "workgroups_per_cu" and "max_threads" could be set but not read before that table existed).
+ * "reg_wires": 3 = the pass kernel with 8 amplitudes per thread and four waves per SIMD where the plan is eligible,
+ * 4 = 16 per thread. */
 int bornvi_get_option(bornvi_handle h, const char* name, long long* value);
 
 /* num_ansatz_params (quantum_born_machine.py:31-38) and gate count of the QNode. */
@@ -223,7 +253,6 @@ int bornvi_bn_score_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, lo
  * are bitwise equal; no allocation or synchronisation: capturable.
  * 1 <= n <= 63, 2 <= B <= BORNVI_STEIN_PAIRS_MAX_B, n * length_scale >= 1 (in double), else BORNVI_ERR_UNSUPPORTED,
  * returned before any launch. */
-#define BORNVI_STEIN_PAIRS_MAX_B (1 << 17)
 size_t bornvi_stein_pairs_workspace_bytes(bornvi_handle h, int n, long long B);
 int bornvi_stein_pairs_rowsum(bornvi_handle h, int n, long long B, double length_scale, const long long* idx,
                               const double* S, double* r, double* total, void* workspace, size_t workspace_bytes,

@@ -9,15 +9,13 @@ collectives all come from PyTorch.
 """
 import ctypes as C
 import os
+import re
 
 import torch  # noqa: F401  (must precede loading the HIP library, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libbornvi_hip.so"
 LIB_PATH = os.environ.get("BORNVI_LIB") or os.path.join(_HERE, LIB_NAME)   # BORNVI_LIB: a tuning build of the same library
-
-BORNVI_OK = 0
-ANSATZ_IDS = {"hardware_efficient": 0, "all_to_all": 1, "basic": 2}
 
 _lib = None
 
@@ -32,170 +30,56 @@ class BnDesc(C.Structure):
                 ("cpt_off", C.c_void_p), ("cpt", C.c_void_p)]
 
 
-_PROTOS = {
-    # name: (restype, argtypes)
-    "bornvi_version": (C.c_int, []),
-    "bornvi_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
-    "bornvi_destroy": (None, [C.c_void_p]),
-    "bornvi_last_error": (C.c_char_p, [C.c_void_p]),
-    "bornvi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_longlong]),
-    "bornvi_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_longlong)]),
-    "bornvi_num_params": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "bornvi_num_gates": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "bornvi_circuit_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bornvi_circuit_probs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_paramshift_probs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                          C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_paramshift_probs_strided": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_paramshift_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bornvi_paramshift_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                         C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_paramshift_dot_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bornvi_paramshift_dot_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_paramshift_dot_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_gate1q_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_int,
-                                      C.POINTER(C.c_double), C.c_void_p]),
-    "bornvi_cnot_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "bornvi_born_probs": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_score_from_cpts": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_stein_gram_build": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_stein_gram_build_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_longlong, C.c_longlong,
-                                               C.c_void_p, C.c_void_p]),
-    "bornvi_stein_gram_ld": (C.c_longlong, [C.c_int]),
-    "bornvi_stein_gram_build_rows_ld": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_longlong, C.c_longlong,
-                                                  C.c_void_p, C.c_longlong, C.c_void_p]),
-    "bornvi_stein_quadform_sym_ld": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_stein_quadform_sym_pairs_ld": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong,
-                                                     C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                     C.c_void_p]),
-    "bornvi_stein_quadform_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_stein_kp_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_longlong, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_stein_quadform_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_stein_quadform": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_stein_quadform_ld": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_stein_quadform_sym_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "bornvi_stein_quadform_sym": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_stein_sym_strip_rows": (C.c_int, []),
-    "bornvi_stein_quadform_sym_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_stein_matvec_kron_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "bornvi_stein_matvec_kron": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_ksd_grad_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_shots_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_shots_histogram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_ulonglong,
-                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_born_table_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_born_table_probs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_born_table_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_reinforce_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
-    "bornvi_reinforce_step": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_elbo_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_elbo_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_mps_probs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                 C.c_void_p]),
-    "bornvi_mps_sample_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_longlong]),
-    "bornvi_mps_environments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_size_t, C.c_void_p]),
-    "bornvi_mps_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_ulonglong, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_score_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_bn_logjoint_samples": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_longlong, C.c_void_p, C.c_double,
-                                             C.c_void_p, C.c_void_p]),
-    "bornvi_bn_score_samples": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_longlong, C.c_void_p, C.c_double,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_stein_pairs_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_longlong]),
-    "bornvi_stein_pairs_rowsum": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_stein_pairs_geometry": (C.c_int, [C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "bornvi_fisher_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_fisher_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
-                                     C.c_size_t, C.c_void_p]),
-    "bornvi_spd_solve_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "bornvi_spd_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_size_t, C.c_void_p]),
-    "bornvi_spd_solve_batched_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_spd_solve_batched": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_score_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                        C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_score_sample_gram_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_longlong]),
-    "bornvi_mps_score_sample_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_score_jvp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_query_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "bornvi_mps_log_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_mps_sample_clamped": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_size_t, C.c_void_p]),
-    "bornvi_mps_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                       C.c_void_p]),
-    "bornvi_mps_canon_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_mps_canonicalise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_bn_sample": (C.c_int, [C.c_void_p, C.POINTER(BnDesc), C.c_int, C.c_longlong, C.c_ulonglong, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_mps_log_marginals_vjp_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "bornvi_mps_log_marginals_vjp_geometry": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
-    "bornvi_mps_log_marginals_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_cg_init": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p]),
-    "bornvi_cg_step": (C.c_int, [C.c_void_p, C.c_longlong, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p]),
-    "bornvi_cg_finish": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]),
-    "bornvi_score_fisher_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_longlong]),
-    "bornvi_score_fisher_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_paramshift_states_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bornvi_paramshift_states": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_qfi_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "bornvi_qfi_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                  C.c_void_p]),
-    "bornvi_clip_cast_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_clip_adam_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
-                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_clip_cast_grad_guard": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bornvi_adjoint_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "bornvi_adjoint_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_size_t, C.c_void_p]),
-    "bornvi_adjoint_vjp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bornvi_plan_describe": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]),
-    "bornvi_plan_param_first_pass": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
-    "bornvi_plan_fast_describe": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
-                                                 C.POINTER(C.c_uint32), C.c_int]),
-    "bornvi_plan_compact_describe": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
-                                                    C.POINTER(C.c_uint32), C.c_int]),
-}
+# include/bornvi.h is the one statement of the ABI: prototypes, status and ansatz codes and every BORNVI_* limit are read
+# from it.  The header keeps to a narrow subset of C (block comments, plain `#define NAME <decimal>`, two enums with
+# explicit values, typedefs, declarations `ret bornvi_name(args);`), and the parser refuses what lies outside it.
+_TYPES = {"int": C.c_int, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "size_t": C.c_size_t,
+          "double": C.c_double, "bornvi_handle": C.c_void_p, "bornvi_stream": C.c_void_p, "const char*": C.c_char_p,
+          "const bornvi_bn_desc*": C.POINTER(BnDesc), "bornvi_handle*": C.POINTER(C.c_void_p)}
 
-EXPORTED_SYMBOLS = tuple(_PROTOS)
+
+def _ctype(text, decl, is_return=False):
+    t = re.sub(r"\s*\*", "*", " ".join(text.split()))
+    if t in _TYPES:
+        return _TYPES[t]
+    if is_return and t == "void":
+        return None
+    if re.fullmatch(r"[\w ]+\*", t):      # every other pointer: device memory, or a host array passed by reference
+        return C.c_void_p
+    raise BornviError(f"bornvi.h: no ctypes mapping for type '{t}' in declaration '{' '.join(decl.split())}'")
+
+
+def parse_header(text):
+    """(defines, enums, prototypes) of the header text: {BORNVI_NAME: int} of the #define lines, {NAME: int} of the enums,
+    {symbol: (restype, argtypes)} in declaration order."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(BORNVI_\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    enums = {}
+    for body in re.findall(r"typedef\s+enum\s*\{(.*?)\}", text, re.S):
+        enums.update((m[1], int(m[2])) for m in re.finditer(r"(\w+)\s*=\s*(-?\d+)", body))
+    text = re.sub(r"typedef\s+(enum|struct)\s*\{.*?\}\s*\w+\s*;|typedef\s[^;{]*;", "", text, flags=re.S)
+    protos = {}
+
+    def declaration(m):
+        args = [] if m[3].strip() == "void" else [_ctype(re.sub(r"\w+\s*$", "", a), m[0]) for a in m[3].split(",")]
+        protos[m[2]] = (_ctype(m[1], m[0], is_return=True), args)
+        return ""
+    rest = re.sub(r"([\w \t\n*]+?)\b(bornvi_\w+)\s*\(([^()]*)\)\s*;", declaration, text)
+    if "".join(rest.split()) not in ("", 'extern"C"{}'):
+        raise BornviError(f"bornvi.h: text the binding cannot read: '{' '.join(rest.split())[:200]}'")
+    return defines, enums, protos
+
+
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi.h")
+if not os.path.exists(HEADER_PATH):
+    raise BornviError(f"{HEADER_PATH} not found: the binding reads the C ABI from it")
+with open(HEADER_PATH) as _f:
+    LIMITS, _ENUMS, PROTOTYPES = parse_header(_f.read())      # LIMITS: every `#define BORNVI_*` integer of the header
+
+BORNVI_OK = _ENUMS["BORNVI_OK"]
+ANSATZ_IDS = {k: _ENUMS["BORNVI_ANSATZ_" + k.upper()] for k in ("hardware_efficient", "all_to_all", "basic")}
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 
 def lib():
@@ -207,7 +91,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in PROTOTYPES.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -24,7 +24,7 @@ from .utils import generate_all_binary_outcomes
 
 class AmortisedMPSInference:
     MAX_SITES = backend.MPS_SAMPLED_MAX_N
-    MAX_ENUMERATED_OBSERVED = 16                # 2^16 evidences: what one mps_log_marginals_vjp call takes
+    MAX_ENUMERATED_OBSERVED = backend.MPS_QUERY_MAX_QUERIES.bit_length() - 1    # 2^16 evidences: one mps_log_marginals_vjp call
     OBJECTIVES = ('joint', 'conditional')
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu'):

@@ -118,7 +118,7 @@ def _evidence_args(mask, value, dev, count=None):
 
 # Largest n of the circuit engines (circuits, parameter shift, fused dot, adjoint) and of the matrix-free Stein mat-vec:
 # the planner's tile and workgroup indices are 16 bits and its tiles hold at most 2^13 amplitudes (include/bornvi.h).
-CIRCUIT_MAX_N = 29
+CIRCUIT_MAX_N = _ext.LIMITS["BORNVI_CIRCUIT_MAX_N"]
 
 
 def _chk_n(n, lo=1, hi=30):
@@ -447,7 +447,7 @@ def born_probs(state, n):
 
 
 # ---- classical Born machine (probability table) ------------------------------------------------------------
-BORN_TABLE_MAX_ROWS = 65535
+BORN_TABLE_MAX_ROWS = _ext.LIMITS["BORNVI_BORN_TABLE_MAX_ROWS"]
 
 
 def _born_table_args(w, mode):
@@ -518,7 +518,7 @@ def born_table_vjp(w, q64, mode, y=None, ksd2=None, entropy_weight=0.0, out=None
     return out
 
 
-REINFORCE_MAX_BATCH = 1 << 24
+REINFORCE_MAX_BATCH = _ext.LIMITS["BORNVI_REINFORCE_MAX_BATCH"]
 
 
 def reinforce_step(idx, logit, log_p, q32, baseline, first, baseline_decay, entropy_coef=0.01, q_floor=1e-10, out=None,
@@ -568,7 +568,7 @@ def reinforce_step(idx, logit, log_p, q32, baseline, first, baseline_decay, entr
 
 
 # ---- exact ELBO ---------------------------------------------------------------------------------------
-ELBO_MAX_ROWS = 65535
+ELBO_MAX_ROWS = _ext.LIMITS["BORNVI_ELBO_MAX_ROWS"]
 
 
 def elbo_weights(q, log_p, q_floor=1e-10, want_w=True, want_entropy=True, out=None):
@@ -610,8 +610,8 @@ def elbo_weights(q, log_p, q_floor=1e-10, want_w=True, want_entropy=True, out=No
 
 
 # ---- matrix-product-state Born machine -------------------------------------------------------------------
-MPS_MAX_N = 26
-MPS_MAX_BOND = 32
+MPS_MAX_N = _ext.LIMITS["BORNVI_MPS_MAX_N"]
+MPS_MAX_BOND = _ext.LIMITS["BORNVI_MPS_MAX_BOND"]
 
 
 _ENUMERATED = object()
@@ -668,8 +668,8 @@ def mps_vjp(cores, g, out=None):
 
 
 # ---- sampled MPS Born machine (no 2^n object) -------------------------------------------------------------
-MPS_SAMPLED_MAX_N = 63
-MPS_SAMPLED_MAX_BATCH = 1 << 24
+MPS_SAMPLED_MAX_N = _ext.LIMITS["BORNVI_MPS_SAMPLED_MAX_N"]
+MPS_SAMPLED_MAX_BATCH = _ext.LIMITS["BORNVI_MPS_SAMPLED_MAX_BATCH"]
 
 
 def _mps_sampled_ws(h, dev, n, D, B):
@@ -733,7 +733,7 @@ def mps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
 
 
 # ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ----------------------------------------------
-MPS_QUERY_MAX_QUERIES = 1 << 16
+MPS_QUERY_MAX_QUERIES = _ext.LIMITS["BORNVI_MPS_QUERY_MAX_QUERIES"]
 
 
 def _mps_query_ws(h, dev, n, D, Q):
@@ -907,7 +907,7 @@ def mps_log_marginals_vjp(cores, mask, value, c, out=None, out_logm=None, status
 
 
 # ---- sampled KSD: scores of p at sampled states, pairwise Stein kernel row sums -----------------------------
-STEIN_PAIRS_MAX_BATCH = 1 << 17
+STEIN_PAIRS_MAX_BATCH = _ext.LIMITS["BORNVI_STEIN_PAIRS_MAX_B"]
 
 
 def bn_score_samples(desc, n, idx, p_floor=1e-30, out=None, want_logp=False):
@@ -970,7 +970,7 @@ def stein_pairs_rowsum(idx, S, n, length_scale=1.0, out=None, total=None):
 
 
 # ---- natural gradient ---------------------------------------------------------------------------------
-FISHER_MAX_PARAMS = 1024
+FISHER_MAX_PARAMS = _ext.LIMITS["BORNVI_FISHER_MAX_PARAMS"]
 
 
 def _chk_positive(v, name, allow_zero=False):
@@ -1143,7 +1143,7 @@ def score_fisher_gram(rows, num_samples, out=None):
     return out
 
 
-SAMPLE_GRAM_MAX_BATCH = FISHER_MAX_PARAMS           # T is [B, B] and spd_solve factors it
+SAMPLE_GRAM_MAX_BATCH = _ext.LIMITS["BORNVI_SAMPLE_GRAM_MAX_BATCH"]           # T is [B, B] and spd_solve factors it
 
 
 def mps_score_sample_gram_workspace_bytes(dev, n, D, num_samples):
@@ -1175,8 +1175,8 @@ def mps_score_sample_gram(cores, idx, out=None, status=None):
 
 
 # ---- matrix-free natural gradient of the sampled MPS Born machine: O v, and conjugate gradients around a product ----
-CG_MAX_PARAMS = (1 << 31) - 1
-CG_STATE_DOUBLES = 8
+CG_MAX_PARAMS = _ext.LIMITS["BORNVI_CG_MAX_PARAMS"]
+CG_STATE_DOUBLES = _ext.LIMITS["BORNVI_CG_STATE_DOUBLES"]
 
 
 def mps_score_jvp(cores, idx, v, scale=1.0, out=None, status=None):
@@ -1347,7 +1347,7 @@ def qfi_gram(phi, psi, out=None):
 
 
 # ---- finite shots -------------------------------------------------------------------------------------
-SHOTS_MAX = (1 << 31) - 1
+SHOTS_MAX = _ext.LIMITS["BORNVI_SHOTS_MAX"]
 
 
 def shots_histogram(probs, n, shots, seed, epoch, include_base=True, p_begin=0, p_stride=1, out=None):

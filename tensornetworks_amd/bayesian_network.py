@@ -17,7 +17,7 @@ import numpy as np
 
 from .utils import generate_all_binary_outcomes
 
-MAX_PARENTS = 8
+MAX_PARENTS = 8     # row length pack_network gives `parents`; the library takes any (bornvi_bn_desc.max_parents), so it is set here
 
 
 class BayesianNetwork:

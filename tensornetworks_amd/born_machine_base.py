@@ -46,7 +46,7 @@ def bits_to_indices(z_samples, n, device=None):
     return (z << torch.arange(n - 1, -1, -1, device=z.device)).sum(dim=1)
 
 
-MAX_EVIDENCE_QUERIES = 1 << 16      # what one bornvi_mps_log_marginals call takes
+MAX_EVIDENCE_QUERIES = backend.MPS_QUERY_MAX_QUERIES      # what one bornvi_mps_log_marginals call takes
 
 
 def pack_evidence(evidence, n):

@@ -517,8 +517,75 @@ int get_adj_plan(bornvi_handle h, int ansatz, int n, int layers, AdjPlan** out) 
   return BORNVI_OK;
 }
 
-bool valid_n_for_dense(int n) { return n >= 1 && n <= 17; }
-bool valid_ld(int n, long long ld) { return ld >= (1ll << n) && (ld & 1) == 0 && ld <= (1ll << n) + 4096; }
+// ---- ranges: one predicate per accepted range, in terms of bornvi.h's limits, and beside it the one text that refuses it.
+bool valid_table_n(int n) { return n >= 1 && n <= BORNVI_TABLE_MAX_N; }
+bool valid_gate_n(int n) { return n >= 1 && n <= BORNVI_GATE_MAX_N; }
+
+bool valid_n_for_dense(int n) { return n >= 1 && n <= BORNVI_DENSE_MAX_N; }
+const char* const DENSE_RANGE = "dense Gram supports 1 <= n <= 17";
+const char* const DENSE_BUILD_RANGE = "dense Gram supports 1 <= n <= 17 (8 * 4^n bytes)";
+bool valid_ld(int n, long long ld) { return ld >= (1ll << n) && (ld & 1) == 0 && ld <= (1ll << n) + BORNVI_DENSE_MAX_LD_PAD; }
+const char* const DENSE_LD_RANGE = "leading dimension must be even, >= 2^n and <= 2^n + 4096";
+// The dense calls without `ld` pass ld = 2^n on to their `_ld` form, which checks everything: only an n that cannot be
+// shifted is refused in front of it, in the callee's words.
+bool shiftable_n(int n) { return n >= 0 && n <= BORNVI_GATE_MAX_N; }
+int refuse_dense_n(bornvi_handle h, const char* range) { return h ? fail(h, BORNVI_ERR_UNSUPPORTED, range) : BORNVI_ERR_INVALID; }
+
+// parameters p_begin, p_begin + p_stride, ... (p_count of them) of a circuit with P parameters (P < 0: unknown ansatz)
+bool valid_param_range(int P, int p_begin, int p_count, int p_stride) {
+  return P >= 0 && p_begin >= 0 && p_count >= 0 && p_stride >= 1 &&
+         (p_count == 0 || (long long)p_begin + (long long)(p_count - 1) * p_stride < P);
+}
+const char* const PARAM_RANGE = "parameter range out of bounds";
+
+bool valid_bn_desc(const bornvi_bn_desc* bn) {
+  return bn->num_nodes >= 1 && bn->num_nodes <= BORNVI_BN_MAX_NODES && bn->max_parents >= 1 && bn->role && bn->n_parents &&
+         bn->parents && bn->cpt_off && bn->cpt;
+}
+const char* const BN_DESC = "bad network descriptor";
+
+// ---- options: one row per name, read by bornvi_set_option and bornvi_get_option alike.  An option lives either in the
+// handle (an engine switch) or in the planner's options; setting one of the latter clears the plan cache.
+enum OptionValues {
+  OPT_ANY,        // stored as given
+  OPT_BOOL,       // stored as value != 0
+  OPT_TRISTATE,   // stored as -1 (value < 0), 0 or 1
+  OPT_RANGE,      // lo <= value <= hi, else refused
+  OPT_RANGE_OR_0, // the same, or 0
+  OPT_RANGE_POW2, // the same and a power of two
+};
+struct Option {
+  const char* name;
+  int bornvi_ctx::*in_ctx;       // where it lives: in the handle ...
+  int PlanOptions::*in_plan;     // ... or in the planner's options (exactly one of the two is set)
+  OptionValues values;
+  long long lo, hi;              // OPT_RANGE*: the accepted values,
+  const char* refusal;           // and what a value outside them is told
+};
+const char* const OPTION_RANGE = "option value out of range";
+const Option OPTIONS[] = {
+    {"workgroups_per_cu", &bornvi_ctx::wgs_per_cu, nullptr, OPT_RANGE, 0, 16, OPTION_RANGE},
+    {"fast_workgroups_per_cu", &bornvi_ctx::fast_wgs_per_cu, nullptr, OPT_RANGE, 0, 16, OPTION_RANGE},
+    {"fast_path", &bornvi_ctx::fast_path, nullptr, OPT_BOOL, 0, 0, nullptr},
+    {"prefix_share", &bornvi_ctx::prefix_share, nullptr, OPT_ANY, 0, 0, nullptr},
+    {"batched_quadform", &bornvi_ctx::batched_quadform, nullptr, OPT_BOOL, 0, 0, nullptr},
+    {"grad_engine", &bornvi_ctx::grad_engine, nullptr, OPT_RANGE, 0, 1, "grad_engine: 0 = parameter shift, 1 = adjoint"},
+    {"zero_support", &bornvi_ctx::zero_support, nullptr, OPT_BOOL, 0, 0, nullptr},
+    {"alternate_walk", &bornvi_ctx::alternate_walk, nullptr, OPT_BOOL, 0, 0, nullptr},
+    {"direct_stages", &bornvi_ctx::direct_stages, nullptr, OPT_ANY, 0, 0, nullptr},   // bits 2..: 1 + the only pass allowed (debug)
+    {"tile_bits", nullptr, &PlanOptions::kmax, OPT_RANGE, 4, 13, OPTION_RANGE},       // (sets "tile_bits_multi" too)
+    {"tile_bits_multi", nullptr, &PlanOptions::kmulti, OPT_RANGE_OR_0, 4, 13, OPTION_RANGE},
+    {"low_bits", nullptr, &PlanOptions::lo, OPT_RANGE, 0, 8, OPTION_RANGE},
+    {"max_threads", nullptr, &PlanOptions::max_threads, OPT_RANGE_POW2, 64, 1024, OPTION_RANGE},
+    {"read_map", nullptr, &PlanOptions::read_map, OPT_TRISTATE, 0, 0, nullptr},       // -1: by the kernel (on with reg_wires = 3)
+    {"reg_wires", nullptr, &PlanOptions::r, OPT_RANGE, 3, 4, OPTION_RANGE},
+    {"contig_out", nullptr, &PlanOptions::contig_out, OPT_BOOL, 0, 0, nullptr},
+};
+const Option* find_option(const char* name) {
+  for (const Option& o : OPTIONS)
+    if (!std::strcmp(name, o.name)) return &o;
+  return nullptr;
+}
 
 }  // namespace
 
@@ -560,40 +627,23 @@ const char* bornvi_last_error(bornvi_handle h) { return h ? h->err.c_str() : g_c
 
 int bornvi_set_option(bornvi_handle h, const char* name, long long value) {
   if (!h || !name) return BORNVI_ERR_INVALID;
-  if (!std::strcmp(name, "workgroups_per_cu")) {
-    if (value < 0 || value > 16) return fail(h, BORNVI_ERR_INVALID, "option value out of range");
-    h->wgs_per_cu = (int)value;
+  const Option* o = find_option(name);
+  if (!o) return fail(h, BORNVI_ERR_INVALID, std::string("unknown option ") + name);
+  int v = (int)value;
+  if (o->values == OPT_BOOL) v = value != 0;
+  else if (o->values == OPT_TRISTATE) v = value < 0 ? -1 : (value != 0 ? 1 : 0);
+  else if (o->values != OPT_ANY) {
+    const long long c = o->in_plan ? (long long)v : value;    // (a planner option has always been narrowed to int before its check)
+    const bool ok = (c >= o->lo && c <= o->hi && (o->values != OPT_RANGE_POW2 || (c & (c - 1)) == 0)) ||
+                    (o->values == OPT_RANGE_OR_0 && c == 0);
+    if (!ok) return fail(h, BORNVI_ERR_INVALID, o->refusal);
+  }
+  if (o->in_ctx) {
+    h->*(o->in_ctx) = v;
     return BORNVI_OK;
   }
-  if (!std::strcmp(name, "fast_path")) { h->fast_path = value ? 1 : 0; return BORNVI_OK; }
-  if (!std::strcmp(name, "prefix_share")) { h->prefix_share = (int)value; return BORNVI_OK; }
-  if (!std::strcmp(name, "batched_quadform")) { h->batched_quadform = value ? 1 : 0; return BORNVI_OK; }
-  if (!std::strcmp(name, "grad_engine")) {
-    if (value != 0 && value != 1) return fail(h, BORNVI_ERR_INVALID, "grad_engine: 0 = parameter shift, 1 = adjoint");
-    h->grad_engine = (int)value;
-    return BORNVI_OK;
-  }
-  if (!std::strcmp(name, "zero_support")) { h->zero_support = value != 0; return BORNVI_OK; }
-  if (!std::strcmp(name, "alternate_walk")) { h->alternate_walk = value != 0; return BORNVI_OK; }
-  if (!std::strcmp(name, "direct_stages")) { h->direct_stages = (int)value; return BORNVI_OK; }   // bits 2..: 1 + the only pass allowed (debug)
-  if (!std::strcmp(name, "fast_workgroups_per_cu")) {
-    if (value < 0 || value > 16) return fail(h, BORNVI_ERR_INVALID, "option value out of range");
-    h->fast_wgs_per_cu = (int)value;
-    return BORNVI_OK;
-  }
-  PlanOptions o = h->opt;
-  if (!std::strcmp(name, "tile_bits")) { o.kmax = (int)value; o.kmulti = (int)value; }
-  else if (!std::strcmp(name, "tile_bits_multi")) o.kmulti = (int)value;
-  else if (!std::strcmp(name, "low_bits")) o.lo = (int)value;
-  else if (!std::strcmp(name, "max_threads")) o.max_threads = (int)value;
-  else if (!std::strcmp(name, "read_map")) o.read_map = value < 0 ? -1 : (value != 0 ? 1 : 0);   // -1: by the kernel (on with reg_wires = 3)
-  else if (!std::strcmp(name, "reg_wires")) o.r = (int)value;
-  else if (!std::strcmp(name, "contig_out")) o.contig_out = value != 0;
-  else return fail(h, BORNVI_ERR_INVALID, std::string("unknown option ") + name);
-  if (o.kmax < 4 || o.kmax > 13 || (o.kmulti != 0 && (o.kmulti < 4 || o.kmulti > 13)) || o.lo < 0 || o.lo > 8 || o.max_threads < 64 || o.max_threads > 1024 ||
-      (o.max_threads & (o.max_threads - 1)) || (o.r != 3 && o.r != 4))
-    return fail(h, BORNVI_ERR_INVALID, "option value out of range");
-  h->opt = o;
+  h->opt.*(o->in_plan) = v;
+  if (o->in_plan == &PlanOptions::kmax) h->opt.kmulti = v;
   for (auto& kv : h->plans) free_plan(kv.second.get());
   h->plans.clear();
   return BORNVI_OK;
@@ -601,21 +651,9 @@ int bornvi_set_option(bornvi_handle h, const char* name, long long value) {
 
 int bornvi_get_option(bornvi_handle h, const char* name, long long* value) {
   if (!h || !name || !value) return BORNVI_ERR_INVALID;
-  if (!std::strcmp(name, "reg_wires")) *value = h->opt.r;
-  else if (!std::strcmp(name, "read_map")) *value = h->opt.read_map;
-  else if (!std::strcmp(name, "tile_bits")) *value = h->opt.kmax;
-  else if (!std::strcmp(name, "tile_bits_multi")) *value = h->opt.kmulti;
-  else if (!std::strcmp(name, "low_bits")) *value = h->opt.lo;
-  else if (!std::strcmp(name, "contig_out")) *value = h->opt.contig_out;
-  else if (!std::strcmp(name, "prefix_share")) *value = h->prefix_share;
-  else if (!std::strcmp(name, "grad_engine")) *value = h->grad_engine;
-  else if (!std::strcmp(name, "fast_path")) *value = h->fast_path;
-  else if (!std::strcmp(name, "direct_stages")) *value = h->direct_stages;
-  else if (!std::strcmp(name, "zero_support")) *value = h->zero_support;
-  else if (!std::strcmp(name, "alternate_walk")) *value = h->alternate_walk;
-  else if (!std::strcmp(name, "batched_quadform")) *value = h->batched_quadform;
-  else if (!std::strcmp(name, "fast_workgroups_per_cu")) *value = h->fast_wgs_per_cu;
-  else return fail(h, BORNVI_ERR_INVALID, std::string("unknown option ") + name);
+  const Option* o = find_option(name);
+  if (!o) return fail(h, BORNVI_ERR_INVALID, std::string("unknown option ") + name);
+  *value = o->in_ctx ? h->*(o->in_ctx) : h->opt.*(o->in_plan);
   return BORNVI_OK;
 }
 
@@ -649,9 +687,7 @@ int bornvi_paramshift_probs_strided(bornvi_handle h, int ansatz, int n, int laye
                                     int p_count, int p_stride, int include_base, double* probs, void* workspace,
                                     size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  const int P = num_params(ansatz, n, layers);
-  if (P < 0 || p_begin < 0 || p_count < 0 || p_stride < 1 || (p_count > 0 && (long long)p_begin + (long long)(p_count - 1) * p_stride >= P))
-    return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+  if (!valid_param_range(num_params(ansatz, n, layers), p_begin, p_count, p_stride)) return fail(h, BORNVI_ERR_INVALID, PARAM_RANGE);
   const long long batch = (include_base ? 1 : 0) + 2ll * p_count;
   return circuit_batch(h, ansatz, n, layers, batch, theta, 1, p_begin, p_stride, include_base ? 1 : 0, probs, workspace,
                        workspace_bytes, (hipStream_t)stream);
@@ -661,7 +697,7 @@ int bornvi_paramshift_probs(bornvi_handle h, int ansatz, int n, int layers, cons
                             int p_end, int include_base, double* probs, void* workspace, size_t workspace_bytes,
                             bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (p_end < p_begin) return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+  if (p_end < p_begin) return fail(h, BORNVI_ERR_INVALID, PARAM_RANGE);
   return bornvi_paramshift_probs_strided(h, ansatz, n, layers, theta, p_begin, p_end - p_begin, 1, include_base, probs,
                                          workspace, workspace_bytes, stream);
 }
@@ -689,7 +725,7 @@ int bornvi_paramshift_grad(bornvi_handle h, int ansatz, int n, int layers, const
   if (ns == 0) return BORNVI_OK;
   if (h->grad_engine == 1) {
     const int P = num_params(ansatz, n, layers);
-    if (P < 0 || p_begin < 0 || p_end > P) return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+    if (P < 0 || p_begin < 0 || p_end > P) return fail(h, BORNVI_ERR_INVALID, PARAM_RANGE);
     if (!workspace || workspace_bytes < bornvi_paramshift_grad_workspace_bytes(h, ansatz, n, layers, p_begin, p_end))
       return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
     const size_t sb = align_up((size_t)16 << n, 256), gb = align_up((size_t)P * 8, 256);
@@ -731,6 +767,15 @@ bool dot_layout(const Plan& p, int n, int p_count, DotLayout& L) {
 bool dot_supported(bornvi_handle h, DevPlan* dp) {
   return dp->d_compact && dp->plan.n_passes >= 2 && dp->plan.k >= 9 && !h->prefix_share && h->grad_engine == 0;
 }
+// what begin and finish have in common: the plan, the layout of the workspace they share, and the refusals of either
+int dot_prepare(bornvi_handle h, int ansatz, int n, int layers, int p_count, void* workspace, size_t workspace_bytes, DevPlan** dp,
+                DotLayout& L) {
+  if (int rc = get_plan(h, ansatz, n, layers, dp)) return rc;
+  if (!dot_supported(h, *dp) || !dot_layout((*dp)->plan, n, p_count, L))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, "the fused parameter-shift dot needs a multi-pass plan of the 8-amplitude kernel (reg_wires = 3), no prefix sharing");
+  if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small or misaligned");
+  return BORNVI_OK;
+}
 // input buffer of pass i when pass 0 starts from |0..0> and writes bufA first
 void* pass_input_buffer(int i, void* bufA, void* bufB) { return i == 0 ? nullptr : ((i & 1) ? bufA : bufB); }
 }  // namespace
@@ -748,16 +793,11 @@ int bornvi_paramshift_dot_begin(bornvi_handle h, int ansatz, int n, int layers, 
                                 int p_stride, double* q_out, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   if (!theta || !q_out) return fail(h, BORNVI_ERR_INVALID, "null pointer");
-  const int P = num_params(ansatz, n, layers);
-  if (P < 0 || p_begin < 0 || p_count < 0 || p_stride < 1 || (p_count > 0 && (long long)p_begin + (long long)(p_count - 1) * p_stride >= P))
-    return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+  if (!valid_param_range(num_params(ansatz, n, layers), p_begin, p_count, p_stride)) return fail(h, BORNVI_ERR_INVALID, PARAM_RANGE);
   DevPlan* dp = nullptr;
-  int rc = get_plan(h, ansatz, n, layers, &dp);
-  if (rc) return rc;
   DotLayout L;
-  if (!dot_supported(h, dp) || !dot_layout(dp->plan, n, p_count, L))
-    return fail(h, BORNVI_ERR_UNSUPPORTED, "the fused parameter-shift dot needs a multi-pass plan of the 8-amplitude kernel (reg_wires = 3), no prefix sharing");
-  if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small or misaligned");
+  int rc = dot_prepare(h, ansatz, n, layers, p_count, workspace, workspace_bytes, &dp, L);
+  if (rc) return rc;
   const Plan& p = dp->plan;
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)workspace;
@@ -779,12 +819,9 @@ int bornvi_paramshift_dot_finish(bornvi_handle h, int ansatz, int n, int layers,
   if (!h) return BORNVI_ERR_INVALID;
   if (!w || p_count < 0 || (p_count > 0 && !grad)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
   DevPlan* dp = nullptr;
-  int rc = get_plan(h, ansatz, n, layers, &dp);
-  if (rc) return rc;
   DotLayout L;
-  if (!dot_supported(h, dp) || !dot_layout(dp->plan, n, p_count, L))
-    return fail(h, BORNVI_ERR_UNSUPPORTED, "the fused parameter-shift dot needs a multi-pass plan of the 8-amplitude kernel (reg_wires = 3), no prefix sharing");
-  if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 15)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small or misaligned");
+  int rc = dot_prepare(h, ansatz, n, layers, p_count, workspace, workspace_bytes, &dp, L);
+  if (rc) return rc;
   const Plan& p = dp->plan;
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)workspace;
@@ -809,7 +846,7 @@ int bornvi_paramshift_dot_finish(bornvi_handle h, int ansatz, int n, int layers,
 int bornvi_gate1q_apply(bornvi_handle h, int n, long long batch, double* state, int wire, const double* U,
                         bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!state || !U || n < 1 || n > 40 || wire < 0 || wire >= n || batch < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  if (!state || !U || !valid_gate_n(n) || wire < 0 || wire >= n || batch < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
   if (batch == 0) return BORNVI_OK;
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_gate1q(state, n, batch, wire, U, (hipStream_t)stream));
@@ -819,7 +856,7 @@ int bornvi_gate1q_apply(bornvi_handle h, int n, long long batch, double* state, 
 int bornvi_cnot_apply(bornvi_handle h, int n, long long batch, double* state, int control, int target,
                       bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!state || n < 2 || n > 40 || control < 0 || control >= n || target < 0 || target >= n || control == target || batch < 0)
+  if (!state || n < 2 || !valid_gate_n(n) || control < 0 || control >= n || target < 0 || target >= n || control == target || batch < 0)
     return fail(h, BORNVI_ERR_INVALID, "bad argument");
   if (batch == 0) return BORNVI_OK;
   DEVICE_SCOPE(h);
@@ -829,7 +866,7 @@ int bornvi_cnot_apply(bornvi_handle h, int n, long long batch, double* state, in
 
 int bornvi_born_probs(bornvi_handle h, int n, long long batch, const double* state, double* probs, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!state || !probs || n < 0 || n > 40 || batch < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  if (!state || !probs || n < 0 || n > BORNVI_GATE_MAX_N || batch < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
   if (batch == 0) return BORNVI_OK;
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_born_probs(state, probs, n, batch, (hipStream_t)stream));
@@ -838,10 +875,8 @@ int bornvi_born_probs(bornvi_handle h, int n, long long batch, const double* sta
 
 int bornvi_score_from_cpts(bornvi_handle h, const bornvi_bn_desc* bn, int n, double* S, double* pxz, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!bn || !S || n < 1 || n > 30) return fail(h, BORNVI_ERR_INVALID, "bad argument");
-  if (bn->num_nodes < 1 || bn->num_nodes > 64 || bn->max_parents < 1 || !bn->role || !bn->n_parents || !bn->parents ||
-      !bn->cpt_off || !bn->cpt)
-    return fail(h, BORNVI_ERR_INVALID, "bad network descriptor");
+  if (!bn || !S || !valid_table_n(n)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  if (!valid_bn_desc(bn)) return fail(h, BORNVI_ERR_INVALID, BN_DESC);
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_score(*bn, n, S, pxz, (hipStream_t)stream));
   return BORNVI_OK;
@@ -850,13 +885,11 @@ int bornvi_score_from_cpts(bornvi_handle h, const bornvi_bn_desc* bn, int n, dou
 // The descriptor checks of the per-sample network calls.  The roles live on the device.  Outside a stream capture they are
 // read back and a summed-out node is refused here; inside one no copy is allowed, and the kernels write NaN for such a descriptor.
 static int check_sample_descriptor(bornvi_handle h, const bornvi_bn_desc* bn, int n, bornvi_stream stream) {
-  if (bn->num_nodes < 1 || bn->num_nodes > 64 || bn->max_parents < 1 || !bn->role || !bn->n_parents || !bn->parents ||
-      !bn->cpt_off || !bn->cpt)
-    return fail(h, BORNVI_ERR_INVALID, "bad network descriptor");
+  if (!valid_bn_desc(bn)) return fail(h, BORNVI_ERR_INVALID, BN_DESC);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
   if (cap == hipStreamCaptureStatusNone) {
-    int32_t role[64];
+    int32_t role[BORNVI_BN_MAX_NODES];
     HIPCHK(h, hipMemcpy(role, bn->role, sizeof(int32_t) * bn->num_nodes, hipMemcpyDeviceToHost));
     for (int v = 0; v < bn->num_nodes; ++v) {
       if (role[v] == -3) return fail(h, BORNVI_ERR_UNSUPPORTED, "a summed-out node (role -3) has no log joint per sample: use the enumerated paths");
@@ -866,10 +899,13 @@ static int check_sample_descriptor(bornvi_handle h, const bornvi_bn_desc* bn, in
   return BORNVI_OK;
 }
 
+static bool valid_bn_samples(int n, long long B) { return n >= 1 && n <= BORNVI_MPS_SAMPLED_MAX_N && B >= 1 && B <= BORNVI_MPS_SAMPLED_MAX_BATCH; }
+static const char* const BN_SAMPLES_RANGE = "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)";
+
 int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx, double p_floor,
                                double* logp, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
+  if (!valid_bn_samples(n, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, BN_SAMPLES_RANGE);
   if (!bn || !idx || !logp || !(p_floor > 0.0) || !std::isfinite(p_floor)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
   DEVICE_SCOPE(h);
   if (int rc = check_sample_descriptor(h, bn, n, stream)) return rc;
@@ -880,7 +916,7 @@ int bornvi_bn_logjoint_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n,
 int bornvi_bn_score_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, const long long* idx, double p_floor,
                             double* S, double* logp, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
+  if (!valid_bn_samples(n, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, BN_SAMPLES_RANGE);
   if (!bn || !idx || !S || !(p_floor > 0.0) || !std::isfinite(p_floor)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
   DEVICE_SCOPE(h);
   if (int rc = check_sample_descriptor(h, bn, n, stream)) return rc;
@@ -891,14 +927,12 @@ int bornvi_bn_score_samples(bornvi_handle h, const bornvi_bn_desc* bn, int n, lo
 // The descriptor checks of bornvi_bn_sample, with the same read-back: every role a tuple position 0 .. n - 1, each taken once,
 // or -3 (drawn and dropped); an observed role and a node listed before one of its parents are refused as unsupported.
 static int check_sampling_descriptor(bornvi_handle h, const bornvi_bn_desc* bn, int n, bornvi_stream stream) {
-  if (bn->num_nodes < 1 || bn->num_nodes > 64 || bn->max_parents < 1 || bn->max_parents > 64 || !bn->role || !bn->n_parents ||
-      !bn->parents || !bn->cpt_off || !bn->cpt)
-    return fail(h, BORNVI_ERR_INVALID, "bad network descriptor");
+  if (!valid_bn_desc(bn) || bn->max_parents > BORNVI_BN_MAX_NODES) return fail(h, BORNVI_ERR_INVALID, BN_DESC);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
   if (cap != hipStreamCaptureStatusNone) return BORNVI_OK;
   const int V = bn->num_nodes, P = bn->max_parents;
-  int32_t role[64], npar[64];
+  int32_t role[BORNVI_BN_MAX_NODES], npar[BORNVI_BN_MAX_NODES];
   std::vector<int32_t> par((size_t)V * P);
   HIPCHK(h, hipMemcpy(role, bn->role, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(npar, bn->n_parents, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
@@ -927,7 +961,7 @@ static int check_sampling_descriptor(bornvi_handle h, const bornvi_bn_desc* bn, 
 int bornvi_bn_sample(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long B, unsigned long long seed,
                      const long long* epoch_dev, long long* idx, double* logp, int* status, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (n < 1 || n > 63 || B < 1 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= B <= 2^24)");
+  if (!valid_bn_samples(n, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, BN_SAMPLES_RANGE);
   if (!bn || !epoch_dev || !idx || !logp || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   DEVICE_SCOPE(h);
   if (int rc = check_sampling_descriptor(h, bn, n, stream)) return rc;
@@ -935,18 +969,19 @@ int bornvi_bn_sample(bornvi_handle h, const bornvi_bn_desc* bn, int n, long long
   return BORNVI_OK;
 }
 
+static bool valid_stein_pairs(int n, long long B) { return n >= 1 && n <= BORNVI_MPS_SAMPLED_MAX_N && B >= 2 && B <= BORNVI_STEIN_PAIRS_MAX_B; }
 static bool stein_pairs_supported(int n, long long B, double length_scale) {
-  return n >= 1 && n <= 63 && B >= 2 && B <= STEIN_PAIRS_MAX_B && std::isfinite(length_scale) && (double)n * length_scale >= 1.0;
+  return valid_stein_pairs(n, B) && std::isfinite(length_scale) && (double)n * length_scale >= 1.0;
 }
 
 size_t bornvi_stein_pairs_workspace_bytes(bornvi_handle h, int n, long long B) {
   (void)h;
-  if (n < 1 || n > 63 || B < 2 || B > STEIN_PAIRS_MAX_B) return 0;
+  if (!valid_stein_pairs(n, B)) return 0;
   return stein_pairs_workspace_bytes(B);
 }
 
 int bornvi_stein_pairs_geometry(long long B, int* tiles_per_range, int* num_ranges) {
-  if (B < 2 || B > STEIN_PAIRS_MAX_B || !tiles_per_range || !num_ranges) return BORNVI_ERR_INVALID;
+  if (B < 2 || B > BORNVI_STEIN_PAIRS_MAX_B || !tiles_per_range || !num_ranges) return BORNVI_ERR_INVALID;
   stein_pairs_geometry(B, tiles_per_range, num_ranges);
   return BORNVI_OK;
 }
@@ -964,7 +999,7 @@ int bornvi_stein_pairs_rowsum(bornvi_handle h, int n, long long B, double length
 }
 
 long long bornvi_stein_gram_ld(int n) {
-  if (n < 1 || n > 17) return 0;
+  if (!valid_n_for_dense(n)) return 0;
   // 256 bytes of padding per row.  Same-box A/B of the band kernel at n = 16 (tools/probes/sym_probe.py, three
   // matrices held at once, twice): pitch 2^n: 2.62 / 2.83 / 2.63 and 2.83 / 2.62 / 2.63 ms by allocation; pitch
   // 2^n + 32: 2.57 / 2.57 / 2.56 and 2.57 / 2.57 / 2.56 ms -- faster, and the dependence on where the matrix landed
@@ -978,10 +1013,10 @@ int bornvi_stein_gram_build_rows_ld(bornvi_handle h, int n, double length_scale,
                                     long long row_end, double* K_rows, long long ld, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   if (!S || (!K_rows && row_end > row_begin)) return fail(h, BORNVI_ERR_INVALID, "null pointer");
-  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17 (8 * 4^n bytes)");
+  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, DENSE_BUILD_RANGE);
   if (!(length_scale > 0.0)) return fail(h, BORNVI_ERR_INVALID, "length_scale must be positive");
   if (row_begin < 0 || row_end < row_begin || row_end > (1ll << n)) return fail(h, BORNVI_ERR_INVALID, "row range out of bounds");
-  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, "leading dimension must be even, >= 2^n and <= 2^n + 4096");
+  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, DENSE_LD_RANGE);
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_gram_build(n, length_scale, S, K_rows, row_begin, row_end, ld, (hipStream_t)stream));
   return BORNVI_OK;
@@ -989,19 +1024,19 @@ int bornvi_stein_gram_build_rows_ld(bornvi_handle h, int n, double length_scale,
 
 int bornvi_stein_gram_build_rows(bornvi_handle h, int n, double length_scale, const double* S, long long row_begin,
                                  long long row_end, double* K_rows, bornvi_stream stream) {
-  if (n < 0 || n > 40) return h ? fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17 (8 * 4^n bytes)") : BORNVI_ERR_INVALID;
+  if (!shiftable_n(n)) return refuse_dense_n(h, DENSE_BUILD_RANGE);
   return bornvi_stein_gram_build_rows_ld(h, n, length_scale, S, row_begin, row_end, K_rows, 1ll << n, stream);
 }
 
 int bornvi_stein_gram_build(bornvi_handle h, int n, double length_scale, const double* S, double* K, bornvi_stream stream) {
-  if (n < 0 || n > 40) return h ? fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17 (8 * 4^n bytes)") : BORNVI_ERR_INVALID;
+  if (!shiftable_n(n)) return refuse_dense_n(h, DENSE_BUILD_RANGE);
   return bornvi_stein_gram_build_rows(h, n, length_scale, S, 0, 1ll << n, K, stream);
 }
 
 int bornvi_stein_kp_pairs(bornvi_handle h, int n, double length_scale, long long M, const long long* zi,
                           const long long* zj, const double* si, const double* sj, double* out, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (n < 1 || n > 30 || M < 0 || (M > 0 && (!zi || !zj || !si || !sj || !out))) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  if (!valid_table_n(n) || M < 0 || (M > 0 && (!zi || !zj || !si || !sj || !out))) return fail(h, BORNVI_ERR_INVALID, "bad argument");
   if (!(length_scale > 0.0)) return fail(h, BORNVI_ERR_INVALID, "length_scale must be positive");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_kp_pairs(n, length_scale, M, zi, zj, si, sj, out, (hipStream_t)stream));
@@ -1010,7 +1045,7 @@ int bornvi_stein_kp_pairs(bornvi_handle h, int n, double length_scale, long long
 
 size_t bornvi_stein_quadform_workspace_bytes(bornvi_handle h, int n, int B) {
   (void)h;
-  if (n < 1 || n > 30) return 0;
+  if (!valid_table_n(n)) return 0;
   size_t b = align_up(quadform_partials(1ll << n) * sizeof(double), 256);
   // the batched (matrix-core) form computes ksd2 from Y: room for Y when the caller does not ask for it
   if (B > 1 && quadform_batched_supported(n, B)) b += align_up((size_t)B * ((size_t)8 << n), 256);
@@ -1022,7 +1057,7 @@ int bornvi_stein_quadform_rows(bornvi_handle h, int n, const double* K_rows, lon
                                size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   if (!q || !ksd2_partial || (!K_rows && row_end > row_begin)) return fail(h, BORNVI_ERR_INVALID, "bad argument");
-  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17");
+  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, DENSE_RANGE);
   if (row_begin < 0 || row_end < row_begin || row_end > (1ll << n)) return fail(h, BORNVI_ERR_INVALID, "row range out of bounds");
   if (!workspace || workspace_bytes < bornvi_stein_quadform_workspace_bytes(h, n, 1))
     return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
@@ -1035,8 +1070,8 @@ int bornvi_stein_quadform_ld(bornvi_handle h, int n, const double* K, long long 
                              double* Y, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   if (!K || !Q || !ksd2 || B < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
-  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17");
-  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, "leading dimension must be even, >= 2^n and <= 2^n + 4096");
+  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, DENSE_RANGE);
+  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, DENSE_LD_RANGE);
   if (!workspace || workspace_bytes < bornvi_stein_quadform_workspace_bytes(h, n, B))
     return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
   DEVICE_SCOPE(h);
@@ -1056,7 +1091,7 @@ int bornvi_stein_quadform_ld(bornvi_handle h, int n, const double* K, long long 
 
 int bornvi_stein_quadform(bornvi_handle h, int n, const double* K, const double* Q, int B, double* ksd2, double* Y,
                           void* workspace, size_t workspace_bytes, bornvi_stream stream) {
-  if (n < 0 || n > 40) return h ? fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17") : BORNVI_ERR_INVALID;
+  if (!shiftable_n(n)) return refuse_dense_n(h, DENSE_RANGE);
   return bornvi_stein_quadform_ld(h, n, K, 1ll << n, Q, B, ksd2, Y, workspace, workspace_bytes, stream);
 }
 
@@ -1070,8 +1105,8 @@ int bornvi_stein_quadform_sym_ld(bornvi_handle h, int n, const double* K, long l
                                  double* y, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   if (!K || !q || !ksd2) return fail(h, BORNVI_ERR_INVALID, "null pointer");
-  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17");
-  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, "leading dimension must be even, >= 2^n and <= 2^n + 4096");
+  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, DENSE_RANGE);
+  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, DENSE_LD_RANGE);
   if (!workspace || workspace_bytes < bornvi_stein_quadform_sym_workspace_bytes(h, n) || ((uintptr_t)workspace & 15))
     return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
   if ((uintptr_t)K & 15) return fail(h, BORNVI_ERR_INVALID, "K must be 16-byte aligned");
@@ -1084,7 +1119,7 @@ int bornvi_stein_quadform_sym_ld(bornvi_handle h, int n, const double* K, long l
 
 int bornvi_stein_quadform_sym(bornvi_handle h, int n, const double* K, const double* q, double* ksd2, double* y,
                               void* workspace, size_t workspace_bytes, bornvi_stream stream) {
-  if (n < 0 || n > 40) return h ? fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17") : BORNVI_ERR_INVALID;
+  if (!shiftable_n(n)) return refuse_dense_n(h, DENSE_RANGE);
   return bornvi_stein_quadform_sym_ld(h, n, K, 1ll << n, q, ksd2, y, workspace, workspace_bytes, stream);
 }
 
@@ -1095,8 +1130,8 @@ int bornvi_stein_quadform_sym_pairs_ld(bornvi_handle h, int n, const double* K_l
                                        double* y_partial, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   if (!q || !ksd2_partial || !y_partial) return fail(h, BORNVI_ERR_INVALID, "null pointer");
-  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17");
-  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, "leading dimension must be even, >= 2^n and <= 2^n + 4096");
+  if (!valid_n_for_dense(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, DENSE_RANGE);
+  if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, DENSE_LD_RANGE);
   if (n < quadform_sym_min_n()) return fail(h, BORNVI_ERR_UNSUPPORTED, "the strip-pair shard needs at least two bands of rows (n >= 9)");
   const long long N = 1ll << n, R = quadform_sym_rows_per_strip();
   const long long ns = N / R, npairs = (ns + 1) / 2;
@@ -1114,7 +1149,7 @@ int bornvi_stein_quadform_sym_pairs_ld(bornvi_handle h, int n, const double* K_l
 int bornvi_stein_quadform_sym_pairs(bornvi_handle h, int n, const double* K_lo, const double* K_hi, long long pair_begin,
                                     long long pair_end, const double* q, double* ksd2_partial, double* y_partial,
                                     void* workspace, size_t workspace_bytes, bornvi_stream stream) {
-  if (n < 0 || n > 40) return h ? fail(h, BORNVI_ERR_UNSUPPORTED, "dense Gram supports 1 <= n <= 17") : BORNVI_ERR_INVALID;
+  if (!shiftable_n(n)) return refuse_dense_n(h, DENSE_RANGE);
   return bornvi_stein_quadform_sym_pairs_ld(h, n, K_lo, K_hi, 1ll << n, pair_begin, pair_end, q, ksd2_partial, y_partial,
                                             workspace, workspace_bytes, stream);
 }
@@ -1165,7 +1200,7 @@ int bornvi_stein_matvec_kron(bornvi_handle h, int n, double length_scale, const 
 int bornvi_ksd_grad_finish(bornvi_handle h, int n, const double* shifted, int n_shift, const double* y,
                            const double* ksd2, double* loss_out, double* dLdq_out, double* grad, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!y || !ksd2 || n < 1 || n > 30 || n_shift < 0 || (n_shift > 0 && (!shifted || !grad)))
+  if (!y || !ksd2 || !valid_table_n(n) || n_shift < 0 || (n_shift > 0 && (!shifted || !grad)))
     return fail(h, BORNVI_ERR_INVALID, "bad argument");
   DEVICE_SCOPE(h);
   hipStream_t st = (hipStream_t)stream;
@@ -1178,7 +1213,7 @@ int bornvi_ksd_grad_finish(bornvi_handle h, int n, const double* shifted, int n_
 
 size_t bornvi_shots_workspace_bytes(bornvi_handle h, int n, int B) {
   if (!h) return 0;
-  if (n < 1 || n > 30 || B < 0) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  if (!valid_table_n(n) || B < 0) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
   return shots_workspace_bytes(n, B);
 }
 
@@ -1186,10 +1221,10 @@ int bornvi_shots_histogram(bornvi_handle h, int n, int B, const double* probs, d
                            unsigned long long seed, const long long* epoch_dev, int include_base, int p_begin, int p_stride,
                            void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (n < 1 || n > 30 || B < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
-  if (shots < 1 || shots > 2147483647ll) return fail(h, BORNVI_ERR_INVALID, "shots must be in [1, 2^31 - 1]");
+  if (!valid_table_n(n) || B < 0) return fail(h, BORNVI_ERR_INVALID, "bad argument");
+  if (shots < 1 || shots > BORNVI_SHOTS_MAX) return fail(h, BORNVI_ERR_INVALID, "shots must be in [1, 2^31 - 1]");
   if (B > 0 && (!probs || !freq || !epoch_dev)) return fail(h, BORNVI_ERR_INVALID, "null pointer");
-  if (p_begin < 0 || p_stride < 1) return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+  if (p_begin < 0 || p_stride < 1) return fail(h, BORNVI_ERR_INVALID, PARAM_RANGE);
   const long long rows_p = B - (include_base ? 1 : 0);
   if (rows_p > 0 && 2ll * (p_begin + ((rows_p - 1) >> 1) * (long long)p_stride) + 2 > 0xffffffffll)
     return fail(h, BORNVI_ERR_INVALID, "circuit ids beyond 32 bits");
@@ -1206,8 +1241,9 @@ int bornvi_shots_histogram(bornvi_handle h, int n, int B, const double* probs, d
 }
 
 static bool valid_born_table(int n, int rows, int mode) {
-  return n >= 0 && n <= 30 && rows >= 1 && rows <= 65535 && (mode == 0 || mode == 1);
+  return n >= 0 && n <= BORNVI_TABLE_MAX_N && rows >= 1 && rows <= BORNVI_BORN_TABLE_MAX_ROWS && (mode == 0 || mode == 1);
 }
+static const char* const BORN_TABLE_RANGE = "bad argument (0 <= n <= 30, 1 <= rows <= 65535, mode 0 or 1)";
 
 size_t bornvi_born_table_workspace_bytes(bornvi_handle h, int n, int rows) {
   if (!h) return 0;
@@ -1218,7 +1254,7 @@ size_t bornvi_born_table_workspace_bytes(bornvi_handle h, int n, int rows) {
 int bornvi_born_table_probs(bornvi_handle h, int n, int rows, int mode, const float* w, float* q32, double* q64,
                             float* entropy, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!valid_born_table(n, rows, mode)) return fail(h, BORNVI_ERR_INVALID, "bad argument (0 <= n <= 30, 1 <= rows <= 65535, mode 0 or 1)");
+  if (!valid_born_table(n, rows, mode)) return fail(h, BORNVI_ERR_INVALID, BORN_TABLE_RANGE);
   if (!w || !q32 || !q64) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!workspace || workspace_bytes < born_table_workspace_bytes(n, rows)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
   DEVICE_SCOPE(h);
@@ -1230,7 +1266,7 @@ int bornvi_born_table_vjp(bornvi_handle h, int n, int rows, int mode, const floa
                           const double* ksd2, double entropy_weight, float* grad, double* loss_out, void* workspace,
                           size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!valid_born_table(n, rows, mode)) return fail(h, BORNVI_ERR_INVALID, "bad argument (0 <= n <= 30, 1 <= rows <= 65535, mode 0 or 1)");
+  if (!valid_born_table(n, rows, mode)) return fail(h, BORNVI_ERR_INVALID, BORN_TABLE_RANGE);
   if (!w || !q64 || !grad) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (loss_out && !ksd2) return fail(h, BORNVI_ERR_INVALID, "loss_out needs ksd2");
   if (!std::isfinite(entropy_weight)) return fail(h, BORNVI_ERR_INVALID, "entropy_weight must be finite");
@@ -1240,7 +1276,7 @@ int bornvi_born_table_vjp(bornvi_handle h, int n, int rows, int mode, const floa
   return BORNVI_OK;
 }
 
-static bool valid_elbo(int n, int rows) { return n >= 1 && n <= 30 && rows >= 1 && rows <= 65535; }
+static bool valid_elbo(int n, int rows) { return valid_table_n(n) && rows >= 1 && rows <= BORNVI_ELBO_MAX_ROWS; }
 
 size_t bornvi_elbo_workspace_bytes(bornvi_handle h, int n, int rows) {
   if (!h) return 0;
@@ -1260,18 +1296,19 @@ int bornvi_elbo_weights(bornvi_handle h, int n, int rows, const double* q, const
   return BORNVI_OK;
 }
 
-static bool valid_mps(int n, int D) { return n >= 1 && n <= 26 && D >= 1 && D <= 32; }
+static bool valid_mps(int n, int D) { return n >= 1 && n <= BORNVI_MPS_MAX_N && D >= 1 && D <= BORNVI_MPS_MAX_BOND; }
+static const char* const MPS_RANGE = "unsupported size (1 <= n <= 26, 1 <= D <= 32)";
 
 size_t bornvi_mps_workspace_bytes(bornvi_handle h, int n, int D) {
   if (!h) return 0;
-  if (!valid_mps(n, D)) { fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 26, 1 <= D <= 32)"); return 0; }
+  if (!valid_mps(n, D)) { fail(h, BORNVI_ERR_UNSUPPORTED, MPS_RANGE); return 0; }
   return mps_workspace_bytes(n, D);
 }
 
 int bornvi_mps_probs(bornvi_handle h, int n, int D, const double* cores, double* q64, float* q32, double* psi, double* Z_out,
                      void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!valid_mps(n, D)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 26, 1 <= D <= 32)");
+  if (!valid_mps(n, D)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_RANGE);
   if (!cores || !q64 || !Z_out) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!workspace || workspace_bytes < mps_workspace_bytes(n, D)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
   DEVICE_SCOPE(h);
@@ -1282,7 +1319,7 @@ int bornvi_mps_probs(bornvi_handle h, int n, int D, const double* cores, double*
 int bornvi_mps_vjp(bornvi_handle h, int n, int D, const double* cores, const double* g, double* grad_cores, void* workspace,
                    size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!valid_mps(n, D)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 26, 1 <= D <= 32)");
+  if (!valid_mps(n, D)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_RANGE);
   if (!cores || !g || !grad_cores) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!workspace || workspace_bytes < mps_workspace_bytes(n, D)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
   DEVICE_SCOPE(h);
@@ -1290,8 +1327,12 @@ int bornvi_mps_vjp(bornvi_handle h, int n, int D, const double* cores, const dou
   return BORNVI_OK;
 }
 
-static bool valid_mps_sample(int n, int D, long long B) { return n >= 1 && n <= 63 && D >= 1 && D <= 32 && B >= 1 && B <= (1ll << 24); }
+static bool valid_mps_canon(int n, int D) { return n >= 1 && n <= BORNVI_MPS_SAMPLED_MAX_N && D >= 1 && D <= BORNVI_MPS_MAX_BOND; }
+static bool valid_mps_sample(int n, int D, long long B) { return valid_mps_canon(n, D) && B >= 1 && B <= BORNVI_MPS_SAMPLED_MAX_BATCH; }
 static const char* const MPS_SAMPLE_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 32, 1 <= B <= 2^24)";
+// the calls that centre score rows need two samples
+static bool valid_mps_sample2(int n, int D, long long B) { return valid_mps_sample(n, D, B) && B >= 2; }
+static const char* const MPS_SAMPLE2_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 32, 2 <= B <= 2^24)";
 
 size_t bornvi_mps_sample_workspace_bytes(bornvi_handle h, int n, int D, long long B) {
   if (!h) return 0;
@@ -1334,14 +1375,16 @@ int bornvi_mps_score_vjp(bornvi_handle h, int n, int D, long long B, const doubl
   return BORNVI_OK;
 }
 
-static bool valid_ld(long long ld, long long B) { return ld >= 64 && ld <= (1ll << 24) && (ld & (ld - 1)) == 0 && ld >= B; }
+static bool valid_ld(long long ld, long long B) {
+  return ld >= BORNVI_SCORE_MIN_LD && ld <= BORNVI_MPS_SAMPLED_MAX_BATCH && (ld & (ld - 1)) == 0 && ld >= B;
+}
 static const char* const SCORE_LD_RANGE = "ld must be a power of two, 64 <= ld <= 2^24, ld >= B";
 
 int bornvi_mps_score_rows(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, int k_begin,
                           int k_count, long long ld, double* rows, int* status, void* workspace, size_t workspace_bytes,
                           bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!valid_mps_sample(n, D, B) || B < 2) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= D <= 32, 2 <= B <= 2^24)");
+  if (!valid_mps_sample2(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_SAMPLE2_RANGE);
   if (!valid_ld(ld, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_LD_RANGE);
   if (k_begin < 0 || k_count < 1 || (long long)k_begin + k_count > n) return fail(h, BORNVI_ERR_INVALID, "site range out of bounds");
   if (!cores || !idx || !rows || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
@@ -1352,7 +1395,7 @@ int bornvi_mps_score_rows(bornvi_handle h, int n, int D, long long B, const doub
   return BORNVI_OK;
 }
 
-static bool valid_sample_gram(int n, int D, long long B) { return valid_mps_sample(n, D, B) && B >= 2 && B <= SAMPLE_GRAM_MAX_B; }
+static bool valid_sample_gram(int n, int D, long long B) { return valid_mps_sample2(n, D, B) && B <= BORNVI_SAMPLE_GRAM_MAX_BATCH; }
 static const char* const SAMPLE_GRAM_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 32, 2 <= B <= 1024)";
 
 size_t bornvi_mps_score_sample_gram_workspace_bytes(bornvi_handle h, int n, int D, long long B) {
@@ -1381,7 +1424,7 @@ int bornvi_mps_score_jvp(bornvi_handle h, int n, int D, long long B, const doubl
                          double scale, double* t, int* status, void* env_workspace, size_t env_workspace_bytes,
                          bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!valid_mps_sample(n, D, B) || B < 2) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= n <= 63, 1 <= D <= 32, 2 <= B <= 2^24)");
+  if (!valid_mps_sample2(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_SAMPLE2_RANGE);
   if (!cores || !idx || !v || !t || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!std::isfinite(scale)) return fail(h, BORNVI_ERR_INVALID, "scale must be finite");
   // a short workspace is refused like a size: nothing is launched
@@ -1393,7 +1436,8 @@ int bornvi_mps_score_jvp(bornvi_handle h, int n, int D, long long B, const doubl
 }
 
 // ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ---------------------------------------------
-static bool valid_mps_query(int n, int D, long long Q) { return n >= 1 && n <= 63 && D >= 1 && D <= 32 && Q >= 1 && Q <= MPS_QUERY_MAX_Q; }
+static bool valid_query_count(long long Q) { return Q >= 1 && Q <= BORNVI_MPS_QUERY_MAX_QUERIES; }
+static bool valid_mps_query(int n, int D, long long Q) { return valid_mps_canon(n, D) && valid_query_count(Q); }
 static const char* const MPS_QUERY_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 32, 1 <= Q <= 2^16)";
 
 size_t bornvi_mps_query_workspace_bytes(bornvi_handle h, int n, int D, int Q) {
@@ -1422,7 +1466,7 @@ size_t bornvi_mps_log_marginals_vjp_workspace_bytes(bornvi_handle h, int n, int 
 
 int bornvi_mps_log_marginals_vjp_geometry(int Q, int* G) {
   if (!G) return BORNVI_ERR_INVALID;
-  if (Q < 1 || Q > MPS_QUERY_MAX_Q) return BORNVI_ERR_UNSUPPORTED;
+  if (!valid_query_count(Q)) return BORNVI_ERR_UNSUPPORTED;
   *G = mps_log_marginals_vjp_groups(Q);
   return BORNVI_OK;
 }
@@ -1466,7 +1510,6 @@ int bornvi_mps_marginals(bornvi_handle h, int n, int D, const double* cores, dou
 }
 
 // ---- canonical form, bond spectra and truncation (kernels_mps_canon.hip) -------------------------------------------
-static bool valid_mps_canon(int n, int D) { return n >= 1 && n <= 63 && D >= 1 && D <= 32; }
 static const char* const MPS_CANON_RANGE = "unsupported size (1 <= n <= 63, 1 <= D_out <= D <= 32, cutoff finite and >= 0)";
 
 size_t bornvi_mps_canon_workspace_bytes(bornvi_handle h, int n, int D) {
@@ -1492,7 +1535,7 @@ int bornvi_mps_canonicalise(bornvi_handle h, int n, int D, int D_out, double cut
 }
 
 // ---- conjugate gradients around a caller's product (kernels_cg.hip) ------------------------------------------------
-static bool valid_cg(long long P) { return P >= 1 && P <= 2147483647ll; }
+static bool valid_cg(long long P) { return P >= 1 && P <= BORNVI_CG_MAX_PARAMS; }
 static const char* const CG_RANGE = "bad argument (1 <= P <= 2^31 - 1)";
 
 int bornvi_cg_init(bornvi_handle h, long long P, const double* g, double* x, double* r, double* p, double* state, int* info,
@@ -1527,7 +1570,8 @@ int bornvi_cg_finish(bornvi_handle h, long long P, const double* g, double* x, c
   return BORNVI_OK;
 }
 
-static bool valid_score_fisher(int R, int nblocks) { return R >= 1 && R <= 1024 && nblocks >= 1 && nblocks <= 65535; }
+static bool valid_gram_order(int P) { return P >= 1 && P <= BORNVI_FISHER_MAX_PARAMS; }      // rows of a Gram block, order of a solve
+static bool valid_score_fisher(int R, int nblocks) { return valid_gram_order(R) && nblocks >= 1 && nblocks <= BORNVI_SCORE_FISHER_MAX_BLOCKS; }
 static const char* const SCORE_FISHER_RANGE = "unsupported size (1 <= R <= 1024, 1 <= nblocks <= 65535)";
 
 size_t bornvi_score_fisher_workspace_bytes(bornvi_handle h, int R, int nblocks, long long ld) {
@@ -1541,7 +1585,7 @@ int bornvi_score_fisher_gram(bornvi_handle h, int R, int nblocks, long long B, l
                              void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   if (!valid_score_fisher(R, nblocks)) return fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_FISHER_RANGE);
-  if (B < 2 || B > (1ll << 24)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (2 <= B <= 2^24)");
+  if (B < 2 || B > BORNVI_MPS_SAMPLED_MAX_BATCH) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (2 <= B <= 2^24)");
   if (!valid_ld(ld, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, SCORE_LD_RANGE);
   if (!rows || !F) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (((uintptr_t)rows) & 15) return fail(h, BORNVI_ERR_INVALID, "rows must be 16-byte aligned");
@@ -1551,7 +1595,7 @@ int bornvi_score_fisher_gram(bornvi_handle h, int R, int nblocks, long long B, l
   return BORNVI_OK;
 }
 
-static bool valid_fisher(int n, int n_shift) { return n >= 1 && n <= 30 && n_shift >= 1 && n_shift <= 1024; }
+static bool valid_fisher(int n, int n_shift) { return valid_table_n(n) && valid_gram_order(n_shift); }
 
 size_t bornvi_fisher_workspace_bytes(bornvi_handle h, int n, int n_shift) {
   if (!h) return 0;
@@ -1574,14 +1618,14 @@ int bornvi_fisher_gram(bornvi_handle h, int n, const double* shifted, int n_shif
 
 size_t bornvi_spd_solve_workspace_bytes(bornvi_handle h, int P) {
   if (!h) return 0;
-  if (P < 1 || P > 1024) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
+  if (!valid_gram_order(P)) { fail(h, BORNVI_ERR_INVALID, "bad argument"); return 0; }
   return spd_solve_workspace_bytes(P);
 }
 
 int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, const double* b, double* x, int* info,
                      void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (P < 1 || P > 1024) return fail(h, BORNVI_ERR_INVALID, "bad argument (1 <= P <= 1024)");
+  if (!valid_gram_order(P)) return fail(h, BORNVI_ERR_INVALID, "bad argument (1 <= P <= 1024)");
   if (!(damping >= 0.0) || !std::isfinite(damping)) return fail(h, BORNVI_ERR_INVALID, "damping must be finite and >= 0");
   if (!A || !b || !x || !info) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!workspace || workspace_bytes < spd_solve_workspace_bytes(P)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
@@ -1590,18 +1634,19 @@ int bornvi_spd_solve(bornvi_handle h, int P, const double* A, double damping, co
   return BORNVI_OK;
 }
 
-static bool valid_spd_batched(int P, int nb) { return P >= 1 && P <= 1024 && nb >= 1 && nb <= 65535; }
+static bool valid_spd_batched(int P, int nb) { return valid_gram_order(P) && nb >= 1 && nb <= BORNVI_SPD_BATCHED_MAX_SYSTEMS; }
+static const char* const SPD_BATCHED_RANGE = "unsupported size (1 <= P <= 1024, 1 <= nb <= 65535)";
 
 size_t bornvi_spd_solve_batched_workspace_bytes(bornvi_handle h, int P, int nb) {
   if (!h) return 0;
-  if (!valid_spd_batched(P, nb)) { fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= P <= 1024, 1 <= nb <= 65535)"); return 0; }
+  if (!valid_spd_batched(P, nb)) { fail(h, BORNVI_ERR_UNSUPPORTED, SPD_BATCHED_RANGE); return 0; }
   return spd_solve_batched_workspace_bytes(P, nb);
 }
 
 int bornvi_spd_solve_batched(bornvi_handle h, int P, int nb, const double* A, double damping, const double* b, double* x, int* info,
                              void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
-  if (!valid_spd_batched(P, nb)) return fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported size (1 <= P <= 1024, 1 <= nb <= 65535)");
+  if (!valid_spd_batched(P, nb)) return fail(h, BORNVI_ERR_UNSUPPORTED, SPD_BATCHED_RANGE);
   if (!(damping >= 0.0) || !std::isfinite(damping)) return fail(h, BORNVI_ERR_INVALID, "damping must be finite and >= 0");
   if (!A || !b || !x || !info) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!workspace || workspace_bytes < spd_solve_batched_workspace_bytes(P, nb)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
@@ -1629,7 +1674,7 @@ int bornvi_paramshift_states(bornvi_handle h, int ansatz, int n, int layers, con
                              int include_base, double* states, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
   if (!h) return BORNVI_ERR_INVALID;
   const int P = num_params(ansatz, n, layers);
-  if (P < 0 || p_begin < 0 || p_count < 0 || (long long)p_begin + p_count > P) return fail(h, BORNVI_ERR_INVALID, "parameter range out of bounds");
+  if (P < 0 || p_begin < 0 || p_count < 0 || (long long)p_begin + p_count > P) return fail(h, BORNVI_ERR_INVALID, PARAM_RANGE);
   include_base = include_base ? 1 : 0;
   const long long rows = (long long)include_base + p_count;
   if (rows == 0) return BORNVI_OK;
@@ -1667,7 +1712,7 @@ int bornvi_paramshift_states(bornvi_handle h, int ansatz, int n, int layers, con
   return BORNVI_OK;
 }
 
-static bool valid_qfi(int n, int P) { return n >= 1 && n <= 30 && P >= 1 && P <= 1024; }
+static bool valid_qfi(int n, int P) { return valid_table_n(n) && valid_gram_order(P); }
 
 size_t bornvi_qfi_workspace_bytes(bornvi_handle h, int n, int P) {
   if (!h) return 0;
@@ -1687,7 +1732,7 @@ int bornvi_qfi_gram(bornvi_handle h, int n, int P, const double* phi, const doub
   return BORNVI_OK;
 }
 
-static bool valid_reinforce(int n, long long B) { return n >= 1 && n <= 30 && B >= 1 && B <= (1ll << 24); }
+static bool valid_reinforce(int n, long long B) { return valid_table_n(n) && B >= 1 && B <= BORNVI_REINFORCE_MAX_BATCH; }
 
 size_t bornvi_reinforce_workspace_bytes(bornvi_handle h, int n, long long B) {
   if (!h) return 0;
@@ -1817,34 +1862,38 @@ int bornvi_adjoint_vjp(bornvi_handle h, int ansatz, int n, int layers, const dou
   return BORNVI_OK;
 }
 
-long long bornvi_plan_describe(int ansatz, int n, int layers, int tile_bits, uint32_t* out, size_t cap_words) {
+// ---- introspection (host only) ------------------------------------------------------------------------------------
+namespace {
+// `tile_bits` of the plan_* calls: bits 0-7 the tile size (0 = default), bit 8 the planner's read_map option, bit 9 the
+// plan with 3 register wires that circuit_pass_r3_kernel runs (r3: what the compact tables always describe)
+bool described_plan(int ansatz, int n, int layers, int tile_bits, bool r3, Plan& p) {
   PlanOptions opt;
-  opt.read_map = (tile_bits & 0x100) ? 1 : 0;    // (bit 8 of tile_bits: the planner's read_map option)
-  opt.r = (tile_bits & 0x200) ? 3 : 4;           // (bit 9: 3 register wires, the plan circuit_pass_r3_kernel runs)
+  opt.read_map = (tile_bits & 0x100) ? 1 : 0;
+  opt.r = r3 ? 3 : 4;
   if (opt.r == 4) opt.max_threads = 512;
-  tile_bits &= 0xff;
-  if (tile_bits > 0) { opt.kmax = tile_bits; opt.kmulti = tile_bits; }
-  Plan p;
+  if (tile_bits & 0xff) opt.kmax = opt.kmulti = tile_bits & 0xff;
   std::string msg;
-  const bool ok = (ansatz == -1) ? make_kron_plan(n, opt, p, msg) : make_plan(ansatz, n, layers, opt, p, msg);
-  if (!ok) return -1;
-  if (out) {
-    const size_t c = p.words.size() < cap_words ? p.words.size() : cap_words;
-    std::memcpy(out, p.words.data(), c * sizeof(uint32_t));
-  }
-  return (long long)p.words.size();
+  return (ansatz == -1) ? make_kron_plan(n, opt, p, msg) : make_plan(ansatz, n, layers, opt, p, msg);
+}
+// a describe call's answer: the word count, with min(cap, words) words and the passes' offsets written where asked for
+long long described_words(const std::vector<uint32_t>& words, uint32_t* out, size_t cap_words, const std::vector<uint32_t>& pass_off,
+                          uint32_t* pass_off_out, int cap_passes) {
+  if (out) std::memcpy(out, words.data(), std::min(words.size(), cap_words) * sizeof(uint32_t));
+  if (pass_off_out)
+    for (int i = 0; i < cap_passes && i < (int)pass_off.size(); ++i) pass_off_out[i] = pass_off[i];
+  return (long long)words.size();
+}
+}  // namespace
+
+long long bornvi_plan_describe(int ansatz, int n, int layers, int tile_bits, uint32_t* out, size_t cap_words) {
+  Plan p;
+  if (!described_plan(ansatz, n, layers, tile_bits, tile_bits & 0x200, p)) return -1;
+  return described_words(p.words, out, cap_words, {}, nullptr, 0);
 }
 
 int bornvi_plan_param_first_pass(int ansatz, int n, int layers, int tile_bits, int* out, int cap) {
-  PlanOptions opt;
-  opt.r = (tile_bits & 0x200) ? 3 : 4;
-  opt.read_map = (tile_bits & 0x100) ? 1 : 0;
-  if (opt.r == 4) opt.max_threads = 512;
-  tile_bits &= 0xff;
-  if (tile_bits > 0) { opt.kmax = tile_bits; opt.kmulti = tile_bits; }
   Plan p;
-  std::string msg;
-  if (ansatz < 0 || !make_plan(ansatz, n, layers, opt, p, msg)) return -1;
+  if (ansatz < 0 || !described_plan(ansatz, n, layers, tile_bits, tile_bits & 0x200, p)) return -1;
   if (out)
     for (int q = 0; q < p.n_params && q < cap; ++q) out[q] = p.param_first_pass[q];
   return p.n_params;
@@ -1852,49 +1901,23 @@ int bornvi_plan_param_first_pass(int ansatz, int n, int layers, int tile_bits, i
 
 long long bornvi_plan_fast_describe(int ansatz, int n, int layers, int tile_bits, uint32_t* out, size_t cap_words,
                                     uint32_t* pass_off_out, int cap_passes) {
-  PlanOptions opt;
-  opt.read_map = (tile_bits & 0x100) ? 1 : 0;
-  opt.r = (tile_bits & 0x200) ? 3 : 4;
-  if (opt.r == 4) opt.max_threads = 512;
-  tile_bits &= 0xff;
-  if (tile_bits > 0) { opt.kmax = tile_bits; opt.kmulti = tile_bits; }
   Plan p;
-  std::string msg;
-  const bool ok = (ansatz == -1) ? make_kron_plan(n, opt, p, msg) : make_plan(ansatz, n, layers, opt, p, msg);
-  if (!ok) return -1;
+  if (!described_plan(ansatz, n, layers, tile_bits, tile_bits & 0x200, p)) return -1;
   FastTables ft;
   if (!build_fast_tables(p, FAST_TABLE_MAX_BYTES, ft)) return 0;
-  if (out) {
-    const size_t c = ft.words.size() < cap_words ? ft.words.size() : cap_words;
-    std::memcpy(out, ft.words.data(), c * sizeof(uint32_t));
-  }
-  if (pass_off_out)
-    for (int i = 0; i < cap_passes && i < (int)ft.pass_off.size(); ++i) pass_off_out[i] = ft.pass_off[i];
-  return (long long)ft.words.size();
+  return described_words(ft.words, out, cap_words, ft.pass_off, pass_off_out, cap_passes);
 }
 
 // Compact tables of the 3-register-wire plan (plan.hpp: CompactTables): returns the number of words (0: not eligible, -1:
 // no plan); every word was checked against its point evaluation by build_compact_tables.
 long long bornvi_plan_compact_describe(int ansatz, int n, int layers, int tile_bits, uint32_t* out, size_t cap_words,
                                        uint32_t* pass_off_out, int cap_passes) {
-  PlanOptions opt;
-  opt.read_map = (tile_bits & 0x100) ? 1 : 0;
-  opt.r = 3;
-  tile_bits &= 0xff;
-  if (tile_bits > 0) { opt.kmax = tile_bits; opt.kmulti = tile_bits; }
   Plan p;
-  std::string msg;
-  const bool ok = (ansatz == -1) ? make_kron_plan(n, opt, p, msg) : make_plan(ansatz, n, layers, opt, p, msg);
-  if (!ok) return -1;
+  if (!described_plan(ansatz, n, layers, tile_bits, true, p)) return -1;
   CompactTables ct;
+  std::string msg;
   if (!r3_plan_eligible(p, ct, msg)) return 0;
-  if (out) {
-    const size_t c = ct.words.size() < cap_words ? ct.words.size() : cap_words;
-    std::memcpy(out, ct.words.data(), c * sizeof(uint32_t));
-  }
-  if (pass_off_out)
-    for (int i = 0; i < cap_passes && i < (int)ct.pass_off.size(); ++i) pass_off_out[i] = ct.pass_off[i];
-  return (long long)ct.words.size();
+  return described_words(ct.words, out, cap_words, ct.pass_off, pass_off_out, cap_passes);
 }
 
 }  // extern "C"

@@ -128,7 +128,6 @@ hipError_t launch_bn_sample(const bornvi_bn_desc& bn, int n, long long B, unsign
                             long long* idx, double* logp, int* status, hipStream_t st);
 
 // ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip): log-marginals, clamped sampler, marginals ----
-constexpr int MPS_QUERY_MAX_Q = 1 << 16;
 size_t mps_query_workspace_bytes(int n, int D, int Q);
 hipError_t launch_mps_log_marginals(int n, int D, int Q, const double* cores, const long long* mask, const long long* value,
                                     double* logm, int* status, void* ws, hipStream_t st);
@@ -148,7 +147,7 @@ hipError_t launch_mps_canonicalise(int n, int D, int D_out, double cutoff, const
                                    double* discarded, int* rank, double* log_norm, int* status, void* ws, hipStream_t st);
 
 // ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
-constexpr int CG_STATE_DOUBLES = 8;      // rr, rr0, iterations, done, relres, fallback, 2 spare
+// state: BORNVI_CG_STATE_DOUBLES doubles -- rr, rr0, iterations, done, relres, fallback, 2 spare
 hipError_t launch_cg_init(long long P, const double* g, double* x, double* r, double* p, double* state, int* info, hipStream_t st);
 hipError_t launch_cg_step(long long P, double damping, double rel_tol, const double* Fp, double* x, double* r, double* p,
                           double* state, hipStream_t st);
@@ -156,13 +155,11 @@ hipError_t launch_cg_finish(long long P, const double* g, double* x, const doubl
                             hipStream_t st);
 
 // ---- sample-space Gram of the sampled MPS's score rows (kernels_mps_sample_gram.hip): T = O O^T / B without the rows ----
-constexpr long long SAMPLE_GRAM_MAX_B = 1024;        // what bornvi_spd_solve factors
 size_t mps_sample_gram_workspace_bytes(int n, int D, long long B);
 hipError_t launch_mps_score_sample_gram(int n, int D, long long B, const double* cores, const long long* idx, double* T, int* status,
                                         void* env_ws, void* ws, hipStream_t st);
 
 // ---- sampled KSD: scores of p at sampled states, pairwise Stein kernel row sums (kernels_ksd_sampled.hip) ----
-constexpr long long STEIN_PAIRS_MAX_B = 1ll << 17;   // B^2 is the cost: 1.7e10 pairs at the cap
 size_t stein_pairs_workspace_bytes(long long B);
 void stein_pairs_geometry(long long B, int* per_tiles, int* G);
 hipError_t launch_bn_score_samples(const bornvi_bn_desc& bn, int n, long long B, const long long* idx, double p_floor, double* S,

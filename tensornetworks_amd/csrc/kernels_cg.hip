@@ -121,7 +121,7 @@ __global__ __launch_bounds__(CG_THREADS) void cg_finish_kernel(long long P, cons
 }  // namespace
 
 hipError_t launch_cg_init(long long P, const double* g, double* x, double* r, double* p, double* state, int* info, hipStream_t st) {
-  static_assert(CG_STATE_DOUBLES >= 8, "state words");
+  static_assert(BORNVI_CG_STATE_DOUBLES >= 8, "state words");
   cg_init_kernel<<<1, CG_THREADS, 0, st>>>(P, g, x, r, p, state, info);
   return hipGetLastError();
 }

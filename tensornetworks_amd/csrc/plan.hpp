@@ -22,6 +22,8 @@
 #include <string>
 #include <vector>
 
+#include "bornvi.h"
+
 namespace bornvi {
 
 enum GateKind : int { G_H = 0, G_RX = 1, G_RY = 2, G_RZ = 3, G_CNOT = 4, G_CZ = 5 };
@@ -286,7 +288,7 @@ inline bool r3_plan_eligible(const Plan& plan, CompactTables& out, std::string& 
 
 // Largest state a plan can address: tile and workgroup indices are 16 bits each and tiles hold at most 2^13 amplitudes,
 // so n - 13 <= 16.
-constexpr int MAX_PLAN_QUBITS = 29;
+constexpr int MAX_PLAN_QUBITS = BORNVI_CIRCUIT_MAX_N;
 // Returns false (with msg) on unsupported sizes.
 bool make_plan(int ansatz, int n, int layers, const PlanOptions& opt, Plan& out, std::string& msg);
 // The gates that end a circuit (everything after its last one-qubit gate), in program order: is_cz = 0: CNOT(a = control,

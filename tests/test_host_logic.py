@@ -30,6 +30,207 @@ def test_library_exports_every_declared_symbol():
     assert lib.bornvi_num_params(7, 3, 1) == -1 and lib.bornvi_num_gates(7, 3, 1) == -1
 
 
+# What the binding's hand-written table said before it was derived from the header, per symbol "return <- arguments" with
+# i32 = int, i64 = long long, u64 = unsigned long long / size_t, f64 = double, ptr = any pointer or handle, str = const char*.
+# A signature changed on purpose changes its line here.
+ABI_KINDS = {
+    "bornvi_version": "i32 <-",
+    "bornvi_create": "i32 <- i32 ptr",
+    "bornvi_destroy": "void <- ptr",
+    "bornvi_last_error": "str <- ptr",
+    "bornvi_set_option": "i32 <- ptr str i64",
+    "bornvi_get_option": "i32 <- ptr str ptr",
+    "bornvi_num_params": "i32 <- i32 i32 i32",
+    "bornvi_num_gates": "i32 <- i32 i32 i32",
+    "bornvi_circuit_workspace_bytes": "u64 <- ptr i32 i32 i32 i32",
+    "bornvi_circuit_probs": "i32 <- ptr i32 i32 i32 i32 ptr ptr ptr u64 ptr",
+    "bornvi_paramshift_probs": "i32 <- ptr i32 i32 i32 ptr i32 i32 i32 ptr ptr u64 ptr",
+    "bornvi_paramshift_probs_strided": "i32 <- ptr i32 i32 i32 ptr i32 i32 i32 i32 ptr ptr u64 ptr",
+    "bornvi_paramshift_grad_workspace_bytes": "u64 <- ptr i32 i32 i32 i32 i32",
+    "bornvi_paramshift_grad": "i32 <- ptr i32 i32 i32 ptr ptr i32 i32 ptr ptr u64 ptr",
+    "bornvi_paramshift_dot_workspace_bytes": "u64 <- ptr i32 i32 i32 i32",
+    "bornvi_paramshift_dot_begin": "i32 <- ptr i32 i32 i32 ptr i32 i32 i32 ptr ptr u64 ptr",
+    "bornvi_paramshift_dot_finish": "i32 <- ptr i32 i32 i32 i32 ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_gate1q_apply": "i32 <- ptr i32 i64 ptr i32 ptr ptr",
+    "bornvi_cnot_apply": "i32 <- ptr i32 i64 ptr i32 i32 ptr",
+    "bornvi_born_probs": "i32 <- ptr i32 i64 ptr ptr ptr",
+    "bornvi_score_from_cpts": "i32 <- ptr ptr i32 ptr ptr ptr",
+    "bornvi_bn_logjoint_samples": "i32 <- ptr ptr i32 i64 ptr f64 ptr ptr",
+    "bornvi_bn_score_samples": "i32 <- ptr ptr i32 i64 ptr f64 ptr ptr ptr",
+    "bornvi_stein_pairs_workspace_bytes": "u64 <- ptr i32 i64",
+    "bornvi_stein_pairs_rowsum": "i32 <- ptr i32 i64 f64 ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_stein_pairs_geometry": "i32 <- i64 ptr ptr",
+    "bornvi_stein_gram_build": "i32 <- ptr i32 f64 ptr ptr ptr",
+    "bornvi_stein_gram_build_rows": "i32 <- ptr i32 f64 ptr i64 i64 ptr ptr",
+    "bornvi_stein_gram_ld": "i64 <- i32",
+    "bornvi_stein_gram_build_rows_ld": "i32 <- ptr i32 f64 ptr i64 i64 ptr i64 ptr",
+    "bornvi_stein_kp_pairs": "i32 <- ptr i32 f64 i64 ptr ptr ptr ptr ptr ptr",
+    "bornvi_stein_quadform_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_stein_quadform": "i32 <- ptr i32 ptr ptr i32 ptr ptr ptr u64 ptr",
+    "bornvi_stein_quadform_ld": "i32 <- ptr i32 ptr i64 ptr i32 ptr ptr ptr u64 ptr",
+    "bornvi_stein_quadform_sym_workspace_bytes": "u64 <- ptr i32",
+    "bornvi_stein_quadform_sym": "i32 <- ptr i32 ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_stein_quadform_sym_ld": "i32 <- ptr i32 ptr i64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_stein_sym_strip_rows": "i32 <-",
+    "bornvi_stein_quadform_sym_pairs": "i32 <- ptr i32 ptr ptr i64 i64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_stein_quadform_sym_pairs_ld": "i32 <- ptr i32 ptr ptr i64 i64 i64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_stein_quadform_rows": "i32 <- ptr i32 ptr i64 i64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_stein_matvec_kron_workspace_bytes": "u64 <- ptr i32",
+    "bornvi_stein_matvec_kron": "i32 <- ptr i32 f64 ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_ksd_grad_finish": "i32 <- ptr i32 ptr i32 ptr ptr ptr ptr ptr ptr",
+    "bornvi_shots_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_shots_histogram": "i32 <- ptr i32 i32 ptr ptr i64 u64 ptr i32 i32 i32 ptr u64 ptr",
+    "bornvi_born_table_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_born_table_probs": "i32 <- ptr i32 i32 i32 ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_born_table_vjp": "i32 <- ptr i32 i32 i32 ptr ptr ptr ptr f64 ptr ptr ptr u64 ptr",
+    "bornvi_reinforce_workspace_bytes": "u64 <- ptr i32 i64",
+    "bornvi_reinforce_step": "i32 <- ptr i32 i64 ptr ptr ptr ptr ptr i32 f64 f64 f64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_elbo_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_elbo_weights": "i32 <- ptr i32 i32 ptr ptr f64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_mps_probs": "i32 <- ptr i32 i32 ptr ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_vjp": "i32 <- ptr i32 i32 ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_sample_workspace_bytes": "u64 <- ptr i32 i32 i64",
+    "bornvi_mps_environments": "i32 <- ptr i32 i32 i64 ptr ptr ptr u64 ptr",
+    "bornvi_mps_sample": "i32 <- ptr i32 i32 i64 ptr u64 ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_score_vjp": "i32 <- ptr i32 i32 i64 ptr ptr ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_fisher_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_fisher_gram": "i32 <- ptr i32 ptr i32 ptr f64 ptr ptr u64 ptr",
+    "bornvi_spd_solve_workspace_bytes": "u64 <- ptr i32",
+    "bornvi_spd_solve": "i32 <- ptr i32 ptr f64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_spd_solve_batched_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_spd_solve_batched": "i32 <- ptr i32 i32 ptr f64 ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_score_rows": "i32 <- ptr i32 i32 i64 ptr ptr i32 i32 i64 ptr ptr ptr u64 ptr",
+    "bornvi_score_fisher_workspace_bytes": "u64 <- ptr i32 i32 i64",
+    "bornvi_score_fisher_gram": "i32 <- ptr i32 i32 i64 i64 ptr ptr ptr u64 ptr",
+    "bornvi_mps_score_sample_gram_workspace_bytes": "u64 <- ptr i32 i32 i64",
+    "bornvi_mps_score_sample_gram": "i32 <- ptr i32 i32 i64 ptr ptr ptr ptr ptr u64 ptr u64 ptr",
+    "bornvi_mps_score_jvp": "i32 <- ptr i32 i32 i64 ptr ptr ptr f64 ptr ptr ptr u64 ptr",
+    "bornvi_mps_query_workspace_bytes": "u64 <- ptr i32 i32 i32",
+    "bornvi_mps_log_marginals": "i32 <- ptr i32 i32 i32 ptr ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_sample_clamped": "i32 <- ptr i32 i32 i64 ptr ptr ptr u64 ptr ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_marginals": "i32 <- ptr i32 i32 ptr ptr ptr ptr u64 ptr",
+    "bornvi_mps_canon_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_mps_canonicalise": "i32 <- ptr i32 i32 i32 f64 ptr ptr ptr ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_bn_sample": "i32 <- ptr ptr i32 i64 u64 ptr ptr ptr ptr ptr",
+    "bornvi_mps_log_marginals_vjp_workspace_bytes": "u64 <- ptr i32 i32 i32",
+    "bornvi_mps_log_marginals_vjp_geometry": "i32 <- i32 ptr",
+    "bornvi_mps_log_marginals_vjp": "i32 <- ptr i32 i32 i32 ptr ptr ptr ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_cg_init": "i32 <- ptr i64 ptr ptr ptr ptr ptr ptr ptr",
+    "bornvi_cg_step": "i32 <- ptr i64 f64 f64 ptr ptr ptr ptr ptr ptr",
+    "bornvi_cg_finish": "i32 <- ptr i64 ptr ptr ptr ptr ptr ptr ptr",
+    "bornvi_paramshift_states_workspace_bytes": "u64 <- ptr i32 i32 i32 i32",
+    "bornvi_paramshift_states": "i32 <- ptr i32 i32 i32 ptr i32 i32 i32 ptr ptr u64 ptr",
+    "bornvi_qfi_workspace_bytes": "u64 <- ptr i32 i32",
+    "bornvi_qfi_gram": "i32 <- ptr i32 i32 ptr ptr ptr ptr u64 ptr",
+    "bornvi_clip_cast_grad": "i32 <- ptr i32 ptr f64 ptr ptr ptr",
+    "bornvi_clip_cast_grad_guard": "i32 <- ptr i32 ptr f64 ptr ptr ptr ptr ptr",
+    "bornvi_clip_adam_step": "i32 <- ptr i32 ptr f64 ptr ptr ptr ptr ptr ptr ptr ptr i32 f64 f64 f64 ptr ptr ptr ptr",
+    "bornvi_adjoint_workspace_bytes": "u64 <- ptr i32 i32 i32",
+    "bornvi_adjoint_state": "i32 <- ptr i32 i32 i32 ptr ptr ptr ptr u64 ptr",
+    "bornvi_adjoint_vjp": "i32 <- ptr i32 i32 i32 ptr ptr ptr ptr ptr u64 ptr",
+    "bornvi_plan_describe": "i64 <- i32 i32 i32 i32 ptr u64",
+    "bornvi_plan_param_first_pass": "i32 <- i32 i32 i32 i32 ptr i32",
+    "bornvi_plan_fast_describe": "i64 <- i32 i32 i32 i32 ptr u64 ptr i32",
+    "bornvi_plan_compact_describe": "i64 <- i32 i32 i32 i32 ptr u64 ptr i32",
+}
+
+# Every limit of the header with the literal the Python backend carried before it read them from there, and the backend
+# constant that now takes its value from it (None: used by the library only).
+ABI_LIMITS = {
+    "BORNVI_CIRCUIT_MAX_N": (29, "CIRCUIT_MAX_N"),
+    "BORNVI_DENSE_MAX_N": (17, None),
+    "BORNVI_DENSE_MAX_LD_PAD": (4096, None),
+    "BORNVI_TABLE_MAX_N": (30, None),
+    "BORNVI_GATE_MAX_N": (40, None),
+    "BORNVI_BN_MAX_NODES": (64, None),
+    "BORNVI_BORN_TABLE_MAX_ROWS": (65535, "BORN_TABLE_MAX_ROWS"),
+    "BORNVI_ELBO_MAX_ROWS": (65535, "ELBO_MAX_ROWS"),
+    "BORNVI_REINFORCE_MAX_BATCH": (1 << 24, "REINFORCE_MAX_BATCH"),
+    "BORNVI_SHOTS_MAX": ((1 << 31) - 1, "SHOTS_MAX"),
+    "BORNVI_MPS_MAX_N": (26, "MPS_MAX_N"),
+    "BORNVI_MPS_MAX_BOND": (32, "MPS_MAX_BOND"),
+    "BORNVI_MPS_SAMPLED_MAX_N": (63, "MPS_SAMPLED_MAX_N"),
+    "BORNVI_MPS_SAMPLED_MAX_BATCH": (1 << 24, "MPS_SAMPLED_MAX_BATCH"),
+    "BORNVI_SCORE_MIN_LD": (64, None),
+    "BORNVI_MPS_QUERY_MAX_QUERIES": (1 << 16, "MPS_QUERY_MAX_QUERIES"),
+    "BORNVI_STEIN_PAIRS_MAX_B": (1 << 17, "STEIN_PAIRS_MAX_BATCH"),
+    "BORNVI_FISHER_MAX_PARAMS": (1024, "FISHER_MAX_PARAMS"),
+    "BORNVI_SAMPLE_GRAM_MAX_BATCH": (1024, "SAMPLE_GRAM_MAX_BATCH"),
+    "BORNVI_SPD_BATCHED_MAX_SYSTEMS": (65535, None),
+    "BORNVI_SCORE_FISHER_MAX_BLOCKS": (65535, None),
+    "BORNVI_CG_MAX_PARAMS": ((1 << 31) - 1, "CG_MAX_PARAMS"),
+    "BORNVI_CG_STATE_DOUBLES": (8, "CG_STATE_DOUBLES"),
+}
+
+
+def _abi_kind(t):
+    import ctypes as C
+    if t is None:
+        return "void"
+    if t is C.c_char_p:
+        return "str"
+    if t is C.c_void_p or issubclass(t, C._Pointer):
+        return "ptr"
+    return {C.c_int: "i32", C.c_longlong: "i64", C.c_ulonglong: "u64", C.c_size_t: "u64", C.c_double: "f64"}[t]
+
+
+def test_prototypes_parsed_from_the_header_are_the_hand_written_ones():
+    from tensornetworks_amd import _ext
+    parsed = {name: f"{_abi_kind(res)} <- {' '.join(_abi_kind(a) for a in args)}".rstrip()
+              for name, (res, args) in _ext.PROTOTYPES.items()}
+    assert len(ABI_KINDS) == 99
+    assert parsed == ABI_KINDS, {k: (parsed.get(k), ABI_KINDS.get(k)) for k in set(parsed) | set(ABI_KINDS) if parsed.get(k) != ABI_KINDS.get(k)}
+    assert _ext.EXPORTED_SYMBOLS == tuple(_ext.PROTOTYPES)
+    lib = _ext.lib()
+    for name, (res, args) in _ext.PROTOTYPES.items():        # what the loaded functions carry is the parsed table
+        assert getattr(lib, name).restype is res and list(getattr(lib, name).argtypes) == list(args), name
+    assert (_ext.BORNVI_OK, _ext.ANSATZ_IDS) == (0, {"hardware_efficient": 0, "all_to_all": 1, "basic": 2})
+
+
+def test_limits_parsed_from_the_header_are_the_backends_literals():
+    from tensornetworks_amd import _ext, backend, born_machine_base
+    from tensornetworks_amd.amortised_vi_sampled import AmortisedMPSInference
+    assert _ext.LIMITS == dict({name: value for name, (value, _) in ABI_LIMITS.items()}, BORNVI_VERSION=100)
+    for name, (value, constant) in ABI_LIMITS.items():
+        if constant is not None:
+            assert getattr(backend, constant) == value == _ext.LIMITS[name], (name, constant)
+    assert born_machine_base.MAX_EVIDENCE_QUERIES == 1 << 16 and AmortisedMPSInference.MAX_ENUMERATED_OBSERVED == 16
+
+
+def test_bn_descriptor_fields_are_the_headers():
+    from tensornetworks_amd import _ext
+    hdr = open(os.path.join(REPO, "include", "bornvi.h")).read()
+    body = re.search(r"typedef struct \{(.*?)\} bornvi_bn_desc;", hdr, re.S).group(1)
+    members = re.findall(r"(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert members == [name for name, _ in _ext.BnDesc._fields_] and len(members) == 7
+
+
+def test_header_parser_refuses_what_it_cannot_map():
+    from tensornetworks_amd import _ext
+    ok = "#define BORNVI_X 7\nint bornvi_f(bornvi_handle h, const float* w, long long* out);\n"
+    assert _ext.parse_header(ok)[0] == {"BORNVI_X": 7} and list(_ext.parse_header(ok)[2]) == ["bornvi_f"]
+    with pytest.raises(_ext.BornviError, match=r"float.*int bornvi_f\(bornvi_handle h, float w\);"):
+        _ext.parse_header("#define BORNVI_X 7\nint bornvi_f(bornvi_handle h, float w);\n")
+    with pytest.raises(_ext.BornviError, match="cannot read"):
+        _ext.parse_header("int bornvi_f(int (*callback)(int));\n")
+
+
+def test_host_only_calls_take_byref_and_arrays():
+    """The parser maps every `T*` to c_void_p where the hand-written table had POINTER(T) for a few host-only calls: byref()
+    and ctypes arrays still pass."""
+    import ctypes as C
+    from tensornetworks_amd import _ext
+    lib = _ext.lib()
+    tiles, ranges, groups = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    assert lib.bornvi_stein_pairs_geometry(4096, C.byref(tiles), C.byref(ranges)) == 0 and tiles.value > 0 and ranges.value > 0
+    assert lib.bornvi_mps_log_marginals_vjp_geometry(300, C.byref(groups)) == 0 and groups.value > 0
+    words = _ext.plan_words(0, 5, 2)
+    first = (C.c_int * 64)()
+    assert lib.bornvi_plan_param_first_pass(0, 5, 2, 0, first, 64) == 30
+    assert list(first[:30]) == list(_ext.plan_param_first_pass(words))
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_product_fails_loudly_without_gpu():
     from tensornetworks_amd import _ext, backend

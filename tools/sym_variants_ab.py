@@ -17,9 +17,8 @@ libs = [os.path.join(os.path.dirname(_ext.__file__), "libbornvi_hip.so")] + sys.
 for rnd in range(2):
     for path in libs:
         L = C.CDLL(path)
-        L.bornvi_stein_quadform_sym_workspace_bytes.restype = C.c_size_t
-        L.bornvi_stein_quadform_sym_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
-        L.bornvi_stein_quadform_sym.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        for name in ("bornvi_create", "bornvi_stein_quadform_sym_workspace_bytes", "bornvi_stein_quadform_sym"):
+            getattr(L, name).restype, getattr(L, name).argtypes = _ext.PROTOTYPES[name]   # (a variant may lack newer symbols)
         h = C.c_void_p()
         assert L.bornvi_create(0, C.byref(h)) == 0
         wsb = L.bornvi_stein_quadform_sym_workspace_bytes(h, n)
