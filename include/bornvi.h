@@ -16,6 +16,14 @@
  *   - workspace is caller-provided; bornvi_*_workspace_bytes gives the size for the full
  *     batch, a smaller workspace makes the library process the batch in chunks
  *     (it must hold at least one circuit);
+ *   - alignment: a pointer needs the alignment of its element type (float64 and int64: 8 bytes,
+ *     float32 and int32: 4, complex128: 16) unless its entry point states more, and what an entry
+ *     point states it enforces: any other address is refused before any launch.  Where a kernel
+ *     reads float64 inputs two at a time (q, y, dLdq, the shifted rows) it uses the device's
+ *     unaligned global loads: 8-byte alignment of those pointers is supported, and results do
+ *     not depend on where a buffer lies.  A workspace may lie at any 8-byte aligned address (the
+ *     library aligns what it carves and the size queries count that) unless its entry point
+ *     asks for 16 bytes;
  *   - a handle is bound to one device and is not thread-safe; distinct handles are.
  *   - outcome index i <-> bitstring bin(i).zfill(n): bit position 0 of the tuple is the MOST
  *     significant bit of i and is wire 0 of the circuit (utils.py:77-91).
@@ -138,7 +146,9 @@ int bornvi_num_gates(int ansatz, int n, int layers);
 
 /* ---- circuit -> Born probabilities (replaces the PennyLane QNode `pqc`, -------------------
  * quantum_born_machine.py:58-128, as called by get_probabilities :132-137).
- * thetas dev [batch, P] float64;  probs dev [batch, 2^n] float64, lexicographic, wire 0 = MSB. */
+ * thetas dev [batch, P] float64;  probs dev [batch, 2^n] float64, lexicographic, wire 0 = MSB.
+ * workspace: 16-byte aligned (the states are carved from the pointer as given), else
+ * BORNVI_ERR_WORKSPACE; the same holds for every bornvi_paramshift_* call below. */
 size_t bornvi_circuit_workspace_bytes(bornvi_handle h, int ansatz, int n, int layers, int batch);
 int bornvi_circuit_probs(bornvi_handle h, int ansatz, int n, int layers, int batch,
                          const double* thetas, double* probs,
@@ -263,7 +273,9 @@ int bornvi_stein_pairs_geometry(long long B, int* tiles_per_range, int* num_rang
 
 /* ---- Stein-kernel Gram matrix (replaces the N^2 calls of get_stein_kernel_kp_value, --------
  * stein_utils.py:138-197 with base_hamming_kernel_torch :30-55, made in
- * ksd_vi_quantum.py:125-141).  K dev [2^n, 2^n] float64 row-major. */
+ * ksd_vi_quantum.py:125-141).  K dev [2^n, 2^n] float64 row-major, 16-byte aligned (so are K_rows
+ * of the two calls below: the kernel stores column pairs, and bornvi_stein_quadform_sym asks the
+ * same of the K it reads); anything else is BORNVI_ERR_INVALID before any launch. */
 int bornvi_stein_gram_build(bornvi_handle h, int n, double length_scale, const double* S,
                             double* K, bornvi_stream stream);
 
@@ -309,7 +321,8 @@ int bornvi_stein_quadform_ld(bornvi_handle h, int n, const double* K, long long 
  * only the upper triangle, i.e. half the HBM traffic of bornvi_stein_quadform; deterministic (column
  * partials in the workspace instead of atomics).  q, y dev [2^n]; ksd2 dev [1].  A dense (unpadded) matrix with
  * n < 14 is handed to the full-matrix kernel: too few 256-row bands to fill the chip, and the matrix is cache-sized
- * (n = 12: 33 us against 93 us); same K q to rounding. */
+ * (n = 12: 33 us against 93 us); same K q to rounding.  K (K_lo and K_hi of the strip-pair shard) and
+ * the workspace: 16-byte aligned, in every bornvi_stein_quadform_sym* call. */
 size_t bornvi_stein_quadform_sym_workspace_bytes(bornvi_handle h, int n);
 int bornvi_stein_quadform_sym(bornvi_handle h, int n, const double* K, const double* q,
                               double* ksd2, double* y, void* workspace, size_t workspace_bytes,
@@ -348,7 +361,8 @@ int bornvi_stein_quadform_rows(bornvi_handle h, int n, const double* K_rows, lon
                                bornvi_stream stream);
 
 /* Matrix-free y = K_p q via the Kronecker structure of K_p (needed where the dense Gram does
- * not fit: n = 20 would be 8 TiB).  q, y dev [2^n]; ksd2 dev [1]. */
+ * not fit: n = 20 would be 8 TiB).  q, y dev [2^n]; ksd2 dev [1].  workspace: 16-byte aligned (the
+ * circuit engine's states are carved from the pointer as given), else BORNVI_ERR_WORKSPACE. */
 size_t bornvi_stein_matvec_kron_workspace_bytes(bornvi_handle h, int n);
 int bornvi_stein_matvec_kron(bornvi_handle h, int n, double length_scale, const double* S,
                              const double* q, double* y, double* ksd2, void* workspace,
@@ -776,7 +790,9 @@ int bornvi_clip_adam_step(bornvi_handle h, int P, const double* grad64, double m
  *   bornvi_adjoint_state: theta dev [P] -> state dev [2^n] complex128 = U(theta)|0..0> (canonical order, wire 0 = MSB),
  *                         probs dev [2^n] = |state|^2 or NULL;
  *   bornvi_adjoint_vjp:   state (as returned above, left untouched), dLdq dev [2^n] -> grad dev [P]
- *                         = d/dtheta sum_z dLdq[z] q_z(theta).  Deterministic (fixed summation order). */
+ *                         = d/dtheta sum_z dLdq[z] q_z(theta).  Deterministic (fixed summation order).
+ * workspace of both: 16-byte aligned (the walk's states are carved from the pointer as given), else
+ * BORNVI_ERR_WORKSPACE. */
 size_t bornvi_adjoint_workspace_bytes(bornvi_handle h, int ansatz, int n, int layers);
 int bornvi_adjoint_state(bornvi_handle h, int ansatz, int n, int layers, const double* theta, double* state,
                          double* probs, void* workspace, size_t workspace_bytes, bornvi_stream stream);

@@ -381,6 +381,7 @@ int circuit_batch(bornvi_handle h, int ansatz, int n, int layers, long long batc
   const Plan& p = dp->plan;
   const size_t pcb = per_circuit_bytes(p);
   if (!ws || ws_bytes < 512) return fail(h, BORNVI_ERR_WORKSPACE, "workspace missing");
+  if ((uintptr_t)ws & 15) return fail(h, BORNVI_ERR_WORKSPACE, "workspace must be 16-byte aligned");   // (the states are carved from the pointer as given)
   // carve: [gates | stateA | stateB], each region 256-byte aligned
   long long bc_max = (long long)((ws_bytes - 512) / pcb);
   if (bc_max > batch) bc_max = batch;
@@ -1017,6 +1018,7 @@ int bornvi_stein_gram_build_rows_ld(bornvi_handle h, int n, double length_scale,
   if (!(length_scale > 0.0)) return fail(h, BORNVI_ERR_INVALID, "length_scale must be positive");
   if (row_begin < 0 || row_end < row_begin || row_end > (1ll << n)) return fail(h, BORNVI_ERR_INVALID, "row range out of bounds");
   if (!valid_ld(n, ld)) return fail(h, BORNVI_ERR_INVALID, DENSE_LD_RANGE);
+  if ((uintptr_t)K_rows & 15) return fail(h, BORNVI_ERR_INVALID, "K must be 16-byte aligned");   // (the kernel stores column pairs)
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_gram_build(n, length_scale, S, K_rows, row_begin, row_end, ld, (hipStream_t)stream));
   return BORNVI_OK;
@@ -1172,6 +1174,7 @@ int bornvi_stein_matvec_kron(bornvi_handle h, int n, double length_scale, const 
   const size_t need = bornvi_stein_matvec_kron_workspace_bytes(h, n);
   if (!need) return h->err.empty() ? fail(h, BORNVI_ERR_UNSUPPORTED, "unsupported n") : BORNVI_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < need) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  if ((uintptr_t)workspace & 15) return fail(h, BORNVI_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   DevPlan* dp = nullptr;
   int rc = get_plan(h, -1, n, 0, &dp);
   if (rc) return rc;
@@ -1807,6 +1810,7 @@ int bornvi_adjoint_state(bornvi_handle h, int ansatz, int n, int layers, const d
   if (rc) return rc;
   if (!state || (!theta && ap->n_params > 0)) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!workspace || workspace_bytes < bornvi_adjoint_workspace_bytes(h, ansatz, n, layers)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  if ((uintptr_t)workspace & 15) return fail(h, BORNVI_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DEVICE_SCOPE(h);
   double* other = (double*)((char*)workspace + 256);
@@ -1835,6 +1839,7 @@ int bornvi_adjoint_vjp(bornvi_handle h, int ansatz, int n, int layers, const dou
   if (ap->n_params == 0) return BORNVI_OK;
   if (!state || !dLdq || !grad || !theta) return fail(h, BORNVI_ERR_INVALID, "null pointer");
   if (!workspace || workspace_bytes < bornvi_adjoint_workspace_bytes(h, ansatz, n, layers)) return fail(h, BORNVI_ERR_WORKSPACE, "workspace too small");
+  if ((uintptr_t)workspace & 15) return fail(h, BORNVI_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DEVICE_SCOPE(h);
   const size_t sb = align_up((size_t)16 << n, 256);

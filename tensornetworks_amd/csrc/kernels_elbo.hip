@@ -61,10 +61,15 @@ __global__ __launch_bounds__(EL_THREADS) void elbo_weights_kernel(const double* 
       o.y = elbo_entry(a.y, p.y, q_floor, loss, qlogq);
       if (wr) reinterpret_cast<double2*>(wr)[i] = o;
     }
-  } else {
-    for (long long i = c0 + threadIdx.x; i < c1; i += EL_THREADS) {
-      const double o = elbo_entry(qr[i], log_p[i], q_floor, loss, qlogq);
-      if (wr) wr[i] = o;
+  } else {        // the same pairs per thread in the same order (N = 2^n, n >= 1, and the chunk are even): the sums' bits do not
+                  // depend on where the caller's buffers lie
+    for (long long i = c0 / 2 + threadIdx.x; i < c1 / 2; i += EL_THREADS) {
+      const double o0 = elbo_entry(qr[2 * i], log_p[2 * i], q_floor, loss, qlogq);
+      const double o1 = elbo_entry(qr[2 * i + 1], log_p[2 * i + 1], q_floor, loss, qlogq);
+      if (wr) {
+        wr[2 * i] = o0;
+        wr[2 * i + 1] = o1;
+      }
     }
   }
   loss = block_sum<EL_WAVES>(loss, lds);
