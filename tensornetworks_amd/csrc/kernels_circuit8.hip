@@ -68,6 +68,18 @@ __device__ __forceinline__ uint32_t xor_cols16(uint32_t v, int nbits, const uint
   return o;
 }
 
+// the bits of j, in order, at the set positions of mask (wave-uniform: scalar code)
+__device__ __forceinline__ uint32_t deposit_bits16(uint32_t j, uint32_t mask) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const uint32_t m = (mask >> i) & 1u;
+    o |= (j & m) << i;
+    j >>= m;
+  }
+  return o;
+}
+
 template <int I>
 __device__ __forceinline__ void gate8(double (&ar)[8], double (&ai)[8], const double (&U)[8]) {
 #pragma unroll
@@ -335,7 +347,9 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
 
   const long long walk_flip = total_tiles - 1;
   const bool walk_rev = (direct_mask & 4) != 0;
-  const bool zskip = init && gbits > 0 && total_tiles < (1ll << 31);
+  // (an INIT pass has no input (plan.cpp: PASS_INIT <=> no in_state), and the launcher sends a pass without input to
+  // <false, false> only: the other two instantiations carry no walk of zero tiles, which costs them SGPR spill moves)
+  const bool zskip = !DOT && !SPREAD && init && gbits > 0 && total_tiles < (1ll << 31);
   const uint32_t zinfo = (direct_mask & 8) ? H[CH_ZINFO] : 0u;
   const uint32_t zgmask = zskip ? zinfo : 0u;
   const uint32_t zslots = (!init && direct_in) ? (zinfo & 0xffu) : 0u;
@@ -385,13 +399,20 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
     // (tiles below 2^9: only the first 2^(k-3) lanes of the one wave hold amplitudes; the fused-dot instantiation is
     // offered for tiles of whole waves only)
     const bool active = DOT ? true : t_t < (ksize >> 3);
-    const bool has_next = Snext < total_tiles;
+    bool has_next = Snext < total_tiles;
     long long Tcur, Tnext;
     if (zskip) {     // INIT pass: the one non-zero tile of every circuit first, spread over all workgroups, then the zero tiles
+      // Only the tiles the pass writes are walked: the zs_nb non-zero tiles, then per circuit the zs_zw zero tiles of the rows
+      // g != 0 with (g & zgmask) == 0 (the others nobody reads: no trip, no barriers; when zgmask covers every row bit the
+      // walk ends at zs_nb).  zs_free: the row bits such a g may have; the j-th such row has the bits of j at those places.
+      // (Formed per trip from zgmask: nothing more is carried round the tile loop.)
+      const uint32_t zs_free = zs_gm1 & ~zgmask, zs_zw = (1u << __popc(zs_free)) - 1u;
+      has_next = Snext < (long long)zs_nb * (1u + zs_zw);
       const uint32_t sc = (uint32_t)(real ? Scur : 0), sn = (uint32_t)(has_next ? Snext : 0);
-      const uint32_t bc_ = sc < zs_nb ? sc : (sc - zs_nb) / zs_gm1, bn_ = sn < zs_nb ? sn : (sn - zs_nb) / zs_gm1;
-      Tcur = sc < zs_nb ? ((long long)sc << gbits) : (((long long)bc_ << gbits) | (1u + (sc - zs_nb - bc_ * zs_gm1)));
-      Tnext = sn < zs_nb ? ((long long)sn << gbits) : (((long long)bn_ << gbits) | (1u + (sn - zs_nb - bn_ * zs_gm1)));
+      const uint32_t zw_ = zs_zw ? zs_zw : 1u;     // (zs_zw == 0: sc, sn < zs_nb, nothing is divided)
+      const uint32_t bc_ = sc < zs_nb ? sc : (sc - zs_nb) / zw_, bn_ = sn < zs_nb ? sn : (sn - zs_nb) / zw_;
+      Tcur = sc < zs_nb ? ((long long)sc << gbits) : (((long long)bc_ << gbits) | deposit_bits16(1u + (sc - zs_nb - bc_ * zw_), zs_free));
+      Tnext = sn < zs_nb ? ((long long)sn << gbits) : (((long long)bn_ << gbits) | deposit_bits16(1u + (sn - zs_nb - bn_ * zw_), zs_free));
     } else {
       Tcur = walk_rev ? walk_flip - Scur : Scur;
       Tnext = walk_rev ? walk_flip - Snext : Snext;
@@ -399,8 +420,7 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
     if (!real && !has_next) break;
     const uint32_t g = real ? (uint32_t)(Tcur & ((1ll << gbits) - 1)) : 0u;
     const long long b = real ? (Tcur >> gbits) : 0;
-    const bool zero_tile = zskip && real && g != 0u;
-    const bool noop_tile = zero_tile && (g & zgmask) != 0u;
+    const bool zero_tile = zskip && real && g != 0u;     // (every zero tile of the walk is one the pass writes)
     const char* __restrict__ gb = reinterpret_cast<const char*>(gates + b * gate_stride);   // this circuit's fused matrices
     // (normalised gates: the pivots' |p|^2 multiply back into the probabilities; slot nfused of the circuit's gate array)
     double scale = 1.0;
@@ -493,7 +513,7 @@ __global__ __launch_bounds__(1024) void circuit_pass_r3_kernel(
     if (real) {
       for (int s = s0 + npeel; s < (zero_tile ? 0 : nstages); ++s) BORNVI_LDS_STAGE8(s);
       // ---- tile out: exactly 8 vector-memory stores per wave (the vmcnt waits count them), here or in the last stage ----
-      if (noop_tile || !active) {
+      if (!active) {
       } else if (zero_tile) {
         const uint32_t off0 = (xor_cols16(t_t, kt, P + PW_OUT_COL) ^ xor_cols16(g, gbits, P + PW_OUT_GCOL)) << out_shift;
 #pragma unroll
