@@ -17,7 +17,7 @@ import torch
 
 from . import backend
 from .bayesian_network import pack_network_for_sampling
-from .born_machine_mps_sampled import SampledMPSBornMachine
+from .born_machine_mps_sampled import SampledMPSBornMachine, append_sweep
 from .sampled_trainer import checked_config, host_update, make_sampled_optimizer
 from .utils import generate_all_binary_outcomes
 
@@ -151,6 +151,35 @@ class AmortisedMPSInference:
                 if sched is not None:
                     msg += f" | LR: {sched.get_last_lr()[0]:.6f}"
                 print(msg)
+        return history
+
+    def train_two_site(self, num_sweeps, lr, descent_steps=5, cutoff=1e-4, max_rank=None, verbose=True, sweep_callback=None):
+        """Training by two-site sweeps, objective 'joint' only: sweep e draws fresh (x, z) ~ p with
+        (seed, e) exactly as loss_and_grad does and runs one round trip of SampledMPSBornMachine.two_site_sweep_ on the draws
+        with weights 1 / B: descent_steps plain steps of size lr per bond, every bond then cut to the rank its spectrum shows
+        (at most max_rank, default the machine's bond_dim: expand_ raises that cap; values go from the small end while their
+        squares sum to <= cutoff).  No optimiser.  sweep_callback(sweep, self), where given, runs after every sweep.  History:
+        loss (the last bond's), bond_loss, rank, discarded, status (the sweep's status word; 16 is added when the network
+        sampler reported a dead draw)."""
+        if isinstance(num_sweeps, bool) or not isinstance(num_sweeps, int) or num_sweeps < 1:
+            raise ValueError(f"num_sweeps must be a positive integer, got {num_sweeps!r}")
+        bm = self.born_machine
+        B, n = self.num_samples, self.num_sites
+        bm._check_two_site(B, None, lr, descent_steps, cutoff, max_rank)
+        self._prepare()
+        history = {'loss': [], 'bond_loss': [], 'rank': [], 'discarded': [], 'status': []}
+        for sweep in range(num_sweeps):
+            self._epoch_dev.fill_(sweep)
+            idx, _, st_s = backend.bn_sample(self._desc[1], n, B, self.seed, self._epoch_dev)
+            self.last_idx = idx
+            report = bm.two_site_sweep_(idx, None, lr, descent_steps, cutoff, max_rank)
+            append_sweep(history, report)
+            if int(st_s.item()) != 0:
+                history['status'][-1] |= 16
+            if sweep_callback is not None:
+                sweep_callback(sweep, self)
+            if verbose:
+                print(f"Sweep {sweep+1}/{num_sweeps} | loss (joint, last bond): {history['loss'][-1]:.6f} | ranks: {history['rank'][-1]}")
         return history
 
     # ---- the fitted q read out per evidence: SampledMPSBornMachine's queries by variable name ----------------------------

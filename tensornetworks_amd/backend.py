@@ -829,6 +829,67 @@ def mps_canonicalise(cores, bond_dim_out=None, cutoff=0.0):
     return out, schmidt, discarded, rank, log_norm, status
 
 
+# ---- two-site sweeps of the sampled MPS (kernels_mps_twosite.hip, include/bornvi_twosite.h) --------
+MPS_TWOSITE_MAX_BOND = _ext.TWOSITE_LIMITS["BORNVI_MPS_TWOSITE_MAX_BOND"]
+MPS_TWOSITE_MAX_BATCH = _ext.TWOSITE_LIMITS["BORNVI_MPS_TWOSITE_MAX_BATCH"]
+MPS_TWOSITE_MAX_STEPS = _ext.TWOSITE_LIMITS["BORNVI_MPS_TWOSITE_MAX_STEPS"]
+
+
+def mps_twosite_args(cores, idx, w, lr, steps, bond_dim_keep, cutoff):
+    """(n, D, B, D_keep) of a two-site sweep's arguments; every argument error is raised here, before any GPU call."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    n, D, _ = _mps_args(cores, 1)
+    if n < 2:
+        raise BornviError("a two-site sweep needs at least two sites (n >= 2)")
+    if D > MPS_TWOSITE_MAX_BOND:
+        raise BornviError(f"two-site sweeps: bond dimension 1 ... {MPS_TWOSITE_MAX_BOND}, got {D}")
+    B = int(idx.numel())
+    if not 1 <= B <= MPS_TWOSITE_MAX_BATCH:
+        raise BornviError(f"number of samples: 1 ... 2^20 per two-site sweep, got {B}")
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= int(steps) <= MPS_TWOSITE_MAX_STEPS:
+        raise BornviError(f"steps must be an integer in 1 ... {MPS_TWOSITE_MAX_STEPS}, got {steps!r}")
+    Dk = D if bond_dim_keep is None else bond_dim_keep
+    if isinstance(Dk, bool) or not isinstance(Dk, (int, np.integer)) or not 1 <= int(Dk) <= D:
+        raise BornviError(f"bond_dim_keep must be an integer in 1 ... {D} (the cores' bond dimension), got {bond_dim_keep!r}")
+    _chk_positive(lr, "lr", allow_zero=True)
+    _chk_positive(cutoff, "cutoff", allow_zero=True)
+    if not cutoff < 1:
+        raise BornviError(f"cutoff must be < 1, got {cutoff!r}")
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    if w is not None:
+        if not torch.is_tensor(w):
+            raise BornviError("w: expected None or a [B] float64 tensor")
+        _chk(w, torch.float64, dev, "w", B)
+    return n, D, B, int(Dk)
+
+
+def mps_twosite_sweep(cores, idx, w=None, lr=0.05, steps=5, bond_dim_keep=None, cutoff=0.0):
+    """One round trip of two-site updates over the bonds of a sampled MPS (bornvi_mps_twosite_sweep): cores float64
+    [n, 2, D, D] on the GPU in canonical form (what mps_canonicalise returns; 2 <= n <= 63, D <= 16), REPLACED IN PLACE;
+    idx int64 [B] samples, w float64 [B] weights or None for 1 / B each -> (loss float64 [2 (n - 1)]: the merged tensor's
+    loss after the last descent step of every bond visited; schmidt float64 [n - 1, D]: the kept values of every bond over
+    their norm, descending, then 0.0; discarded float64 [n - 1]; rank int32 [n - 1]; status int32 [1]: a sum of 1 (non-finite
+    cores or norm: outputs NaN), 2 (some psi of a sample was 0 or not finite: left out at that bond), 4 (a factorisation did
+    not converge), 8 (the cores were not canonical on entry)).  bond_dim_keep (default D) and cutoff cut every bond as
+    mps_canonicalise does."""
+    n, D, B, Dk = mps_twosite_args(cores, idx, w, lr, steps, bond_dim_keep, cutoff)
+    dev = cores.device
+    h = _ext.handle_for(dev)
+    loss = torch.empty(2 * (n - 1), dtype=torch.float64, device=dev)
+    schmidt = torch.empty(n - 1, D, dtype=torch.float64, device=dev)
+    discarded = torch.empty(n - 1, dtype=torch.float64, device=dev)
+    rank = torch.empty(n - 1, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = _ws(dev, _cached_size(h, "bornvi_mps_twosite_workspace_bytes", n, D, B), f"mps_twosite_{n}_{D}_{B}")
+    h.call("bornvi_mps_twosite_sweep", n, D, B, _ptr(cores), _ptr(idx), _ptr(w) if w is not None else None, float(lr), int(steps),
+           Dk, float(cutoff), _ptr(loss), _ptr(schmidt), _ptr(discarded), _ptr(rank), _ptr(status), _ptr(ws), ws.numel(),
+           _ext.stream_ptr(dev))
+    return loss, schmidt, discarded, rank, status
+
+
 def bn_descriptor(packed, dev):
     """(device arrays, BnDesc) of bayesian_network.pack_network's dict; the arrays must outlive every call that uses the
     descriptor.  A network with a summed-out node is refused by bn_logjoint_samples, not here."""

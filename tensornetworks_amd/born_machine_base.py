@@ -275,7 +275,9 @@ class MPSCores:
         """Cuts the bonds as canonical_cores does and makes `cores` a NEW nn.Parameter [n, 2, D', D']: D' = bond_dim when
         given (at most the current D; D itself cuts by `cutoff` alone), else the largest kept rank.  Returns the report.  An optimiser built on the
         old parameter is stale: build a new one (the trainers build theirs inside train(), so train -> compress_ -> train
-        works as it stands)."""
+        works as it stands).  The same holds after SampledMPSBornMachine.two_site_sweep_ / fit_two_site and
+        AmortisedMPSInference.train_two_site, which keep the parameter but rewrite its data in another gauge: the Adam moments
+        of an optimiser built earlier mean nothing afterwards."""
         out, _, report = self._canonical(bond_dim, cutoff)
         if bond_dim is None:
             rank = report["rank"]

@@ -8,15 +8,30 @@ A sample is an int64 outcome index, idx = sum_k z_k 2^(n-k) (tuple position 0 = 
 bit row; the conversion, like the `cores` parameter, its checks, initialisations and messages, is born_machine_base's, shared
 with MPSBornMachine.  The fitted q is read out exactly, at any n, by marginals / pair_marginals / log_marginal / sample_given (DESIGN.md section
 6l): an evidence is a partial assignment {tuple position: 0 or 1}.
+two_site_sweep_ / fit_two_site train the cores on given samples by two-site (DMRG-style) sweeps that set every bond's rank from
+its spectrum.
 For n <= 26 the enumerated q is still there (probabilities64 / get_probabilities, through
 backend.mps_probs); above that those raise.
 """
+import math
+
 import torch
 import torch.nn as nn
 
 from . import backend
 from .born_machine_base import MPSCores, bits_to_indices, indices_to_bits, new_mps_cores, pack_evidence
 from .born_machine_mps import _MPSProbs
+
+
+def append_sweep(history, report):
+    """One two-site sweep's report appended to a history {'loss', 'bond_loss', 'rank', 'discarded', 'status'} of lists: the
+    sweep's one read-back."""
+    loss = report["loss"].cpu().tolist()
+    history["loss"].append(loss[-1])
+    history["bond_loss"].append(loss)
+    history["rank"].append(report["rank"].cpu().tolist())
+    history["discarded"].append(report["discarded"].cpu().tolist())
+    history["status"].append(int(report["status"].item()))
 
 
 class SampledMPSBornMachine(MPSCores, nn.Module):
@@ -85,6 +100,79 @@ class SampledMPSBornMachine(MPSCores, nn.Module):
         if x_condition is not None:
             raise ValueError("x_condition provided but Born machine is not conditional.")
         return self.log_prob(self.indices_of(z_samples)).to(z_samples.device)
+
+    # ---- two-site sweeps (backend.mps_twosite_sweep): bond ranks set by the data -------------------
+    def _samples_as_indices(self, idx_or_bits):
+        """int64 [B] outcome indices of an index vector or of [B, n] rows of 0 / 1, on the host's side of any GPU call."""
+        x = torch.as_tensor(idx_or_bits)
+        if x.dim() == 2:
+            return self.indices_of(x)
+        if x.dim() != 1 or x.dtype not in (torch.int64, torch.int32):
+            raise ValueError("samples: an integer index vector [B] or [B, n] rows of 0 / 1")
+        x = x.to(torch.int64)
+        n = self.num_latent_vars
+        if x.numel() and (int(x.min()) < 0 or (n < 63 and int(x.max()) >= (1 << n))):
+            raise ValueError(f"samples: an outcome index lies outside 0 ... 2^{n} - 1")
+        return x
+
+    def _check_two_site(self, num, weights, lr, steps, cutoff, max_rank):
+        D = self.bond_dim
+        if self.num_latent_vars < 2:
+            raise ValueError("two-site sweeps need at least two sites")
+        if D > backend.MPS_TWOSITE_MAX_BOND:
+            raise ValueError(f"two-site sweeps take a bond dimension of at most {backend.MPS_TWOSITE_MAX_BOND}, got {D}")
+        if not 1 <= num <= backend.MPS_TWOSITE_MAX_BATCH:
+            raise ValueError(f"two-site sweeps take 1 ... 2^20 samples, got {num}")
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr < 0:
+            raise ValueError(f"lr must be a finite number >= 0, got {lr!r}")
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= backend.MPS_TWOSITE_MAX_STEPS:
+            raise ValueError(f"steps must be an integer in 1 ... {backend.MPS_TWOSITE_MAX_STEPS}, got {steps!r}")
+        self._check_cut(max_rank, cutoff, D)
+        if not cutoff < 1:
+            raise ValueError(f"cutoff must be < 1, got {cutoff!r}")
+        if weights is not None:
+            w = torch.as_tensor(weights)
+            if w.dim() != 1 or w.numel() != num or not w.dtype.is_floating_point or bool((w < 0).any()) \
+                    or not bool(torch.isfinite(w).all()):
+                raise ValueError(f"weights: {num} finite numbers >= 0, one per sample")
+
+    def two_site_sweep_(self, idx_or_bits, weights=None, lr=0.05, steps=5, cutoff=1e-4, max_rank=None, canonicalise=True):
+        """One round trip of two-site (DMRG-style) updates on the given samples, in place: every pair of neighbouring cores
+        is merged, takes `steps` plain descent steps of size lr on the samples' weighted negative log-likelihood, and is
+        split again by an SVD that keeps at most max_rank (default: the bond dimension) values and drops from the small end
+        while the dropped squares sum to <= cutoff.  Each bond so takes the rank the data supports, inside the fixed
+        [n, 2, D, D] storage (compress_ shrinks it, expand_ raises the cap).  canonicalise: bring the cores to canonical form
+        first (canonicalise_()); pass False only for cores a sweep or canonicalise_() has just written.  Returns
+        {'loss' float64 [2 (n - 1)] (per bond visited), 'schmidt' float64 [n - 1, D], 'discarded' float64 [n - 1], 'rank'
+        int32 [n - 1], 'status' int32 [1]}, detached, on the compute device.  Like compress_, a sweep rewrites the cores in
+        another gauge: the Adam moments of an optimiser built earlier mean nothing afterwards; build a new one."""
+        idx = self._samples_as_indices(idx_or_bits)
+        self._check_two_site(int(idx.numel()), weights, lr, steps, cutoff, max_rank)
+        if canonicalise:
+            self.canonicalise_()
+        cores, home = MPSCores.kernel_input(self, detach=True)
+        if cores.data_ptr() == self.cores.data_ptr():
+            cores = cores.clone()
+        dev = cores.device
+        idx = idx.to(device=dev, dtype=torch.int64).contiguous()
+        w = None if weights is None else torch.as_tensor(weights).to(device=dev, dtype=torch.float64).contiguous()
+        loss, schmidt, discarded, rank, status = backend.mps_twosite_sweep(cores, idx, w, float(lr), steps, max_rank, float(cutoff))
+        with torch.no_grad():
+            self.cores.data.copy_(cores.to(device=home, dtype=self.cores.dtype))
+        return {"loss": loss, "schmidt": schmidt, "discarded": discarded, "rank": rank, "status": status}
+
+    def fit_two_site(self, data, num_sweeps, weights=None, lr=0.05, steps=5, cutoff=1e-4, max_rank=None):
+        """Maximum-likelihood training on a data set by two-site sweeps: data is [B, n] rows of 0 / 1 or an index vector [B];
+        num_sweeps round trips of two_site_sweep_ on it (the first from the canonical form of the current cores).  Returns the
+        history {'loss' (the last bond's, per sweep), 'bond_loss', 'rank', 'discarded', 'status'}: lists of num_sweeps entries."""
+        if isinstance(num_sweeps, bool) or not isinstance(num_sweeps, int) or num_sweeps < 1:
+            raise ValueError(f"num_sweeps must be a positive integer, got {num_sweeps!r}")
+        idx = self._samples_as_indices(data)
+        self._check_two_site(int(idx.numel()), weights, lr, steps, cutoff, max_rank)
+        history = {"loss": [], "bond_loss": [], "rank": [], "discarded": [], "status": []}
+        for _ in range(num_sweeps):
+            append_sweep(history, self.two_site_sweep_(idx, weights, lr, steps, cutoff, max_rank))
+        return history
 
     # ---- exact queries (DESIGN.md section 6l): detached, on the compute device -----------------------------------
     def _evidence(self, evidence, single=False):

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bornvi.h"
+#include "bornvi_twosite.h"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -1534,6 +1535,35 @@ int bornvi_mps_canonicalise(bornvi_handle h, int n, int D, int D_out, double cut
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_mps_canonicalise(n, D, D_out, cutoff, cores, cores_out, schmidt, discarded, rank, log_norm, status, workspace,
                                     (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+// ---- two-site sweeps of the sampled MPS (kernels_mps_twosite.hip; declared in bornvi_twosite.h) ---------------------
+static const char* const MPS_TWOSITE_RANGE =
+    "unsupported size (2 <= n <= 63, 1 <= D_keep <= D <= 16, 1 <= B <= 2^20, 1 <= steps <= 64, lr finite and >= 0, 0 <= cutoff < 1)";
+static bool valid_mps_twosite(int n, int D, long long B) {
+  return n >= 2 && n <= BORNVI_MPS_SAMPLED_MAX_N && D >= 1 && D <= BORNVI_MPS_TWOSITE_MAX_BOND && B >= 1 && B <= BORNVI_MPS_TWOSITE_MAX_BATCH;
+}
+
+size_t bornvi_mps_twosite_workspace_bytes(bornvi_handle h, int n, int D, long long B) {
+  if (!h) return 0;
+  if (!valid_mps_twosite(n, D, B)) { fail(h, BORNVI_ERR_UNSUPPORTED, MPS_TWOSITE_RANGE); return 0; }
+  return mps_twosite_workspace_bytes(n, D, B);
+}
+
+int bornvi_mps_twosite_sweep(bornvi_handle h, int n, int D, long long B, double* cores, const long long* idx, const double* w,
+                             double lr, int steps, int D_keep, double cutoff, double* loss, double* schmidt, double* discarded,
+                             int* rank, int* status, void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_mps_twosite(n, D, B) || steps < 1 || steps > BORNVI_MPS_TWOSITE_MAX_STEPS || D_keep < 1 || D_keep > D || !(lr >= 0.0) ||
+      !std::isfinite(lr) || !(cutoff >= 0.0) || !(cutoff < 1.0))
+    return fail(h, BORNVI_ERR_UNSUPPORTED, MPS_TWOSITE_RANGE);
+  if (!cores || !idx || !loss || !schmidt || !discarded || !rank || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!workspace || workspace_bytes < mps_twosite_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mps_twosite_sweep(n, D, B, cores, idx, w, lr, steps, D_keep, cutoff, loss, schmidt, discarded, rank, status, workspace,
+                                     (hipStream_t)stream));
   return BORNVI_OK;
 }
 

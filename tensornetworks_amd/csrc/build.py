@@ -9,8 +9,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_mps_sample_gram.hip", "kernels_mps_query.hip", "kernels_mps_canon.hip", "kernels_ksd_sampled.hip", "kernels_cg.hip", "plan.cpp"]
-HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "shots_dev.hpp", "mps_sample_dev.hpp", "syrk_f64.hpp", "reduce_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", "bornvi.h")]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_mps_sample_gram.hip", "kernels_mps_query.hip", "kernels_mps_canon.hip", "kernels_mps_twosite.hip", "kernels_ksd_sampled.hip", "kernels_cg.hip", "plan.cpp"]
+HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "shots_dev.hpp", "mps_sample_dev.hpp", "mps_canon_dev.hpp", "syrk_f64.hpp", "reduce_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", h) for h in ("bornvi.h", "bornvi_twosite.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-I" + os.path.join(REPO, "include"), "-I" + HERE,
@@ -74,6 +74,11 @@ RESOURCE_BUDGET = {
     "mps_logm_vjp_kernel": (0, 0),                # gradient of log-marginals: the environment step's code in both directions
     "mps_logm_vjp_finish_kernel": (0, 0),
     "mps_canon_kernel": (0, 0),                   # canonical form (kernels_mps_canon.hip): everything lives in LDS, no per-lane arrays
+    "mts_init_kernel": (0, 0),                    # two-site sweeps (kernels_mps_twosite.hip): l and r of a sample (2 x 16 doubles)
+    "mts_right_kernel": (0, 0),                   # and the four blocks' accumulators in registers; the bond kernel lives in
+    "mts_advance_kernel": (0, 0),                 # LDS like the canonicaliser, no scratch
+    "mts_accum_kernel": (0, 0),
+    "mts_bond_kernel": (0, 0),
     "bn_sample_kernel": (0, 0),                   # ancestral draws from the network: the node values are one 64-bit register
     "cg_init_kernel": (0, 0),                     # the CG recurrence (kernels_cg.hip)
     "cg_step_kernel": (0, 0),

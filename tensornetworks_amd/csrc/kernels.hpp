@@ -146,6 +146,12 @@ size_t mps_canon_workspace_bytes(int n, int D);
 hipError_t launch_mps_canonicalise(int n, int D, int D_out, double cutoff, const double* cores, double* cores_out, double* schmidt,
                                    double* discarded, int* rank, double* log_norm, int* status, void* ws, hipStream_t st);
 
+// ---- two-site sweeps of the sampled MPS (kernels_mps_twosite.hip): one round trip over the bonds, a chain of small launches ----
+size_t mps_twosite_workspace_bytes(int n, int D, long long B);
+hipError_t launch_mps_twosite_sweep(int n, int D, long long B, double* cores, const long long* idx, const double* w, double lr,
+                                    int steps, int D_keep, double cutoff, double* loss, double* schmidt, double* discarded, int* rank,
+                                    int* status, void* ws, hipStream_t st);
+
 // ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
 // state: BORNVI_CG_STATE_DOUBLES doubles -- rr, rr0, iterations, done, relres, fallback, 2 spare
 hipError_t launch_cg_init(long long P, const double* g, double* x, double* r, double* p, double* state, int* info, hipStream_t st);
