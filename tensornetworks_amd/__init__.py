@@ -7,7 +7,7 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
-           "SampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
+           "SampledMPSBornMachine", "ComplexSampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
            "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "CGFisherPreconditioner",
            "AmortisedMPSInference", "generate_all_binary_outcomes", "calculate_tvd"]
 
@@ -40,6 +40,9 @@ def __getattr__(name):
     if name == "SampledMPSBornMachine":
         from .born_machine_mps_sampled import SampledMPSBornMachine
         return SampledMPSBornMachine
+    if name == "ComplexSampledMPSBornMachine":
+        from .born_machine_cmps_sampled import ComplexSampledMPSBornMachine
+        return ComplexSampledMPSBornMachine
     if name == "SampledELBOVariationalInference":
         from .elbo_vi_sampled import SampledELBOVariationalInference
         return SampledELBOVariationalInference

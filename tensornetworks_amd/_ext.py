@@ -82,12 +82,19 @@ ANSATZ_IDS = {k: _ENUMS["BORNVI_ANSATZ_" + k.upper()] for k in ("hardware_effici
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 # include/bornvi_twosite.h: the two-site sweeps' family, a header of its own in the same subset of C, read by the same parser
-# into tables of its own (LIMITS, PROTOTYPES and EXPORTED_SYMBOLS above are bornvi.h's alone); lib() binds both sets.
+# into tables of its own (LIMITS, PROTOTYPES and EXPORTED_SYMBOLS above are bornvi.h's alone); lib() binds every set.
 TWOSITE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_twosite.h")
 if not os.path.exists(TWOSITE_HEADER_PATH):
     raise BornviError(f"{TWOSITE_HEADER_PATH} not found: the binding reads the C ABI from it")
 with open(TWOSITE_HEADER_PATH) as _f:
     TWOSITE_LIMITS, _, TWOSITE_PROTOTYPES = parse_header(_f.read())
+
+# include/bornvi_cmps.h: the complex-cores sampled MPS, the third header, read the same way into tables of its own
+CMPS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_cmps.h")
+if not os.path.exists(CMPS_HEADER_PATH):
+    raise BornviError(f"{CMPS_HEADER_PATH} not found: the binding reads the C ABI from it")
+with open(CMPS_HEADER_PATH) as _f:
+    CMPS_LIMITS, _, CMPS_PROTOTYPES = parse_header(_f.read())
 
 
 def lib():
@@ -99,7 +106,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in {**PROTOTYPES, **TWOSITE_PROTOTYPES}.items():
+        for name, (res, args) in {**PROTOTYPES, **TWOSITE_PROTOTYPES, **CMPS_PROTOTYPES}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -732,6 +732,85 @@ def mps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
     return out, out_logq, status
 
 
+# ---- sampled MPS Born machine with complex cores (kernels_cmps.hip, include/bornvi_cmps.h) ----------
+CMPS_MAX_BOND = _ext.CMPS_LIMITS["BORNVI_CMPS_MAX_BOND"]
+
+
+def _cmps_args(cores, num_samples):
+    """(n, D, B) of complex cores float64 [n, 2, D, D, 2] ((re, im) last) and a sample count; every argument error is raised
+    here, before any GPU call."""
+    if not torch.is_tensor(cores) or cores.dim() != 5 or cores.shape[1] != 2 or cores.shape[2] != cores.shape[3] or cores.shape[4] != 2:
+        raise BornviError(f"cores: expected an [n, 2, D, D, 2] tensor (re, im last), got "
+                          f"{tuple(cores.shape) if torch.is_tensor(cores) else type(cores)}")
+    n, D = int(cores.shape[0]), int(cores.shape[2])
+    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
+    if not 1 <= D <= CMPS_MAX_BOND:
+        raise BornviError(f"cores: complex bond dimension 1 ... {CMPS_MAX_BOND}, got {D}")
+    return n, D, _sample_count(num_samples)
+
+
+def _cmps_ws(h, dev, n, D, B):
+    """One workspace per (n, D, B) and stream: cmps_environments leaves the environments in it for the two calls after it."""
+    return _ws(dev, _cached_size(h, "bornvi_cmps_workspace_bytes", n, D, B), f"cmps_{n}_{D}_{B}")
+
+
+def cmps_environments(cores, num_samples):
+    """Left and right environments of a complex MPS and log Z (bornvi_cmps_environments): cores float64 [n, 2, D, D, 2] on the
+    GPU, 1 <= n <= 63, 1 <= D <= 16 -> log Z float64 [1].  The environments stay in the cached workspace of (n, D, num_samples)
+    for cmps_sample and cmps_score_vjp: call those next, with the same cores and sample count, on this stream."""
+    n, D, B = _cmps_args(cores, num_samples)
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    h = _ext.handle_for(dev)
+    log_Z = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _cmps_ws(h, dev, n, D, B)
+    h.call("bornvi_cmps_environments", n, D, B, _ptr(cores), _ptr(log_Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return log_Z
+
+
+def cmps_sample(cores, num_samples, seed, epoch, out_idx=None, out_logq=None, status=None):
+    """Exact ancestral draws from a complex MPS Born machine (bornvi_cmps_sample), after cmps_environments(cores, num_samples):
+    -> (idx int64 [B], logq float64 [B], status int32 [1]) as mps_sample; the uniforms are mps_sample's at (seed, epoch, b, k)."""
+    n, D, B = _cmps_args(cores, num_samples)
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    seed = _seed_word(seed)
+    if not torch.is_tensor(epoch):
+        raise BornviError("epoch: expected an int64 device tensor [1]")
+    _chk(epoch, torch.int64, dev, "epoch", 1)
+    h = _ext.handle_for(dev)
+    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
+    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _cmps_ws(h, dev, n, D, B)
+    h.call("bornvi_cmps_sample", n, D, B, _ptr(cores), seed, _ptr(epoch), _ptr(out_idx), _ptr(out_logq),
+           _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out_idx, out_logq, status
+
+
+def cmps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
+    """Score-function gradient of a complex MPS Born machine (bornvi_cmps_score_vjp), after cmps_environments(cores, len(idx)):
+    idx int64 [B], w float64 [B] -> (grad float64 [n, 2, D, D, 2] = the gradient of sum_b w_b log q(idx_b) in the real and
+    imaginary parts of cores, logq float64 [B], status int32 [1]: 0, or 2 when some psi(idx_b) is 0 or not finite)."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    n, D, B = _cmps_args(cores, int(idx.numel()))
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    if not torch.is_tensor(w):
+        raise BornviError("w: expected a [B] float64 tensor")
+    _chk(w, torch.float64, dev, "w", B)
+    h = _ext.handle_for(dev)
+    out = _out(out, torch.float64, dev, "out", tuple(cores.shape))
+    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _cmps_ws(h, dev, n, D, B)
+    h.call("bornvi_cmps_score_vjp", n, D, B, _ptr(cores), _ptr(idx), _ptr(w), _ptr(out_logq), _ptr(out), _ptr(status), _ptr(ws),
+           ws.numel(), _ext.stream_ptr(dev))
+    return out, out_logq, status
+
+
 # ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ----------------------------------------------
 MPS_QUERY_MAX_QUERIES = _ext.LIMITS["BORNVI_MPS_QUERY_MAX_QUERIES"]
 

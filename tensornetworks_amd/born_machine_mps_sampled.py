@@ -53,6 +53,16 @@ class SampledMPSBornMachine(MPSCores, nn.Module):
         """(cores detached as a contiguous float64 tensor on the compute device, the parameter's own device)."""
         return super().kernel_input(detach=True)
 
+    # ---- the three calls a trainer needs (ComplexSampledMPSBornMachine has the same three) -------------------------------
+    def environments(self, cores, num_samples):
+        return backend.mps_environments(cores, num_samples)
+
+    def draw(self, cores, num_samples, seed, epoch_dev):
+        return backend.mps_sample(cores, num_samples, seed, epoch_dev)
+
+    def score_gradient(self, cores, idx, w):
+        return backend.mps_score_vjp(cores, idx, w)
+
     # ---- samples ----------------------------------------------------------------------------------------------
     def sample_indices(self, num_samples, seed=None, epoch=0):
         """(idx int64 [num], logq float64 [num]) on the compute device: exact draws z ~ q and their log q.  A pure function

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bornvi.h"
+#include "bornvi_cmps.h"
 #include "bornvi_twosite.h"
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -1564,6 +1565,54 @@ int bornvi_mps_twosite_sweep(bornvi_handle h, int n, int D, long long B, double*
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_mps_twosite_sweep(n, D, B, cores, idx, w, lr, steps, D_keep, cutoff, loss, schmidt, discarded, rank, status, workspace,
                                      (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+// ---- sampled MPS with complex cores (kernels_cmps.hip; declared in bornvi_cmps.h) -------------------------------------
+static const char* const CMPS_RANGE = "unsupported size (1 <= n <= 63, 1 <= D <= 16, 1 <= B <= 2^24)";
+static bool valid_cmps(int n, int D, long long B) {
+  return n >= 1 && n <= BORNVI_MPS_SAMPLED_MAX_N && D >= 1 && D <= BORNVI_CMPS_MAX_BOND && B >= 1 && B <= BORNVI_MPS_SAMPLED_MAX_BATCH;
+}
+
+size_t bornvi_cmps_workspace_bytes(bornvi_handle h, int n, int D, long long B) {
+  if (!h) return 0;
+  if (!valid_cmps(n, D, B)) { fail(h, BORNVI_ERR_UNSUPPORTED, CMPS_RANGE); return 0; }
+  return cmps_workspace_bytes(n, D, B);
+}
+
+int bornvi_cmps_environments(bornvi_handle h, int n, int D, long long B, const double* cores, double* log_Z_out, void* workspace,
+                             size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_cmps(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, CMPS_RANGE);
+  if (!cores) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!workspace || workspace_bytes < cmps_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_cmps_environments(n, D, B, cores, log_Z_out, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_cmps_sample(bornvi_handle h, int n, int D, long long B, const double* cores, unsigned long long seed,
+                       const long long* epoch_dev, long long* idx, double* logq, int* status, void* workspace, size_t workspace_bytes,
+                       bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_cmps(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, CMPS_RANGE);
+  if (!cores || !epoch_dev || !idx || !logq || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < cmps_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_cmps_sample(n, D, B, cores, seed, epoch_dev, idx, logq, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_cmps_score_vjp(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, const double* w,
+                          double* logq, double* grad_cores, int* status, void* workspace, size_t workspace_bytes,
+                          bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_cmps(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, CMPS_RANGE);
+  if (!cores || !idx || !w || !logq || !grad_cores || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < cmps_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_cmps_score_vjp(n, D, B, cores, idx, w, logq, grad_cores, status, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

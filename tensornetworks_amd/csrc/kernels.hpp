@@ -152,6 +152,14 @@ hipError_t launch_mps_twosite_sweep(int n, int D, long long B, double* cores, co
                                     int steps, int D_keep, double cutoff, double* loss, double* schmidt, double* discarded, int* rank,
                                     int* status, void* ws, hipStream_t st);
 
+// ---- sampled MPS Born machine with complex cores (kernels_cmps.hip): cores [n, 2, D, D, 2], D <= 16 ----
+size_t cmps_workspace_bytes(int n, int D, long long B);
+hipError_t launch_cmps_environments(int n, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st);
+hipError_t launch_cmps_sample(int n, int D, long long B, const double* cores, unsigned long long seed, const long long* epoch_dev,
+                              long long* idx, double* logq, int* status, void* ws, hipStream_t st);
+hipError_t launch_cmps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
+                                 double* grad_cores, int* status, void* ws, hipStream_t st);
+
 // ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
 // state: BORNVI_CG_STATE_DOUBLES doubles -- rr, rr0, iterations, done, relres, fallback, 2 spare
 hipError_t launch_cg_init(long long P, const double* g, double* x, double* r, double* p, double* state, int* info, hipStream_t st);

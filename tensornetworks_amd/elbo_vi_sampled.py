@@ -6,6 +6,8 @@ estimated from B exact samples per epoch, with the score-function gradient
   grad L = E[(f - b) grad log q],  f = log q - log p,  b the leave-one-out mean (unbiased):  w_b = (f_b - mean f) / (B - 1).
 An epoch (sampled_trainer.SampledTrainer owns it): mps_environments, mps_sample (idx, log q), bn_logjoint_samples (log p),
 the mean and w as torch elementwise ops on B doubles, mps_score_vjp -> cores.grad; then the guarded update.
+born_machine_config['cores'] = 'complex' trains a ComplexSampledMPSBornMachine through the cmps_* calls instead (bond_dim <= 16;
+the enumerated report then covers n <= 20).
 
 log p floors every CPT FACTOR at p_floor, where elbo_objective.ElboObjective floors the product p(x, z): at n = 60 a
 legitimate joint lies far below 1e-30.  The two agree whenever no factor is below the floor and the product is >= p_floor.

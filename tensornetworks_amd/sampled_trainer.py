@@ -1,7 +1,8 @@
 """The epoch of the sampled MPS trainers, owned once: no 2^n object at any n <= 63.
 
-An epoch: mps_environments, mps_sample with (seed, epoch) -> (idx, log q); the objective's weights w_b from the samples
-(the subclass: `sample_weights`); mps_score_vjp -> sum_b w_b grad log q(z_b); then the NaN/Inf guard, clip and Adam or SGD
+An epoch: the machine's environments, its draw with (seed, epoch) -> (idx, log q); the objective's weights w_b from the
+samples (the subclass: `sample_weights`); its score_gradient -> sum_b w_b grad log q(z_b) (for real cores mps_environments,
+mps_sample and mps_score_vjp, for born_machine_config['cores'] = 'complex' the cmps_* three: the epoch names no family); then the NaN/Inf guard, clip and Adam or SGD
 with cosine annealing through torch.optim on the float64 cores: the enumerated trainers' own make_optimizer and
 guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every epoch, the same ones on a rerun.
 With `natural_gradient` (natural_gradient.SampledFisherPreconditioner.coerce says what it accepts) the gradient is replaced,
@@ -25,6 +26,7 @@ import torch
 
 from . import backend
 from .bayesian_network import pack_network
+from .born_machine_cmps_sampled import ENUMERATED_MAX_N, ComplexSampledMPSBornMachine
 from .born_machine_mps_sampled import SampledMPSBornMachine
 from .ksd_vi import guarded_update, make_optimizer
 from .natural_gradient import CGFisherPreconditioner, SampledFisherPreconditioner, SampleSpaceFisherPreconditioner
@@ -70,8 +72,14 @@ class SampledTrainer:
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu',
                  p_floor=1e-30, natural_gradient=None):
-        cfg, B = checked_config(born_machine_config, ('bond_dim', 'num_samples', 'seed', 'init_method'), self.MIN_SAMPLES,
+        cfg, B = checked_config(born_machine_config, ('bond_dim', 'num_samples', 'seed', 'init_method', 'cores'), self.MIN_SAMPLES,
                                 self.MAX_SAMPLES, self.SAMPLES_RANGE)
+        kind = cfg.get('cores', 'real')
+        if kind not in ('real', 'complex'):
+            raise ValueError(f"born_machine_config['cores'] must be 'real' or 'complex', got {kind!r}")
+        if kind == 'complex' and natural_gradient is not None:
+            raise ValueError("natural_gradient is not offered with complex cores: the Fisher estimates exist for the real "
+                             "family (born_machine_config['cores'] = 'real') only")
         if isinstance(p_floor, bool) or not isinstance(p_floor, (int, float)) or not np.isfinite(p_floor) or not p_floor > 0:
             raise ValueError(f"p_floor must be a positive finite number, got {p_floor!r}")
         self.bn = bayesian_network
@@ -83,9 +91,9 @@ class SampledTrainer:
         self.seed = cfg.get('seed', 0)
         self.p_floor = float(p_floor)
         self.device = torch.device(device)
-        self.born_machine = SampledMPSBornMachine(self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4),
-                                                  init_method=cfg.get('init_method', 'small_random'),
-                                                  seed=self.seed).to(self.device)
+        family = ComplexSampledMPSBornMachine if kind == 'complex' else SampledMPSBornMachine
+        self.born_machine = family(self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4),
+                                   init_method=cfg.get('init_method', 'small_random'), seed=self.seed).to(self.device)
         self.natural_gradient = SampledFisherPreconditioner.coerce(natural_gradient)
         if self.natural_gradient is not None:
             self.natural_gradient.plan(self.num_latent_vars, int(self.born_machine.cores.shape[2]), B)
@@ -106,8 +114,8 @@ class SampledTrainer:
         cores, _ = self.born_machine.kernel_input()
         B = self.num_samples
         self._epoch_dev.fill_(int(epoch))
-        backend.mps_environments(cores, B)
-        idx, logq, st_s = backend.mps_sample(cores, B, self.seed, self._epoch_dev)
+        self.born_machine.environments(cores, B)
+        idx, logq, st_s = self.born_machine.draw(cores, B, self.seed, self._epoch_dev)
         return cores, idx, logq, st_s
 
     def sample_weights(self, idx, logq):
@@ -122,7 +130,7 @@ class SampledTrainer:
         if isinstance(self.natural_gradient, SampleSpaceFisherPreconditioner):      # delta = O^T u: the plain O^T w need not run
             grad, _ = self.natural_gradient.precondition_weights(cores, idx, w.contiguous())
             return loss, grad, logq.mean(), st_s | self.natural_gradient.status
-        grad, _, st_g = backend.mps_score_vjp(cores, idx, w.contiguous())
+        grad, _, st_g = self.born_machine.score_gradient(cores, idx, w.contiguous())
         if self.natural_gradient is not None:
             grad, _ = self.natural_gradient.precondition(cores, idx, grad)
             return loss, grad, logq.mean(), st_s | st_g | self.natural_gradient.status
@@ -140,14 +148,16 @@ class SampledTrainer:
         the momentum of optimizer_type="sgd" (0.9: make_optimizer's; 0 gives the plain step lr * delta); Adam has none and
         ignores it.
         true_posterior_for_tvd: a float tensor [2^n] (stein_utils.true_posterior_table), honoured for n <= 26 only, where
-        q is enumerated by mps_probs for the report.  History: the trainer's LOSS_KEYS, grad_norm, logq_mean, status,
-        and for n <= 26 with a posterior: tvd and kl (= exact KL(q || posterior))."""
+        q is enumerated by mps_probs for the report (complex cores: for n <= 20, by log_prob over all 2^n indices).  History:
+        the trainer's LOSS_KEYS, grad_norm, logq_mean, status, and for n <= 26 (complex cores: n <= 20) with a posterior: tvd
+        and kl (= exact KL(q || posterior))."""
         if self.num_observed_vars > 0 and set(x_observation_dict.keys()) != set(self.observed_vars_names):
             raise ValueError("Keys in x_observation_dict must match self.observed_vars_names.")
         bm = self.born_machine
         self._prepare_observation(x_observation_dict)
         opt, sched = make_sampled_optimizer(bm, lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas, sgd_momentum)
-        exact = true_posterior_for_tvd is not None and self.num_latent_vars <= backend.MPS_MAX_N
+        max_n = ENUMERATED_MAX_N if isinstance(bm, ComplexSampledMPSBornMachine) else backend.MPS_MAX_N
+        exact = true_posterior_for_tvd is not None and self.num_latent_vars <= max_n
         history = {k: [] for k in self.LOSS_KEYS + ('grad_norm', 'logq_mean', 'status')}
         if exact:
             history['tvd'], history['kl'] = [], []
@@ -214,7 +224,8 @@ class SampledTrainer:
         return self.born_machine.sample_given(self._evidence_by_name(evidence), num_samples, seed=seed, epoch=epoch)
 
     def exact_report(self, posterior):
-        """(TVD, KL(q || posterior)) of the current cores against a posterior table [2^n], by enumeration (n <= 26)."""
+        """(TVD, KL(q || posterior)) of the current cores against a posterior table [2^n], by enumeration: the machine's
+        probabilities64() (n <= 26 by mps_probs; complex cores n <= 20 by log_prob over all indices)."""
         with torch.no_grad():
             q = self.born_machine.probabilities64().detach()
             p = posterior.to(device=q.device, dtype=torch.float64).reshape(-1)
