@@ -9,7 +9,8 @@ __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachin
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
            "SampledMPSBornMachine", "ComplexSampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
            "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "CGFisherPreconditioner",
-           "AmortisedMPSInference", "generate_all_binary_outcomes", "calculate_tvd"]
+           "AmortisedMPSInference", "HammingMixtureKernel", "MMDObjective", "QuantumMMDTrainer", "ClassicalMMDTrainer",
+           "SampledMMDTrainer", "generate_all_binary_outcomes", "calculate_tvd"]
 
 
 def __getattr__(name):
@@ -61,4 +62,19 @@ def __getattr__(name):
     if name == "AmortisedMPSInference":
         from .amortised_vi_sampled import AmortisedMPSInference
         return AmortisedMPSInference
+    if name == "HammingMixtureKernel":
+        from .hamming_kernel import HammingMixtureKernel
+        return HammingMixtureKernel
+    if name == "MMDObjective":
+        from .mmd_objective import MMDObjective
+        return MMDObjective
+    if name == "QuantumMMDTrainer":
+        from .mmd_quantum import QuantumMMDTrainer
+        return QuantumMMDTrainer
+    if name == "ClassicalMMDTrainer":
+        from .mmd_classical import ClassicalMMDTrainer
+        return ClassicalMMDTrainer
+    if name == "SampledMMDTrainer":
+        from .mmd_sampled import SampledMMDTrainer
+        return SampledMMDTrainer
     raise AttributeError(name)

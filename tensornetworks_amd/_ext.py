@@ -96,6 +96,13 @@ if not os.path.exists(CMPS_HEADER_PATH):
 with open(CMPS_HEADER_PATH) as _f:
     CMPS_LIMITS, _, CMPS_PROTOTYPES = parse_header(_f.read())
 
+# include/bornvi_mmd.h: MMD with a Hamming-distance kernel, the fourth header, read the same way into tables of its own
+MMD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_mmd.h")
+if not os.path.exists(MMD_HEADER_PATH):
+    raise BornviError(f"{MMD_HEADER_PATH} not found: the binding reads the C ABI from it")
+with open(MMD_HEADER_PATH) as _f:
+    MMD_LIMITS, _, MMD_PROTOTYPES = parse_header(_f.read())
+
 
 def lib():
     """The loaded library; raises if it has not been built (no fallback)."""
@@ -106,7 +113,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in {**PROTOTYPES, **TWOSITE_PROTOTYPES, **CMPS_PROTOTYPES}.items():
+        for name, (res, args) in {**PROTOTYPES, **TWOSITE_PROTOTYPES, **CMPS_PROTOTYPES, **MMD_PROTOTYPES}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -609,8 +609,86 @@ def elbo_weights(q, log_p, q_floor=1e-10, want_w=True, want_entropy=True, out=No
     return neg_elbo, entropy, w
 
 
+# ---- MMD with a Hamming-distance kernel (include/bornvi_mmd.h) --------------------------------------------------
+MMD_TILE_BITS = _ext.MMD_LIMITS["BORNVI_MMD_TILE_BITS"]
+MMD_HIGH_BITS = _ext.MMD_LIMITS["BORNVI_MMD_HIGH_BITS"]
+MMD_MAX_SCALES = _ext.MMD_LIMITS["BORNVI_MMD_MAX_SCALES"]
+HAMMING_PAIRS_MAX_A = _ext.MMD_LIMITS["BORNVI_HAMMING_PAIRS_MAX_A"]
+HAMMING_PAIRS_MAX_B = _ext.MMD_LIMITS["BORNVI_HAMMING_PAIRS_MAX_B"]
+
+
+def mmd_passes(n):
+    """Tile passes of mmd_weights with w at n variables (bornvi_mmd_passes: 1, 3 or 5; host only, no GPU needed)."""
+    _chk_n(n)
+    return int(_ext.lib().bornvi_mmd_passes(int(n)))
+
+
+def mmd_weights(q, target, lam, want_w=True, out=None):
+    """Squared MMD of q against target under the kernel whose Walsh-Hadamard spectrum is lam (bornvi_mmd_weights): q float64
+    [2^n] on the GPU, target float64 [2^n] or None (zeros), lam float64 [n + 1] -> (loss [1] = d^T K d with d = q - target,
+    w [2^n] = 2 K d or None).  out: destination of w.  Every argument error is raised here, before any GPU call."""
+    if not torch.is_tensor(q) or not torch.is_tensor(lam) or q.dim() != 1 or lam.dim() != 1:
+        raise BornviError("mmd_weights: q must be a [2^n] tensor and lam a [n + 1] tensor")
+    N = int(q.numel())
+    if N < 2 or N & (N - 1):
+        raise BornviError(f"q: {N} entries is not 2^n with n >= 1")
+    n = N.bit_length() - 1
+    _chk_n(n)
+    if int(lam.numel()) != n + 1:
+        raise BornviError(f"lam: expected {n + 1} entries (n = {n}), got {int(lam.numel())}")
+    if target is not None and (not torch.is_tensor(target) or target.dim() != 1):
+        raise BornviError("mmd_weights: target must be a [2^n] tensor or None")
+    if out is not None and not want_w:
+        raise BornviError("mmd_weights: out is the destination of w, which want_w=False leaves out")
+    dev = q.device
+    h = _ext.handle_for(dev)
+    _chk(q, torch.float64, dev, "q")
+    _chk(lam, torch.float64, dev, "lam")
+    if target is not None:
+        _chk(target, torch.float64, dev, "target", N)
+    w = None
+    if want_w:
+        w = out if out is not None else torch.empty(N, dtype=torch.float64, device=dev)
+        _chk(w, torch.float64, dev, "out", N)
+    for name, t in (("q", q), ("target", target), ("out", w)):
+        if t is not None and t.data_ptr() % 16:
+            raise BornviError(f"{name}: the storage must be 16-byte aligned")
+    loss = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _ws(dev, _cached_size(h, "bornvi_mmd_workspace_bytes", n), "mmd")
+    h.call("bornvi_mmd_weights", n, _ptr(q), _ptr(target) if target is not None else None, _ptr(lam), _ptr(loss),
+           _ptr(w) if w is not None else None, _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return loss, w
+
+
+def hamming_pairs_rowsum(za, zb, kappa, skip_same_index=False, want_counts=False):
+    """Row sums of a Hamming-distance kernel between two lists of states (bornvi_hamming_pairs_rowsum): za int64 [A], zb int64
+    [B], kappa float64 [n + 1] -> (r float64 [A], r_a = sum_j kappa[popcount(za_a xor zb_j)], without j = a when
+    skip_same_index; total float64 [1] = sum_a r_a; counts int32 [A, n + 1] or None).  1 <= A <= 2^17, 1 <= B <= 2^20; the
+    states' bits at or above n must be 0.  Every argument error is raised here, before any GPU call."""
+    if not torch.is_tensor(kappa) or kappa.dim() != 1 or not 2 <= int(kappa.numel()) <= MPS_SAMPLED_MAX_N + 1:
+        raise BornviError("kappa: expected a [n + 1] float64 tensor, 1 <= n <= 63")
+    n = int(kappa.numel()) - 1
+    if not torch.is_tensor(za) or za.dim() != 1 or not 1 <= int(za.numel()) <= HAMMING_PAIRS_MAX_A:
+        raise BornviError("za: expected a [A] int64 tensor, 1 <= A <= 2^17")
+    if not torch.is_tensor(zb) or zb.dim() != 1 or not 1 <= int(zb.numel()) <= HAMMING_PAIRS_MAX_B:
+        raise BornviError("zb: expected a [B] int64 tensor, 1 <= B <= 2^20")
+    dev = za.device
+    h = _ext.handle_for(dev)
+    A, B = int(za.numel()), int(zb.numel())
+    _chk(za, torch.int64, dev, "za")
+    _chk(zb, torch.int64, dev, "zb")
+    _chk(kappa, torch.float64, dev, "kappa")
+    r = torch.empty(A, dtype=torch.float64, device=dev)
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    counts = torch.empty((A, n + 1), dtype=torch.int32, device=dev) if want_counts else None
+    ws = _ws(dev, _cached_size(h, "bornvi_hamming_pairs_workspace_bytes", n, A, B), f"hamming_pairs_{n}_{A}_{B}")
+    h.call("bornvi_hamming_pairs_rowsum", n, A, _ptr(za), B, _ptr(zb), 1 if skip_same_index else 0, _ptr(kappa), _ptr(r), _ptr(total),
+           _ptr(counts) if counts is not None else None, _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return r, total, counts
+
+
 # ---- matrix-product-state Born machine -------------------------------------------------------------------
-MPS_MAX_N = _ext.LIMITS["BORNVI_MPS_MAX_N"]
+MPS_MAX_N =_ext.LIMITS["BORNVI_MPS_MAX_N"]
 MPS_MAX_BOND = _ext.LIMITS["BORNVI_MPS_MAX_BOND"]
 
 

@@ -14,6 +14,7 @@
 
 #include "bornvi.h"
 #include "bornvi_cmps.h"
+#include "bornvi_mmd.h"
 #include "bornvi_twosite.h"
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -1613,6 +1614,51 @@ int bornvi_cmps_score_vjp(bornvi_handle h, int n, int D, long long B, const doub
   if (!workspace || workspace_bytes < cmps_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_cmps_score_vjp(n, D, B, cores, idx, w, logq, grad_cores, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+// ---- MMD with a Hamming-distance kernel (kernels_mmd.hip; declared in bornvi_mmd.h) ------------------------------------
+static const char* const MMD_RANGE = "unsupported size (1 <= n <= 30)";
+static const char* const HAMMING_PAIRS_RANGE = "unsupported size (1 <= n <= 63, 1 <= A <= 2^17, 1 <= B <= 2^20)";
+static bool valid_hamming_pairs(int n, long long A, long long B) {
+  return n >= 1 && n <= BORNVI_MPS_SAMPLED_MAX_N && A >= 1 && A <= BORNVI_HAMMING_PAIRS_MAX_A && B >= 1 && B <= BORNVI_HAMMING_PAIRS_MAX_B;
+}
+
+int bornvi_mmd_passes(int n) { return valid_table_n(n) ? mmd_passes(n) : 0; }
+
+size_t bornvi_mmd_workspace_bytes(bornvi_handle h, int n) {
+  if (!h) return 0;
+  if (!valid_table_n(n)) { fail(h, BORNVI_ERR_UNSUPPORTED, MMD_RANGE); return 0; }
+  return mmd_workspace_bytes(n);
+}
+
+int bornvi_mmd_weights(bornvi_handle h, int n, const double* q, const double* target, const double* lam, double* loss, double* w,
+                       void* workspace, size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_table_n(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, MMD_RANGE);
+  if (!q || !lam || !loss) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if ((((uintptr_t)q) | ((uintptr_t)target) | ((uintptr_t)w)) & 15) return fail(h, BORNVI_ERR_INVALID, "q, target and w must be 16-byte aligned");
+  if (!workspace || workspace_bytes < mmd_workspace_bytes(n)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_mmd_weights(n, q, target, lam, loss, w, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+size_t bornvi_hamming_pairs_workspace_bytes(bornvi_handle h, int n, long long A, long long B) {
+  if (!h) return 0;
+  if (!valid_hamming_pairs(n, A, B)) { fail(h, BORNVI_ERR_UNSUPPORTED, HAMMING_PAIRS_RANGE); return 0; }
+  return hamming_pairs_workspace_bytes(n, A, B);
+}
+
+int bornvi_hamming_pairs_rowsum(bornvi_handle h, int n, long long A, const long long* za, long long B, const long long* zb,
+                                int skip_same_index, const double* kappa, double* r, double* total, int* counts, void* workspace,
+                                size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_hamming_pairs(n, A, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, HAMMING_PAIRS_RANGE);
+  if (!za || !zb || !kappa || !r || !total) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < hamming_pairs_workspace_bytes(n, A, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_hamming_pairs_rowsum(n, A, za, B, zb, skip_same_index, kappa, r, total, counts, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

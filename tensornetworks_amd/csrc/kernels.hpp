@@ -160,6 +160,15 @@ hipError_t launch_cmps_sample(int n, int D, long long B, const double* cores, un
 hipError_t launch_cmps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
                                  double* grad_cores, int* status, void* ws, hipStream_t st);
 
+// ---- MMD with a Hamming-distance kernel (kernels_mmd.hip): Walsh-Hadamard weights, pair counts by xor + popcount ----
+int mmd_passes(int n);       // tile passes of a call with w: 1, 3, 5
+size_t mmd_workspace_bytes(int n);
+hipError_t launch_mmd_weights(int n, const double* q, const double* target, const double* lam, double* loss, double* w, void* ws,
+                              hipStream_t st);
+size_t hamming_pairs_workspace_bytes(int n, long long A, long long B);
+hipError_t launch_hamming_pairs_rowsum(int n, long long A, const long long* za, long long B, const long long* zb, int skip_same_index,
+                                       const double* kappa, double* r, double* total, int* counts, void* ws, hipStream_t st);
+
 // ---- conjugate gradients on the device (kernels_cg.hip): the recurrence of (F + damping I) x = g around a caller's product ----
 // state: BORNVI_CG_STATE_DOUBLES doubles -- rr, rr0, iterations, done, relres, fallback, 2 spare
 hipError_t launch_cg_init(long long P, const double* g, double* x, double* r, double* p, double* state, int* info, hipStream_t st);
