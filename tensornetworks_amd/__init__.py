@@ -7,7 +7,8 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
-           "SampledMPSBornMachine", "ComplexSampledMPSBornMachine", "SampledELBOVariationalInference", "SampledKSDVariationalInference",
+           "SampledMPSBornMachine", "ComplexSampledMPSBornMachine", "PurifiedSampledMPSBornMachine",
+           "SampledELBOVariationalInference", "SampledKSDVariationalInference",
            "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "CGFisherPreconditioner",
            "AmortisedMPSInference", "HammingMixtureKernel", "MMDObjective", "QuantumMMDTrainer", "ClassicalMMDTrainer",
            "SampledMMDTrainer", "generate_all_binary_outcomes", "calculate_tvd"]
@@ -44,6 +45,9 @@ def __getattr__(name):
     if name == "ComplexSampledMPSBornMachine":
         from .born_machine_cmps_sampled import ComplexSampledMPSBornMachine
         return ComplexSampledMPSBornMachine
+    if name == "PurifiedSampledMPSBornMachine":
+        from .born_machine_lps_sampled import PurifiedSampledMPSBornMachine
+        return PurifiedSampledMPSBornMachine
     if name == "SampledELBOVariationalInference":
         from .elbo_vi_sampled import SampledELBOVariationalInference
         return SampledELBOVariationalInference

@@ -103,6 +103,13 @@ if not os.path.exists(MMD_HEADER_PATH):
 with open(MMD_HEADER_PATH) as _f:
     MMD_LIMITS, _, MMD_PROTOTYPES = parse_header(_f.read())
 
+# include/bornvi_lps.h: the locally purified sampled MPS, the fifth header, read the same way into tables of its own
+LPS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_lps.h")
+if not os.path.exists(LPS_HEADER_PATH):
+    raise BornviError(f"{LPS_HEADER_PATH} not found: the binding reads the C ABI from it")
+with open(LPS_HEADER_PATH) as _f:
+    LPS_LIMITS, _, LPS_PROTOTYPES = parse_header(_f.read())
+
 
 def lib():
     """The loaded library; raises if it has not been built (no fallback)."""
@@ -113,7 +120,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in {**PROTOTYPES, **TWOSITE_PROTOTYPES, **CMPS_PROTOTYPES, **MMD_PROTOTYPES}.items():
+        for name, (res, args) in {**PROTOTYPES, **TWOSITE_PROTOTYPES, **CMPS_PROTOTYPES, **MMD_PROTOTYPES, **LPS_PROTOTYPES}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

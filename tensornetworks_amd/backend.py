@@ -889,6 +889,95 @@ def cmps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
     return out, out_logq, status
 
 
+# ---- sampled MPS Born machine as a locally purified state (kernels_lps.hip, include/bornvi_lps.h) ----
+LPS_MAX_BOND = _ext.LPS_LIMITS["BORNVI_LPS_MAX_BOND"]
+LPS_MAX_PURIFICATION = _ext.LPS_LIMITS["BORNVI_LPS_MAX_PURIFICATION"]
+
+
+def _lps_args(cores, num_samples):
+    """(n, m, D, B) of purified cores float64 [n, 2, m, D, D] and a sample count; every argument error is raised here, before
+    any GPU call."""
+    if not torch.is_tensor(cores) or cores.dim() != 5 or cores.shape[1] != 2 or cores.shape[3] != cores.shape[4]:
+        raise BornviError(f"cores: expected an [n, 2, m, D, D] tensor, got "
+                          f"{tuple(cores.shape) if torch.is_tensor(cores) else type(cores)}")
+    n, m, D = int(cores.shape[0]), int(cores.shape[2]), int(cores.shape[3])
+    _chk_n(n, 1, MPS_SAMPLED_MAX_N)
+    if not 1 <= D <= LPS_MAX_BOND:
+        raise BornviError(f"cores: purified bond dimension 1 ... {LPS_MAX_BOND}, got {D}")
+    if not 1 <= m <= LPS_MAX_PURIFICATION:
+        raise BornviError(f"cores: purification dimension 1 ... {LPS_MAX_PURIFICATION}, got {m}")
+    return n, m, D, _sample_count(num_samples)
+
+
+def _lps_ws(h, dev, n, m, D, B):
+    """One workspace per (n, m, D, B) and stream: lps_environments leaves the environments in it for the two calls after it."""
+    return _ws(dev, _cached_size(h, "bornvi_lps_workspace_bytes", n, m, D, B), f"lps_{n}_{m}_{D}_{B}")
+
+
+def lps_environments(cores, num_samples):
+    """Left and right environments of a locally purified MPS and log Z (bornvi_lps_environments): cores float64
+    [n, 2, m, D, D] on the GPU, 1 <= n <= 63, 1 <= D <= 16, 1 <= m <= 4 -> log Z float64 [1].  The environments stay in the
+    cached workspace of (n, m, D, num_samples) for lps_sample and lps_score_vjp: call those next, with the same cores and
+    sample count, on this stream."""
+    n, m, D, B = _lps_args(cores, num_samples)
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    h = _ext.handle_for(dev)
+    log_Z = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _lps_ws(h, dev, n, m, D, B)
+    h.call("bornvi_lps_environments", n, m, D, B, _ptr(cores), _ptr(log_Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return log_Z
+
+
+def lps_sample(cores, num_samples, seed, epoch, out_idx=None, out_aux=None, status=None, want_aux=False):
+    """Exact draws from a locally purified MPS (bornvi_lps_sample), after lps_environments(cores, num_samples):
+    -> (idx int64 [B], aux int64 [B, 2] or None, status int32 [1]).  The uniforms are mps_sample's at (seed, epoch, b, k).
+    aux (want_aux, or an out_aux to fill) holds the purification indices drawn beside the bits, two bits a site; there is
+    no logq here (lps_score_vjp with out=False gives it)."""
+    n, m, D, B = _lps_args(cores, num_samples)
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    seed = _seed_word(seed)
+    if not torch.is_tensor(epoch):
+        raise BornviError("epoch: expected an int64 device tensor [1]")
+    _chk(epoch, torch.int64, dev, "epoch", 1)
+    h = _ext.handle_for(dev)
+    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
+    if out_aux is not None or want_aux:
+        out_aux = _out(out_aux, torch.int64, dev, "out_aux", (B, 2))
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _lps_ws(h, dev, n, m, D, B)
+    h.call("bornvi_lps_sample", n, m, D, B, _ptr(cores), seed, _ptr(epoch), _ptr(out_idx),
+           _ptr(out_aux) if out_aux is not None else None, _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out_idx, out_aux, status
+
+
+def lps_score_vjp(cores, idx, w=None, out=None, out_logq=None, status=None):
+    """log q and the score-function gradient of a locally purified MPS (bornvi_lps_score_vjp), after
+    lps_environments(cores, len(idx)): idx int64 [B], w float64 [B] -> (grad float64 [n, 2, m, D, D] = the gradient of
+    sum_b w_b log q(idx_b), logq float64 [B], status int32 [1]: 0, or 2 when some T(idx_b) is 0 or not finite).
+    out=False (then w may be None): logq only, the same bits, no right sweep and no gradient work -> (None, logq, status)."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    n, m, D, B = _lps_args(cores, int(idx.numel()))
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    want = out is not False
+    if want or w is not None:
+        if not torch.is_tensor(w):
+            raise BornviError("w: expected a [B] float64 tensor")
+        _chk(w, torch.float64, dev, "w", B)
+    h = _ext.handle_for(dev)
+    out = _out(out, torch.float64, dev, "out", tuple(cores.shape)) if want else None
+    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _lps_ws(h, dev, n, m, D, B)
+    h.call("bornvi_lps_score_vjp", n, m, D, B, _ptr(cores), _ptr(idx), _ptr(w) if w is not None else None, _ptr(out_logq),
+           _ptr(out) if want else None, _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out, out_logq, status
+
+
 # ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ----------------------------------------------
 MPS_QUERY_MAX_QUERIES = _ext.LIMITS["BORNVI_MPS_QUERY_MAX_QUERIES"]
 

@@ -14,6 +14,7 @@
 
 #include "bornvi.h"
 #include "bornvi_cmps.h"
+#include "bornvi_lps.h"
 #include "bornvi_mmd.h"
 #include "bornvi_twosite.h"
 #include "kernels.hpp"
@@ -1614,6 +1615,56 @@ int bornvi_cmps_score_vjp(bornvi_handle h, int n, int D, long long B, const doub
   if (!workspace || workspace_bytes < cmps_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_cmps_score_vjp(n, D, B, cores, idx, w, logq, grad_cores, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+// ---- sampled MPS as a locally purified state (kernels_lps.hip; declared in bornvi_lps.h) -----------------------------------
+static const char* const LPS_RANGE = "unsupported size (1 <= n <= 63, 1 <= m <= 4, 1 <= D <= 16, 1 <= B <= 2^24)";
+static bool valid_lps(int n, int m, int D, long long B) {
+  return n >= 1 && n <= BORNVI_MPS_SAMPLED_MAX_N && m >= 1 && m <= BORNVI_LPS_MAX_PURIFICATION && D >= 1 && D <= BORNVI_LPS_MAX_BOND &&
+         B >= 1 && B <= BORNVI_MPS_SAMPLED_MAX_BATCH;
+}
+
+size_t bornvi_lps_workspace_bytes(bornvi_handle h, int n, int m, int D, long long B) {
+  if (!h) return 0;
+  if (!valid_lps(n, m, D, B)) { fail(h, BORNVI_ERR_UNSUPPORTED, LPS_RANGE); return 0; }
+  return lps_workspace_bytes(n, m, D, B);
+}
+
+int bornvi_lps_environments(bornvi_handle h, int n, int m, int D, long long B, const double* cores, double* log_Z_out, void* workspace,
+                            size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_lps(n, m, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, LPS_RANGE);
+  if (!cores) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!workspace || workspace_bytes < lps_workspace_bytes(n, m, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_lps_environments(n, m, D, B, cores, log_Z_out, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_lps_sample(bornvi_handle h, int n, int m, int D, long long B, const double* cores, unsigned long long seed,
+                      const long long* epoch_dev, long long* idx, long long* aux, int* status, void* workspace, size_t workspace_bytes,
+                      bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_lps(n, m, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, LPS_RANGE);
+  if (!cores || !epoch_dev || !idx || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");      // aux may be NULL
+  if (!workspace || workspace_bytes < lps_workspace_bytes(n, m, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_lps_sample(n, m, D, B, cores, seed, epoch_dev, idx, aux, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_lps_score_vjp(bornvi_handle h, int n, int m, int D, long long B, const double* cores, const long long* idx, const double* w,
+                         double* logq, double* grad_cores, int* status, void* workspace, size_t workspace_bytes,
+                         bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_lps(n, m, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, LPS_RANGE);
+  // grad_cores may be NULL (logq only), and then w is not read and may be NULL too
+  if (!cores || !idx || !logq || !status || (grad_cores && !w)) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < lps_workspace_bytes(n, m, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_lps_score_vjp(n, m, D, B, cores, idx, w, logq, grad_cores, status, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

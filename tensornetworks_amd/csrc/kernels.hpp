@@ -160,6 +160,14 @@ hipError_t launch_cmps_sample(int n, int D, long long B, const double* cores, un
 hipError_t launch_cmps_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
                                  double* grad_cores, int* status, void* ws, hipStream_t st);
 
+// ---- sampled MPS Born machine as a locally purified state (kernels_lps.hip): cores [n, 2, m, D, D], D <= 16, m <= 4 ----
+size_t lps_workspace_bytes(int n, int m, int D, long long B);
+hipError_t launch_lps_environments(int n, int m, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st);
+hipError_t launch_lps_sample(int n, int m, int D, long long B, const double* cores, unsigned long long seed, const long long* epoch_dev,
+                             long long* idx, long long* aux, int* status, void* ws, hipStream_t st);
+hipError_t launch_lps_score_vjp(int n, int m, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
+                                double* grad_cores, int* status, void* ws, hipStream_t st);
+
 // ---- MMD with a Hamming-distance kernel (kernels_mmd.hip): Walsh-Hadamard weights, pair counts by xor + popcount ----
 int mmd_passes(int n);       // tile passes of a call with w: 1, 3, 5
 size_t mmd_workspace_bytes(int n);
