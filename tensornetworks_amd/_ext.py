@@ -81,34 +81,22 @@ BORNVI_OK = _ENUMS["BORNVI_OK"]
 ANSATZ_IDS = {k: _ENUMS["BORNVI_ANSATZ_" + k.upper()] for k in ("hardware_efficient", "all_to_all", "basic")}
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
-# include/bornvi_twosite.h: the two-site sweeps' family, a header of its own in the same subset of C, read by the same parser
-# into tables of its own (LIMITS, PROTOTYPES and EXPORTED_SYMBOLS above are bornvi.h's alone); lib() binds every set.
-TWOSITE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_twosite.h")
-if not os.path.exists(TWOSITE_HEADER_PATH):
-    raise BornviError(f"{TWOSITE_HEADER_PATH} not found: the binding reads the C ABI from it")
-with open(TWOSITE_HEADER_PATH) as _f:
-    TWOSITE_LIMITS, _, TWOSITE_PROTOTYPES = parse_header(_f.read())
-
-# include/bornvi_cmps.h: the complex-cores sampled MPS, the third header, read the same way into tables of its own
-CMPS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_cmps.h")
-if not os.path.exists(CMPS_HEADER_PATH):
-    raise BornviError(f"{CMPS_HEADER_PATH} not found: the binding reads the C ABI from it")
-with open(CMPS_HEADER_PATH) as _f:
-    CMPS_LIMITS, _, CMPS_PROTOTYPES = parse_header(_f.read())
-
-# include/bornvi_mmd.h: MMD with a Hamming-distance kernel, the fourth header, read the same way into tables of its own
-MMD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_mmd.h")
-if not os.path.exists(MMD_HEADER_PATH):
-    raise BornviError(f"{MMD_HEADER_PATH} not found: the binding reads the C ABI from it")
-with open(MMD_HEADER_PATH) as _f:
-    MMD_LIMITS, _, MMD_PROTOTYPES = parse_header(_f.read())
-
-# include/bornvi_lps.h: the locally purified sampled MPS, the fifth header, read the same way into tables of its own
-LPS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bornvi_lps.h")
-if not os.path.exists(LPS_HEADER_PATH):
-    raise BornviError(f"{LPS_HEADER_PATH} not found: the binding reads the C ABI from it")
-with open(LPS_HEADER_PATH) as _f:
-    LPS_LIMITS, _, LPS_PROTOTYPES = parse_header(_f.read())
+# The side headers include/bornvi_<name>.h, each a family's own in the same subset of C: the two-site sweeps, the complex-cores
+# sampled MPS, MMD with a Hamming-distance kernel, the locally purified sampled MPS.  The same parser reads each into tables of
+# its own, <NAME>_HEADER_PATH, <NAME>_LIMITS and <NAME>_PROTOTYPES (LIMITS, PROTOTYPES and EXPORTED_SYMBOLS above are
+# bornvi.h's alone); lib() binds every set.
+_SIDE = {}
+for _name in ("twosite", "cmps", "mmd", "lps"):
+    _path = os.path.join(os.path.dirname(_HERE), "include", f"bornvi_{_name}.h")
+    if not os.path.exists(_path):
+        raise BornviError(f"{_path} not found: the binding reads the C ABI from it")
+    with open(_path) as _f:
+        _limits, _, _protos = parse_header(_f.read())
+    _SIDE[_name] = (_path, _limits, _protos)
+TWOSITE_HEADER_PATH, TWOSITE_LIMITS, TWOSITE_PROTOTYPES = _SIDE["twosite"]
+CMPS_HEADER_PATH, CMPS_LIMITS, CMPS_PROTOTYPES = _SIDE["cmps"]
+MMD_HEADER_PATH, MMD_LIMITS, MMD_PROTOTYPES = _SIDE["mmd"]
+LPS_HEADER_PATH, LPS_LIMITS, LPS_PROTOTYPES = _SIDE["lps"]
 
 
 def lib():
@@ -120,10 +108,11 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in {**PROTOTYPES, **TWOSITE_PROTOTYPES, **CMPS_PROTOTYPES, **MMD_PROTOTYPES, **LPS_PROTOTYPES}.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
+        for protos in [PROTOTYPES] + [side[2] for side in _SIDE.values()]:
+            for name, (res, args) in protos.items():
+                fn = getattr(handle, name)
+                fn.restype = res
+                fn.argtypes = args
         _lib = handle
     return _lib
 

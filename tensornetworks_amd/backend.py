@@ -5,7 +5,9 @@ shapes / dtypes / devices and passes raw pointers.  Everything here needs an MI3
 live on a 'cuda' (PyTorch-ROCm) device.  There is no CPU path.
 """
 import ctypes as C
+import math
 import os
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -84,7 +86,7 @@ def _out(t, dtype, dev, name, shape):
     """The optional output `t`, checked for the element count of `shape` (an int or a tuple), or a new tensor of that shape."""
     if t is None:
         return torch.empty(shape, dtype=dtype, device=dev)
-    _chk(t, dtype, dev, name, np.prod(shape))
+    _chk(t, dtype, dev, name, math.prod(shape) if isinstance(shape, tuple) else shape)      # not np.prod: 3 us a call
     return t
 
 
@@ -750,23 +752,90 @@ MPS_SAMPLED_MAX_N = _ext.LIMITS["BORNVI_MPS_SAMPLED_MAX_N"]
 MPS_SAMPLED_MAX_BATCH = _ext.LIMITS["BORNVI_MPS_SAMPLED_MAX_BATCH"]
 
 
+class _SampledFamily(NamedTuple):
+    """What tells the three sampled families' calls apart on the host (the real, the complex-cores and the purified one)."""
+    prefix: str          # the entry points are bornvi_<prefix>_environments / _sample / _score_vjp
+    args: Callable       # (cores, num_samples) -> the entry points' leading integers (..., B); raises every argument error
+    size_query: str      # the workspace size query's symbol, taking those integers
+    tag: str             # the workspace tag: the family's prefix and a %d for each of those integers
+
+
+def _sampled_ws(fam, h, dev, dims):
+    """One workspace per family, dims and stream: the environments call leaves the environments in it for the two after it."""
+    return _ws(dev, _cached_size(h, fam.size_query, *dims), fam.tag % dims)
+
+
+def _sampled_environments(fam, cores, num_samples):
+    dims = fam.args(cores, num_samples)
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    h = _ext.handle_for(dev)
+    log_Z = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _sampled_ws(fam, h, dev, dims)
+    h.call(f"bornvi_{fam.prefix}_environments", *dims, _ptr(cores), _ptr(log_Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return log_Z
+
+
+def _sampled_sample(fam, cores, num_samples, seed, epoch, out_idx, second, status, second_dtype=torch.float64,
+                    second_name="out_logq", second_cols=None, want_second=True):
+    """-> (idx, second, status).  second: the sampler's per-sample output beside idx (logq float64 [B], or with second_cols = 2
+    the purified family's aux int64 [B, 2]), filled when given or when want_second, else None and a NULL pointer."""
+    dims = fam.args(cores, num_samples)
+    B = dims[-1]
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    seed = _seed_word(seed)
+    if not torch.is_tensor(epoch):
+        raise BornviError("epoch: expected an int64 device tensor [1]")
+    _chk(epoch, torch.int64, dev, "epoch", 1)
+    h = _ext.handle_for(dev)
+    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
+    if second is not None or want_second:
+        second = _out(second, second_dtype, dev, second_name, B if second_cols is None else (B, second_cols))
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _sampled_ws(fam, h, dev, dims)
+    h.call(f"bornvi_{fam.prefix}_sample", *dims, _ptr(cores), seed, _ptr(epoch), _ptr(out_idx),
+           _ptr(second) if second is not None else None, _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out_idx, second, status
+
+
+def _sampled_score(fam, cores, idx, w, out, out_logq, status, gradient_optional=False):
+    """-> (grad, logq, status).  gradient_optional: out=False asks for logq alone (then w may be None) -> grad None."""
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise BornviError("idx: expected a [B] int64 tensor")
+    dims = fam.args(cores, int(idx.numel()))
+    B = dims[-1]
+    dev = cores.device
+    _chk(cores, torch.float64, dev, "cores")
+    _chk(idx, torch.int64, dev, "idx", B)
+    want = not (gradient_optional and out is False)
+    if want or w is not None:
+        if not torch.is_tensor(w):
+            raise BornviError("w: expected a [B] float64 tensor")
+        _chk(w, torch.float64, dev, "w", B)
+    h = _ext.handle_for(dev)
+    out = _out(out, torch.float64, dev, "out", tuple(cores.shape)) if want else None
+    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
+    status = _out(status, torch.int32, dev, "status", 1)
+    ws = _sampled_ws(fam, h, dev, dims)
+    h.call(f"bornvi_{fam.prefix}_score_vjp", *dims, _ptr(cores), _ptr(idx), _ptr(w) if w is not None else None, _ptr(out_logq),
+           _ptr(out) if want else None, _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
+    return out, out_logq, status
+
+
+_MPS = _SampledFamily("mps", _mps_args, "bornvi_mps_sample_workspace_bytes", "mps_sampled_%d_%d_%d")
+
+
 def _mps_sampled_ws(h, dev, n, D, B):
-    """One workspace per (n, D, B) and stream: mps_environments leaves the environments in it for the two calls after it."""
-    return _ws(dev, _cached_size(h, "bornvi_mps_sample_workspace_bytes", n, D, B), f"mps_sampled_{n}_{D}_{B}")
+    """The real family's workspace of (n, D, B): the Fisher and Stein calls read the environments mps_environments left in it."""
+    return _sampled_ws(_MPS, h, dev, (n, D, B))
 
 
 def mps_environments(cores, num_samples):
     """Left and right environments of an MPS and log Z (bornvi_mps_environments): cores float64 [n, 2, D, D] on the GPU,
     1 <= n <= 63 -> log Z float64 [1].  The environments stay in the cached workspace of (n, D, num_samples) for
     mps_sample and mps_score_vjp: call those next, with the same cores and sample count, on this stream."""
-    n, D, B = _mps_args(cores, num_samples)
-    dev = cores.device
-    h = _ext.handle_for(dev)
-    _chk(cores, torch.float64, dev, "cores")
-    log_Z = torch.empty(1, dtype=torch.float64, device=dev)
-    ws = _mps_sampled_ws(h, dev, n, D, B)
-    h.call("bornvi_mps_environments", n, D, B, _ptr(cores), _ptr(log_Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
-    return log_Z
+    return _sampled_environments(_MPS, cores, num_samples)
 
 
 def mps_sample(cores, num_samples, seed, epoch, out_idx=None, out_logq=None, status=None):
@@ -774,40 +843,14 @@ def mps_sample(cores, num_samples, seed, epoch, out_idx=None, out_logq=None, sta
     -> (idx int64 [B] outcome indices, logq float64 [B] = log q(idx), status int32 [1]: 0, or 1 when a sample met
     conditional masses summing to 0 or a non-finite number).  Draw k of sample b is a pure function of (seed, epoch, b, k).
     epoch: an int64 device tensor [1] (read by the kernel: a captured graph sees its value at replay time)."""
-    n, D, B = _mps_args(cores, num_samples)
-    dev = cores.device
-    h = _ext.handle_for(dev)
-    _chk(cores, torch.float64, dev, "cores")
-    seed = _seed_word(seed)
-    _chk(epoch, torch.int64, dev, "epoch", 1)
-    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
-    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
-    status = _out(status, torch.int32, dev, "status", 1)
-    ws = _mps_sampled_ws(h, dev, n, D, B)
-    h.call("bornvi_mps_sample", n, D, B, _ptr(cores), seed, _ptr(epoch), _ptr(out_idx), _ptr(out_logq),
-           _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
-    return out_idx, out_logq, status
+    return _sampled_sample(_MPS, cores, num_samples, seed, epoch, out_idx, out_logq, status)
 
 
 def mps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
     """Score-function gradient of an MPS Born machine (bornvi_mps_score_vjp), after mps_environments(cores, len(idx)):
     idx int64 [B] outcome indices in [0, 2^n), w float64 [B] -> (grad float64 [n, 2, D, D] = sum_b w_b grad log q(idx_b),
     logq float64 [B], status int32 [1]: 0, or 2 when some psi(idx_b) is 0 or not finite).  out: destination of grad."""
-    if not torch.is_tensor(idx) or idx.dim() != 1:
-        raise BornviError("idx: expected a [B] int64 tensor")
-    n, D, B = _mps_args(cores, int(idx.numel()))
-    dev = cores.device
-    h = _ext.handle_for(dev)
-    _chk(cores, torch.float64, dev, "cores")
-    _chk(idx, torch.int64, dev, "idx", B)
-    _chk(w, torch.float64, dev, "w", B)
-    out = _out(out, torch.float64, dev, "out", tuple(cores.shape))
-    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
-    status = _out(status, torch.int32, dev, "status", 1)
-    ws = _mps_sampled_ws(h, dev, n, D, B)
-    h.call("bornvi_mps_score_vjp", n, D, B, _ptr(cores), _ptr(idx), _ptr(w), _ptr(out_logq), _ptr(out), _ptr(status), _ptr(ws),
-           ws.numel(), _ext.stream_ptr(dev))
-    return out, out_logq, status
+    return _sampled_score(_MPS, cores, idx, w, out, out_logq, status)
 
 
 # ---- sampled MPS Born machine with complex cores (kernels_cmps.hip, include/bornvi_cmps.h, DESIGN.md section 6p) ----------
@@ -827,66 +870,27 @@ def _cmps_args(cores, num_samples):
     return n, D, _sample_count(num_samples)
 
 
-def _cmps_ws(h, dev, n, D, B):
-    """One workspace per (n, D, B) and stream: cmps_environments leaves the environments in it for the two calls after it."""
-    return _ws(dev, _cached_size(h, "bornvi_cmps_workspace_bytes", n, D, B), f"cmps_{n}_{D}_{B}")
+_CMPS = _SampledFamily("cmps", _cmps_args, "bornvi_cmps_workspace_bytes", "cmps_%d_%d_%d")
 
 
 def cmps_environments(cores, num_samples):
     """Left and right environments of a complex MPS and log Z (bornvi_cmps_environments): cores float64 [n, 2, D, D, 2] on the
     GPU, 1 <= n <= 63, 1 <= D <= 16 -> log Z float64 [1].  The environments stay in the cached workspace of (n, D, num_samples)
     for cmps_sample and cmps_score_vjp: call those next, with the same cores and sample count, on this stream."""
-    n, D, B = _cmps_args(cores, num_samples)
-    dev = cores.device
-    _chk(cores, torch.float64, dev, "cores")
-    h = _ext.handle_for(dev)
-    log_Z = torch.empty(1, dtype=torch.float64, device=dev)
-    ws = _cmps_ws(h, dev, n, D, B)
-    h.call("bornvi_cmps_environments", n, D, B, _ptr(cores), _ptr(log_Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
-    return log_Z
+    return _sampled_environments(_CMPS, cores, num_samples)
 
 
 def cmps_sample(cores, num_samples, seed, epoch, out_idx=None, out_logq=None, status=None):
     """Exact ancestral draws from a complex MPS Born machine (bornvi_cmps_sample), after cmps_environments(cores, num_samples):
     -> (idx int64 [B], logq float64 [B], status int32 [1]) as mps_sample; the uniforms are mps_sample's at (seed, epoch, b, k)."""
-    n, D, B = _cmps_args(cores, num_samples)
-    dev = cores.device
-    _chk(cores, torch.float64, dev, "cores")
-    seed = _seed_word(seed)
-    if not torch.is_tensor(epoch):
-        raise BornviError("epoch: expected an int64 device tensor [1]")
-    _chk(epoch, torch.int64, dev, "epoch", 1)
-    h = _ext.handle_for(dev)
-    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
-    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
-    status = _out(status, torch.int32, dev, "status", 1)
-    ws = _cmps_ws(h, dev, n, D, B)
-    h.call("bornvi_cmps_sample", n, D, B, _ptr(cores), seed, _ptr(epoch), _ptr(out_idx), _ptr(out_logq),
-           _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
-    return out_idx, out_logq, status
+    return _sampled_sample(_CMPS, cores, num_samples, seed, epoch, out_idx, out_logq, status)
 
 
 def cmps_score_vjp(cores, idx, w, out=None, out_logq=None, status=None):
     """Score-function gradient of a complex MPS Born machine (bornvi_cmps_score_vjp), after cmps_environments(cores, len(idx)):
     idx int64 [B], w float64 [B] -> (grad float64 [n, 2, D, D, 2] = the gradient of sum_b w_b log q(idx_b) in the real and
     imaginary parts of cores, logq float64 [B], status int32 [1]: 0, or 2 when some psi(idx_b) is 0 or not finite)."""
-    if not torch.is_tensor(idx) or idx.dim() != 1:
-        raise BornviError("idx: expected a [B] int64 tensor")
-    n, D, B = _cmps_args(cores, int(idx.numel()))
-    dev = cores.device
-    _chk(cores, torch.float64, dev, "cores")
-    _chk(idx, torch.int64, dev, "idx", B)
-    if not torch.is_tensor(w):
-        raise BornviError("w: expected a [B] float64 tensor")
-    _chk(w, torch.float64, dev, "w", B)
-    h = _ext.handle_for(dev)
-    out = _out(out, torch.float64, dev, "out", tuple(cores.shape))
-    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
-    status = _out(status, torch.int32, dev, "status", 1)
-    ws = _cmps_ws(h, dev, n, D, B)
-    h.call("bornvi_cmps_score_vjp", n, D, B, _ptr(cores), _ptr(idx), _ptr(w), _ptr(out_logq), _ptr(out), _ptr(status), _ptr(ws),
-           ws.numel(), _ext.stream_ptr(dev))
-    return out, out_logq, status
+    return _sampled_score(_CMPS, cores, idx, w, out, out_logq, status)
 
 
 # ---- sampled MPS Born machine as a locally purified state (kernels_lps.hip, include/bornvi_lps.h, DESIGN.md section 6r) ----
@@ -909,9 +913,7 @@ def _lps_args(cores, num_samples):
     return n, m, D, _sample_count(num_samples)
 
 
-def _lps_ws(h, dev, n, m, D, B):
-    """One workspace per (n, m, D, B) and stream: lps_environments leaves the environments in it for the two calls after it."""
-    return _ws(dev, _cached_size(h, "bornvi_lps_workspace_bytes", n, m, D, B), f"lps_{n}_{m}_{D}_{B}")
+_LPS = _SampledFamily("lps", _lps_args, "bornvi_lps_workspace_bytes", "lps_%d_%d_%d_%d")
 
 
 def lps_environments(cores, num_samples):
@@ -919,14 +921,7 @@ def lps_environments(cores, num_samples):
     [n, 2, m, D, D] on the GPU, 1 <= n <= 63, 1 <= D <= 16, 1 <= m <= 4 -> log Z float64 [1].  The environments stay in the
     cached workspace of (n, m, D, num_samples) for lps_sample and lps_score_vjp: call those next, with the same cores and
     sample count, on this stream."""
-    n, m, D, B = _lps_args(cores, num_samples)
-    dev = cores.device
-    _chk(cores, torch.float64, dev, "cores")
-    h = _ext.handle_for(dev)
-    log_Z = torch.empty(1, dtype=torch.float64, device=dev)
-    ws = _lps_ws(h, dev, n, m, D, B)
-    h.call("bornvi_lps_environments", n, m, D, B, _ptr(cores), _ptr(log_Z), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
-    return log_Z
+    return _sampled_environments(_LPS, cores, num_samples)
 
 
 def lps_sample(cores, num_samples, seed, epoch, out_idx=None, out_aux=None, status=None, want_aux=False):
@@ -934,22 +929,8 @@ def lps_sample(cores, num_samples, seed, epoch, out_idx=None, out_aux=None, stat
     -> (idx int64 [B], aux int64 [B, 2] or None, status int32 [1]).  The uniforms are mps_sample's at (seed, epoch, b, k).
     aux (want_aux, or an out_aux to fill) holds the purification indices drawn beside the bits, two bits a site; there is
     no logq here (lps_score_vjp with out=False gives it)."""
-    n, m, D, B = _lps_args(cores, num_samples)
-    dev = cores.device
-    _chk(cores, torch.float64, dev, "cores")
-    seed = _seed_word(seed)
-    if not torch.is_tensor(epoch):
-        raise BornviError("epoch: expected an int64 device tensor [1]")
-    _chk(epoch, torch.int64, dev, "epoch", 1)
-    h = _ext.handle_for(dev)
-    out_idx = _out(out_idx, torch.int64, dev, "out_idx", B)
-    if out_aux is not None or want_aux:
-        out_aux = _out(out_aux, torch.int64, dev, "out_aux", (B, 2))
-    status = _out(status, torch.int32, dev, "status", 1)
-    ws = _lps_ws(h, dev, n, m, D, B)
-    h.call("bornvi_lps_sample", n, m, D, B, _ptr(cores), seed, _ptr(epoch), _ptr(out_idx),
-           _ptr(out_aux) if out_aux is not None else None, _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
-    return out_idx, out_aux, status
+    return _sampled_sample(_LPS, cores, num_samples, seed, epoch, out_idx, out_aux, status, second_dtype=torch.int64,
+                           second_name="out_aux", second_cols=2, want_second=want_aux)
 
 
 def lps_score_vjp(cores, idx, w=None, out=None, out_logq=None, status=None):
@@ -957,25 +938,7 @@ def lps_score_vjp(cores, idx, w=None, out=None, out_logq=None, status=None):
     lps_environments(cores, len(idx)): idx int64 [B], w float64 [B] -> (grad float64 [n, 2, m, D, D] = the gradient of
     sum_b w_b log q(idx_b), logq float64 [B], status int32 [1]: 0, or 2 when some T(idx_b) is 0 or not finite).
     out=False (then w may be None): logq only, the same bits, no right sweep and no gradient work -> (None, logq, status)."""
-    if not torch.is_tensor(idx) or idx.dim() != 1:
-        raise BornviError("idx: expected a [B] int64 tensor")
-    n, m, D, B = _lps_args(cores, int(idx.numel()))
-    dev = cores.device
-    _chk(cores, torch.float64, dev, "cores")
-    _chk(idx, torch.int64, dev, "idx", B)
-    want = out is not False
-    if want or w is not None:
-        if not torch.is_tensor(w):
-            raise BornviError("w: expected a [B] float64 tensor")
-        _chk(w, torch.float64, dev, "w", B)
-    h = _ext.handle_for(dev)
-    out = _out(out, torch.float64, dev, "out", tuple(cores.shape)) if want else None
-    out_logq = _out(out_logq, torch.float64, dev, "out_logq", B)
-    status = _out(status, torch.int32, dev, "status", 1)
-    ws = _lps_ws(h, dev, n, m, D, B)
-    h.call("bornvi_lps_score_vjp", n, m, D, B, _ptr(cores), _ptr(idx), _ptr(w) if w is not None else None, _ptr(out_logq),
-           _ptr(out) if want else None, _ptr(status), _ptr(ws), ws.numel(), _ext.stream_ptr(dev))
-    return out, out_logq, status
+    return _sampled_score(_LPS, cores, idx, w, out, out_logq, status, gradient_optional=True)
 
 
 # ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ----------------------------------------------

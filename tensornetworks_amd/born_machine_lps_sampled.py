@@ -8,9 +8,10 @@ of the hierarchy of Glasser et al. 2019.  Every site carries a second index mu t
 The real Born MPS is m = 1 (from_real), the complex Born MPS at bond D is a purified one at bond 2 D with m = 2 at one site
 (from_complex); the non-negative MPS / hidden Markov family is contained too.
 
-The training surface is ComplexSampledMPSBornMachine's: kernel_input, environments, draw, score_gradient, sample_indices,
-score_vjp, log_prob, bits_of, indices_of, sample, get_log_q_z_x, num_parameters, bond_dim (bornvi_lps_environments / _sample /
-_score_vjp).  For n <= 20 the enumerated q is read out by log_prob over all 2^n indices (probabilities64 / get_probabilities,
+The training surface is born_machine_sampled's SampledSurface, the one the real and the complex machine have: kernel_input,
+sample_indices, score_vjp, log_prob, bits_of, indices_of, sample, get_log_q_z_x, num_parameters, through this file's three
+hooks environments, draw and score_gradient (bornvi_lps_environments / _sample / _score_vjp); bond_dim and log_prob are its
+own.  For n <= 20 the enumerated q is read out by log_prob over all 2^n indices (probabilities64 / get_probabilities,
 detached).  Canonical form, bond spectra, compress_ / expand_, the posterior queries and two-site sweeps exist for the real
 family only (SampledMPSBornMachine); here each raises a ValueError that says so.
 """
@@ -20,41 +21,24 @@ import torch
 import torch.nn as nn
 
 from . import backend
-from .born_machine_base import bits_to_indices, indices_to_bits
-from .born_machine_cmps_sampled import ENUMERATED_MAX_N, ComplexSampledMPSBornMachine
+from .born_machine_sampled import SampledSurface, checked_init_method, checked_int, checked_seed, refuse
 
+ENUMERATED_MAX_N = SampledSurface.ENUMERATED_MAX_N          # probabilities64: log_prob over all 2^n indices in one call
 
-def _refused(name):
-    def method(self, *args, **kwargs):
-        raise ValueError(f"{name} is not offered for purified cores: it exists for the real family (SampledMPSBornMachine) only")
-    method.__name__ = name
-    method.__doc__ = f"Not offered for purified cores (SampledMPSBornMachine has {name})."
-    return method
-
-
-def _checked_int(value, lo, hi, what):
-    if isinstance(value, bool) or not isinstance(value, int) or not lo <= value <= hi:
-        raise ValueError(f"{what} must be an integer in {lo} ... {hi}, got {value!r}")
-    return value
-
-
-class PurifiedSampledMPSBornMachine(nn.Module):
+@refuse
+class PurifiedSampledMPSBornMachine(SampledSurface, nn.Module):
     """Locally purified MPS Born machine whose surface is samples, log q of samples and the score-function gradient."""
-
-    REFUSED = ComplexSampledMPSBornMachine.REFUSED
+    CORES = "purified cores"
 
     def __init__(self, num_latent_vars, bond_dim=4, purification_dim=2, init_method='small_random', conditioning_dim=0, seed=0):
         if conditioning_dim != 0:
             raise ValueError("PurifiedSampledMPSBornMachine is not conditional: conditioning_dim must be 0.")
-        _checked_int(num_latent_vars, 1, backend.MPS_SAMPLED_MAX_N, "num_latent_vars")
-        _checked_int(bond_dim, 1, backend.LPS_MAX_BOND, "bond_dim (purified cores)")
-        _checked_int(purification_dim, 1, backend.LPS_MAX_PURIFICATION, "purification_dim")
-        if init_method not in ('small_random', 'zero', 'random'):
-            raise ValueError(f"init_method must be 'small_random', 'zero' or 'random', got {init_method!r}")
-        if isinstance(seed, bool) or not isinstance(seed, int):
-            raise ValueError(f"seed must be an integer, got {seed!r}")
+        n = checked_int(num_latent_vars, 1, backend.MPS_SAMPLED_MAX_N, "num_latent_vars")
+        D = checked_int(bond_dim, 1, backend.LPS_MAX_BOND, "bond_dim (purified cores)")
+        m = checked_int(purification_dim, 1, backend.LPS_MAX_PURIFICATION, "purification_dim")
+        checked_init_method(init_method)
+        checked_seed(seed)
         super().__init__()
-        n, D, m = num_latent_vars, bond_dim, purification_dim
         eye = torch.eye(D, dtype=torch.float64).expand(n, 2, D, D)
         rest = torch.zeros(n, 2, m - 1, D, D, dtype=torch.float64)
         if init_method == 'zero':            # psi(z, 0) = 2^(-n/2) for every z and nothing else: the exactly uniform q
@@ -65,20 +49,15 @@ class PurifiedSampledMPSBornMachine(nn.Module):
         else:                                # the real family's variance 1 / (2 D), split between the m matrices
             first = torch.randn(n, 2, D, D, dtype=torch.float64) / math.sqrt(2.0 * D * m)
             rest = torch.randn(n, 2, m - 1, D, D, dtype=torch.float64) / math.sqrt(2.0 * D * m)
-        self.num_latent_vars = n
-        self.conditioning_dim = 0
-        self.seed = seed
-        self._draws = 0            # epoch of the next sample() call: successive calls draw fresh samples
+        self._init_sampled(n, seed)
         self.cores = nn.Parameter(torch.cat((first.unsqueeze(2), rest), dim=2).contiguous())
 
     # ---- constructors from other states ---------------------------------------------------------------------------
     @classmethod
-    def _with_cores(cls, cores, seed=0):
-        n, m, D = int(cores.shape[0]), int(cores.shape[2]), int(cores.shape[3])
-        machine = cls(n, bond_dim=D, purification_dim=m, init_method='zero', seed=seed)
-        with torch.no_grad():
-            machine.cores.copy_(cores)
-        return machine
+    def _of(cls, cores, machine):
+        """The machine of purified cores [n, 2, m, D, D] built on the CPU, with `machine`'s seed, on `machine`'s device."""
+        out = cls._with_cores(cores, seed=getattr(machine, "seed", 0), bond_dim=int(cores.shape[3]), purification_dim=int(cores.shape[2]))
+        return out.to(machine.cores.device)
 
     @classmethod
     def from_real(cls, machine, purification_dim=1):
@@ -88,11 +67,11 @@ class PurifiedSampledMPSBornMachine(nn.Module):
             raise ValueError("from_real takes a real MPS machine with cores [n, 2, D, D]")
         if cores.shape[2] > backend.LPS_MAX_BOND:
             raise ValueError(f"purified cores take a bond dimension of at most {backend.LPS_MAX_BOND}, got {int(cores.shape[2])}")
-        m = _checked_int(purification_dim, 1, backend.LPS_MAX_PURIFICATION, "purification_dim")
+        m = checked_int(purification_dim, 1, backend.LPS_MAX_PURIFICATION, "purification_dim")
         re = cores.detach().to(device="cpu", dtype=torch.float64)
         out = torch.zeros(re.shape[0], 2, m, re.shape[2], re.shape[3], dtype=torch.float64)
         out[:, :, 0] = re
-        return cls._with_cores(out, seed=getattr(machine, "seed", 0)).to(cores.device)
+        return cls._of(out, machine)
 
     @classmethod
     def from_complex(cls, machine):
@@ -114,7 +93,7 @@ class PurifiedSampledMPSBornMachine(nn.Module):
         out[:, :, 0, D:, :D] = -Y
         out[:, :, 0, D:, D:] = X
         out[n - 1, :, 1, :, 0] = out[n - 1, :, 0, :, D]
-        return cls._with_cores(out, seed=getattr(machine, "seed", 0)).to(cores.device)
+        return cls._of(out, machine)
 
     # ---- the parameter ---------------------------------------------------------------------------------------------
     @property
@@ -125,16 +104,7 @@ class PurifiedSampledMPSBornMachine(nn.Module):
     def purification_dim(self):
         return int(self.cores.shape[2])
 
-    @property
-    def num_parameters(self):
-        return self.cores.numel()
-
-    def kernel_input(self):
-        """(cores detached as a contiguous float64 [n, 2, m, D, D] tensor on the compute device, the parameter's own device)."""
-        home = self.cores.device
-        return self.cores.detach().to(device=backend.compute_device(home), dtype=torch.float64).contiguous(), home
-
-    # ---- the three calls a trainer needs (the real and the complex machine have the same three) -------------------------
+    # ---- the three calls the shared surface and a trainer need -----------------------------------------------------------
     def environments(self, cores, num_samples):
         return backend.lps_environments(cores, num_samples)
 
@@ -148,74 +118,9 @@ class PurifiedSampledMPSBornMachine(nn.Module):
     def score_gradient(self, cores, idx, w):
         return backend.lps_score_vjp(cores, idx, w)
 
-    # ---- samples ----------------------------------------------------------------------------------------------
-    def sample_indices(self, num_samples, seed=None, epoch=0):
-        """(idx int64 [num], logq float64 [num]) on the compute device: exact draws z ~ q and their log q.  A pure function
-        of (cores, seed, epoch): seed defaults to the machine's own."""
-        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
-            raise ValueError(f"num_samples must be a positive integer, got {num_samples!r}")
-        cores, _ = self.kernel_input()
-        ep = torch.tensor([int(epoch)], dtype=torch.int64, device=cores.device)
-        self.environments(cores, num_samples)
-        idx, logq, _ = self.draw(cores, num_samples, self.seed if seed is None else seed, ep)
-        return idx, logq
-
-    def bits_of(self, idx):
-        """float32 bit rows [B, n] of outcome indices."""
-        return indices_to_bits(idx, self.num_latent_vars)
-
-    def indices_of(self, z_samples):
-        """int64 outcome indices of bit rows [B, n]."""
-        return bits_to_indices(z_samples, self.num_latent_vars)
-
-    def sample(self, num_samples=1, x_condition=None):
-        """float32 bit rows [num, n] on the parameter's device, from the draws of sample_indices (fresh ones every call)."""
-        if x_condition is not None:
-            raise ValueError("x_condition provided but conditioning_dim is 0.")
-        idx, _ = self.sample_indices(num_samples, epoch=self._draws)
-        self._draws += 1
-        return self.bits_of(idx).to(self.cores.device)
-
-    def score_vjp(self, idx, w):
-        """(grad float64 [n, 2, m, D, D] = the gradient of sum_b w_b log q(idx_b) in the parameter, logq float64 [B]) on the
-        compute device."""
-        cores, _ = self.kernel_input()
-        idx = idx.to(device=cores.device, dtype=torch.int64).contiguous()
-        w = w.to(device=cores.device, dtype=torch.float64).contiguous()
-        self.environments(cores, int(idx.numel()))
-        grad, logq, _ = self.score_gradient(cores, idx, w)
-        return grad, logq
-
     def log_prob(self, idx):
         """log q(idx), float64 [B] (-inf where T is 0): the score call without a gradient."""
         cores, _ = self.kernel_input()
         idx = idx.reshape(-1).to(device=cores.device, dtype=torch.int64).contiguous()
         self.environments(cores, int(idx.numel()))
         return backend.lps_score_vjp(cores, idx, out=False)[1]
-
-    def get_log_q_z_x(self, z_samples, x_condition=None):
-        """log q(z) for a batch of bit rows, float64."""
-        if x_condition is not None:
-            raise ValueError("x_condition provided but Born machine is not conditional.")
-        return self.log_prob(self.indices_of(z_samples)).to(z_samples.device)
-
-    # ---- the enumerated distribution, where it exists ------------------------------------------------------------
-    def probabilities64(self, x_condition=None):
-        """float64 [2^n] on the parameter's device, detached (n <= 20): exp(log_prob) of all 2^n indices, one call."""
-        if x_condition is not None:
-            raise ValueError("x_condition provided but conditioning_dim is 0.")
-        if self.num_latent_vars > ENUMERATED_MAX_N:
-            raise ValueError(f"the 2^n probabilities exist for num_latent_vars <= {ENUMERATED_MAX_N} only "
-                             f"(got {self.num_latent_vars}): use sample_indices and log_prob")
-        dev = backend.compute_device(self.cores.device)
-        idx = torch.arange(1 << self.num_latent_vars, dtype=torch.int64, device=dev)
-        return torch.exp(self.log_prob(idx)).to(self.cores.device)
-
-    def get_probabilities(self, x_condition=None):
-        """float32 [1, 2^n], detached (n <= 20)."""
-        return self.probabilities64(x_condition).to(torch.float32).unsqueeze(0)
-
-
-for _name in PurifiedSampledMPSBornMachine.REFUSED:
-    setattr(PurifiedSampledMPSBornMachine, _name, _refused(_name))
-del _name

@@ -6,7 +6,9 @@ An exact draw z ~ q costs O(n D^2) (ancestral sampling against the right environ
 grad log q(z) for a given z (bornvi_mps_environments / bornvi_mps_sample / bornvi_mps_score_vjp).
 A sample is an int64 outcome index, idx = sum_k z_k 2^(n-k) (tuple position 0 = the most significant bit), or a float32
 bit row; the conversion, like the `cores` parameter, its checks, initialisations and messages, is born_machine_base's, shared
-with MPSBornMachine.  The fitted q is read out exactly, at any n, by marginals / pair_marginals / log_marginal / sample_given (DESIGN.md section
+with MPSBornMachine.  The sample surface (sample_indices, score_vjp, log_prob, sample, ...) is born_machine_sampled's
+SampledSurface, shared with the complex-cores and the locally purified family: this file states the three hooks it goes
+through (environments, draw, score_gradient) and what the real family alone has.  The fitted q is read out exactly, at any n, by marginals / pair_marginals / log_marginal / sample_given (DESIGN.md section
 6l): an evidence is a partial assignment {tuple position: 0 or 1}.
 two_site_sweep_ / fit_two_site train the cores on given samples by two-site (DMRG-style) sweeps that set every bond's rank from
 its spectrum.
@@ -19,8 +21,9 @@ import torch
 import torch.nn as nn
 
 from . import backend
-from .born_machine_base import MPSCores, bits_to_indices, indices_to_bits, new_mps_cores, pack_evidence
+from .born_machine_base import MPSCores, new_mps_cores, pack_evidence
 from .born_machine_mps import _MPSProbs
+from .born_machine_sampled import SampledSurface, checked_seed
 
 
 def append_sweep(history, report):
@@ -34,26 +37,20 @@ def append_sweep(history, report):
     history["status"].append(int(report["status"].item()))
 
 
-class SampledMPSBornMachine(MPSCores, nn.Module):
+class SampledMPSBornMachine(SampledSurface, MPSCores, nn.Module):
     """MPS Born machine whose surface is samples, log q of samples and the score-function gradient."""
+    ENUMERATED_MAX_N = backend.MPS_MAX_N       # probabilities64: backend.mps_probs
+    NATURAL_GRADIENT = True
 
     def __init__(self, num_latent_vars, bond_dim=4, init_method='small_random', conditioning_dim=0, seed=0):
         cores = new_mps_cores("SampledMPSBornMachine", num_latent_vars, bond_dim, init_method, conditioning_dim,
                               backend.MPS_SAMPLED_MAX_N)
-        if isinstance(seed, bool) or not isinstance(seed, int):
-            raise ValueError(f"seed must be an integer, got {seed!r}")
+        checked_seed(seed)
         super().__init__()
-        self.num_latent_vars = num_latent_vars
-        self.conditioning_dim = 0
-        self.seed = seed
-        self._draws = 0            # epoch of the next sample() call: successive calls draw fresh samples
+        self._init_sampled(num_latent_vars, seed)
         self.cores = cores
 
-    def kernel_input(self):
-        """(cores detached as a contiguous float64 tensor on the compute device, the parameter's own device)."""
-        return super().kernel_input(detach=True)
-
-    # ---- the three calls a trainer needs (ComplexSampledMPSBornMachine has the same three) -------------------------------
+    # ---- the three calls the shared surface and a trainer need -----------------------------------------------------------
     def environments(self, cores, num_samples):
         return backend.mps_environments(cores, num_samples)
 
@@ -62,54 +59,6 @@ class SampledMPSBornMachine(MPSCores, nn.Module):
 
     def score_gradient(self, cores, idx, w):
         return backend.mps_score_vjp(cores, idx, w)
-
-    # ---- samples ----------------------------------------------------------------------------------------------
-    def sample_indices(self, num_samples, seed=None, epoch=0):
-        """(idx int64 [num], logq float64 [num]) on the compute device: exact draws z ~ q and their log q.  A pure function
-        of (cores, seed, epoch): seed defaults to the machine's own."""
-        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
-            raise ValueError(f"num_samples must be a positive integer, got {num_samples!r}")
-        cores, _ = self.kernel_input()
-        ep = torch.tensor([int(epoch)], dtype=torch.int64, device=cores.device)
-        backend.mps_environments(cores, num_samples)
-        idx, logq, _ = backend.mps_sample(cores, num_samples, self.seed if seed is None else seed, ep)
-        return idx, logq
-
-    def bits_of(self, idx):
-        """float32 bit rows [B, n] of outcome indices."""
-        return indices_to_bits(idx, self.num_latent_vars)
-
-    def indices_of(self, z_samples):
-        """int64 outcome indices of bit rows [B, n] (validated like MPSBornMachine.get_log_q_z_x)."""
-        return bits_to_indices(z_samples, self.num_latent_vars)
-
-    def sample(self, num_samples=1, x_condition=None):
-        """float32 bit rows [num, n] on the parameter's device, from the draws of sample_indices (fresh ones every call)."""
-        if x_condition is not None:
-            raise ValueError("x_condition provided but conditioning_dim is 0.")
-        idx, _ = self.sample_indices(num_samples, epoch=self._draws)
-        self._draws += 1
-        return self.bits_of(idx).to(self.cores.device)
-
-    def score_vjp(self, idx, w):
-        """(grad float64 [n, 2, D, D] = sum_b w_b grad log q(idx_b), logq float64 [B]) on the compute device."""
-        cores, _ = self.kernel_input()
-        idx = idx.to(device=cores.device, dtype=torch.int64).contiguous()
-        w = w.to(device=cores.device, dtype=torch.float64).contiguous()
-        backend.mps_environments(cores, int(idx.numel()))
-        grad, logq, _ = backend.mps_score_vjp(cores, idx, w)
-        return grad, logq
-
-    def log_prob(self, idx):
-        """log q(idx), float64 [B] (-inf where psi is 0)."""
-        idx = idx.reshape(-1)
-        return self.score_vjp(idx, torch.zeros(idx.numel(), dtype=torch.float64, device=idx.device))[1]
-
-    def get_log_q_z_x(self, z_samples, x_condition=None):
-        """log q(z) for a batch of bit rows, float64 (no floor: it is evaluated per sample, not read from a table)."""
-        if x_condition is not None:
-            raise ValueError("x_condition provided but Born machine is not conditional.")
-        return self.log_prob(self.indices_of(z_samples)).to(z_samples.device)
 
     # ---- two-site sweeps (backend.mps_twosite_sweep, DESIGN.md section 6o): bond ranks set by the data -------------------
     def _samples_as_indices(self, idx_or_bits):
@@ -239,14 +188,6 @@ class SampledMPSBornMachine(MPSCores, nn.Module):
     # ---- the enumerated distribution, where it exists ------------------------------------------------------------
     def probabilities64(self, x_condition=None):
         """float64 [2^n], differentiable (n <= 26): backend.mps_probs, as MPSBornMachine."""
-        if x_condition is not None:
-            raise ValueError("x_condition provided but conditioning_dim is 0.")
-        if self.num_latent_vars > backend.MPS_MAX_N:
-            raise ValueError(f"the 2^n probabilities exist for num_latent_vars <= {backend.MPS_MAX_N} only "
-                             f"(got {self.num_latent_vars}): use sample_indices and log_prob")
+        self._check_enumerated(x_condition)
         cores, home = MPSCores.kernel_input(self)
         return _MPSProbs.apply(cores).to(home)
-
-    def get_probabilities(self, x_condition=None):
-        """float32 [1, 2^n], differentiable (n <= 26)."""
-        return self.probabilities64(x_condition).to(torch.float32).unsqueeze(0)

@@ -3,7 +3,8 @@
 An epoch: the machine's environments, its draw with (seed, epoch) -> (idx, log q); the objective's weights w_b from the
 samples (the subclass: `sample_weights`); its score_gradient -> sum_b w_b grad log q(z_b) (for real cores mps_environments,
 mps_sample and mps_score_vjp, for born_machine_config['cores'] = 'complex' the cmps_* three, for 'purified' (with
-'purification_dim') the lps_* three: the epoch names no family); then the NaN/Inf guard, clip and Adam or SGD
+'purification_dim') the lps_* three: the epoch names no family -- the one table FAMILIES picks the machine's class, and
+everything else is asked of the machine, born_machine_sampled.SampledSurface); then the NaN/Inf guard, clip and Adam or SGD
 with cosine annealing through torch.optim on the float64 cores: the enumerated trainers' own make_optimizer and
 guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every epoch, the same ones on a rerun.
 With `natural_gradient` (natural_gradient.SampledFisherPreconditioner.coerce says what it accepts) the gradient is replaced,
@@ -27,11 +28,17 @@ import torch
 
 from . import backend
 from .bayesian_network import pack_network
-from .born_machine_cmps_sampled import ENUMERATED_MAX_N, ComplexSampledMPSBornMachine
+from .born_machine_cmps_sampled import ComplexSampledMPSBornMachine
 from .born_machine_lps_sampled import PurifiedSampledMPSBornMachine
 from .born_machine_mps_sampled import SampledMPSBornMachine
 from .ksd_vi import guarded_update, make_optimizer
 from .natural_gradient import CGFisherPreconditioner, SampledFisherPreconditioner, SampleSpaceFisherPreconditioner
+
+# born_machine_config['cores'] -> (the machine's class, the config keys that go with this family alone).  What else the
+# epoch needs of a family it asks the machine: environments / draw / score_gradient, bond_dim, ENUMERATED_MAX_N,
+# NATURAL_GRADIENT and CORES (born_machine_sampled.SampledSurface).
+FAMILIES = {'real': (SampledMPSBornMachine, ()), 'complex': (ComplexSampledMPSBornMachine, ()),
+            'purified': (PurifiedSampledMPSBornMachine, ('purification_dim',))}
 
 
 def checked_config(born_machine_config, allowed_keys, min_samples, max_samples, samples_range):
@@ -74,18 +81,18 @@ class SampledTrainer:
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu',
                  p_floor=1e-30, natural_gradient=None):
-        cfg, B = checked_config(born_machine_config, ('bond_dim', 'num_samples', 'seed', 'init_method', 'cores', 'purification_dim'),
+        family_keys = tuple(key for _, keys in FAMILIES.values() for key in keys)
+        cfg, B = checked_config(born_machine_config, ('bond_dim', 'num_samples', 'seed', 'init_method', 'cores') + family_keys,
                                 self.MIN_SAMPLES, self.MAX_SAMPLES, self.SAMPLES_RANGE)
         kind = cfg.get('cores', 'real')
-        if kind not in ('real', 'complex', 'purified'):
+        if kind not in FAMILIES:
             raise ValueError(f"born_machine_config['cores'] must be 'real', 'complex' or 'purified', got {kind!r}")
-        if 'purification_dim' in cfg and kind != 'purified':
-            raise ValueError("born_machine_config['purification_dim'] goes with 'cores': 'purified' only")
-        if kind == 'complex' and natural_gradient is not None:
-            raise ValueError("natural_gradient is not offered with complex cores: the Fisher estimates exist for the real "
-                             "family (born_machine_config['cores'] = 'real') only")
-        if kind == 'purified' and natural_gradient is not None:
-            raise ValueError("natural_gradient is not offered with purified cores: the Fisher estimates exist for the real "
+        family, own_keys = FAMILIES[kind]
+        for owner, (_, keys) in FAMILIES.items():
+            for key in set(keys).intersection(cfg).difference(own_keys):
+                raise ValueError(f"born_machine_config[{key!r}] goes with 'cores': {owner!r} only")
+        if natural_gradient is not None and not family.NATURAL_GRADIENT:
+            raise ValueError(f"natural_gradient is not offered with {family.CORES}: the Fisher estimates exist for the real "
                              "family (born_machine_config['cores'] = 'real') only")
         if isinstance(p_floor, bool) or not isinstance(p_floor, (int, float)) or not np.isfinite(p_floor) or not p_floor > 0:
             raise ValueError(f"p_floor must be a positive finite number, got {p_floor!r}")
@@ -98,17 +105,12 @@ class SampledTrainer:
         self.seed = cfg.get('seed', 0)
         self.p_floor = float(p_floor)
         self.device = torch.device(device)
-        if kind == 'purified':
-            self.born_machine = PurifiedSampledMPSBornMachine(
-                self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4), purification_dim=cfg.get('purification_dim', 2),
-                init_method=cfg.get('init_method', 'small_random'), seed=self.seed).to(self.device)
-        else:
-            family = ComplexSampledMPSBornMachine if kind == 'complex' else SampledMPSBornMachine
-            self.born_machine = family(self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4),
-                                       init_method=cfg.get('init_method', 'small_random'), seed=self.seed).to(self.device)
+        self.born_machine = family(self.num_latent_vars, bond_dim=cfg.get('bond_dim', 4),
+                                   init_method=cfg.get('init_method', 'small_random'), seed=self.seed,
+                                   **{key: cfg[key] for key in own_keys if key in cfg}).to(self.device)
         self.natural_gradient = SampledFisherPreconditioner.coerce(natural_gradient)
         if self.natural_gradient is not None:
-            self.natural_gradient.plan(self.num_latent_vars, int(self.born_machine.cores.shape[2]), B)
+            self.natural_gradient.plan(self.num_latent_vars, self.born_machine.bond_dim, B)
         self._desc = None
         self.last_idx = None
 
@@ -168,8 +170,7 @@ class SampledTrainer:
         bm = self.born_machine
         self._prepare_observation(x_observation_dict)
         opt, sched = make_sampled_optimizer(bm, lr_born_machine, num_epochs, use_lr_scheduler, optimizer_type, adam_betas, sgd_momentum)
-        max_n = ENUMERATED_MAX_N if isinstance(bm, (ComplexSampledMPSBornMachine, PurifiedSampledMPSBornMachine)) else backend.MPS_MAX_N
-        exact = true_posterior_for_tvd is not None and self.num_latent_vars <= max_n
+        exact = true_posterior_for_tvd is not None and self.num_latent_vars <= bm.ENUMERATED_MAX_N
         history = {k: [] for k in self.LOSS_KEYS + ('grad_norm', 'logq_mean', 'status')}
         if exact:
             history['tvd'], history['kl'] = [], []
