@@ -7,7 +7,7 @@ from .utils import generate_all_binary_outcomes, calculate_tvd  # noqa: F401
 
 __all__ = ["QuantumBornMachine", "KSDVariationalInference", "ClassicalBornMachine", "MPSBornMachine", "ClassicalKSDVariationalInference",
            "ClassicalAdversarialVariationalInference", "ELBOVariationalInference", "ClassicalELBOVariationalInference",
-           "SampledMPSBornMachine", "ComplexSampledMPSBornMachine", "PurifiedSampledMPSBornMachine",
+           "SampledMPSBornMachine", "ComplexSampledMPSBornMachine", "PurifiedSampledMPSBornMachine", "TreeSampledBornMachine",
            "SampledELBOVariationalInference", "SampledKSDVariationalInference",
            "SampledFisherPreconditioner", "SampleSpaceFisherPreconditioner", "CGFisherPreconditioner",
            "AmortisedMPSInference", "HammingMixtureKernel", "MMDObjective", "QuantumMMDTrainer", "ClassicalMMDTrainer",
@@ -48,6 +48,9 @@ def __getattr__(name):
     if name == "PurifiedSampledMPSBornMachine":
         from .born_machine_lps_sampled import PurifiedSampledMPSBornMachine
         return PurifiedSampledMPSBornMachine
+    if name == "TreeSampledBornMachine":
+        from .born_machine_ttn_sampled import TreeSampledBornMachine
+        return TreeSampledBornMachine
     if name == "SampledELBOVariationalInference":
         from .elbo_vi_sampled import SampledELBOVariationalInference
         return SampledELBOVariationalInference

@@ -82,11 +82,11 @@ ANSATZ_IDS = {k: _ENUMS["BORNVI_ANSATZ_" + k.upper()] for k in ("hardware_effici
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 # The side headers include/bornvi_<name>.h, each a family's own in the same subset of C: the two-site sweeps, the complex-cores
-# sampled MPS, MMD with a Hamming-distance kernel, the locally purified sampled MPS.  The same parser reads each into tables of
+# sampled MPS, MMD with a Hamming-distance kernel, the locally purified sampled MPS, the tree tensor network.  The same parser reads each into tables of
 # its own, <NAME>_HEADER_PATH, <NAME>_LIMITS and <NAME>_PROTOTYPES (LIMITS, PROTOTYPES and EXPORTED_SYMBOLS above are
 # bornvi.h's alone); lib() binds every set.
 _SIDE = {}
-for _name in ("twosite", "cmps", "mmd", "lps"):
+for _name in ("twosite", "cmps", "mmd", "lps", "ttn"):
     _path = os.path.join(os.path.dirname(_HERE), "include", f"bornvi_{_name}.h")
     if not os.path.exists(_path):
         raise BornviError(f"{_path} not found: the binding reads the C ABI from it")
@@ -97,6 +97,7 @@ TWOSITE_HEADER_PATH, TWOSITE_LIMITS, TWOSITE_PROTOTYPES = _SIDE["twosite"]
 CMPS_HEADER_PATH, CMPS_LIMITS, CMPS_PROTOTYPES = _SIDE["cmps"]
 MMD_HEADER_PATH, MMD_LIMITS, MMD_PROTOTYPES = _SIDE["mmd"]
 LPS_HEADER_PATH, LPS_LIMITS, LPS_PROTOTYPES = _SIDE["lps"]
+TTN_HEADER_PATH, TTN_LIMITS, TTN_PROTOTYPES = _SIDE["ttn"]
 
 
 def lib():

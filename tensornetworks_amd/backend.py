@@ -941,6 +941,55 @@ def lps_score_vjp(cores, idx, w=None, out=None, out_logq=None, status=None):
     return _sampled_score(_LPS, cores, idx, w, out, out_logq, status, gradient_optional=True)
 
 
+# ---- sampled Born machine on a binary tree tensor network (kernels_ttn.hip, include/bornvi_ttn.h) ----
+TTN_MAX_BOND = _ext.TTN_LIMITS["BORNVI_TTN_MAX_BOND"]
+
+
+def ttn_tree_shape(num_latent_vars):
+    """(h, L) of the tree over n variables: h = max(1, ceil(log2 n)) levels of nodes, L = 2^h leaf positions."""
+    _chk_n(num_latent_vars, 1, MPS_SAMPLED_MAX_N)
+    h = max(1, (int(num_latent_vars) - 1).bit_length())
+    return h, 1 << h
+
+
+def _ttn_family(num_latent_vars):
+    """The family record of the tree over n variables: the cores [L - 1, D, D, D] do not say n (positions >= n are padding)."""
+    if isinstance(num_latent_vars, bool) or not isinstance(num_latent_vars, int):
+        raise BornviError(f"num_latent_vars: expected an integer, got {num_latent_vars!r}")
+    _, L = ttn_tree_shape(num_latent_vars)
+
+    def args(cores, num_samples):
+        if not torch.is_tensor(cores) or cores.dim() != 4 or not cores.shape[1] == cores.shape[2] == cores.shape[3] or cores.shape[0] != L - 1:
+            raise BornviError(f"cores: expected an [L - 1, D, D, D] tensor with L = {L} (n = {num_latent_vars}), got "
+                              f"{tuple(cores.shape) if torch.is_tensor(cores) else type(cores)}")
+        D = int(cores.shape[1])
+        if not 2 <= D <= TTN_MAX_BOND:
+            raise BornviError(f"cores: tree bond dimension 2 ... {TTN_MAX_BOND}, got {D}")
+        return num_latent_vars, D, _sample_count(num_samples)
+    return _SampledFamily("ttn", args, "bornvi_ttn_workspace_bytes", "ttn_%d_%d_%d")
+
+
+def ttn_environments(cores, num_latent_vars, num_samples):
+    """Up and down densities of a tree tensor network and log Z (bornvi_ttn_environments): cores float64 [L - 1, D, D, D] on
+    the GPU, 1 <= n <= 63, 2 <= D <= 8 -> log Z float64 [1].  The environments stay in the cached workspace of
+    (n, D, num_samples) for ttn_sample and ttn_score_vjp: call those next, with the same cores and sample count, on this stream."""
+    return _sampled_environments(_ttn_family(num_latent_vars), cores, num_samples)
+
+
+def ttn_sample(cores, num_latent_vars, num_samples, seed, epoch, out_idx=None, out_logq=None, status=None):
+    """Exact depth-first draws from a tree tensor network (bornvi_ttn_sample), after ttn_environments: -> (idx int64 [B],
+    logq float64 [B], status int32 [1]) as mps_sample; the uniforms are mps_sample's at (seed, epoch, b, k = position + 1)."""
+    return _sampled_sample(_ttn_family(num_latent_vars), cores, num_samples, seed, epoch, out_idx, out_logq, status)
+
+
+def ttn_score_vjp(cores, num_latent_vars, idx, w=None, out=None, out_logq=None, status=None):
+    """log q and the score-function gradient of a tree tensor network (bornvi_ttn_score_vjp), after ttn_environments(cores, n,
+    len(idx)): idx int64 [B], w float64 [B] -> (grad float64 [L - 1, D, D, D] = the gradient of sum_b w_b log q(idx_b), exactly
+    0.0 in the dead entries, logq float64 [B], status int32 [1]: 0, or 2 when some psi(idx_b) is 0 or not finite).
+    out=False (then w may be None): logq only, the same bits, no down sweep and no gradient work -> (None, logq, status)."""
+    return _sampled_score(_ttn_family(num_latent_vars), cores, idx, w, out, out_logq, status, gradient_optional=True)
+
+
 # ---- exact posterior queries of the sampled MPS (kernels_mps_query.hip) ----------------------------------------------
 MPS_QUERY_MAX_QUERIES = _ext.LIMITS["BORNVI_MPS_QUERY_MAX_QUERIES"]
 

@@ -15,6 +15,7 @@
 #include "bornvi.h"
 #include "bornvi_cmps.h"
 #include "bornvi_lps.h"
+#include "bornvi_ttn.h"
 #include "bornvi_mmd.h"
 #include "bornvi_twosite.h"
 #include "kernels.hpp"
@@ -1665,6 +1666,55 @@ int bornvi_lps_score_vjp(bornvi_handle h, int n, int m, int D, long long B, cons
   if (!workspace || workspace_bytes < lps_workspace_bytes(n, m, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
   DEVICE_SCOPE(h);
   HIPCHK(h, launch_lps_score_vjp(n, m, D, B, cores, idx, w, logq, grad_cores, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+// ---- sampled Born machine on a binary tree tensor network (kernels_ttn.hip; declared in bornvi_ttn.h) ------------------------
+static const char* const TTN_RANGE = "unsupported size (1 <= n <= 63, 2 <= D <= 8, 1 <= B <= 2^24)";
+static bool valid_ttn(int n, int D, long long B) {
+  return n >= 1 && n <= BORNVI_MPS_SAMPLED_MAX_N && D >= 2 && D <= BORNVI_TTN_MAX_BOND && B >= 1 && B <= BORNVI_MPS_SAMPLED_MAX_BATCH;
+}
+
+size_t bornvi_ttn_workspace_bytes(bornvi_handle h, int n, int D, long long B) {
+  if (!h) return 0;
+  if (!valid_ttn(n, D, B)) { fail(h, BORNVI_ERR_UNSUPPORTED, TTN_RANGE); return 0; }
+  return ttn_workspace_bytes(n, D, B);
+}
+
+int bornvi_ttn_environments(bornvi_handle h, int n, int D, long long B, const double* cores, double* log_Z_out, void* workspace,
+                            size_t workspace_bytes, bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_ttn(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, TTN_RANGE);
+  if (!cores) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  // a short workspace is refused like a size: nothing is launched
+  if (!workspace || workspace_bytes < ttn_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_ttn_environments(n, D, B, cores, log_Z_out, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_ttn_sample(bornvi_handle h, int n, int D, long long B, const double* cores, unsigned long long seed,
+                      const long long* epoch_dev, long long* idx, double* logq, int* status, void* workspace, size_t workspace_bytes,
+                      bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_ttn(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, TTN_RANGE);
+  if (!cores || !epoch_dev || !idx || !logq || !status) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < ttn_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_ttn_sample(n, D, B, cores, seed, epoch_dev, idx, logq, status, workspace, (hipStream_t)stream));
+  return BORNVI_OK;
+}
+
+int bornvi_ttn_score_vjp(bornvi_handle h, int n, int D, long long B, const double* cores, const long long* idx, const double* w,
+                         double* logq, double* grad_cores, int* status, void* workspace, size_t workspace_bytes,
+                         bornvi_stream stream) {
+  if (!h) return BORNVI_ERR_INVALID;
+  if (!valid_ttn(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, TTN_RANGE);
+  // grad_cores may be NULL (logq only), and then w is not read and may be NULL too
+  if (!cores || !idx || !logq || !status || (grad_cores && !w)) return fail(h, BORNVI_ERR_INVALID, "null pointer");
+  if (!workspace || workspace_bytes < ttn_workspace_bytes(n, D, B)) return fail(h, BORNVI_ERR_UNSUPPORTED, "workspace too small");
+  DEVICE_SCOPE(h);
+  HIPCHK(h, launch_ttn_score_vjp(n, D, B, cores, idx, w, logq, grad_cores, status, workspace, (hipStream_t)stream));
   return BORNVI_OK;
 }
 

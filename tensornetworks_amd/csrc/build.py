@@ -9,8 +9,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 REPO = os.path.dirname(PKG)
-SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_mps_sample_gram.hip", "kernels_mps_query.hip", "kernels_mps_canon.hip", "kernels_mps_twosite.hip", "kernels_cmps.hip", "kernels_lps.hip", "kernels_mmd.hip", "kernels_ksd_sampled.hip", "kernels_cg.hip", "plan.cpp"]
-HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "shots_dev.hpp", "mps_sample_dev.hpp", "mps_canon_dev.hpp", "syrk_f64.hpp", "reduce_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", h) for h in ("bornvi.h", "bornvi_twosite.h", "bornvi_cmps.h", "bornvi_mmd.h", "bornvi_lps.h")]
+SOURCES = ["api.hip", "kernels_circuit.hip", "kernels_circuit8.hip", "kernels_stein.hip", "kernels_batched.hip", "kernels_adjoint.hip", "kernels_shots.hip", "kernels_born_table.hip", "kernels_reinforce.hip", "kernels_elbo.hip", "kernels_fisher.hip", "kernels_qfi.hip", "kernels_mps.hip", "kernels_mps_sample.hip", "kernels_mps_sample_gram.hip", "kernels_mps_query.hip", "kernels_mps_canon.hip", "kernels_mps_twosite.hip", "kernels_cmps.hip", "kernels_lps.hip", "kernels_ttn.hip", "kernels_mmd.hip", "kernels_ksd_sampled.hip", "kernels_cg.hip", "plan.cpp"]
+HEADERS = [os.path.join(HERE, h) for h in ("plan.hpp", "kernels.hpp", "circuit_dev.hpp", "philox_dev.hpp", "shots_dev.hpp", "mps_sample_dev.hpp", "mps_canon_dev.hpp", "syrk_f64.hpp", "reduce_dev.hpp", "ttn_dev.hpp", "exports.map")] + [os.path.join(REPO, "include", h) for h in ("bornvi.h", "bornvi_twosite.h", "bornvi_cmps.h", "bornvi_mmd.h", "bornvi_lps.h", "bornvi_ttn.h")]
 OUT = os.path.join(PKG, "libbornvi_hip.so")
 OBJ = os.path.join(HERE, "_obj")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-I" + os.path.join(REPO, "include"), "-I" + HERE,
@@ -87,6 +87,10 @@ RESOURCE_BUDGET = {
     "lps_sample_kernel": (0, 0),                  # doubles) in registers; a wave of the score kernel a density, its operands and 2 m gradient
     "lps_score_kernel": (0, 0),                   # tiles (4 doubles each); no scratch in any instantiation
     "lps_score_finish_kernel": (0, 0),
+    "ttn_env_kernel": (0, 0),                     # tree tensor network (kernels_ttn.hip): the sampler keeps a density and one row's
+    "ttn_sample_kernel": (0, 0),                  # products (2 x 64 doubles at D = 8) in registers, its stack in LDS or the workspace;
+    "ttn_score_kernel": (0, 0),                   # the score kernel three vectors and four accumulator tiles; no scratch in any
+    "ttn_score_finish_kernel": (0, 0),            # instantiation
     "mmd_pass_kernel": (0, 0),                    # MMD (kernels_mmd.hip): a tile's 16 doubles per thread and a radix-16 round in
     "mmd_finish_kernel": (0, 0),                  # registers, the tile and the pair counts' histogram columns in LDS, no scratch
     "hamming_pairs_kernel": (0, 0),

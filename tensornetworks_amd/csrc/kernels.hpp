@@ -168,6 +168,14 @@ hipError_t launch_lps_sample(int n, int m, int D, long long B, const double* cor
 hipError_t launch_lps_score_vjp(int n, int m, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
                                 double* grad_cores, int* status, void* ws, hipStream_t st);
 
+// ---- sampled Born machine on a binary tree tensor network (kernels_ttn.hip): cores [L - 1, D, D, D], 2 <= D <= 8 ----
+size_t ttn_workspace_bytes(int n, int D, long long B);
+hipError_t launch_ttn_environments(int n, int D, long long B, const double* cores, double* logZ_out, void* ws, hipStream_t st);
+hipError_t launch_ttn_sample(int n, int D, long long B, const double* cores, unsigned long long seed, const long long* epoch_dev,
+                             long long* idx, double* logq, int* status, void* ws, hipStream_t st);
+hipError_t launch_ttn_score_vjp(int n, int D, long long B, const double* cores, const long long* idx, const double* w, double* logq,
+                                double* grad_cores, int* status, void* ws, hipStream_t st);
+
 // ---- MMD with a Hamming-distance kernel (kernels_mmd.hip): Walsh-Hadamard weights, pair counts by xor + popcount ----
 int mmd_passes(int n);       // tile passes of a call with w: 1, 3, 5
 size_t mmd_workspace_bytes(int n);

@@ -23,7 +23,7 @@ class SampledMMDTrainer(SampledTrainer):
     SAMPLES_RANGE = "3 ... 2^17"
 
     def __init__(self, num_vars, born_machine_config, device='cpu', *, length_scales=(0.25, 1.0, 4.0), natural_gradient=None):
-        """born_machine_config: bond_dim, num_samples (3 ... 2^17), seed, init_method, cores ('real', 'complex' or 'purified' with purification_dim)."""
+        """born_machine_config: bond_dim, num_samples (3 ... 2^17), seed, init_method, cores ('real', 'complex', 'purified' with purification_dim, or 'tree')."""
         objective = MMDObjective(num_vars, length_scales, device)        # (checks num_vars and the length scales)
         names = [f"z{i}" for i in range(objective.num_vars)]
         super().__init__(None, names, [], born_machine_config, device=device, natural_gradient=natural_gradient)

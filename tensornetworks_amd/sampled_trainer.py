@@ -3,7 +3,7 @@
 An epoch: the machine's environments, its draw with (seed, epoch) -> (idx, log q); the objective's weights w_b from the
 samples (the subclass: `sample_weights`); its score_gradient -> sum_b w_b grad log q(z_b) (for real cores mps_environments,
 mps_sample and mps_score_vjp, for born_machine_config['cores'] = 'complex' the cmps_* three, for 'purified' (with
-'purification_dim') the lps_* three: the epoch names no family -- the one table FAMILIES picks the machine's class, and
+'purification_dim') the lps_* three, for 'tree' the ttn_* three: the epoch names no family -- the tables FAMILIES and TREE_FAMILIES pick the machine's class, and
 everything else is asked of the machine, born_machine_sampled.SampledSurface); then the NaN/Inf guard, clip and Adam or SGD
 with cosine annealing through torch.optim on the float64 cores: the enumerated trainers' own make_optimizer and
 guarded_update (ksd_vi.py).  Epoch e draws with (seed, e): fresh samples every epoch, the same ones on a rerun.
@@ -31,6 +31,7 @@ from .bayesian_network import pack_network
 from .born_machine_cmps_sampled import ComplexSampledMPSBornMachine
 from .born_machine_lps_sampled import PurifiedSampledMPSBornMachine
 from .born_machine_mps_sampled import SampledMPSBornMachine
+from .born_machine_ttn_sampled import TreeSampledBornMachine
 from .ksd_vi import guarded_update, make_optimizer
 from .natural_gradient import CGFisherPreconditioner, SampledFisherPreconditioner, SampleSpaceFisherPreconditioner
 
@@ -39,6 +40,10 @@ from .natural_gradient import CGFisherPreconditioner, SampledFisherPreconditione
 # NATURAL_GRADIENT and CORES (born_machine_sampled.SampledSurface).
 FAMILIES = {'real': (SampledMPSBornMachine, ()), 'complex': (ComplexSampledMPSBornMachine, ()),
             'purified': (PurifiedSampledMPSBornMachine, ('purification_dim',))}
+# The same for the families that are no chain: FAMILIES is the table of the matrix-product states (its three entries are what
+# the chains' host definition is checked against), the tree tensor network has this one, and the trainer reads both.
+TREE_FAMILIES = {'tree': (TreeSampledBornMachine, ())}
+ALL_FAMILIES = {**FAMILIES, **TREE_FAMILIES}
 
 
 def checked_config(born_machine_config, allowed_keys, min_samples, max_samples, samples_range):
@@ -81,14 +86,14 @@ class SampledTrainer:
 
     def __init__(self, bayesian_network, latent_vars_names, observed_vars_names, born_machine_config, device='cpu',
                  p_floor=1e-30, natural_gradient=None):
-        family_keys = tuple(key for _, keys in FAMILIES.values() for key in keys)
+        family_keys = tuple(key for _, keys in ALL_FAMILIES.values() for key in keys)
         cfg, B = checked_config(born_machine_config, ('bond_dim', 'num_samples', 'seed', 'init_method', 'cores') + family_keys,
                                 self.MIN_SAMPLES, self.MAX_SAMPLES, self.SAMPLES_RANGE)
         kind = cfg.get('cores', 'real')
-        if kind not in FAMILIES:
-            raise ValueError(f"born_machine_config['cores'] must be 'real', 'complex' or 'purified', got {kind!r}")
-        family, own_keys = FAMILIES[kind]
-        for owner, (_, keys) in FAMILIES.items():
+        if kind not in ALL_FAMILIES:
+            raise ValueError(f"born_machine_config['cores'] must be 'real', 'complex', 'purified' or 'tree', got {kind!r}")
+        family, own_keys = ALL_FAMILIES[kind]
+        for owner, (_, keys) in ALL_FAMILIES.items():
             for key in set(keys).intersection(cfg).difference(own_keys):
                 raise ValueError(f"born_machine_config[{key!r}] goes with 'cores': {owner!r} only")
         if natural_gradient is not None and not family.NATURAL_GRADIENT:
